@@ -8,11 +8,13 @@
 
 One "step" = one optimisation step on a synthetic batch of 16 images per GPU (BASELINE.json configs[1]); inputs
 (uint8 images, encoded anchor targets) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
-Regions, in order: W warm-up steps | the TIMED region (exactly K steps between barrier + synchronize pairs: `value`, `ms_per_step`) | two
-more regions of the same K steps (`repeats`: min / median over the three, so a 2-3 % change is told from noise) | the roofline region (the
-same K steps with two HIP events per convolution launch: `roofline`, `kernels`, `event_recording`) | two steps with the weight-gradient
-stream off (`roofline.serialized`) | the strong-scaling leg (`strong`: BASELINE.json configs[2]'s global batch of 128 on these N GPUs,
-16-image towers) | inference / target-encoder / CPU-baseline legs.
+A plain run is: W warm-up steps | the TIMED region (exactly K steps between barrier + synchronize pairs: `value`, `ms_per_step`) |
+--dump-outputs DIR (what the last timed step handed its caller, as DIR/<name>.npy; that step starts from the seeded initial state) |
+the line.
+--full adds, in order: two more regions of the same K steps (`repeats`: min / median over the three, so a 2-3 % change is told from
+noise) | the roofline region (the same K steps with two HIP events per convolution launch: `roofline`, `kernels`, `event_recording`) |
+two steps with the weight-gradient stream off (`roofline.serialized`) | the strong-scaling legs (`strong`: BASELINE.json configs[2]'s
+global batch of 128 on these N GPUs, 16-image towers; `strong16`) | inference / target-encoder / CPU-baseline legs.
 """
 import argparse
 import json
@@ -24,6 +26,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: places kept of each flat parameter buffer (16 MiB of float32; three buffers)
 
 
 def spawn_ranks(n):
@@ -193,6 +196,38 @@ def cpu_baseline(seconds_budget=25.0):
                                          "sample": "median of %d such forwards with torch.set_num_threads(1)" % n1}}
 
 
+def model_state(trainer):
+    """The device tensors a training step reads besides its batch and writes back: flat weights, momenta (and the fp16 build's loss scale)."""
+    return [t for t in (trainer.flat.w, trainer.flat.v, trainer.ls_state) if t is not None]
+
+
+def restore_model_state(trainer, snapshot):
+    """Puts the state model_state() saved back and refreshes the packed convolution weights, as the optimizer does after its update."""
+    from dan_amd import ops
+    for t, s in zip(model_state(trainer), snapshot):
+        t.copy_(s)
+    ops.WEIGHT_EPOCH += 1
+    ops.repack_all()
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last train_step handed its caller, as out_dir/<name>.npy - every loss term's accumulator
+    [ce_sum, n_selected, loc_sum, n_pos] and the L2 term (float64), the flat weights, gradients and momenta (float32).  A buffer longer
+    than DUMP_SAMPLE is written at a fixed, seeded sample of DUMP_SAMPLE places (sorted), the same for every build of one model."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, _, acc in trainer.last:
+        np.save(os.path.join(out_dir, "loss_%s.npy" % name), acc.detach().double().cpu().numpy())
+    flat = trainer.flat
+    np.save(os.path.join(out_dir, "l2.npy"), flat.l2.detach().double().cpu().numpy())
+    idx = None
+    if flat.total > DUMP_SAMPLE:
+        idx = torch.randperm(flat.total, generator=torch.Generator().manual_seed(20180817))[:DUMP_SAMPLE].sort().values.to(flat.w.device)
+    for name, t in (("weights", flat.w), ("gradients", flat.g), ("momenta", flat.v)):
+        np.save(os.path.join(out_dir, name + ".npy"), (t if idx is None else t[idx]).detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -208,7 +243,13 @@ def main():
     ap.add_argument("--strong16-global-batch", type=int, default=16,
                     help="SURVEY 8(e)'s own strong series: 'S3FD 16 -> 2 per rank' - a fixed global batch of 16 on the N ranks, 16 / N images per "
                          "rank as one tower (tf_replicate_model_fn.py:458-498); 0 = skip")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of K steps each (the first one is `value`; all of them are in `repeats`)")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also run every other leg (repeats, roofline, strong scaling, inference, target encoder, CPU "
+                         "baseline) and report it in the line; off by default: a plain run times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float32 / float64, 48 MiB at most); that step "
+                         "starts from the seeded initial model state, so the files are the same in every run")
+    ap.add_argument("--repeats", type=int, default=3, help="with --full: timed regions of K steps each (the first one is `value`; all of them are in `repeats`)")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="capture the training step (incl. the bucketed RCCL all-reduce when N > 1) in a hipGraph; off by default")
@@ -316,6 +357,11 @@ def main():
     # has only ever run on a ONE-rank communicator (one-GPU boxes), so it is taken only when --graph asks for it.
     if B < (4 if args.model == "sfd" else 8) and not args.eager and world == 1:
         args.graph = True
+    # --dump-outputs: the LAST timed step starts again from the seeded initial state, so what it writes is one training step of the seeded
+    # model on the seeded batch, the same in every run.  (The weight and bias gradients are summed with fp32 atomics whose order varies by
+    # ~1e-7; over a trajectory of steps the training amplifies that to percent-level differences of the end state, which no comparison of
+    # two runs or two builds could tell from a bug.)  One copy + one repack inside the timed region; plain runs do neither.
+    initial_state = [t.clone() for t in model_state(trainer)] if args.dump_outputs else None
     if args.graph:                                    # (data-parallel steps are captured too: RCCL collectives are device-side)
         trainer.enable_graph(*step_args)
     for _ in range(args.warmup):
@@ -326,10 +372,48 @@ def main():
     # the events moved to a second, equally long region right behind this one: VERDICT r3 item 9.)
     ops.PROFILE = ops.PROFILE_BYTES = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if initial_state is not None and i == args.steps - 1:
+            restore_model_state(trainer, initial_state)
         trainer.train_step(*step_args)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
+
+    def headline(dt):
+        """The line's headline fields (dt: the timed region's wall time, slowest rank); reads the last step's losses (synchronises)."""
+        rccl_info = None
+        if trainer.buckets.rccl is not None and rccl_log and os.path.exists(rccl_log):
+            try:
+                rccl_info = rccl_debug_parse(open(rccl_log, errors="replace").read())
+                rccl_info["bucket_bytes"] = int(getattr(trainer.buckets, "bucket_bytes", 0)) or None
+            except Exception as ex:                                    # the log format is RCCL's business: never fail the bench over it
+                rccl_info = {"error": repr(ex)}
+        lv = trainer.loss_values()
+        first = [k for k in lv if k not in ("l2", "total")][0]
+        return {
+            "metric": "640x640 images/sec/node (train fwd+bwd)", "value": round(world * B * args.steps / dt, 3), "unit": "images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": _lib.ACT_NAME, "data": "synthetic",
+            "config": {"workload": "%s, %dx%d %s training (fwd+bwd+SGD), batch %d per GPU" % (workload, S, S, _lib.ACT_NAME, B),
+                       "global_batch": world * B, "parallelism": "dp%d" % world, "anchors_per_image": anchors.num_anchors,
+                       "step_launch": "hipGraph replay" if args.graph else "eager",
+                       "rccl_ranks": trainer.buckets.rccl.world if trainer.buckets.rccl is not None else 1,
+                       "rccl": rccl_info,
+                       "dp_transport": (("rccl %d called by libdanhip (danhip_comm_*), control plane %s" % (trainer.buckets.rccl.version, dist.get_backend() if multi else "none"))
+                                        if trainer.buckets.rccl is not None else (trainer.buckets.transport if trainer.buckets.enabled else None)),
+                       "dp_comm": (os.environ.get("DANHIP_DP_COMM", "allreduce") + "/" + os.environ.get("DANHIP_DP_BUCKET_DTYPE", "f32")) if trainer.buckets.enabled else None,
+                       "weight_gradient_stream": bool((not trainer.buckets.enabled or trainer.buckets.device_collectives) and ops.WGRAD_STREAM)},
+            "loss": {"ce": round(lv[first][0], 4), "loc": round(lv[first][1], 4), "l2": round(lv["l2"], 4)},
+        }
+
+    if not args.full:
+        (dt,) = max_over_ranks(dt)
+        if rank == 0:
+            print(json.dumps(headline(dt)), flush=True)
+        shutdown_distributed(trainer)
+        return
     # ---- the same region again (--repeats - 1 times): `value` stays the FIRST region's; min / median over all of them say how much of a
     # difference between two lines is noise
     region_dts = [dt]
@@ -486,17 +570,7 @@ def main():
             enc_out = {"value": round(B / et, 1), "unit": "images/sec", "ms_per_batch": round(et * 1e3, 3), "gt_boxes_in_batch": int(sum(g.shape[0] for g in gts)),
                        "what": "IoU + small-mining match + target encode for the batch, one call (danhip_encode_anchors_batched), bit-exact index work"}
 
-    rccl_info = None
-    if rank == 0 and trainer.buckets.rccl is not None and rccl_log and os.path.exists(rccl_log):
-        try:
-            rccl_info = rccl_debug_parse(open(rccl_log, errors="replace").read())
-            rccl_info["bucket_bytes"] = int(getattr(trainer.buckets, "bucket_bytes", 0)) or None
-        except Exception as ex:                                    # the log format is RCCL's business: never fail the bench over it
-            rccl_info = {"error": repr(ex)}
     if rank == 0:
-        lv = trainer.loss_values()
-        first = [k for k in lv if k not in ("l2", "total")][0]
-        ce, ll, l2 = lv[first][0], lv[first][1], lv["l2"]
         # ---- roofline of the dominant kernel (HIP events recorded on the launch stream inside the timed region)
         # A bracket [e0, launch, e1] also times whatever the stream waited for between e0 and the launch: on a host-bound graph (DAN: ~1100
         # launches per step) the queue runs dry and a bracket can hold milliseconds of host time (profiles/r5/size1024_lines.jsonl line 1:
@@ -582,19 +656,8 @@ def main():
                                 "flop_per_byte": round(f_ / nb, 1), "algorithmic_bytes_per_launch": round(nb / n_),
                                 "traffic": (round(pmc[l_]["hbm_bytes_per_launch"]) if l_ in pmc else None)})
         roof["hbm_bound_convs"] = hbm[:8]
-        out = {
-            "metric": "640x640 images/sec/node (train fwd+bwd)", "value": round(world * B * args.steps / dt, 3), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": _lib.ACT_NAME, "data": "synthetic",
-            "config": {"workload": "%s, %dx%d %s training (fwd+bwd+SGD), batch %d per GPU" % (workload, S, S, _lib.ACT_NAME, B),
-                       "global_batch": world * B, "parallelism": "dp%d" % world, "anchors_per_image": anchors.num_anchors,
-                       "step_launch": "hipGraph replay" if args.graph else "eager",
-                       "rccl_ranks": trainer.buckets.rccl.world if trainer.buckets.rccl is not None else 1,
-                       "rccl": rccl_info,
-                       "dp_transport": (("rccl %d called by libdanhip (danhip_comm_*), control plane %s" % (trainer.buckets.rccl.version, dist.get_backend() if multi else "none"))
-                                        if trainer.buckets.rccl is not None else (trainer.buckets.transport if trainer.buckets.enabled else None)),
-                       "dp_comm": (os.environ.get("DANHIP_DP_COMM", "allreduce") + "/" + os.environ.get("DANHIP_DP_BUCKET_DTYPE", "f32")) if trainer.buckets.enabled else None,
-                       "weight_gradient_stream": bool((not trainer.buckets.enabled or trainer.buckets.device_collectives) and ops.WGRAD_STREAM)},
+        out = headline(dt)
+        out.update({
             "event_recording": {"steps": prof_steps, "ms_per_step": round(dt_prof / prof_steps * 1e3, 3), "launch": "eager",
                                 "what": "the roofline region: the same steps repeated right after the timed region with two HIP events per convolution launch "
                                         "(the timed region records none); its own wall time per step shows what the events cost"},
@@ -603,10 +666,9 @@ def main():
                         "median_ms_per_step": round(sorted(region_dts)[len(region_dts) // 2] / args.steps * 1e3, 3),
                         "value_at_median": round(world * B * args.steps / sorted(region_dts)[len(region_dts) // 2], 3)},
             "strong": strong, "strong16": strong16,
-            "loss": {"ce": round(ce, 4), "loc": round(ll, 4), "l2": round(l2, 4)},
             "roofline": roof,
             "kernels": [{"kernel": l, "ms_per_step": round(m / prof_steps, 3), "tflops": round(f / (m * 1e-3) / 1e12, 1)} for m, l, _, f in stats[:6]],
-        }
+        })
         if eval_out:
             out["eval"] = eval_out
         if enc_out:

@@ -282,7 +282,7 @@ def test_bench_line_of_a_two_rank_run_on_one_gpu(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(DANHIP_DP_TRANSPORT="gloo", DANHIP_BENCH_RCCL_LOG="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--size", "128",
-           "--strong-global-batch", "8", "--repeats", "2", "--eager", "--no-cpu-baseline", "--no-eval"]
+           "--strong-global-batch", "8", "--repeats", "2", "--eager", "--no-cpu-baseline", "--no-eval", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[:3000], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -307,7 +307,7 @@ def test_bench_line_of_a_two_rank_run_on_the_rccl_transport(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "DANHIP_DP_TRANSPORT")}
     env.update(DANHIP_RCCL_PATH=FAKE_RCCL, DANHIP_DP_NO_FALLBACK="1", DANHIP_BENCH_RCCL_LOG="0", DANHIP_COMM_TIMEOUT_S="240", FAKE_RCCL_TIMEOUT_S="200")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--size", "128",
-           "--strong-global-batch", "8", "--repeats", "2", "--eager", "--no-cpu-baseline", "--no-eval"]
+           "--strong-global-batch", "8", "--repeats", "2", "--eager", "--no-cpu-baseline", "--no-eval", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[:3000], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -3,7 +3,7 @@
 # (DEBUG_CLR_GRAPH_PACKET_CAPTURE = 0: branches of a captured graph run on several streams instead of one AQL packet batch;
 # DEBUG_HIP_FORCE_GRAPH_QUEUES = n: number of those streams).  usage: bash tools/ab_graph_modes.sh [rounds] [extra bench args]
 R=${1:-2}; shift
-COMMON="--steps 40 --no-cpu-baseline --no-eval --strong-global-batch 0 --strong16-global-batch 0 --no-serialized-roofline --events-steps 1 --repeats 2 $@"
+COMMON="--full --steps 40 --no-cpu-baseline --no-eval --strong-global-batch 0 --strong16-global-batch 0 --no-serialized-roofline --events-steps 1 --repeats 2 $@"
 run() { name=$1; shift; out=$(env "$@" python3 bench.py $COMMON $EXTRA 2>/dev/null | tail -1); python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); print('%-28s %s  %s' % (sys.argv[2], d['repeats']['ms_per_step'], d['config']['step_launch']))" "$out" "$name"; }
