@@ -52,11 +52,14 @@ SIGNATURES = {
     "danhip_conv2d_fwd_ws": [DESC, P, P, P, P, ctypes.c_int, ctypes.c_int, P, P, ctypes.c_size_t, P],
     "danhip_conv2d_fwd_f32": [DESC, P, P, P, P, ctypes.c_int, P, P],
     "danhip_maxpool2x2_fwd_f32": [P, P, I32, I32, I32, I32, P],
-    "danhip_split3_f32": [P, P, I64, I32, I32, ctypes.c_int, P],
+    "danhip_split_set_range_flag": [P],
+    "danhip_split3_f32": [P, P, I64, I32, I32, ctypes.c_int, I32, P],
     "danhip_unsplit3_f32": [P, P, I64, I32, I32, P],
+    "danhip_unsplit3_scaled_f32": [P, P, I64, I32, I32, I32, P],
     "danhip_maxpool2x2_split3": [P, P, I32, I32, I32, I32, P],
-    "danhip_l2norm_split3": [P, P, P, I64, I32, P],
-    "danhip_conv3x3_c3_f32_split3": [P, P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
+    "danhip_l2norm_split3": [P, P, P, I64, I32, I32, I32, P],
+    "danhip_conv3x3_c3_f32_split3": [P, P, P, P, I32, I32, I32, I32, ctypes.c_int, I32, P],
+    "danhip_conv2d_fwd_split": [DESC, P, P, P, P, ctypes.c_int, ctypes.c_int, I32, P, ctypes.c_size_t, P],
     "danhip_l2norm_fwd_f32": [P, P, P, I64, I32, P],
     "danhip_resize_bilinear_add_fwd_f32": [P, P, P, I32, I32, I32, I32, I32, I32, P],
     "danhip_avgpool2x2s1_same_fwd_f32": [P, P, I32, I32, I32, I32, P],

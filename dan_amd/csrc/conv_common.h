@@ -47,7 +47,26 @@ struct ConvArgs {
   float* fuse_dw;
   float* fuse_db;
   int fuse_cin_real;
+  // Split-operand evaluation (danhip_conv2d_fwd_split; 0 everywhere else): the forward epilogue computes v = fma(acc, 2^acc_exp, bias) - the
+  // power of two undoes the exponents of the weights, of the input limbs and of the output map exactly, and costs nothing where a bias is
+  // added anyway.  A limb-layout output raises *range_flag (if set) for a value the hi limb cannot hold (|v| >= 65520).
+  int acc_exp;
+  int* range_flag;
 };
+
+// 2^acc_exp (acc_exp in [-126, 127]) from the kernel argument with scalar integer operations
+__device__ __forceinline__ float dh_acc_scale(const ConvArgs& a) { return __builtin_bit_cast(float, (a.acc_exp + 127) << 23); }
+
+// *flag = 1 when one of the N values is outside half's finite range (|v| >= 65520 rounds hi to inf and lo to -inf: the next convolution would
+// sum inf - inf = NaN, which a ReLU turns into 0); split_infer.hip, checked on the host by ops.split_range_check.  The maximum ignores a NaN:
+// one can only come from an inf limb, which its writer flagged.
+template <int N>
+__device__ __forceinline__ void dh_range_check(const float* v, int* flag) {
+  float m = fabsf(v[0]);
+#pragma unroll
+  for (int r = 1; r < N; ++r) m = fmaxf(m, fabsf(v[r]));
+  if (!(m < 65520.f) && flag) *flag = 1;
+}
 
 // hi / lo limbs of 4 fp32 values as two packed pairs each (the build's 16-bit type: IEEE half where split_out is allowed)
 __device__ __forceinline__ void dh_split4(const float v[4], uint2& hi, uint2& lo) {
@@ -59,6 +78,9 @@ __device__ __forceinline__ void dh_split4(const float v[4], uint2& hi, uint2& lo
   lo.x = pack2bf(v[0] - h[0], v[1] - h[1]);
   lo.y = pack2bf(v[2] - h[2], v[3] - h[3]);
 }
+
+// the device flag the split-operand limb writers raise (split_infer.hip, danhip_split_set_range_flag; null = none)
+int* danhip_split_range_flag();
 
 // true when launch_conv's kernel for these args writes a.pool_y itself (conv_halo_c64.hip / conv_halo.hip forward tiles)
 bool danhip_conv_pool_fusable(const ConvArgs& a);
@@ -181,8 +203,12 @@ __device__ __forceinline__ void conv_store4(const ConvArgs& a, float v[4], size_
   const size_t orr = m * (size_t)a.Co + co;         // residual: always dense
   const bool full = (co + 4 <= a.Co) && ((a.Co & 3) == 0);
   if (a.bias) {
+    const float sc = dh_acc_scale(a);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) if (co + r < a.Co) v[r] += a.bias[co + r];
+    for (int r = 0; r < 4; ++r) if (co + r < a.Co) v[r] = fmaf(v[r], sc, a.bias[co + r]);
+  } else if (a.acc_exp) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] *= dh_acc_scale(a);
   }
   if (a.relu && co < a.relu_co) {
 #pragma unroll
@@ -201,6 +227,7 @@ __device__ __forceinline__ void conv_store4(const ConvArgs& a, float v[4], size_
   } else {
     bf16_t* y = reinterpret_cast<bf16_t*>(a.y) + o;
     if (a.split_out) {                                  // (forward only, Co % 8 == 0: always a full quad)
+      dh_range_check<4>(v, a.range_flag);
       uint2 hi, lo;
       dh_split4(v, hi, lo);
       *reinterpret_cast<uint2*>(y) = hi;

@@ -74,7 +74,8 @@ template <bool DGRAD>
 __device__ __forceinline__ void halo_finish4(const ConvArgs& a, const f32x4& acc, const float4& b, const uint2& in0, const uint2& in1, size_t o) {
   float v[4] = {acc[0], acc[1], acc[2], acc[3]};
   if (!DGRAD) {
-    v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
+    const float sc = dh_acc_scale(a);                  // (1 outside the split-operand path: fma(acc, 1, b) = acc + b)
+    v[0] = fmaf(v[0], sc, b.x); v[1] = fmaf(v[1], sc, b.y); v[2] = fmaf(v[2], sc, b.z); v[3] = fmaf(v[3], sc, b.w);
     if (a.relu) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = dh_relu(v[r]);
@@ -114,8 +115,9 @@ __device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo
                                               const uint4& in1, size_t o) {
   float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   if (!DGRAD) {
+    const float sc = dh_acc_scale(a);                  // (1 outside the split-operand path: fma(acc, 1, b) = acc + b)
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] += b[r];
+    for (int r = 0; r < 8; ++r) v[r] = fmaf(v[r], sc, b[r]);
     if (a.relu) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) v[r] = dh_relu(v[r]);
@@ -127,6 +129,7 @@ __device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo
       return u32x4{0u, 0u, 0u, 0u};
     }
     if (a.split_out) {                  // limb layout of the next convolution (split_infer.hip): o = pixel * 3 Co + co, set by the caller
+      dh_range_check<8>(v, a.range_flag);
       uint2 h0, l0, h1, l1;
       dh_split4(v, h0, l0);
       dh_split4(v + 4, h1, l1);
@@ -487,7 +490,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           for (int r = 0; r < 4; ++r) {
             const int co = wn * TC + c * 16 + fq * 4 + r;
             if (ok && co < a.Co) {
-              float v = acc[c][p][r] + (a.bias ? a.bias[co] : 0.f);
+              float v = fmaf(acc[c][p][r], dh_acc_scale(a), a.bias ? a.bias[co] : 0.f);
               if (a.relu) v = dh_relu(v);
               if (a.out_f32) reinterpret_cast<float*>(a.y)[m * a.Co + co] = v;
               else reinterpret_cast<bf16_t*>(a.y)[m * a.Co + co] = f2bf(v);

@@ -250,8 +250,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
       const size_t om = (size_t)m * a.ldm + co, orr = (size_t)m * a.Co + co;
       const bool full = (co + 4 <= a.Co) && ((a.Co & 3) == 0);
       if (a.bias) {
+        const float sc = dh_acc_scale(a);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) if (co + r < a.Co) v[r] += a.bias[co + r];
+        for (int r = 0; r < 4; ++r) if (co + r < a.Co) v[r] = fmaf(v[r], sc, a.bias[co + r]);
+      } else if (a.acc_exp) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] *= dh_acc_scale(a);
       }
       if (a.relu && co < a.relu_co) {
 #pragma unroll
@@ -270,6 +274,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
       } else {
         bf16_t* y = reinterpret_cast<bf16_t*>(a.y) + o;
         if (a.split_out) {                                // the next convolution's [hi | lo | hi] limb layout (split_infer.hip)
+          dh_range_check<4>(v, a.range_flag);
           uint2 hi, lo;
           dh_split4(v, hi, lo);
           *reinterpret_cast<uint2*>(y) = hi;
@@ -741,6 +746,29 @@ extern "C" int danhip_conv2d_fwd_ws(const danhip_conv_desc* d, const uint16_t* x
   ConvArgs a = fwd_args(d);
   a.x = x; a.w = wf_packed; a.bias = bias; a.mask = nullptr; a.resid = residual; a.y = y;
   a.relu = relu; a.out_f32 = (out_dtype == DANHIP_F32); a.accumulate = 0; a.split_out = (out_dtype == DANHIP_SPLIT3);
+  if (ws && ws_bytes >= danhip_conv2d_workspace_bytes(d, 0) && ws_bytes > 0) a.splitk_ws = reinterpret_cast<float*>(ws);
+  return launch_conv(a, (hipStream_t)stream);
+}
+
+// Split-operand evaluation (split_infer.hip): a forward call over the limb layout whose weights carry a power-of-two exponent.
+// v = acc * 2^acc_exp + bias (the caller folds the output map's exponent into acc_exp and the bias); out_dtype DANHIP_SPLIT3 stores v's limbs,
+// DANHIP_F32 v.  Limb values outside half's range raise the library's range flag (danhip_split_set_range_flag).
+extern "C" int danhip_conv2d_fwd_split(const danhip_conv_desc* d, const uint16_t* x3, const uint16_t* wf_packed, const float* bias, void* y,
+                                       int out_dtype, int relu, int32_t acc_exp, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  DH_REQUIRE(x3 && wf_packed && y, DANHIP_EINVAL, "conv2d_fwd_split: null pointer");
+  DH_REQUIRE(out_dtype == DANHIP_F32 || out_dtype == DANHIP_SPLIT3, DANHIP_EINVAL, "conv2d_fwd_split: out_dtype must be DANHIP_F32 or DANHIP_SPLIT3");
+  DH_REQUIRE(danhip_act_dtype() == DANHIP_F16, DANHIP_EINVAL, "conv2d_fwd_split: needs the fp16 build (IEEE-half limbs)");
+  DH_REQUIRE(acc_exp >= -126 && acc_exp <= 127, DANHIP_EINVAL, "conv2d_fwd_split: acc_exp = %d outside [-126, 127]", acc_exp);
+  if (out_dtype == DANHIP_SPLIT3) {
+    DH_REQUIRE(d->Cout % 8 == 0, DANHIP_EINVAL, "conv2d_fwd_split: DANHIP_SPLIT3 output needs Cout %% 8 == 0");
+    DH_REQUIRE((int64_t)d->N * d->Ho * d->Wo * 3 * d->Cout < (1ll << 31), DANHIP_EINVAL, "conv2d_fwd_split: the limb-layout output exceeds 2^31 elements");
+  }
+  ConvArgs a = fwd_args(d);
+  a.x = x3; a.w = wf_packed; a.bias = bias; a.y = y;
+  a.relu = relu; a.out_f32 = (out_dtype == DANHIP_F32); a.split_out = (out_dtype == DANHIP_SPLIT3);
+  a.acc_exp = acc_exp; a.range_flag = a.split_out ? danhip_split_range_flag() : nullptr;
   if (ws && ws_bytes >= danhip_conv2d_workspace_bytes(d, 0) && ws_bytes > 0) a.splitk_ws = reinterpret_cast<float*>(ws);
   return launch_conv(a, (hipStream_t)stream);
 }

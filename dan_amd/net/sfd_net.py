@@ -142,7 +142,7 @@ class VGG16Backbone(object):
             wf = self.vs.fuse((pre[0] + "kernel", pre[1] + "kernel"), axis=3)          # one block in the trainer's flat buffer, or None
             bf = self.vs.fuse((pre[0] + "bias", pre[1] + "bias"), axis=0)
             if wf is None or bf is None:
-                wf, bf = torch.cat([wl, wc], dim=3).contiguous(), torch.cat([bl, bc])
+                wf, bf = ops.cat_static([wl, wc], 3), ops.cat_static([bl, bc], 0)
             h = ops.conv2d(feat, wf, bf, stride=1, relu=False, out_f32=True)
             if ops.TRACE is not None and ncls > 2:           # the max-out decision of this level (tests: imposed on the oracle graph)
                 ops.TRACE.setdefault("maxout", {})[id(wc)] = h.detach()[..., 4:]
@@ -162,14 +162,19 @@ import contextlib
 @contextlib.contextmanager
 def precision_scope(precision):
     """precision "split": the fp32 inference path with its convolutions as split-operand products on the fp16 MFMA (ops.SPLIT_EVAL,
-    csrc/split_infer.hip) for the duration of the forward pass; anything else leaves the ops' context alone."""
+    csrc/split_infer.hip) for the duration of the forward pass, which then fails with ops.SplitRangeError if a map left the limbs' range
+    (ops.split_range_check; the flag is cleared on entry); anything else leaves the ops' context alone."""
     ctx = ops.context()
     prev = ctx.SPLIT_EVAL
     ctx.SPLIT_EVAL = precision == "split"
+    if precision == "split":
+        ops.split_range_reset()
     try:
         yield
     finally:
         ctx.SPLIT_EVAL = prev
+    if precision == "split":
+        ops.split_range_check()
 
 
 def prepare_input(img_u8_rgb, precision="act"):

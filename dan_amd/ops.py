@@ -655,18 +655,71 @@ def _conv2d_f32(x, w, b, stride, relu, residual, padding):
 # currency between ops (every non-convolution op is the fp32 path's); a convolution takes its input in the 3C half layout [hi | lo | hi]
 # — from the producing convolution's epilogue when it left one behind (`_dh_split3`), else converted here — and runs the fp16 build's
 # ordinary kernels over 3C input channels with weights [hi | hi | lo].
-_SPLIT_W = {}                # id(variable) -> (stamp, weakref, packed fp16 weights): evaluation weights are static, packed once
+#
+# Range.  Half limbs carry 22 significand bits only where both are normal numbers and hi is finite: |v| in [2^-3, 65504].  So every
+# operand is moved there by a power of two (exact, and undone exactly in fp32):
+#   - weights: per tensor, max|w * 2^e| in [2^13, 2^14) (_split_weight); the epilogue multiplies the accumulator by 2^-e;
+#   - maps: a limb map holds x * 2^-LIMB_EXP (the exponent rides on the limb view as `_dh_exp`), so maps of magnitude up to
+#     65504 * 2^LIMB_EXP = 262080 are carried; below 2^(LIMB_EXP-3) = 0.5 the lo limb is subnormal (absolute step 2^-22 of the value).
+# A value outside that range (or a NaN) raises a device flag in whichever kernel writes the limbs; split_range_check() reads it and raises
+# SplitRangeError (the models call it at the end of a "split" forward pass: net/sfd_net.py precision_scope).
+LIMB_EXP = 2
+_SPLIT_W = {}                # id(variable) -> (stamp, weakref, (packed fp16 weights, exponent)): evaluation weights are static, packed once
+_RANGE_FLAG = [None]         # the int32 device flag registered with both libraries (danhip_split_set_range_flag)
+
+
+class SplitRangeError(FloatingPointError):
+    """A split-operand evaluation met a value outside the limbs' range (|x| >= 65520 * 2^exponent of its map, or NaN): its result is void."""
+
+
+def _range_flag(device):
+    f = _RANGE_FLAG[0]
+    if f is None or f.device != device:
+        f = torch.zeros(1, dtype=torch.int32, device=device)
+        call("danhip_split_set_range_flag", ptr(f))
+        _lib.call_f16("danhip_split_set_range_flag", ptr(f))
+        _RANGE_FLAG[0] = f
+    return f
+
+
+def split_range_reset():
+    """Clears the range flag (asynchronously, on the current stream) - at the start of an evaluation, so that a flag left behind by an aborted
+    or unchecked call is not charged to it."""
+    f = _RANGE_FLAG[0]
+    if f is not None:
+        f.zero_()
+
+
+def split_range_check():
+    """Raises SplitRangeError when a limb writer met a value outside the limbs' range since the last check (and clears the flag).  Waits for
+    the current stream."""
+    f = _RANGE_FLAG[0]
+    if f is not None and int(f.item()):
+        f.zero_()
+        raise SplitRangeError("split-operand evaluation: a value outside the half limbs' range (|x| >= 65520 * 2^exponent of its map, or NaN); "
+                              "the result would be silently wrong - evaluate with precision='fp32'")
+
+
+def _weight_exp(w):
+    """e with max|w * 2^e| in [2^13, 2^14) (0 for an all-zero tensor): frexp's exponent, so exactly e - s for w * 2^s."""
+    import math
+    m = float(w.detach().abs().max())
+    if m == 0.0 or not math.isfinite(m):
+        return 0
+    return 14 - math.frexp(m)[1]
 
 
 def _split_weight(d3, w, cin):
-    """HWIO fp32 [kh, kw, cin, cout] -> the fp16 build's forward packing of [w_hi | w_hi | w_lo | 0] over d3.Cin = 3 cin (+ padding) channels."""
+    """HWIO fp32 [kh, kw, cin, cout] -> (the fp16 build's forward packing of [w_hi | w_hi | w_lo | 0] of w * 2^e over d3.Cin = 3 cin
+    (+ padding) channels, e)."""
     import weakref
     key = id(w)
     stamp = (WEIGHT_EPOCH, w._version, w.data_ptr(), d3.Cin)
     e = _SPLIT_W.get(key)
     if e is not None and e[0] == stamp and e[1]() is w:
         return e[2]
-    wd = w.detach().float()
+    ex = _weight_exp(w)
+    wd = w.detach().float() * 2.0 ** ex                     # (exact)
     hi = wd.half().float()
     lo = (wd - hi).half().float()
     w3 = torch.cat([hi, hi, lo], dim=2).contiguous()
@@ -674,17 +727,57 @@ def _split_weight(d3, w, cin):
     _lib.call_f16("danhip_conv_packed_dims", ctypes.byref(d3), 0, ctypes.byref(r), ctypes.byref(c))
     wf = torch.empty((r.value, c.value), dtype=torch.float16, device=w.device)
     _lib.call_f16("danhip_pack_conv_weight", ctypes.byref(d3), ptr(w3), 3 * cin, ptr(wf), None, stream())
-    if isinstance(w, torch.nn.Parameter) or hasattr(w, "_danhip_grad"):        # (a per-call concatenation of head kernels is not worth caching)
-        _SPLIT_W[key] = (stamp, weakref.ref(w, lambda _r, k=key: _SPLIT_W.pop(k, None)), wf)
-    return wf
+    if isinstance(w, torch.nn.Parameter) or hasattr(w, "_danhip_grad") or getattr(w, "_dh_static", False):
+        _SPLIT_W[key] = (stamp, weakref.ref(w, lambda _r, k=key: _SPLIT_W.pop(k, None)), (wf, ex))
+    return wf, ex
 
 
-def _limb_view(x3, C):
+_CAT_STATIC = {}
+
+
+def cat_static(parts, dim):
+    """torch.cat(parts, dim).contiguous(); during a split-operand evaluation without autograd the SAME tensor while no part changed, so that
+    its limb packing and weight exponent are computed once (_split_weight: a fresh concatenation per call would cost a host round trip
+    for its exponent)."""
+    if not (_CTX.SPLIT_EVAL and not torch.is_grad_enabled()):
+        return torch.cat(parts, dim).contiguous()
+    key = (tuple(id(p) for p in parts), dim)
+    stamp = (WEIGHT_EPOCH,) + tuple((p._version, p.data_ptr()) for p in parts)
+    e = _CAT_STATIC.get(key)
+    if e is not None and e[0] == stamp and all(r() is p for r, p in zip(e[2], parts)):
+        return e[1]
+    import weakref
+    t = torch.cat(parts, dim).contiguous()
+    t._dh_static = True
+    evict = lambda _r, k=key: _CAT_STATIC.pop(k, None)         # the entry goes when any of its parts does
+    _CAT_STATIC[key] = (stamp, t, tuple(weakref.ref(p, evict) for p in parts))
+    return t
+
+
+def _split_bias(b, exp):
+    """b * 2^-exp in fp32 (exact), cached like the packed weights for parameters."""
+    import weakref
+    if exp == 0:
+        return b.detach().float()
+    key = ("bias", id(b))
+    stamp = (WEIGHT_EPOCH, b._version, b.data_ptr(), exp)
+    e = _SPLIT_W.get(key)
+    if e is not None and e[0] == stamp and e[1]() is b:
+        return e[2]
+    bs = b.detach().float() * 2.0 ** -exp
+    if isinstance(b, torch.nn.Parameter) or hasattr(b, "_danhip_grad") or getattr(b, "_dh_static", False):
+        _SPLIT_W[key] = (stamp, weakref.ref(b, lambda _r, k=key: _SPLIT_W.pop(k, None)), bs)
+    return bs
+
+
+def _limb_view(x3, C, exp=0):
     """The tensor a split-mode convolution hands on: shape [.., C] (the nets read channel counts from it), IEEE half, a strided view of the
-    HI limbs of the [.., 3C] limb-layout map, which rides along as `_dh_split3`.  Consumers inside this module: conv2d and max_pool_2x2
-    take the limb layout as it is; every other op widens it to fp32 first (_f32_in)."""
+    HI limbs of the [.., 3C] limb-layout map, which rides along as `_dh_split3`, with its exponent `_dh_exp` (the limbs hold x * 2^-exp).
+    Consumers inside this module: conv2d, max_pool_2x2 and l2_normalize take the limb layout as it is; every other op widens it to fp32
+    first (_f32_in)."""
     v = x3[..., :C]
     v._dh_split3 = x3
+    v._dh_exp = exp
     return v
 
 
@@ -692,12 +785,16 @@ def _is_limbs(x):
     return getattr(x, "_dh_split3", None) is not None
 
 
+def _limb_exp(x):
+    return getattr(x, "_dh_exp", 0)
+
+
 def unsplit3(x):
-    """limb view -> contiguous fp32 NHWC (hi + lo)."""
+    """limb view -> contiguous fp32 NHWC (hi + lo) * 2^exp."""
     x3 = x._dh_split3
     C = x.shape[-1]
     y = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
-    call("danhip_unsplit3_f32", ptr(x3), ptr(y), y.numel() // C, C, x3.shape[-1], stream())
+    call("danhip_unsplit3_scaled_f32", ptr(x3), ptr(y), y.numel() // C, C, x3.shape[-1], _limb_exp(x), stream())
     return y
 
 
@@ -713,14 +810,16 @@ def _f32_in(*ts):
     return out[0] if len(out) == 1 else out
 
 
-def split3(x):
-    """fp32 NHWC [.., C] (or a limb view) -> IEEE-half [.., C3] = [hi | lo | hi | 0-padding], C3 = 3C rounded up to 8."""
+def split3(x, exp=0):
+    """fp32 NHWC [.., C] -> IEEE-half [.., C3] = [hi | lo | hi | 0-padding] of x * 2^-exp, C3 = 3C rounded up to 8 (a limb view: its own
+    map, whatever exp says)."""
     if _is_limbs(x):
         return x._dh_split3
+    _range_flag(x.device)
     C = x.shape[-1]
     C3 = (3 * C + 7) // 8 * 8
     x3 = torch.empty(x.shape[:-1] + (C3,), dtype=torch.float16, device=x.device)
-    call("danhip_split3_f32", ptr(x.contiguous()), ptr(x3), x.numel() // C, C, C3, 0, stream())
+    call("danhip_split3_f32", ptr(x.contiguous()), ptr(x3), x.numel() // C, C, C3, 0, -exp, stream())
     return x3
 
 
@@ -730,13 +829,14 @@ def _conv2d_split(x, w, b, stride, relu, residual, padding, want_f32=False):
     N, H, W, C = x.shape
     kh, kw, cin, cout = w.shape
     assert cin == C, "split conv: input channels must match the kernel"
+    _range_flag(x.device)
     if (C == 3 and cout == 64 and kh == 3 and kw == 3 and stride == 1 and padding == "same" and residual is None and not want_f32
             and not _is_limbs(x) and x.dtype == torch.float32):
         # the first layer: 27 products per output - an exact fp32 FMA chain written straight in the limb layout (split_infer.hip)
         y3 = torch.empty((N, H, W, 3 * cout), dtype=torch.float16, device=x.device)
         call("danhip_conv3x3_c3_f32_split3", ptr(x.contiguous()), ptr(w.detach().float().contiguous()), ptr(b.detach().float()) if b is not None else None,
-             ptr(y3), N, H, W, cout, int(relu), stream())
-        return _limb_view(y3, cout)
+             ptr(y3), N, H, W, cout, int(relu), -LIMB_EXP, stream())
+        return _limb_view(y3, cout, LIMB_EXP)
     # tensors of the 16-bit kernels are addressed with 32-bit element offsets: 3C input channels (the deformable GEMM's 27 x 256 at 160 x 160)
     # or 3 Cout output limbs can exceed 2^31 elements at batch 16 — such a call runs in batch slices
     C3 = (3 * C + 7) // 8 * 8
@@ -744,12 +844,13 @@ def _conv2d_split(x, w, b, stride, relu, residual, padding, want_f32=False):
     nmax = ((1 << 31) - 1) // max(H * W * C3, ho * wo * 3 * ((cout + 7) // 8 * 8))
     if N > nmax >= 1:
         residual = _f32_in(residual)
-        parts = [_conv2d_split(x[i:i + nmax] if not _is_limbs(x) else _limb_view(x._dh_split3[i:i + nmax], C), w, b, stride, relu,
+        parts = [_conv2d_split(x[i:i + nmax] if not _is_limbs(x) else _limb_view(x._dh_split3[i:i + nmax], C, _limb_exp(x)), w, b, stride, relu,
                                None if residual is None else residual[i:i + nmax], padding, want_f32=True) for i in range(0, N, nmax)]
         return torch.cat(parts, dim=0)
-    x3 = split3(x)
+    xe = _limb_exp(x) if _is_limbs(x) else LIMB_EXP
+    x3 = split3(x, xe)
     d3 = _desc(N, H, W, x3.shape[-1], cout, kh, kw, stride, padding == "valid")
-    wf = _split_weight(d3, w, cin)
+    wf, we = _split_weight(d3, w, cin)
     limbs = not want_f32 and residual is None and cout % 8 == 0 and N * d3.Ho * d3.Wo * 3 * cout < (1 << 31)
     if limbs:
         y = torch.empty((N, d3.Ho, d3.Wo, 3 * cout), dtype=torch.float16, device=x.device)
@@ -757,10 +858,11 @@ def _conv2d_split(x, w, b, stride, relu, residual, padding, want_f32=False):
         y = torch.empty((N, d3.Ho, d3.Wo, cout), dtype=torch.float32, device=x.device)
     n = _lib.lib_f16().danhip_conv2d_workspace_bytes(ctypes.byref(d3), 0) if -(-(N * d3.Ho * d3.Wo) // 128) * -(-cout // 128) <= 160 else 0
     ws = torch.empty(n, dtype=torch.uint8, device=x.device) if n else None
-    _lib.call_f16("danhip_conv2d_fwd_ws", ctypes.byref(d3), ptr(x3), ptr(wf), ptr(b.detach().float()) if b is not None else None, ptr(y),
-                  SPLIT3 if limbs else F32, int(relu), None, ptr(ws), n, stream())
+    ye = LIMB_EXP if limbs else 0                        # the output map's exponent, folded into the epilogue's power of two and the bias
+    _lib.call_f16("danhip_conv2d_fwd_split", ctypes.byref(d3), ptr(x3), ptr(wf), ptr(_split_bias(b, ye)) if b is not None else None, ptr(y),
+                  SPLIT3 if limbs else F32, int(relu), xe - we - ye, ptr(ws), n, stream())
     if limbs:
-        return _limb_view(y, cout)
+        return _limb_view(y, cout, LIMB_EXP)
     if residual is not None:                             # (added after the activation, as the 16-bit kernels' fused residual is)
         y.add_(_f32_in(residual))
     return y
@@ -880,7 +982,7 @@ def max_pool_2x2(x):
         if C % 8 == 0 and x._dh_split3.shape[-1] == 3 * C:
             y3 = torch.empty((N, (H + 1) // 2, (W + 1) // 2, 3 * C), dtype=torch.float16, device=x.device)
             call("danhip_maxpool2x2_split3", ptr(x._dh_split3), ptr(y3), N, H, W, C, stream())
-            return _limb_view(y3, C)
+            return _limb_view(y3, C, _limb_exp(x))
         x = unsplit3(x)
     if _f32_infer(x):
         N, H, W, C = x.shape
@@ -967,8 +1069,9 @@ def l2_normalize(x, gamma):
     if _is_limbs(x) and x.shape[-1] % 8 == 0 and x._dh_split3.shape[-1] == 3 * x.shape[-1]:
         C = x.shape[-1]                                      # split-operand mode: normalised on the limb layout, for the head convolution that follows
         y3 = torch.empty_like(x._dh_split3)
-        call("danhip_l2norm_split3", ptr(x._dh_split3), ptr(gamma.detach().float()), ptr(y3), y3.numel() // (3 * C), C, stream())
-        return _limb_view(y3, C)
+        _range_flag(x.device)
+        call("danhip_l2norm_split3", ptr(x._dh_split3), ptr(gamma.detach().float()), ptr(y3), y3.numel() // (3 * C), C, _limb_exp(x), 0, stream())
+        return _limb_view(y3, C)            # (|y| <= |gamma|: exponent 0)
     x = _f32_in(x)
     if _f32_infer(x):
         y = torch.empty_like(x)

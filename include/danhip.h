@@ -554,16 +554,28 @@ int danhip_comm_allgather(void* comm, const void* send, void* recv, int64_t send
  * map X3 = [hi | lo | hi] (hi = half(x), lo = half(x - hi)), C3 = 3C rounded up to 8; with weights W3 = [hi | hi | lo] along Cin the
  * ordinary 16-bit convolution of the fp16 build (libdanhip_f16.so: danhip_conv2d_fwd with Cin = C3, fp32 output) computes
  * hi.hi + lo.hi + hi.lo with exact products and fp32 accumulation.  These entry points are identical in both builds (always IEEE half).
- * relu != 0: max(x, 0) first.  danhip_maxpool2x2_split3: tf.layers.max_pooling2d([2,2],[2,2],'same') on the 3C layout (C % 8 == 0). */
-int danhip_split3_f32(const float* x, uint16_t* y3, int64_t M, int32_t C, int32_t C3, int relu, void* stream);
+ * relu != 0: max(x, 0) first.  danhip_maxpool2x2_split3: tf.layers.max_pooling2d([2,2],[2,2],'same') on the 3C layout (C % 8 == 0).
+ *
+ * Exponents: a limb map may hold x * 2^e instead of x (e = its exponent; exp / in_exp / out_exp below are such powers of two, applied exactly):
+ * the split path keeps every map and weight tensor inside half's range this way.  A limb writer that meets a value hi cannot hold (|x * 2^e|
+ * >= 65520, or NaN) sets the int32 device flag registered with danhip_split_set_range_flag (NULL = no flag); the caller reads it after the
+ * evaluation and fails - the limbs of such a value are inf / -inf, which the next convolution turns into NaN and a ReLU into 0. */
+int danhip_split_set_range_flag(int32_t* flag);
+int danhip_split3_f32(const float* x, uint16_t* y3, int64_t M, int32_t C, int32_t C3, int relu, int32_t exp, void* stream);
 int danhip_unsplit3_f32(const uint16_t* x3, float* y, int64_t M, int32_t C, int32_t C3, void* stream);
-int danhip_maxpool2x2_split3(const uint16_t* x3, uint16_t* y3, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+int danhip_unsplit3_scaled_f32(const uint16_t* x3, float* y, int64_t M, int32_t C, int32_t C3, int32_t exp, void* stream);     /* y = (hi + lo) * 2^exp */
+int danhip_maxpool2x2_split3(const uint16_t* x3, uint16_t* y3, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);     /* keeps the exponent */
 /* l2_normalize (net/sfd_net.py:68-79) on the limb layout -> limb layout; the arithmetic of unsplit -> danhip_l2norm_fwd_f32 -> split in one pass */
-int danhip_l2norm_split3(const uint16_t* x3, const float* gamma, uint16_t* y3, int64_t M, int32_t C, void* stream);
+int danhip_l2norm_split3(const uint16_t* x3, const float* gamma, uint16_t* y3, int64_t M, int32_t C, int32_t in_exp, int32_t out_exp, void* stream);
 /* The first layer of the split-operand path (conv1_1: 3x3 / stride 1 / 'same', x fp32 [N,H,W,3], w HWIO fp32 [3,3,3,64]) as an exact fp32 FMA chain,
- * stored straight in the next convolution's limb layout y3 [N,H,W,192]; bias may be NULL. */
+ * stored straight in the next convolution's limb layout y3 [N,H,W,192] with exponent out_exp; bias may be NULL. */
 int danhip_conv3x3_c3_f32_split3(const float* x, const float* w_hwio, const float* bias, uint16_t* y3, int32_t N, int32_t H, int32_t W, int32_t Cout,
-                                 int relu, void* stream);
+                                 int relu, int32_t out_exp, void* stream);
+/* fp16 build: danhip_conv2d_fwd_ws over a limb map x3 (Cin = C3) with limb weights that carry a power-of-two exponent: v = acc * 2^acc_exp + bias
+ * (acc_exp in [-126, 127]; the caller folds the output map's exponent into acc_exp and bias), relu?; out_dtype DANHIP_F32 stores v,
+ * DANHIP_SPLIT3 v's limbs (Cout % 8 == 0).  The bf16 build refuses it. */
+int danhip_conv2d_fwd_split(const danhip_conv_desc* d, const uint16_t* x3, const uint16_t* wf_packed, const float* bias, void* y, int out_dtype,
+                            int relu, int32_t acc_exp, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- fp32 inference path (csrc/f32_infer.hip): the evaluation graphs of eval_sfd.py:232-283 / eval_pb.py / eval_dan.py:299-404 with fp32
  * storage and arithmetic end to end, for the north-star tolerance "eval box outputs within 1e-4 of the reference".  NHWC fp32

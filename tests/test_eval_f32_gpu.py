@@ -53,7 +53,9 @@ def test_single_stage_eval_boxes_fp32(which, h, w, dev):
     single_stage_case(which, h, w, dev, "fp32")
 
 
-def single_stage_case(which, h, w, dev, precision):
+def single_stage_case(which, h, w, dev, precision, rescale=None):
+    """rescale(P, x) -> Params for the model under test (tests/test_split_ranges_gpu.py: a function-preserving rescaling); the oracle runs
+    the original P."""
     from dan_amd import synthetic
     from dan_amd.train_pb import PBModel
     from dan_amd.train_sfd import AnchorConfig, SFDModel
@@ -64,7 +66,7 @@ def single_stage_case(which, h, w, dev, precision):
     with torch.no_grad():
         loc_r, cls_r = ofwd(ON.Params(P.t), x)
     model = (SFDModel if which == "sfd" else PBModel)(device=dev)
-    model.vs.load_tf_named(P.t)
+    model.vs.load_tf_named(rescale(P, x).t if rescale is not None else P.t)
     model.precision = precision
     anchors = AnchorConfig(h, w, dev)
     with torch.no_grad():
@@ -88,7 +90,7 @@ def test_dan_eval_boxes_fp32(deform, h, w, dev):
     dan_eval_case(deform, h, w, dev)
 
 
-def dan_eval_case(deform, h, w, dev, logits16_tol=None, precision="fp32"):
+def dan_eval_case(deform, h, w, dev, logits16_tol=None, precision="fp32", rescale=None):
     """One image through the DAN evaluation graph on the fp32 path against the oracle (logits, stage-1 boxes, routed stage-2 boxes, scores);
     logits16_tol: also compare the 16-bit path's four logit tensors at that fraction of the reference scale (tests/test_size_1024_gpu.py)."""
     from dan_amd import synthetic
@@ -100,7 +102,7 @@ def dan_eval_case(deform, h, w, dev, logits16_tol=None, precision="fp32"):
     with torch.no_grad():
         (l1r, c1r), (l2r, c2r) = fwd(ON.Params(P.t), x)
     model = DANModel(device=dev, deform=deform)
-    model.vs.load_tf_named(P.t)
+    model.vs.load_tf_named(rescale(P, x).t if rescale is not None else P.t)
     anchors = dan_anchor_config(h, w, dev)
     if logits16_tol is not None:
         with torch.no_grad():
