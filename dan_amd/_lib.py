@@ -89,6 +89,7 @@ SIGNATURES = {
     "danhip_maxpool2x2_bwd": [P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
     "danhip_l2norm_fwd": [P, P, P, I64, I32, P],
     "danhip_l2norm_bwd": [P, P, P, P, P, I64, I32, ctypes.c_int, ctypes.c_int, P],
+    "danhip_l2norm_bwd_pool_scatter": [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_int, ctypes.c_int, ctypes.c_int, P],
     "danhip_preprocess_u8": [P, P, I64, P],
     "danhip_resize_bilinear_add_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, P],
     "danhip_resize_bilinear_add_bwd": [P, P, I32, I32, I32, I32, I32, I32, ctypes.c_int, P],

@@ -197,6 +197,28 @@ __global__ void l2norm_fwd_kernel(const bf16_t* __restrict__ x, const float* __r
   }
 }
 
+// The arithmetic of the L2-norm backward, shared by l2norm_bwd_kernel and the gradient-junction kernel below.  Which products fuse with the
+// following add is WRITTEN OUT (contraction off, explicit fmaf) - as the compiler had chosen for l2norm_bwd_kernel - because left to the
+// compiler the choice depends on the surrounding code, and the junction kernel must reproduce l2norm_bwd_kernel bit for bit.
+// One lane's share of the two per-pixel sums over its 8 channels ...
+__device__ __forceinline__ void l2_bwd_sums(const float* f, const float* g, const float* gm, float& ss, float& dot) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { ss = ss + f[i] * f[i]; dot = __builtin_fmaf(g[i] * gm[i], f[i], dot); }
+}
+// ... one element of dx (before anything already in the destination is added) ...
+__device__ __forceinline__ float l2_bwd_term(float f, float g, float gm, float inv, float k, int relu_mask) {
+#pragma clang fp contract(off)
+  float t = gm * inv * g - f * k;
+  if (relu_mask && !(f > 0.f)) t = 0.f;                      // x is a ReLU output: fold the producer's ReLU backward in
+  return t;
+}
+// ... and one pixel's contribution to dgamma
+__device__ __forceinline__ float l2_bwd_dgamma(float dg, float f, float g, float inv) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(g * f, inv, dg);
+}
+
 // dx = gamma*inv*dy - x*inv^3 * sum_c(dy*gamma*x)   (second term dropped where sum x^2 <= 1e-10: clamp inactive grad)
 // dgamma[c] += sum_pix dy*x*inv.  dx is ACCUMULATED into when `accumulate` (the tapped map also feeds the next conv block).
 template <int LPP, int VPL>
@@ -230,8 +252,7 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
 #pragma unroll
         for (int i = 0; i < 8; ++i) { f[v][i] = 0.f; g[v][i] = 0.f; }
       }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { ss += f[v][i] * f[v][i]; dot += g[v][i] * gm[v][i] * f[v][i]; }
+      l2_bwd_sums(f[v], g[v], gm[v], ss, dot);
     }
     ss = pixel_sum<LPP, VPL>(ss);
     dot = pixel_sum<LPP, VPL>(dot);
@@ -245,11 +266,10 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
         if (accumulate) unpack8(*reinterpret_cast<const uint4*>(dx + o), old);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          float t = gm[v][i] * inv * g[v][i] - f[v][i] * k;
-          if (relu_mask && !(f[v][i] > 0.f)) t = 0.f;          // x is a ReLU output: fold the producer's ReLU backward in
+          float t = l2_bwd_term(f[v][i], g[v][i], gm[v][i], inv, k, relu_mask);
           if (accumulate) t += old[i];
           r[i] = t;
-          dg[v][i] += g[v][i] * f[v][i] * inv;
+          dg[v][i] = l2_bwd_dgamma(dg[v][i], f[v][i], g[v][i], inv);
         }
         *reinterpret_cast<uint4*>(dx + o) = pack8(r);
       }
@@ -259,6 +279,100 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
   for (int v = 0; v < VPL; ++v)
 #pragma unroll
     for (int i = 0; i < 8; ++i) atomicAdd(sg + (v * LPP + l) * 8 + i, dg[v][i]);     // LDS atomics: PPW * waves adders per channel
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(dgamma + c, sg[c]);
+}
+
+// ------------------------------------------------------------------ gradient junction: L2-norm backward + max-pool scatter, dx written once
+// A tapped backbone map (conv3_3 / conv4_3 / conv5_3) receives the gradient of its detection head's L2 norm AND the scatter of the next
+// block's pooled gradient.  As two launches (l2norm_bwd_kernel, then maxpool_bwd_arg_kernel accumulating) that is 3 + 2.28 map-sized HBM
+// passes; here LPP lanes own one 2 x 2 pool window, read x and the head's dy of its four pixels, the pooled dy and the 2-bit codes once,
+// and store dx once: 3.28 passes.  The intermediate rounding of the two-launch form is reproduced - the first delivery (+ what the slot
+// held when `accumulate`) is rounded to 16 bits before the second is added - so dx is bit-identical to it; `pool_first` is the other
+// arrival order (scatter, then L2 norm).  dgamma: as l2norm_bwd_kernel (per-lane partial sums over other pixel sets, so equal up to fp32
+// summation order only).
+template <int LPP>
+__global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
+                                                                      const bf16_t* __restrict__ dy, const unsigned char* __restrict__ arg,
+                                                                      const bf16_t* __restrict__ pdy, bf16_t* __restrict__ dx,
+                                                                      float* __restrict__ dgamma, int N, int H, int W, int C, int Ho, int Wo,
+                                                                      int accumulate, int relu_mask, int pool_first) {
+  constexpr int PPW = 64 / LPP;                    // windows per wave
+  extern __shared__ float sg[];                    // [C] block-level dgamma accumulator
+  for (int c = threadIdx.x; c < C; c += blockDim.x) sg[c] = 0.f;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int sub = lane / LPP, l = lane % LPP;
+  const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const long nwaves = (long)gridDim.x * (blockDim.x >> 6);
+  const long NW = (long)N * Ho * Wo;
+  float gm[8], dg[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { gm[i] = gamma[l * 8 + i]; dg[i] = 0.f; }
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  for (long w0 = wave * PPW; w0 < NW; w0 += nwaves * PPW) {          // (wave-uniform trip count: the shuffles below need every lane)
+    const long win = w0 + sub;
+    const bool okw = win < NW;
+    long p = okw ? win : 0;
+    const int wo = (int)(p % Wo); p /= Wo;
+    const int ho = (int)(p % Ho);
+    const int n = (int)(p / Ho);
+    unsigned codes = 0;
+    uint4 gyr = z, xr[4], gr[4];
+    long off[4];
+    bool ok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int h = ho * 2 + (t >> 1), w = wo * 2 + (t & 1);
+      ok[t] = okw && h < H && w < W;
+      off[t] = (((long)n * H + h) * W + w) * C + l * 8;
+      xr[t] = ok[t] ? *reinterpret_cast<const uint4*>(x + off[t]) : z;
+      gr[t] = ok[t] ? *reinterpret_cast<const uint4*>(dy + off[t]) : z;
+    }
+    if (okw) {
+      codes = *reinterpret_cast<const unsigned short*>(arg + win * (C / 4) + l * 2);
+      gyr = *reinterpret_cast<const uint4*>(pdy + win * C + l * 8);
+    }
+    float gy[8];
+    unpack8(gyr, gy);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float f[8], g[8];
+      unpack8(xr[t], f);
+      unpack8(gr[t], g);
+      float ss = 0.f, dot = 0.f;
+      l2_bwd_sums(f, g, gm, ss, dot);
+      ss = pixel_sum<LPP, 1>(ss);
+      dot = pixel_sum<LPP, 1>(dot);
+      const float inv = rsqrtf(fmaxf(ss, 1e-10f));
+      const float k = (ss > 1e-10f) ? dot * inv * inv * inv : 0.f;
+      if (ok[t]) {
+        float a[8], b[8], old[8];
+        if (accumulate) unpack8(*reinterpret_cast<const uint4*>(dx + off[t]), old);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          b[i] = l2_bwd_term(f[i], g[i], gm[i], inv, k, relu_mask);
+          a[i] = (((codes >> (2 * i)) & 3u) == (unsigned)t) ? gy[i] : 0.f;
+          dg[i] = l2_bwd_dgamma(dg[i], f[i], g[i], inv);
+        }
+        if (!pool_first) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) { const float s = a[i]; a[i] = b[i]; b[i] = s; }
+        }
+        // a: the delivery that came first, b: the second one
+        if (accumulate) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) a[i] += old[i];
+        }
+        unpack8(pack8(a), a);                                // what the first launch would have stored
+#pragma unroll
+        for (int i = 0; i < 8; ++i) b[i] += a[i];
+        *reinterpret_cast<uint4*>(dx + off[t]) = pack8(b);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) atomicAdd(sg + l * 8 + i, dg[i]);
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(dgamma + c, sg[c]);
 }
@@ -545,6 +659,38 @@ extern "C" int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const ui
     case 512: hipLaunchKernelGGL((l2norm_bwd_kernel<64, 1>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
     default: hipLaunchKernelGGL((l2norm_bwd_kernel<64, 2>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
   }
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
+                                              uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate,
+                                              int relu_mask, int pool_first, void* stream) {
+  DH_REQUIRE(x && gamma && dy && arg && pooled_dy && dx && dgamma && N > 0 && H > 0 && W > 0, DANHIP_EINVAL, "l2norm_bwd_pool_scatter: bad arguments");
+  DH_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, DANHIP_EINVAL, "l2norm_bwd_pool_scatter: C=%d unsupported", C);
+  hipStream_t s = (hipStream_t)stream;
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const int lpp = C / 8, ppw = 64 / lpp;
+  // 512-thread blocks, two per CU at up to 128 registers a lane; at most 512 of them (C contended atomics each: see danhip_l2norm_bwd), sized
+  // so that every block walks the same number of windows
+  const long nwin = (long)N * Ho * Wo;
+  long blocks = (nwin + 8 * ppw - 1) / (8 * ppw);
+  if (blocks > 512) {
+    const long sweeps = (blocks + 511) / 512;
+    blocks = (blocks + sweeps - 1) / sweeps;
+  }
+  const dim3 g((unsigned)blocks), b(512);
+  const size_t lds = (size_t)C * sizeof(float);
+#define DH_JUNCTION(LPP) \
+  hipLaunchKernelGGL((l2norm_bwd_pool_scatter_kernel<LPP>), g, b, lds, s, x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, Ho, Wo, accumulate, \
+                     relu_mask, pool_first)
+  switch (C) {
+    case 64: DH_JUNCTION(8); break;
+    case 128: DH_JUNCTION(16); break;
+    case 256: DH_JUNCTION(32); break;
+    default: DH_JUNCTION(64); break;
+  }
+#undef DH_JUNCTION
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

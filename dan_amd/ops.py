@@ -33,6 +33,8 @@ class OpsContext(object):
       USE_SLOTS        False: activation gradients travel through autograd's own edges instead of the direct hand-off (GradSlot)
       USE_RELU_BITS    [DANHIP_RELU_BITS, 1]  0: ReLU masks read as 16-bit activations instead of bit masks
       USE_POOL_ARG     [DANHIP_POOL_ARG, 1]   0: max-pool backward re-reads the activation instead of the 2-bit arg-max codes
+      USE_JUNCTION     [DANHIP_JUNCTION, 1]   0: a map that feeds an L2 norm and a 2 x 2 max-pool gets their two gradients by two launches
+                       (l2norm_bwd, then maxpool2x2_bwd_arg accumulating) instead of one danhip_l2norm_bwd_pool_scatter (dx bit-identical)
       POOL_ONLY_TRAIN  [DANHIP_POOL_ONLY_TRAIN, 1]  0: the training forward of a conv whose only consumer is a fused pool still writes its map
       KEEP_DEFORM_COL  False: the deformable backward re-samples the im2col buffer as the reference does instead of keeping the forward's
       WGRAD_STREAM     [DANHIP_WGRAD_STREAM, 1]  0: weight gradients on the data gradients' stream
@@ -49,7 +51,7 @@ class OpsContext(object):
     and algorithmic bytes per convolution launch).
     Per-step state a trainer arms: GRAD_READY_HOOK (a parameter's gradient is final), LOSS_SCALE_DEV (device scalar of the dynamic loss
     scale), wgrad (the second backward stream: {"on", "side", "main", "keep"})."""
-    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "SPLIT_EVAL", "TRACE",
+    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "SPLIT_EVAL", "TRACE",
                  "PROFILE", "PROFILE_BYTES", "GRAD_READY_HOOK", "LOSS_SCALE_DEV", "wgrad")
 
     def __init__(self, **overrides):
@@ -58,6 +60,7 @@ class OpsContext(object):
         self.USE_SLOTS = True
         self.USE_RELU_BITS = env("DANHIP_RELU_BITS", "1") == "1"
         self.USE_POOL_ARG = env("DANHIP_POOL_ARG", "1") == "1"
+        self.USE_JUNCTION = env("DANHIP_JUNCTION", "1") == "1"
         self.POOL_ONLY_TRAIN = env("DANHIP_POOL_ONLY_TRAIN", "1") == "1"
         self.KEEP_DEFORM_COL = True
         self.WGRAD_STREAM = env("DANHIP_WGRAD_STREAM", "1") == "1"
@@ -304,16 +307,39 @@ class GradSlot(object):
     epilogue — and returns None to autograd.  The producer's backward then takes the buffer.  Consumers that do not
     know about slots (plain torch ops) still work: their gradient arrives through autograd and is merged in."""
 
-    __slots__ = ("shape", "dtype", "device", "is_relu", "buf", "count")
+    __slots__ = ("shape", "dtype", "device", "is_relu", "buf", "count", "taps", "pending")
 
     def __init__(self, t, is_relu, channels=None):
         self.shape, self.dtype, self.device, self.is_relu = t.shape, t.dtype, t.device, is_relu
         if channels is not None:                         # ragged Cout: the buffer carries the channel-padded gradient layout
             self.shape = tuple(t.shape[:-1]) + (channels,)
         self.buf, self.count = None, 0
+        self.taps, self.pending = 0, None                # gradient junction (USE_JUNCTION): see defer()
+
+    def defer(self, kind, alone, payload):
+        """A delivery of a gradient junction (kind: TAP_L2NORM / TAP_POOL) takes its turn - buffer and accumulate flag exactly as
+        target() hands them out - but is not launched yet: the partner's backward, if it is the next delivery, pops it and launches
+        both as one kernel.  Any other delivery, or the producer's take(), first launches it on its own (`alone(buffer, acc)`), so
+        the order of the roundings in the buffer never changes."""
+        buf, acc = self.target()
+        self.pending = (kind, acc, alone, payload)
+
+    def pop_pending(self, kind):
+        """-> (acc, payload) of the deferred delivery if it is of this kind (it is then the caller's to launch), else None."""
+        p = self.pending
+        if p is None or p[0] != kind:
+            return None
+        self.pending = None
+        return p[1], p[3]
+
+    def flush(self):
+        p, self.pending = self.pending, None
+        if p is not None:
+            p[2](self.buf, p[1])
 
     def target(self):
         """-> (buffer, accumulate flag) for the next delivery."""
+        self.flush()
         if self.buf is None:
             self.buf = torch.empty(self.shape, dtype=self.dtype, device=self.device)
             self.count = 0
@@ -322,6 +348,7 @@ class GradSlot(object):
         return self.buf, acc
 
     def take(self):
+        self.flush()
         b, n = self.buf, self.count
         self.buf, self.count = None, 0
         return b if n > 0 else None
@@ -330,6 +357,14 @@ class GradSlot(object):
 # USE_SLOTS = False (tests): every activation gradient travels through autograd's own edges instead of the direct hand-off, which gives
 # the parity tests a second, independent route through the same kernels (tests/test_grad_parity_gpu.py)
 # (USE_SLOTS: a field of OpsContext, see the top of the module)
+
+
+TAP_L2NORM, TAP_POOL = 1, 2      # GradSlot.taps: the consumers of a gradient junction, registered by their forward passes
+
+
+def _junction_ok(slot, dy, C):
+    """May this backward node of a tapped map (it receives no raw autograd gradient: dy) defer to / fuse with its partner?"""
+    return _CTX.USE_JUNCTION and slot.taps == (TAP_L2NORM | TAP_POOL) and dy is None and C in (64, 128, 256, 512)
 
 
 def _slot_of(t):
@@ -938,6 +973,8 @@ class _MaxPool(torch.autograd.Function):
         ctx.save_for_backward(x if arg is None else None)
         ctx.dims = (N, H, W, C)
         ctx.xslot, ctx.yslot = xslot, yslot
+        if xslot is not None and arg is not None:
+            xslot.taps |= TAP_POOL
         ctx.set_materialize_grads(False)
         return y
 
@@ -960,13 +997,32 @@ class _MaxPool(torch.autograd.Function):
         if ctx.xslot is not None:
             # the pooled maximum is > 0 exactly where its source is, so a gradient masked at the pooled level scatters to
             # an already ReLU-masked gradient; an unmasked one (autograd path) is masked by the producer's own backward
-            buf, acc = ctx.xslot.target() if _pool_deliver_ok(ctx, dy) else (None, 0)
+            xs = ctx.xslot
+            if ctx.arg is not None and _pool_deliver_ok(ctx, dy) and _junction_ok(xs, dy, C):
+                first = xs.pop_pending(TAP_L2NORM)
+                if first is not None:                    # the L2-norm branch is waiting: both gradients in one pass, dx written once
+                    buf, _ = xs.target()
+                    _junction(first[1], (ctx.arg, g, (N, H, W, C)), buf, first[0], xs.is_relu, 0)
+                elif xs.pending is None:                 # first of the two to arrive
+                    xs.defer(TAP_POOL, scatter, (ctx.arg, g, (N, H, W, C)))
+                else:
+                    scatter(*xs.target())
+                return None, None, None, None, None
+            buf, acc = xs.target() if _pool_deliver_ok(ctx, dy) else (None, 0)
             if buf is not None:
                 scatter(buf, acc)
                 return None, None, None, None, None
         dx = torch.empty((N, H, W, C), dtype=g.dtype, device=g.device)
         scatter(dx, 0)
         return dx, None, None, None, None
+
+
+def _junction(l2, pool, buf, acc, is_relu, pool_first):
+    """One launch for the two gradients of a tapped map (csrc/elementwise.hip, l2norm_bwd_pool_scatter_kernel)."""
+    x, gamma, g, dg = l2
+    arg, pg, (N, H, W, C) = pool
+    call("danhip_l2norm_bwd_pool_scatter", ptr(x), ptr(gamma), ptr(g), ptr(arg), ptr(pg), ptr(buf), ptr(dg), N, H, W, C, acc, 1 if is_relu else 0,
+         pool_first, stream())
 
 
 def _pool_deliver_ok(ctx, dy):
@@ -1040,6 +1096,8 @@ class _L2Norm(torch.autograd.Function):
         ctx.save_for_backward(x, gamma.detach())
         ctx.g_param = g_param
         ctx.xslot, ctx.yslot = xslot, yslot
+        if xslot is not None and x.dim() == 4:
+            xslot.taps |= TAP_L2NORM
         ctx.set_materialize_grads(False)
         return y
 
@@ -1056,8 +1114,18 @@ class _L2Norm(torch.autograd.Function):
         dg = sink if sink is not None else torch.zeros_like(gamma)
         xs = ctx.xslot
         if xs is not None:
-            buf, acc = xs.target()
-            call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc, 1 if xs.is_relu else 0, stream())
+            def alone(buf, acc):
+                call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc, 1 if xs.is_relu else 0, stream())
+
+            first = xs.pop_pending(TAP_POOL) if _junction_ok(xs, dy, x.shape[-1]) else None
+            if first is not None:                        # the pool's scatter is waiting: both gradients in one pass, dx written once
+                buf, _ = xs.target()
+                _junction((x, gamma, g, dg), first[1], buf, first[0], xs.is_relu, 1)
+            elif sink is not None and _junction_ok(xs, dy, x.shape[-1]) and xs.pending is None:
+                # first of the two to arrive.  (Only with a gradient sink: a dgamma handed back to autograd must be complete on return.)
+                xs.defer(TAP_L2NORM, alone, (x, gamma, g, dg))
+            else:
+                alone(*xs.target())
             dx = None
         else:
             dx = torch.empty_like(x)

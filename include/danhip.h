@@ -235,6 +235,13 @@ int danhip_maxpool2x2_bwd_arg(const uint8_t* arg, const uint16_t* dy, uint16_t* 
 int danhip_l2norm_fwd(const uint16_t* x, const float* gamma, uint16_t* y, int64_t M, int32_t C, void* stream);
 int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
                       int32_t C, int accumulate, int relu_mask, void* stream);
+/* Gradient junction of a tapped map x [N,H,W,C] (C in {64,128,256,512}) that feeds an L2 norm AND a 2 x 2 max-pool: one pass that equals
+ * danhip_l2norm_bwd(x, gamma, dy, dx, dgamma, N*H*W, C, accumulate, relu_mask) followed by danhip_maxpool2x2_bwd_arg(arg, pooled_dy, dx, ...,
+ * accumulate = 1) - or, with pool_first, the scatter (accumulate) followed by the L2 norm (accumulate = 1) - with dx written once.  dx is
+ * bit-identical to the two calls (the 16-bit rounding between them is reproduced); dgamma agrees up to fp32 summation order. */
+int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
+                                   uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate, int relu_mask,
+                                   int pool_first, void* stream);
 /* tf.image.resize_bilinear(up, size(lateral)) (TF1 legacy mapping src = dst*(in/out), align_corners=False) fused with the
  * LFPN lateral add: out = lateral + resize(up) (lateral may be NULL) — net/pb_net.py:209-217, net/danet.py:363-371.
  * up bf16 [N,Hi,Wi,C], lateral/out bf16 [N,Ho,Wo,C], C % 8 == 0.  bwd: d_up (=|+= if accumulate) from d_out (the lateral's
