@@ -112,6 +112,10 @@ SIGNATURES = {
     "danhip_maxpool3x3s2_same_bwd": [P, P, P, I32, I32, I32, I32, P],
     "danhip_resize_u8_linear": [P, I32, I32, P, I32, I32, I32, ctypes.c_double, ctypes.c_double, P],
     "danhip_bbox_vote": [P, P, I32, I32, ctypes.c_double, I32, P, P, P, ctypes.c_size_t, P],
+    "danhip_wider_quantize": [P, ctypes.c_int, P, P, I32, I32, I32, P, P, I32, I32, P, P],
+    "danhip_wider_score_range": [P, I64, P, P, ctypes.c_size_t, P],
+    "danhip_wider_eval": [P, P, I64, P, P, P, I64, P, I32, I32, I32, I32, ctypes.c_double, P, ctypes.c_size_t, P, P],
+    "danhip_wider_ap": [P, ctypes.c_size_t, P, I64, I32, I32, I32, P, P, P, P, P, P],
     "danhip_deform_sample_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
     "danhip_deform_sample_bwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
     "danhip_deform_conv_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
@@ -234,6 +238,10 @@ def _load(so_path, act_name):
         L.danhip_deform_conv_fused.restype = ctypes.c_int
         L.danhip_deform_conv_fused.argtypes = [I32] * 9
         L.danhip_bbox_vote_workspace_bytes.argtypes = [I32, I32]
+        L.danhip_wider_score_range_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_wider_score_range_workspace_bytes.argtypes = []
+        L.danhip_wider_eval_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_wider_eval_workspace_bytes.argtypes = [I32, I32, I32]
         for name, args in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the export is missing
             fn.restype = ctypes.c_int

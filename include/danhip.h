@@ -508,6 +508,60 @@ int danhip_bbox_vote(const double* det, const int32_t* counts, int32_t B, int32_
                      float* out, int32_t* num_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------------
+ * WIDER FACE evaluation (csrc/wider_eval_exact.hip; ABI 5): from the detections write_to_txt (eval_dan.py:243-261) would print to the
+ * easy / medium / hard average precision, on the device.  The protocol (dan_amd/wider_eval.py states it in full), IEEE double in the
+ * order written, no FMA contraction:
+ *   1 scores -> (score - lo) / (hi - lo), lo / hi over every detection of every image (hi == lo: all 0);
+ *   2 per image, detections by descending score, equal scores by ascending index;
+ *   3 per image and subset: count_face += kept boxes; an image without detections or without boxes adds nothing else (its detections are
+ *     NOT false positives); else each detection h takes the FIRST box j of maximum overlap (corners x + w, y + h; +1 convention); overlap
+ *     >= iou_threshold: j not kept -> proposal[h] = -1, else the first such h turns recall[j] to 1 (a later one stays a false positive);
+ *     pred_recall[h] = #{recall == 1} after h;
+ *   4 thresholds t = 0..T-1, thr = 1 - (t+1)/T, r = last detection with score >= thr: curve[s][t] += (#{h <= r: proposal == 1},
+ *     pred_recall[r]), summed over the images in integers;
+ *   5 precision = curve[.][1] / curve[.][0] (0 where curve[.][0] == 0), recall = curve[.][1] / count_face, mrec = [0, recall, 1],
+ *     mpre = [0, precision, 0] made non-increasing from the back, AP = sum over the steps of mrec, ascending; count_face == 0: AP = 0.
+ * Layouts.  Ground truth as CSR: gt_offsets int32 [I+1], gt_boxes double [G,4] rows (x, y, w, h), gt_keep uint8 [G] with bit s = kept in
+ * subset s (S <= DANHIP_WIDER_MAX_SUBSETS).  Detections for steps 1-5 as CSR too: det_offsets int32 [I+1], det_rows double [D,5] rows
+ * (x, y, w, h, score), at most DANHIP_WIDER_MAX_DETS rows per image; scores and boxes are finite, w, h >= 0.
+ *   danhip_wider_quantize    : the text route + compaction.  dets [B,Nmax,5] (in_dtype DANHIP_F32, or DANHIP_WIDER_F64 with quantize = 0),
+ *                              num int32 [B] (clamped to [0, Nmax]), image_index int32 [B].  quantize != 0: rows are fp32 (xmin, ymin, xmax,
+ *                              ymax, score); bw = xmax - xmin + 1, bh = ymax - ymin + 1 in fp32; a row stays iff ceil(bh) >= 10 and bw > 1
+ *                              and score > 0.01f; it becomes (floor xmin, floor ymin, ceil bw, ceil bh, rint(double(score) * 1000) / 1000) -
+ *                              the doubles that parsing write_to_txt's text gives.  quantize == 0: rows are (x, y, w, h, score), all kept.
+ *                              Image image_index[b]'s rows go, in order, to store_rows double [I,cap,5] at [image_index[b]], their number to
+ *                              store_counts int32 [I] (the caller fills it with -1 = "not added" first).  Nmax <= cap <= DANHIP_WIDER_MAX_DETS.
+ *   danhip_wider_score_range : step 1's lo, hi -> range double [2] (D == 0: 0, 0).  Two launches, no atomics.
+ *   danhip_wider_eval        : steps 1-4 for all S subsets in one launch (a persistent grid; one workgroup per image at a time; rank sort,
+ *                              boxes through LDS tiles, an LDS atomicMin per box, a block prefix sum, a binary search per threshold); the
+ *                              curve goes to the workspace as per-workgroup uint32 partial sums.  max_dets = the caller's bound on an image's
+ *                              detections: above DANHIP_WIDER_MAX_DETS -> DANHIP_EINVAL.  I <= 2^20, T <= DANHIP_WIDER_MAX_THRESHOLDS.
+ *   danhip_wider_ap          : the same workspace -> curves int64 [S,T,2], count_face int64 [S] (every box of gt_keep counts, whether or not
+ *                              its image had detections), precision / recall double [S,T], ap double [S] (step 5).  Two launches.
+ * status int32 [1] (zeroed by the caller, OR-ed by the kernels, read by the caller after the evaluation): DANHIP_WIDER_EINDEX an
+ * image_index outside [0, I) (that image is skipped), _ETWICE an image stored twice, _ECOUNT more detections in an image than the bound
+ * (skipped), _EOFFSETS offsets that leave [0, D] / [0, G] or decrease (skipped).  Nothing is ever written or read out of bounds.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_WIDER_MAX_DETS 2048
+#define DANHIP_WIDER_MAX_SUBSETS 8
+#define DANHIP_WIDER_MAX_THRESHOLDS 2046
+#define DANHIP_WIDER_F64 4
+#define DANHIP_WIDER_EINDEX 1
+#define DANHIP_WIDER_ETWICE 2
+#define DANHIP_WIDER_ECOUNT 4
+#define DANHIP_WIDER_EOFFSETS 8
+int danhip_wider_quantize(const void* dets, int in_dtype, const int32_t* num, const int32_t* image_index, int32_t B, int32_t Nmax,
+                          int32_t quantize, double* store_rows, int32_t* store_counts, int32_t I, int32_t cap, int32_t* status, void* stream);
+size_t danhip_wider_score_range_workspace_bytes(void);
+int danhip_wider_score_range(const double* det_rows, int64_t D, double* range, void* workspace, size_t workspace_bytes, void* stream);
+size_t danhip_wider_eval_workspace_bytes(int32_t I, int32_t S, int32_t T);
+int danhip_wider_eval(const int32_t* det_offsets, const double* det_rows, int64_t D, const int32_t* gt_offsets, const double* gt_boxes,
+                      const uint8_t* gt_keep, int64_t G, const double* range, int32_t I, int32_t S, int32_t T, int32_t max_dets,
+                      double iou_threshold, void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+int danhip_wider_ap(const void* workspace, size_t workspace_bytes, const uint8_t* gt_keep, int64_t G, int32_t I, int32_t S, int32_t T,
+                    int64_t* curves, int64_t* count_face, double* precision, double* recall, double* ap, void* stream);
+
+/* --------------------------------------------------------------------------------------------------
  * On-device training input pipeline: the image half of preprocess_for_train
  * (preprocessing/dan_preprocessing.py:677-733) in one pass from the decoded uint8 image [H,W,3] (RGB) to the network input
  * [out_h,out_w,8] (16-bit, B-mean, G-mean, R-mean, 0 x5):  [0,1] conversion -> distort_color (:98-150) -> crop window with
