@@ -190,7 +190,7 @@ __global__ void avgpool_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* 
 // thread owns 8 channels, strides rows; block-level reduction through LDS; one fp32 atomic per channel per block.
 __global__ void bn_reduce_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, const float* __restrict__ mean,
                                  const float* __restrict__ rstd, float* __restrict__ s1, float* __restrict__ s2, long M, int C) {
-  // s1[c] += sum a ; s2[c] += sum a*a            (b == nullptr: forward statistics)
+  // s1[c] += sum a ; s2[c] += sum a*a            (b == nullptr; the forward statistics use bn_stats_kernel)
   // s1[c] += sum a ; s2[c] += sum a*(b-mean)*rstd (backward: a = dy, b = x)
   const int cg = C / 8;
   const int g = threadIdx.x % cg, rsub = threadIdx.x / cg, tpr = blockDim.x / cg;
@@ -227,24 +227,55 @@ __global__ void bn_reduce_kernel(const bf16_t* __restrict__ a, const bf16_t* __r
   }
 }
 
-// mean/var from the sums; optionally updates the moving averages: moving = moving*m + batch*(1-m).  tf.layers.batch_normalization on a
-// 4-D input takes TF1's FUSED path, which normalises with the biased batch variance but feeds the moving average the Bessel-corrected
+// Forward statistics: per-channel sum(x) and sum(x^2) in DOUBLE (per-thread accumulators, LDS reduction, one double atomic per channel per
+// block).  The fp32 form lost the variance of a channel with |mean| >> std to the cancellation in E[x^2] - mean^2, and its 1024 serial
+// fp32 atomics per channel alone cost up to 3e-6 of E[x^2] (tests/test_hbm_layers_gpu.py, bn-C64-shifted-loops / bn-C2048-random).  The
+// square of a 16-bit value is exact in fp32, so every addend is exact and the sums carry 53 bits.
+__global__ void bn_stats_kernel(const bf16_t* __restrict__ x, double* __restrict__ s1, double* __restrict__ s2, long M, int C) {
+  const int cg = C / 8;
+  const int g = threadIdx.x % cg, rsub = threadIdx.x / cg, tpr = blockDim.x / cg;
+  double t1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (rsub < tpr) {
+    for (long r = (long)blockIdx.x * tpr + rsub; r < M; r += (long)gridDim.x * tpr) {
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(x + r * C + g * 8), f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { t1[i] += (double)f[i]; t2[i] += (double)(f[i] * f[i]); }
+    }
+  }
+  extern __shared__ double redd[];
+  double* r1 = redd;
+  double* r2 = redd + blockDim.x * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { r1[threadIdx.x * 8 + i] = t1[i]; r2[threadIdx.x * 8 + i] = t2[i]; }
+  __syncthreads();
+  if (threadIdx.x < cg) {
+    for (int k = 1; k < tpr; ++k)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { t1[i] += r1[(k * cg + threadIdx.x) * 8 + i]; t2[i] += r2[(k * cg + threadIdx.x) * 8 + i]; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { atomicAdd(s1 + threadIdx.x * 8 + i, t1[i]); atomicAdd(s2 + threadIdx.x * 8 + i, t2[i]); }
+  }
+}
+
+// mean/var from the (double) sums; optionally updates the moving averages: moving = moving*m + batch*(1-m).  tf.layers.batch_normalization
+// on a 4-D input takes TF1's FUSED path, which normalises with the biased batch variance but feeds the moving average the Bessel-corrected
 // one (var * M / (M - 1), nn_impl.fused_batch_norm's batch_var output)
-__global__ void bn_finalize_kernel(const float* __restrict__ s1, const float* __restrict__ s2, float* __restrict__ mean, float* __restrict__ rstd,
-                                   float* __restrict__ var_out, float* __restrict__ mov_mean, float* __restrict__ mov_var, float inv_m, float eps,
+__global__ void bn_finalize_kernel(const double* __restrict__ s1, const double* __restrict__ s2, float* __restrict__ mean, float* __restrict__ rstd,
+                                   float* __restrict__ var_out, float* __restrict__ mov_mean, float* __restrict__ mov_var, double m, float eps,
                                    float momentum, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float mu = s1[c] * inv_m;
-  float var = s2[c] * inv_m - mu * mu;
-  var = fmaxf(var, 0.f);
+  const double mud = s1[c] / m;
+  double vard = s2[c] / m - mud * mud;
+  vard = vard > 0.0 ? vard : 0.0;
+  const float mu = (float)mud, var = (float)vard;
   mean[c] = mu;
-  rstd[c] = rsqrtf(var + eps);
+  rstd[c] = (float)(1.0 / sqrt(vard + (double)eps));
   if (var_out) var_out[c] = var;
   if (mov_mean) mov_mean[c] = mov_mean[c] * momentum + mu * (1.f - momentum);
   if (mov_var) {
-    const float m = 1.f / inv_m;
-    const float unbiased = m > 1.f ? var * (m / (m - 1.f)) : var;
+    const float unbiased = m > 1.0 ? (float)(vard * (m / (m - 1.0))) : var;
     mov_var[c] = mov_var[c] * momentum + unbiased * (1.f - momentum);
   }
 }
@@ -424,25 +455,26 @@ int bn_check(const void* x, int64_t M, int32_t C, const char* what) {
 }
 }  // namespace
 
-/* workspace: 2*C floats (sums), zeroed inside */
+/* workspace: 2*C doubles = 4*C floats, 8-byte aligned (sum x, sum x^2), zeroed inside */
 extern "C" int danhip_batchnorm_fwd_train(const uint16_t* x, const float* gamma, const float* beta, uint16_t* y, float* save_mean,
                                           float* save_rstd, float* moving_mean, float* moving_var, int64_t M, int32_t C, float eps,
                                           float momentum, int relu, float* workspace, void* stream) {
   int rc = bn_check(x, M, C, "batchnorm_fwd_train");
   if (rc) return rc;
   DH_REQUIRE(gamma && beta && y && save_mean && save_rstd && workspace, DANHIP_EINVAL, "batchnorm_fwd_train: null pointer");
+  DH_REQUIRE(((uintptr_t)workspace & 7) == 0, DANHIP_EINVAL, "batchnorm_fwd_train: the workspace (2*C doubles) must be 8-byte aligned");
+  double* sums = reinterpret_cast<double*>(workspace);
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(workspace, 0, sizeof(float) * 2 * C, s) != hipSuccess) { danhip_set_error("batchnorm: memset failed"); return DANHIP_ELAUNCH; }
+  if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, s) != hipSuccess) { danhip_set_error("batchnorm: memset failed"); return DANHIP_ELAUNCH; }
   const int cg = C / 8;
   const int block = cg <= 256 ? 256 / cg * cg : cg;        // multiple of cg (>= 1 row per block)
   const int tpr = block / cg;
   int grid = (int)((M + tpr - 1) / tpr);
   if (grid > 1024) grid = 1024;
-  hipLaunchKernelGGL(bn_reduce_kernel, dim3(grid), dim3(block), sizeof(float) * block * 16, s, x, (const bf16_t*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, workspace, workspace + C, (long)M, C);
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(block), sizeof(double) * block * 16, s, x, sums, sums + C, (long)M, C);
   DH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, workspace, workspace + C, save_mean, save_rstd, (float*)nullptr,
-                     moving_mean, moving_var, 1.0f / (float)M, eps, momentum, C);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, sums, sums + C, save_mean, save_rstd, (float*)nullptr,
+                     moving_mean, moving_var, (double)M, eps, momentum, C);
   DH_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * cg)), dim3(256), 0, s, x, save_mean, save_rstd, gamma, beta, y, (long)M, C, relu);
   DH_LAUNCH_CHECK();

@@ -1814,7 +1814,7 @@ class _BatchNorm(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         rstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+        ws = torch.empty(2 * C, dtype=torch.float64, device=x.device)      # sum x, sum x^2 in double
         call("danhip_batchnorm_fwd_train", ptr(x), ptr(gamma.detach()), ptr(beta.detach()), ptr(y), ptr(mean), ptr(rstd), ptr(moving_mean), ptr(moving_var),
              M, C, float(eps), float(momentum), int(relu), ptr(ws), stream())
         ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else None)

@@ -275,7 +275,7 @@ int danhip_slice_deliver(const uint16_t* dy, int32_t ldy, int32_t c0, int32_t C,
                          int accumulate, int64_t M, void* stream);
 /* tf.layers.batch_normalization over the channel axis of [M,C] (M = N*H*W) — the conv_bn_relu / bn_relu / conv_bn surface of
  * net/sfd_net.py:91-119 (momentum 0.997, eps 1e-5).  Training: batch statistics (biased variance), optional moving-average
- * update, optional fused ReLU; workspace = 2*C floats.  Inference: caller passes mean and rstd = rsqrt(var + eps).
+ * update, optional fused ReLU; workspace = 2*C doubles (4*C floats, 8-byte aligned).  Inference: caller passes mean and rstd = rsqrt(var + eps).
  * Backward: dgamma, dbeta are overwritten. */
 int danhip_batchnorm_fwd_train(const uint16_t* x, const float* gamma, const float* beta, uint16_t* y, float* save_mean,
                                float* save_rstd, float* moving_mean, float* moving_var, int64_t M, int32_t C, float eps,

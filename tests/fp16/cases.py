@@ -69,6 +69,16 @@ def main():
     assert (y.float().cpu() - ref.detach()).abs().max().item() <= 2.0 ** -9 * ref.abs().max().item()
     assert (xd.grad.float().cpu() - xr.grad).abs().max().item() <= 2.0 ** -8 * xr.grad.abs().max().item() + 1e-3
     n += 1
+    # the same kernels against float64 references at sizes where their grid-stride loops take a second trip, per-element bounds and exact
+    # reductions (tests/hbm_layers.py: the bf16 suite's cases on a reduced list - one looping shape per kernel family plus the odd shape)
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hbm_layers as HL
+    t0 = time.time()
+    for cid in HL.FP16_IDS:
+        HL.run_case(cid, H, dev)
+    hbm_seconds = time.time() - t0
+    n += 1
 
     # S3FD forward against the oracle in fp16-storage emulation
     from dan_amd.train_sfd import AnchorConfig, SFDModel
@@ -148,7 +158,7 @@ def main():
     checked = GC.train_step_case("dan_deform", 1024, 1024, dev, H, grad_tol=0.05)
     assert checked > 100
     n += 1
-    print("FP16-OK", n, "groups; DAN-Deform losses", ["%.4f" % t for t in totals])
+    print("FP16-OK", n, "groups; DAN-Deform losses", ["%.4f" % t for t in totals], "; hbm_layers group: %d cases in %.0f s" % (len(HL.FP16_IDS), hbm_seconds))
 
 
 if __name__ == "__main__":
