@@ -35,6 +35,20 @@ class PackEntry(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("kh", "kw", "cin", "cin_real", "cout", "rows_f", "cols_f", "rows_b", "cols_b", "co8", "first_block", "pad_")]
 
 
+class JpegInfo(ctypes.Structure):
+    """danhip_jpeg_info"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "ncomp", "mode", "reason", "reserved")] + [("coef_count", ctypes.c_int64)]
+
+
+class JpegDesc(ctypes.Structure):
+    """danhip_jpeg_desc: one image of a decode batch (filled by danhip_jpeg_entropy_decode_batch, read by the two device launches)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "ncomp", "mode")] + \
+               [(n, ctypes.c_int32 * 3) for n in ("blocks_w", "blocks_h", "comp_w", "comp_h", "quant_index")] + \
+               [(n, ctypes.c_int32) for n in ("status", "idct_groups", "rgb_groups")] + [("reserved", ctypes.c_int32 * 2)] + \
+               [("coef_offset", ctypes.c_int64), ("coef_count", ctypes.c_int64), ("plane_offset", ctypes.c_int64 * 3),
+                ("out_offset", ctypes.c_int64), ("quant", (ctypes.c_uint16 * 64) * 4)]
+
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -148,6 +162,8 @@ SIGNATURES = {
     "danhip_comm_allreduce_sum": [P, P, I64, ctypes.c_int, P],
     "danhip_comm_reduce_scatter_sum": [P, P, P, I64, ctypes.c_int, P],
     "danhip_comm_allgather": [P, P, P, I64, ctypes.c_int, P],
+    "danhip_jpeg_entropy_decode_batch": [P, P, I32, I32, P, I64, P, P],
+    "danhip_jpeg_reconstruct_batch": [P, I64, P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
 }
@@ -242,6 +258,12 @@ def _load(so_path, act_name):
         L.danhip_wider_score_range_workspace_bytes.argtypes = []
         L.danhip_wider_eval_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_wider_eval_workspace_bytes.argtypes = [I32, I32, I32]
+        L.danhip_jpeg_inspect.restype = ctypes.c_int           # a reason code (>= 0), not a status
+        L.danhip_jpeg_inspect.argtypes = [P, I64, ctypes.POINTER(JpegInfo)]
+        L.danhip_jpeg_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_jpeg_workspace_bytes.argtypes = [P, I32]
+        L.danhip_jpeg_output_bytes.restype = I64
+        L.danhip_jpeg_output_bytes.argtypes = [P, I32]
         for name, args in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the export is missing
             fn.restype = ctypes.c_int

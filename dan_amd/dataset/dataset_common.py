@@ -247,7 +247,7 @@ def decode_record(payload, decode=True):
 
 # ---------------------------------------------------------------------------------------------------------- the batch generator
 def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_readers, num_preprocessing_threads, image_preprocessing_fn,
-                   anchor_encoder, num_epochs=None, is_training=True, seed=None):
+                   anchor_encoder, num_epochs=None, is_training=True, seed=None, decode_device=None):
     """dataset_common.py:33-193 as a generator of batches (lists of per-image entries; stacking is the caller's, the anchor encoder's
     outputs have fixed shapes).
 
@@ -256,7 +256,10 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
     shuffle buffer of capacity 64 * batch_size once it holds 8 * batch_size (:178-186) and an image whose boxes are all gone after
     the augmentation is skipped (keep_input, :182).  Evaluation entries: [image, filename, shape, output_shape, gbboxes] (:173-176) in
     file order, final batch allowed to be smaller (:188-193).
-    num_readers / num_preprocessing_threads are accepted for signature parity; reading is sequential here."""
+    num_readers / num_preprocessing_threads are accepted for signature parity; reading is sequential here.
+    decode_device: None = images are decoded on the host with Pillow, one by one (image_preprocessing_fn gets numpy uint8 [H,W,3]); a
+    device = the same records, selected by the same draws of the same generator, are decoded in groups of batch_size by
+    dataset.jpeg.JpegDecoder and image_preprocessing_fn gets uint8 [H,W,3] tensors on that device (what preprocess_for_train takes)."""
     if split_name not in data_splits_num:
         raise ValueError('split name %s was not recognized.' % split_name)
     files = sorted(glob.glob(file_pattern.format(split_name)))
@@ -275,8 +278,8 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
                     yield payload
             epoch += 1
 
-    def entry(payload):
-        item = decode_record(payload)
+    def entry(payload, item=None):
+        item = item if item is not None else decode_record(payload)
         g_bboxes = item['object/bbox']
         if is_training:
             # isinvalid_mask = tf.ones_like(g_invalid < 1) (:123): every annotated face is kept
@@ -294,22 +297,47 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
         return [image, item['filename'], item['shape'], output_shape, g_bboxes]
 
     capacity, min_after = 64 * batch_size, 8 * batch_size
-    buf, batch = [], []
-    for payload in records():
-        if is_training:
-            buf.append(payload)
-            if len(buf) < min(capacity, min_after + batch_size):
-                continue
-            payload = buf.pop(rng.randrange(len(buf)))
-        e = entry(payload)
-        if e is None:
-            continue
-        batch.append(e)
-        if len(batch) == batch_size:
-            yield batch
-            batch = []
-    while buf:                                                           # drain the shuffle buffer at the end of the last epoch
-        e = entry(buf.pop(rng.randrange(len(buf))))
+
+    def selected():
+        """The payloads in the order they are consumed: the shuffle-buffer walk (training) or file order (evaluation)."""
+        buf = []
+        for payload in records():
+            if is_training:
+                buf.append(payload)
+                if len(buf) < min(capacity, min_after + batch_size):
+                    continue
+                payload = buf.pop(rng.randrange(len(buf)))
+            yield payload
+        while buf:                                                       # drain the shuffle buffer at the end of the last epoch
+            yield buf.pop(rng.randrange(len(buf)))
+
+    def entries():
+        if decode_device is None:
+            for payload in selected():
+                yield entry(payload)
+            return
+        from .jpeg import JpegDecoder                                    # needs torch and libdanhip: only on this path
+        decoder = JpegDecoder(decode_device)
+        group = []
+
+        def flush():
+            images = decoder.decode_batch([it['image'] for it in group])
+            for it, image in zip(group, images):
+                it['image'] = image
+                yield entry(None, it)
+            del group[:]
+
+        for payload in selected():
+            group.append(decode_record(payload, decode=False))
+            if len(group) == batch_size:
+                for e in flush():
+                    yield e
+        if group:
+            for e in flush():
+                yield e
+
+    batch = []
+    for e in entries():
         if e is None:
             continue
         batch.append(e)

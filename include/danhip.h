@@ -574,6 +574,86 @@ int danhip_augment_preprocess(const uint8_t* src, int32_t H, int32_t W, int32_t 
                               int32_t win_y, int32_t win_x, int32_t win_h, int32_t win_w, int32_t flip, uint16_t* dst, int32_t out_h,
                               int32_t out_w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* --------------------------------------------------------------------------------------------------
+ * Baseline JPEG decode in front of the input pipeline (ABI version 6): a record's 'image/encoded' bytes -> the uint8 [H,W,3] RGB device
+ * image danhip_augment_preprocess reads, equal bit for bit to what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy upsampling) decodes.
+ * The serial half - marker parsing, Huffman decoding - runs on host threads (csrc/jpeg_entropy.cpp, no HIP call: these entry points work in
+ * a process without a GPU); dequantisation, the islow IDCT, fancy chroma upsampling and YCbCr -> RGB are two launches per BATCH
+ * (csrc/jpeg_exact.hip: jpeg_idct_kernel, jpeg_upsample_rgb_kernel), each a grid over (image, tile) through the descriptor table.
+ * Accepted: SOF0 / SOF1, 8 bit, Huffman, ONE interleaved scan; 1 component (grey), or 3 components Y Cb Cr with luma sampling 1x1 (4:4:4),
+ * 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1; up to 4 quantisation tables of 8 or 16 bit; any DHT set; DRI / RSTn; FF00 stuffing; JFIF
+ * APP0 / EXIF / COM segments skipped; 1x1 up to DANHIP_JPEG_MAX_DIM per side (checked before anything is sized from the header).
+ * Everything else is refused ON THE HOST with one of the reason codes below (the caller then decodes that image some other way); so is a
+ * block whose dequantised coefficients have a sum of squares above DANHIP_JPEG_MAX_BLOCK_ENERGY: up to there no 16-bit intermediate of
+ * libjpeg-turbo's vector IDCT wraps or saturates and no 32-bit one of the kernel overflows (an 8-bit image's own blocks stay below 1024^2
+ * plus their quantisation error), beyond it the two need not agree.
+ * Coefficients: int16, per image at coef_offset (a multiple of 64 elements), the component planes one after the other, a plane's 8x8
+ * blocks in raster order of the component's block grid (padded to whole MCUs), a block's 64 values de-zigzagged and COLUMN-major
+ * (element col*8 + row), so that a lane's one 16-byte load is a column of the first IDCT pass.
+ * No index the device uses is taken from the file: the kernels see descriptors that danhip_jpeg_entropy_decode_batch computed, and
+ * danhip_jpeg_reconstruct_batch re-derives every field from (width, height, mode) and checks it against the buffer sizes before a launch.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_MAX_DIM 16384
+#define DANHIP_JPEG_MAX_BLOCK_ENERGY 2073600      /* 1440^2 */
+#define DANHIP_JPEG_MAX_THREADS 16
+#define DANHIP_JPEG_GREY 0
+#define DANHIP_JPEG_444 1
+#define DANHIP_JPEG_422 2
+#define DANHIP_JPEG_420 3
+/* reason codes (info.reason, status_out[i], desc.status); 0 = decoded / decodable on the device */
+#define DANHIP_JPEG_ENOTJPEG 1       /* no SOI, or no marker where one must be */
+#define DANHIP_JPEG_ETRUNCATED 2     /* the stream ends (or meets a marker) before the header / the scan is complete */
+#define DANHIP_JPEG_EPROGRESSIVE 3   /* SOF2 */
+#define DANHIP_JPEG_EARITHMETIC 4    /* SOF9..SOF15 */
+#define DANHIP_JPEG_EPRECISION 5     /* sample precision other than 8 (12 bit) */
+#define DANHIP_JPEG_EMULTISCAN 6     /* a scan that does not carry every component */
+#define DANHIP_JPEG_ECOMPONENTS 7    /* 4 components (CMYK / YCCK), or any count but 1 and 3 */
+#define DANHIP_JPEG_EADOBE 8         /* Adobe APP14 with transform != 1 */
+#define DANHIP_JPEG_ERGBIDS 9        /* component ids 'R' 'G' 'B' */
+#define DANHIP_JPEG_ESAMPLING 10     /* sampling factors other than 4:4:4 / 4:2:2 / 4:2:0 (4:1:1, 4:4:0, ...) */
+#define DANHIP_JPEG_EHUFFMAN 11      /* a code no table holds, a run past coefficient 63, a DC value outside int16 */
+#define DANHIP_JPEG_ETOOLARGE 12     /* a side above DANHIP_JPEG_MAX_DIM */
+#define DANHIP_JPEG_ETABLE 13        /* a malformed or missing DQT / DHT, a malformed SOF / SOS / DRI */
+#define DANHIP_JPEG_EUNSUPPORTED 14  /* lossless / hierarchical frames, DNL, a second frame */
+#define DANHIP_JPEG_ERESTART 15      /* the expected RSTn is not where the restart interval puts it */
+#define DANHIP_JPEG_ECOEFRANGE 16    /* a block above DANHIP_JPEG_MAX_BLOCK_ENERGY */
+#define DANHIP_JPEG_ECAPACITY 17     /* coef_out has no room for this image */
+typedef struct danhip_jpeg_info {
+  int32_t width, height, ncomp, mode; /* mode: DANHIP_JPEG_GREY .. DANHIP_JPEG_420 */
+  int32_t reason, reserved;
+  int64_t coef_count;                 /* int16 elements danhip_jpeg_entropy_decode_batch writes for this image (0 when refused) */
+} danhip_jpeg_info;
+typedef struct danhip_jpeg_desc {
+  int32_t width, height, ncomp, mode;
+  int32_t blocks_w[3], blocks_h[3];   /* block grid of each component (whole MCUs); a plane's pitch is blocks_w * 8 bytes */
+  int32_t comp_w[3], comp_h[3];       /* the component's own size ceil(width * h / hmax) x ceil(height * v / vmax): the upsampling edges */
+  int32_t quant_index[3];
+  int32_t status;                     /* reason code; != 0: every count and offset below is 0, the image takes no device work */
+  int32_t idct_groups, rgb_groups;    /* workgroups of launch 1 (32 blocks each) and launch 2 (256 lanes x 8 pixels each) */
+  int32_t reserved[2];
+  int64_t coef_offset, coef_count;    /* int16 elements */
+  int64_t plane_offset[3];            /* bytes into the workspace, multiples of 256 */
+  int64_t out_offset;                 /* bytes into out, a multiple of 256; the image is width * height * 3 bytes there */
+  uint16_t quant[4][64];              /* row-major (de-zigzagged) */
+} danhip_jpeg_desc;
+/* header only: dims, mode, coefficient count, reason (also returned).  info may not be NULL. */
+int danhip_jpeg_inspect(const uint8_t* data, int64_t n, danhip_jpeg_info* info);
+/* B streams on min(threads, B, DANHIP_JPEG_MAX_THREADS) host threads (threads < 1: 1).  Image i's coefficients go to
+ * coef_out[descs_out[i].coef_offset ...]: offsets are handed out in order to the images whose header is accepted; an image that is refused
+ * later (a truncated scan, a bad code) keeps its slot and nothing outside that slot is written.  status_out[i] = reason code, 0 = decoded.
+ * The device offsets (planes, output, workgroup counts) are handed out afterwards to the decoded images alone.  Returns DANHIP_EINVAL for bad
+ * arguments, else DANHIP_OK whatever the per-image statuses are. */
+int danhip_jpeg_entropy_decode_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, int32_t threads, int16_t* coef_out,
+                                     int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out);
+size_t danhip_jpeg_workspace_bytes(const danhip_jpeg_desc* descs, int32_t B);     /* host descriptors; 0 when none is decodable or one is malformed */
+int64_t danhip_jpeg_output_bytes(const danhip_jpeg_desc* descs, int32_t B);       /* likewise */
+/* The two launches.  descs_host / descs_dev: the same B descriptors in host and in device memory (the host copy is validated and sizes the
+ * grids, the kernels read the device copy); coef_dev: int16 [coef_count], 16-byte aligned; out: uint8 [out_bytes].  launches (may be NULL)
+ * receives the number of kernels launched: 2, or 0 when no descriptor is decodable.  B <= 65535. */
+int danhip_jpeg_reconstruct_batch(const int16_t* coef_dev, int64_t coef_count, const danhip_jpeg_desc* descs_host,
+                                  const danhip_jpeg_desc* descs_dev, int32_t B, uint8_t* out, int64_t out_bytes, void* workspace,
+                                  size_t workspace_bytes, int32_t* launches, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange (csrc/comm.cpp): the all-reduce(sum) of tf_replicate_model_fn.py:633-645
  * (_compute_sum_on_device: add_n over the towers' gradients, after _scale_loss :615-631 put 1/N into every tower's loss) issued
