@@ -164,6 +164,9 @@ SIGNATURES = {
     "danhip_comm_allgather": [P, P, P, I64, ctypes.c_int, P],
     "danhip_jpeg_entropy_decode_batch": [P, P, I32, I32, P, I64, P, P],
     "danhip_jpeg_reconstruct_batch": [P, I64, P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
+    "danhip_jpeg_scan_prepare_batch": [P, P, I32, P, ctypes.c_size_t, I64, P, P],
+    "danhip_jpeg_huffman_decode_batch": [P, P, ctypes.c_size_t, I32, P, I64, P, P, P, ctypes.c_size_t, P, P, P],
+    "danhip_jpeg_entropy_emulate_batch": [P, ctypes.c_size_t, I32, P, P, I64, I32, P, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
 }
@@ -264,6 +267,12 @@ def _load(so_path, act_name):
         L.danhip_jpeg_workspace_bytes.argtypes = [P, I32]
         L.danhip_jpeg_output_bytes.restype = I64
         L.danhip_jpeg_output_bytes.argtypes = [P, I32]
+        L.danhip_jpeg_scan_staging_bytes.restype = ctypes.c_size_t
+        L.danhip_jpeg_scan_staging_bytes.argtypes = [P, P, I32]
+        L.danhip_jpeg_scan_device_bytes.restype = ctypes.c_size_t
+        L.danhip_jpeg_scan_device_bytes.argtypes = [P]
+        L.danhip_jpeg_scan_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_jpeg_scan_workspace_bytes.argtypes = [P]
         for name, args in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the export is missing
             fn.restype = ctypes.c_int

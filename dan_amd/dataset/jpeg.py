@@ -1,7 +1,11 @@
 """Baseline JPEG records decoded on the device, bit for bit what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy upsampling) gives.
 
-The serial half (markers, Huffman) runs in libdanhip on a few host threads (csrc/jpeg_entropy.cpp) and leaves quantised coefficients in a
-pinned buffer; dequantisation, inverse DCT, chroma upsampling and colour conversion are two launches per BATCH (csrc/jpeg_exact.hip).
+By default the serial half (markers, Huffman) runs in libdanhip on a few host threads (csrc/jpeg_entropy.cpp) and leaves quantised
+coefficients in a pinned buffer; dequantisation, inverse DCT, chroma upsampling and colour conversion are two launches per BATCH
+(csrc/jpeg_exact.hip).  With entropy="device" the host keeps the markers alone: one pass over the scan that looks for FF only, then the
+stuffed stream itself is uploaded and a self-synchronising parallel Huffman decoder (csrc/jpeg_huffman_exact.hip, a fixed number of
+launches per BATCH) writes the same coefficient buffer, bit for bit, on the device.  One copy of a status word per image comes back; an
+image the device stage gave up on goes through the host stage, which stays the authority (stats["entropy_retry"]).
 A stream the host validator refuses (progressive, CMYK, 4:1:1, truncated, ... - include/danhip.h lists the reason codes) never reaches
 the device: it goes through dataset_common.decode_image (Pillow) and is counted in `stats`.
 
@@ -27,12 +31,18 @@ def _align(v, a=256):
 
 
 class JpegDecoder(object):
-    def __init__(self, device, threads=4):
+    def __init__(self, device, threads=4, entropy="host"):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("JpegDecoder decodes on the GPU; use dataset_common.decode_image on the host")
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device', got %r" % (entropy,))
+        self.entropy = entropy
         self.threads = max(1, min(int(threads), MAX_THREADS))
-        self.stats = {"device": 0, "fallback": {}, "launches": 0, "entropy_seconds": 0.0}
+        # entropy_device: images whose coefficients came from the device; entropy_retry: images the device stage handed back to the host stage
+        self.stats = {"device": 0, "fallback": {}, "launches": 0, "entropy_seconds": 0.0, "entropy_device": 0, "entropy_retry": 0,
+                      "upload_bytes": 0, "huffman_ms": None}
+        self.time_huffman = False                         # diagnosis (tools/bench_jpeg_entropy.py): device-event time of the Huffman launches
         self._pinned = None                               # [descriptors | coefficients] of the batch in flight
         self._uploaded = None                             # event after the upload that reads _pinned
 
@@ -55,6 +65,18 @@ class JpegDecoder(object):
             return []
         if B > 65535:
             return self.decode_batch(datas[:65535]) + self.decode_batch(datas[65535:])
+        return self._decode_device_entropy(datas) if self.entropy == "device" else self._decode_host_entropy(datas)
+
+    def _fallback(self, datas, status, results):
+        for i in range(len(datas)):
+            if status[i] > 0:
+                name = REASONS.get(status[i], str(status[i]))
+                self.stats["fallback"][name] = self.stats["fallback"].get(name, 0) + 1
+                results[i] = torch.from_numpy(dataset_common.decode_image(datas[i]).copy()).to(self.device)
+        return results
+
+    def _decode_host_entropy(self, datas):
+        B = len(datas)
         L = lib()
         info = JpegInfo()
         capacity = 0
@@ -77,6 +99,7 @@ class JpegDecoder(object):
             with torch.cuda.device(self.device):
                 dev_in = torch.empty(head + 2 * capacity, dtype=torch.uint8, device=self.device)
                 dev_in.copy_(pinned[:head + 2 * capacity], non_blocking=True)          # descriptors and coefficients: one upload
+                self.stats["upload_bytes"] += head + 2 * capacity
                 self._uploaded = torch.cuda.Event()
                 self._uploaded.record()
                 ws_bytes = L.danhip_jpeg_workspace_bytes(descs, B)
@@ -91,9 +114,78 @@ class JpegDecoder(object):
                     d = descs[i]
                     results[i] = out[d.out_offset:d.out_offset + d.height * d.width * 3].view(d.height, d.width, 3)
                     self.stats["device"] += 1
-        for i in range(B):
-            if status[i] != 0:
-                name = REASONS.get(status[i], str(status[i]))
-                self.stats["fallback"][name] = self.stats["fallback"].get(name, 0) + 1
-                results[i] = torch.from_numpy(dataset_common.decode_image(datas[i]).copy()).to(self.device)
-        return results
+        return self._fallback(datas, status, results)
+
+    def _decode_device_entropy(self, datas):
+        """Markers on the host, Huffman on the device; the images whose device status is not 0 go through _decode_host_entropy."""
+        B = len(datas)
+        L = lib()
+        info = JpegInfo()
+        capacity = 0
+        for d in datas:
+            if L.danhip_jpeg_inspect(d, len(d), ctypes.byref(info)) == 0:
+                capacity += info.coef_count
+        ptrs = (ctypes.c_char_p * B)(*datas)
+        sizes = (ctypes.c_int64 * B)(*[len(d) for d in datas])
+        need = L.danhip_jpeg_scan_staging_bytes(ptrs, sizes, B)
+        head = _align(B * _DESC_BYTES)
+        pinned = self._staging(head + need)
+        base = pinned.data_ptr()
+        descs = (JpegDesc * B).from_address(base)
+        status = (ctypes.c_int32 * B)()
+        staging = ctypes.c_void_p(base + head)
+        t0 = time.perf_counter()
+        call("danhip_jpeg_scan_prepare_batch", ptrs, sizes, B, staging, need, capacity, descs, status)
+        self.stats["entropy_seconds"] += time.perf_counter() - t0
+        used = L.danhip_jpeg_scan_device_bytes(staging)
+        out_bytes = L.danhip_jpeg_output_bytes(descs, B)
+        results = [None] * B
+        retry = [i for i in range(B) if status[i] < 0]    # DANHIP_JPEG_HOSTONLY
+        if out_bytes > 0:                                 # at least one image for the device
+            with torch.cuda.device(self.device):
+                dev_in = torch.empty(head + used, dtype=torch.uint8, device=self.device)
+                dev_in.copy_(pinned[:head + used], non_blocking=True)                  # descriptors, tables and the stuffed streams: one upload
+                self.stats["upload_bytes"] += head + used
+                self._uploaded = torch.cuda.Event()
+                self._uploaded.record()
+                coef = torch.empty(max(capacity, 8), dtype=torch.int16, device=self.device)
+                hws_bytes = L.danhip_jpeg_scan_workspace_bytes(staging)
+                hws = torch.empty(hws_bytes, dtype=torch.uint8, device=self.device)
+                dev_status = torch.empty(B, dtype=torch.int32, device=self.device)
+                ws_bytes = L.danhip_jpeg_workspace_bytes(descs, B)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                out = torch.empty(out_bytes, dtype=torch.uint8, device=self.device)
+                n_huff, n_rec = ctypes.c_int32(0), ctypes.c_int32(0)
+                if self.time_huffman:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                call("danhip_jpeg_huffman_decode_batch", staging, ctypes.c_void_p(dev_in.data_ptr() + head), used, B, ptr(coef), capacity, descs,
+                     ptr(dev_in), ptr(hws), hws_bytes, ptr(dev_status), ctypes.byref(n_huff), stream())
+                if self.time_huffman:
+                    e1.record()
+                # the geometry comes from the header: the pair can be enqueued before any status is known
+                call("danhip_jpeg_reconstruct_batch", ptr(coef), capacity, descs, ptr(dev_in), B, ptr(out), out_bytes, ptr(ws), ws_bytes,
+                     ctypes.byref(n_rec), stream())
+                host_status = dev_status.cpu().tolist()   # the one synchronisation this path adds
+                if self.time_huffman:
+                    self.stats["huffman_ms"] = (self.stats["huffman_ms"] or 0.0) + e0.elapsed_time(e1)
+            self.coef = coef                              # the last batch's coefficient buffer (tests compare it with the host stage's)
+            self.stats["launches"] += n_huff.value + n_rec.value
+            for i in range(B):
+                if status[i] != 0:
+                    continue
+                if host_status[i] != 0:
+                    retry.append(i)
+                    continue
+                d = descs[i]
+                results[i] = out[d.out_offset:d.out_offset + d.height * d.width * 3].view(d.height, d.width, 3)
+                self.stats["device"] += 1
+                self.stats["entropy_device"] += 1
+        refused = [int(v) for v in status]
+        if retry:                                         # the host stage decodes them, or names the reason and they take the Pillow fallback
+            retry.sort()
+            self.stats["entropy_retry"] += len(retry)
+            again = self._decode_host_entropy([datas[i] for i in retry])
+            for i, image in zip(retry, again):
+                results[i] = image
+        return self._fallback(datas, refused, results)

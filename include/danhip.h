@@ -654,6 +654,55 @@ int danhip_jpeg_reconstruct_batch(const int16_t* coef_dev, int64_t coef_count, c
                                   const danhip_jpeg_desc* descs_dev, int32_t B, uint8_t* out, int64_t out_bytes, void* workspace,
                                   size_t workspace_bytes, int32_t* launches, void* stream);
 
+/* --------------------------------------------------------------------------------------------------
+ * Huffman decoding on the device (ABI version 7): the entropy stage of the decoder above as a self-synchronising parallel Huffman decoder
+ * (Klein & Wiseman; Weissenberger & Schmidt 2018), opt-in.  The host keeps what is O(header): danhip_jpeg_scan_prepare_batch parses the
+ * same headers, makes ONE pass over the scan that looks for FF only (the end of the scan, every RSTn when DRI is set), and packs into one
+ * staging buffer: per-image geometry, one SEGMENT per restart interval, one work item per SUBSEQUENCE (DANHIP_JPEG_SUBSEQ_BYTES stuffed
+ * bytes of a segment), the workgroups (at most DANHIP_JPEG_SUBSEQ_PER_GROUP items whose bytes fit one LDS window), the chunks of the DC
+ * prefix sum, the Huffman tables the scans use and the scan bytes, left stuffed.  The upload is that buffer: about the streams themselves.
+ * csrc/jpeg_huffman_exact.hip then writes the SAME int16 coefficient buffer danhip_jpeg_entropy_decode_batch writes, bit for bit, in
+ * 5 + DANHIP_JPEG_SYNC_ROUNDS launches whatever the data and the batch size are:
+ *   zero the buffer | speculate: every lane decodes its subsequence from state (block 0 of the MCU, coefficient 0) and the group iterates
+ *   "decode from the predecessor's exit" to its fixed point | DANHIP_JPEG_SYNC_ROUNDS times the same step, a group's first lane seeded with
+ *   the previous group's last exit of the launch before | write: prefix sum of completed blocks, one more decode from the final entry that
+ *   stores the coefficients and VERIFIES that it reproduces the stored exit | two launches of DC prefix sum, int16 range and block energy.
+ * A chain of exits that reproduces itself from a segment's true start is the serial decode; an image where it does not (more group seams in
+ * one restart interval than rounds can carry), or whose scan the device finds malformed, gets a non-zero word in status_dev and the caller
+ * hands it to danhip_jpeg_entropy_decode_batch, which stays the authority for reason codes.  The descriptors are the ones the host stage
+ * fills, so danhip_jpeg_reconstruct_batch runs unchanged behind either.
+ * No index the device uses leaves a range that the host derived from the header: stream reads are bounded by the segment and the staged
+ * window (zero bits beyond), coefficient writes by the segment's block count and the image's slot, loops by constants; no workgroup waits
+ * for another inside a launch; danhip_jpeg_huffman_decode_batch re-derives and checks every table of the staging buffer before a launch.
+ * danhip_jpeg_entropy_emulate_batch runs the same phases through the same routines (csrc/jpeg_huffman.h) on the host with checked indexing.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_SUBSEQ_BYTES 128
+#define DANHIP_JPEG_SUBSEQ_PER_GROUP 256
+#define DANHIP_JPEG_SYNC_ROUNDS 2
+#define DANHIP_JPEG_DEV_NOTSYNC 1     /* status bits of the device stage: the exits did not reach their fixed point */
+#define DANHIP_JPEG_DEV_ERROR 2       /* a bad code, run or category; bits beyond a segment; a DC value or a block energy out of range */
+#define DANHIP_JPEG_HOSTONLY (-1)     /* prepare status: a decodable header whose scan (1 GiB or more) is left to the host stage */
+/* upper bound of the staging bytes danhip_jpeg_scan_prepare_batch needs for these streams (headers only; 0: bad arguments) */
+size_t danhip_jpeg_scan_staging_bytes(const uint8_t* const* datas, const int64_t* sizes, int32_t B);
+/* status_out[i]: 0 = prepared for the device; a reason code = refused, with the code the host stage gives (a header it refuses, an RSTn
+ * that is missing or out of sequence); DANHIP_JPEG_HOSTONLY.  descs_out as danhip_jpeg_entropy_decode_batch fills them: coefficient slots in
+ * order to every accepted header, device offsets to the prepared images.  staging: 16-byte aligned. */
+int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, void* staging, size_t staging_bytes,
+                                   int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out);
+size_t danhip_jpeg_scan_device_bytes(const void* staging);       /* the prefix of a prepared staging buffer that the device needs */
+size_t danhip_jpeg_scan_workspace_bytes(const void* staging);    /* device workspace of danhip_jpeg_huffman_decode_batch */
+/* The launches.  staging_host / staging_dev: the same prepared bytes in host and device memory (the host copy is validated, the kernels
+ * read the device copy); coef_dev: int16 [coef_count], 16-byte aligned, written whole; status_dev: int32 [B] in device memory, 0 = decoded.
+ * launches (may be NULL) receives the number of kernels launched: 5 + DANHIP_JPEG_SYNC_ROUNDS, or 0 when no image is prepared. */
+int danhip_jpeg_huffman_decode_batch(const void* staging_host, const void* staging_dev, size_t staging_bytes, int32_t B, int16_t* coef_dev,
+                                     int64_t coef_count, const danhip_jpeg_desc* descs_host, const danhip_jpeg_desc* descs_dev,
+                                     void* workspace, size_t workspace_bytes, int32_t* status_dev, int32_t* launches, void* stream);
+/* The same phases on the host.  sync_rounds < 0: DANHIP_JPEG_SYNC_ROUNDS (another value is for tests of the verify step).  coef_out: the
+ * slots of the prepared images are written, nothing else.  range_errors (may be NULL) receives the number of indices the checked accessors
+ * refused: 0 unless the decoder is wrong. */
+int danhip_jpeg_entropy_emulate_batch(const void* staging, size_t staging_bytes, int32_t B, const danhip_jpeg_desc* descs, int16_t* coef_out,
+                                      int64_t coef_count, int32_t sync_rounds, int32_t* status_out, int64_t* range_errors);
+
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange (csrc/comm.cpp): the all-reduce(sum) of tf_replicate_model_fn.py:633-645
  * (_compute_sum_on_device: add_n over the towers' gradients, after _scale_loss :615-631 put 1/N into every tower's loss) issued
