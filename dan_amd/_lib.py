@@ -222,6 +222,8 @@ def _load(so_path, act_name):
         L.danhip_conv_kernel_label.argtypes = [DESC, ctypes.c_int]
         L.danhip_conv_wgrad_kernel_label.restype = ctypes.c_char_p
         L.danhip_conv_wgrad_kernel_label.argtypes = [DESC]
+        L.danhip_conv_last_launch_label.restype = ctypes.c_char_p
+        L.danhip_conv_last_launch_label.argtypes = []
         L.danhip_match_workspace_bytes.argtypes = [I32, I32]
         L.danhip_encode_anchors_batched_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_encode_anchors_batched_workspace_bytes.argtypes = [I32, I32, I32]

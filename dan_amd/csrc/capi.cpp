@@ -6,6 +6,8 @@
 #include <atomic>
 #include <mutex>
 
+#include <hip/hip_runtime.h>
+
 #include "../../include/danhip.h"
 
 static thread_local char g_err[512] = "";
@@ -64,6 +66,17 @@ int danhip_option(const char* name) {
   return o ? o->value.load(std::memory_order_relaxed) : 0;
 }
 extern "C" int danhip_get_option(const char* name) { return danhip_option(name); }
+
+// Compute units of the current device: asked once per process, 256 (the MI355X's count) when there is no device.
+int dh_cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
+    return v;
+  }();
+  return n;
+}
 extern "C" int danhip_set_option(const char* name, int value) {
   Opt* o = find_opt(name);
   if (!o) { danhip_set_error("set_option: unknown option '%s'", name ? name : "(null)"); return DANHIP_EINVAL; }

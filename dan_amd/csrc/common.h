@@ -34,6 +34,9 @@ int danhip_zero_async(void* ptr, size_t bytes, hipStream_t stream);
 // kernel-selection switch by name (capi.cpp: danhip_set_option / environment default)
 int danhip_option(const char* name);
 
+// Compute units of the current device (capi.cpp): asked once per process, 256 (the MI355X's count) when there is no device.
+int dh_cu_count();
+
 // ---------------------------------------------------------------- error plumbing (never throws across the ABI)
 void danhip_set_error(const char* fmt, ...);
 #define DH_REQUIRE(cond, code, ...)                  \

@@ -172,12 +172,7 @@ bool c8_eligible(const ConvArgs& a) {
          !a.accumulate && !a.out_f32 && a.H == a.Ho && a.W == a.Wo && a.Kpad >= 96 && (long)a.N * a.H * ((a.W + 15) / 16) < (1l << 31);
 }
 
-}  // namespace
-
-const char* danhip_conv_c8_label(const ConvArgs& a) { return c8_eligible(a) ? "conv3x3_c8_kernel<true>" : nullptr; }
-
-int danhip_launch_conv_c8(const ConvArgs& a, hipStream_t s) {
-  if (!c8_eligible(a)) return 1;
+int launch_c8(const ConvArgs& a, hipStream_t s) {
   C8Geom g{};
   g.units_x = (a.W + 15) / 16;
   g.units = (long)a.N * a.H * g.units_x;
@@ -189,4 +184,15 @@ int danhip_launch_conv_c8(const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((conv3x3_c8_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, a, g);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
+}
+
+}  // namespace
+
+ConvInstance conv_c8_select(const ConvArgs& a) {
+  ConvInstance i;
+  if (!c8_eligible(a)) return i;
+  i.label = "conv3x3_c8_kernel<true>";
+  i.launch = &launch_c8;
+  i.emits_bits = true;                                   // writes the ReLU bit mask beside its output (no pooled one)
+  return i;
 }

@@ -1,4 +1,4 @@
-// Shared between the convolution kernels (conv_igemm.hip: flat-M implicit GEMM; conv_halo.hip: halo-reuse 3x3).
+// Shared between the convolution kernels: their argument block, the epilogue helpers and the kernel selection (ConvInstance below).
 #pragma once
 #include "common.h"
 
@@ -82,11 +82,6 @@ __device__ __forceinline__ void dh_split4(const float v[4], uint2& hi, uint2& lo
 // the device flag the split-operand limb writers raise (split_infer.hip, danhip_split_set_range_flag; null = none)
 int* danhip_split_range_flag();
 
-// true when launch_conv's kernel for these args writes a.pool_y itself (conv_halo_c64.hip / conv_halo.hip forward tiles)
-bool danhip_conv_pool_fusable(const ConvArgs& a);
-bool danhip_conv_halo_pool_fusable(const ConvArgs& a);
-bool danhip_conv_c64_eligible(const ConvArgs& a);
-
 // packed max of two pairs of NON-NEGATIVE 16-bit floats (ReLU outputs): they order like signed 16-bit integers, and a
 // stray -0.0 (0x8000) is the smallest value.  One v_pk_max_i16.
 typedef __attribute__((ext_vector_type(2))) short s16x2;
@@ -162,38 +157,66 @@ __device__ __forceinline__ unsigned dh_or_rows(unsigned x) {
 // value of lane ^ 1 (DPP quad_perm [1,0,3,2])
 __device__ __forceinline__ unsigned dh_lane_xor1(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
 
-// Halo-reuse 3x3/stride-1 kernel (conv_halo.hip).  Returns DANHIP_OK when it launched, 1 when the shape is not
-// eligible (caller falls back to the flat-M kernel), negative on a launch error.
-int danhip_launch_conv_halo(const ConvArgs& a, hipStream_t s);
-bool danhip_conv_halo_takes_bits(const ConvArgs& a);
-bool danhip_conv_halo_emits_bits(const ConvArgs& a);   // the forward instance for these args writes ConvArgs::bits_out (and pool_bits_out with a fused pool)   // the data-gradient instance for these args reads ConvArgs::mask_bits
-const char* danhip_conv_halo_label(const ConvArgs& a, bool dgrad);
-// 64 -> 64 channel special case with register-resident weights (conv_halo_c64.hip); same return convention.
-int danhip_launch_conv_c64(const ConvArgs& a, hipStream_t s);
-const char* danhip_conv_c64_label(const ConvArgs& a, bool dgrad);   // kernel-instance label or nullptr when not eligible
+// ---- kernel selection.  Every convolution call picks ONE kernel instance, and everything that has to know which - the launch, the
+// kernel-label functions (danhip_conv_kernel_label / danhip_conv_wgrad_kernel_label: ops._prof_end and bench.py file measured time under
+// these names) and the capability queries ops.py asks before each layer - reads the same selection:
+//   * each family file exports one select(args) that returns its instance for these arguments or "not mine" (launch == nullptr); forward
+//     or data gradient is decided there, by the family's own rule, from the arguments;
+//   * select_conv (conv_igemm.hip) / select_wgrad (conv_wgrad.hip) hold the order of precedence between the families;
+//   * dh_run_instance is the one place that calls an instance's launch function (and remembers its label for
+//     danhip_conv_last_launch_label).
+// A label is the exact demangled kernel name the profiler reports, written once, next to the template instance it names.
+struct ConvInstance {
+  const char* label = nullptr;
+  int (*launch)(const ConvArgs&, hipStream_t) = nullptr;      // DANHIP_OK or a negative status
+  // what THIS call gets from the instance (the queries of danhip.h build representative arguments and read these):
+  bool fuses_pool = false;      // writes a.pool_y (2x2 max-pool of y) in its epilogue ...
+  bool skips_y = false;         // ... and then takes y == NULL (only the pooled map is stored)
+  bool emits_bits = false;      // forward: writes a.bits_out (and a.pool_bits_out beside a fused pool)
+  bool takes_bits = false;      // data gradient: reads the ReLU mask as a.mask_bits
+  bool folds_first = false;     // data gradient of conv1_2: folds conv1_1's weight gradient in (a.fuse_*), dx is never stored
+  explicit operator bool() const { return launch != nullptr; }
+};
+ConvInstance conv_c8_select(const ConvArgs& a);          // conv_c8.hip: 8 (= 3 padded) -> 64 channel first layer, store-bound
+ConvInstance conv_c64_select(const ConvArgs& a);         // conv_halo_c64.hip: 3x3, 64 -> 64 channels, register-resident weights (views too)
+ConvInstance conv_halo_select(const ConvArgs& a);        // conv_halo.hip: halo-reuse 3x3 / stride 1 on large dense maps
+ConvInstance conv_pointwise_select(const ConvArgs& a);   // conv_pointwise.hip: streaming GEMM, 1x1 (and tap forms) with 64-multiple channels
 
-// 8 (= 3 padded) -> 64 channel first layer, store-bound (conv_c8.hip); same return convention, forward only.
-int danhip_launch_conv_c8(const ConvArgs& a, hipStream_t s);
-const char* danhip_conv_c8_label(const ConvArgs& a);
+// A weight-gradient call (x / dy with pixel pitches ldx / ldy; ws: optional slab scratch) and its instance: conv_wgrad_rows.hip (3x3 'same',
+// row-streaming), conv_wgrad_pw.hip (1x1, 256 x 256 gradient tile), conv_wgrad_c8.hip (first layer), else the generic tiles of conv_wgrad.hip.
+struct WgradCall {
+  const danhip_conv_desc* d;
+  const bf16_t* x;
+  const bf16_t* dy;
+  float* dw;
+  float* db;
+  int cin_real, ldx, ldy;
+  void* ws;
+  size_t ws_bytes;
+};
+struct WgradInstance {
+  const char* label = nullptr;
+  int (*launch)(const WgradCall&, hipStream_t) = nullptr;
+  explicit operator bool() const { return launch != nullptr; }
+};
+WgradInstance wgrad_rows_select(const WgradCall& c);
+WgradInstance wgrad_pw_select(const WgradCall& c);
+WgradInstance wgrad_c8_select(const WgradCall& c);
+size_t wgrad_rows_workspace_bytes(const danhip_conv_desc* d);      // slab scratch the family's launch would use; 0 = none / not its shape
+size_t wgrad_pw_workspace_bytes(const danhip_conv_desc* d);
 
-// Pointwise (1x1 / stride 1) streaming GEMM (conv_pointwise.hip): forward (bias, ReLU) and data gradient (mask, accumulate); same return convention.
-int danhip_launch_conv_pointwise(const ConvArgs& a, hipStream_t s);
-const char* danhip_conv_pointwise_label(const ConvArgs& a, bool dgrad);
-
-// Row-streaming 3x3/stride-1 weight gradient with a register window of X fragments (conv_wgrad_rows.hip): DANHIP_OK when launched,
-// 1 when the shape is not eligible.
-const char* danhip_wgrad_rows_label(const danhip_conv_desc* d);
-// Pointwise (1x1 / stride 1) weight gradient, 256 x 256 gradient tile per workgroup (conv_wgrad_pw.hip); same return convention.
-const char* danhip_wgrad_pw_label(const danhip_conv_desc* d);
-int danhip_launch_wgrad_pw(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s,
-                           void* ws = nullptr, size_t ws_bytes = 0, int ldx = 0, int ldy = 0);      // ldx / ldy: pixel pitches (0 = dense)
-size_t danhip_wgrad_pw_workspace_bytes(const danhip_conv_desc* d);
-int danhip_launch_wgrad_rows(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s,
-                             void* ws = nullptr, size_t ws_bytes = 0, int ldx = 0, int ldy = 0);      // ldx / ldy: pixel pitches (0 = dense)
-size_t danhip_wgrad_rows_workspace_bytes(const danhip_conv_desc* d);
-// First-layer weight gradient (3x3 / stride 1, 8-channel image with <= 4 real channels, 64 outputs; conv_wgrad_c8.hip)
-bool danhip_wgrad_c8_eligible(const danhip_conv_desc* d, int cin_real, int ldx, int ldy);
-int danhip_launch_wgrad_c8(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s);
+// label of the instance most recently launched on this thread (danhip_conv_last_launch_label); "" before the first launch
+inline const char*& dh_last_launch_label() {
+  static thread_local const char* label = "";
+  return label;
+}
+// Launches the selected instance: its status, or 1 when the selection was "not mine".
+template <class Instance, class Args>
+int dh_run_instance(const Instance& inst, const Args& a, hipStream_t s) {
+  if (!inst) return 1;
+  dh_last_launch_label() = inst.label;
+  return inst.launch(a, s);
+}
 
 // Epilogue for one lane's 4 consecutive output channels [co, co+4) of output pixel m (shared by both kernels).
 __device__ __forceinline__ void conv_store4(const ConvArgs& a, float v[4], size_t m, int co) {

@@ -1051,14 +1051,10 @@ bool plan_halo(const ConvArgs& a, HaloPlan* p) {
   return true;
 }
 
-int cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
+// the lean epilogue (descriptor stores; the only one that takes y == NULL) of the NCU == 0 instances
+bool halo_lean(const ConvArgs& a) {
+  return !a.out_f32 && !a.split_out && !a.mask && !a.resid && (int64_t)a.N * a.H * a.W * a.Co * 2 <= (1ll << 31) &&
+         (!danhip_option("halo_general_epilogue") || !a.y);
 }
 
 template <int TH, int TW, int BN, int WM, int WN, int TPS, int NSW, bool DGRAD, int NCU = 0, bool POOL = false>
@@ -1079,8 +1075,7 @@ int launch_halo_cfg(const ConvArgs& a, hipStream_t s) {
   g.cch = (a.C + 63) / 64;
   g.crem = (a.C % 64) / 8;
   g.b2 = danhip_option("halo_b2");
-  g.fast = (NCU == 0 && !a.out_f32 && !a.split_out && !a.mask && !a.resid && (int64_t)a.N * a.H * a.W * a.Co * 2 <= (1ll << 31) &&
-            (!danhip_option("halo_general_epilogue") || !a.y)) ? 1 : 0;
+  g.fast = (NCU == 0 && halo_lean(a)) ? 1 : 0;
   if (!a.y && !(g.fast && POOL)) { danhip_set_error("conv_halo: y == NULL (pool-only) needs the pool-fusing instance with the lean epilogue"); return DANHIP_EINVAL; }
 #ifdef H_TRACE
   g.trace = h_trace_buffer();
@@ -1089,7 +1084,7 @@ int launch_halo_cfg(const ConvArgs& a, hipStream_t s) {
   g.div_txy = make_fastdiv(g.tiles_x * g.tiles_y);
   g.div_nb = make_fastdiv(g.NB);
   const long items = (long)g.sp_items * g.NB;
-  int G = cu_count();
+  int G = dh_cu_count();
   g.grouped = 0;
   if (items >= G && (G % 8) == 0 && ((G / 8) % g.NB) == 0 && g.NB > 1) g.grouped = 1;
   if (items < G) G = (int)items;
@@ -1098,76 +1093,59 @@ int launch_halo_cfg(const ConvArgs& a, hipStream_t s) {
   return DANHIP_OK;
 }
 
-// configurations: <TH, TW, BN, WM, WN, TPS, NSW>
-//   128-wide : 4x2 waves (64 px x 64 co each), 1 tap / step, 4-deep ring
-//    64-wide : 8x1 waves (32 px x 64 co each), 1 tap / step, 4-deep ring.  (The 3-taps-per-step form <.., 3, 3> is correct
-//              and kept instantiable, but measured slower on conv1_2 / conv2_1-dgrad: with one or two chunks per item the
-//              per-item epilogue + patch DMA land in one long mem phase.)
-template <bool DGRAD>
-int launch_halo(const ConvArgs& a, const HaloPlan& p, hipStream_t s) {
-  if (p.head) {
-    if (DGRAD) return 1;
-    return p.th == 8 ? launch_halo_cfg<8, 32, 64, 8, 1, 3, 3, false, 1>(a, s) : launch_halo_cfg<16, 16, 64, 8, 1, 3, 3, false, 1>(a, s);
-  }
-  if constexpr (!DGRAD) {
-    if (a.pool_y && p.bn == 128)                   // fused 2x2 max-pool epilogue (the 128-wide tiles own whole row pairs per wave)
-      return p.th == 8 ? launch_halo_cfg<8, 32, 128, 4, 2, 1, 4, false, 0, true>(a, s) : launch_halo_cfg<16, 16, 128, 4, 2, 1, 4, false, 0, true>(a, s);
-  }
-  if (p.th == 8) {
-    static const int exp3 = [] { const char* e = getenv("DANHIP_HALO_TPS3"); return e ? atoi(e) : 0; }();      // experiment: 64-wide tiles, 3 taps per phase
-    if (exp3 && !a.mask_bits && !a.bits_out && !a.pool_y && a.Co <= 512) return launch_halo_cfg<8, 32, 64, 8, 1, 3, 3, DGRAD>(a, s);
-    if (p.bn == 128) return launch_halo_cfg<8, 32, 128, 4, 2, 1, 4, DGRAD>(a, s);
-    return launch_halo_cfg<8, 32, 64, 8, 1, 1, 4, DGRAD>(a, s);
-  }
-  if (p.bn == 128) return launch_halo_cfg<16, 16, 128, 4, 2, 1, 4, DGRAD>(a, s);
-  return launch_halo_cfg<16, 16, 64, 8, 1, 1, 4, DGRAD>(a, s);
+template <int TH, int TW, int BN, int WM, int WN, int TPS, int NSW, bool DGRAD, int NCU = 0, bool POOL = false>
+ConvInstance halo_instance(const char* label) {
+  ConvInstance i;
+  i.label = label;
+  i.launch = &launch_halo_cfg<TH, TW, BN, WM, WN, TPS, NSW, DGRAD, NCU, POOL>;
+  return i;
 }
 
 }  // namespace
 
-// dgrad mode = no bias / relu / residual / fp32 output requested (the data-gradient call); forward otherwise.
-int danhip_launch_conv_halo(const ConvArgs& a, hipStream_t s) {
+// dgrad mode = no bias / relu / residual / fp32 or limb-layout output requested (the data-gradient call) and not a thin head; forward otherwise.
+ConvInstance conv_halo_select(const ConvArgs& a) {
   HaloPlan p;
-  if (!plan_halo(a, &p)) return 1;
+  if (!plan_halo(a, &p)) return {};
   const bool dgrad = !a.bias && !a.relu && !a.resid && !a.out_f32 && !a.split_out && !p.head;
-  if (a.split_out && p.head) return 1;
-  if (a.mask_bits && !(dgrad && p.bn == 128 && a.Co % 128 == 0)) return 1;
-  if (!dgrad && a.accumulate) return 1;
-  if (!dgrad && a.mask) return 1;
-  return dgrad ? launch_halo<true>(a, p, s) : launch_halo<false>(a, p, s);
-}
-
-bool danhip_conv_halo_emits_bits(const ConvArgs& a) {
-  HaloPlan p;
-  if (!plan_halo(a, &p) || p.head || p.bn != 128 || a.Co % 128 != 0) return false;
-  return a.bias && a.relu && !a.resid && !a.out_f32 && !a.mask && !a.accumulate;      // forward conv_relu
-}
-
-bool danhip_conv_halo_takes_bits(const ConvArgs& a) {
-  HaloPlan p;
-  if (!plan_halo(a, &p) || p.head || p.bn != 128 || a.Co % 128 != 0) return false;
-  return !a.bias && !a.relu && !a.resid && !a.out_f32;                 // the data-gradient form
-}
-
-bool danhip_conv_halo_pool_fusable(const ConvArgs& a) {
-  HaloPlan p;
-  if (!plan_halo(a, &p) || p.head || p.bn != 128 || a.Co % 64 != 0) return false;
-  return a.bias && a.relu && !a.resid && !a.out_f32 && !a.mask && !a.accumulate;      // forward conv_relu only
-}
-
-const char* danhip_conv_halo_label(const ConvArgs& a, bool dgrad) {
-  HaloPlan p;
-  if (!plan_halo(a, &p)) return nullptr;
+  if (a.split_out && p.head) return {};
+  if (a.mask_bits && !(dgrad && p.bn == 128 && a.Co % 128 == 0)) return {};
+  if (!dgrad && (a.accumulate || a.mask)) return {};
+  // configurations: <TH, TW, BN, WM, WN, TPS, NSW, DGRAD, NCU, POOL>
+  //   128-wide : 4x2 waves (64 px x 64 co each), 1 tap / step, 4-deep ring
+  //    64-wide : 8x1 waves (32 px x 64 co each), 1 tap / step, 4-deep ring.  (The 3-taps-per-step form <.., 3, 3> is correct
+  //              and kept instantiable, but measured slower on conv1_2 / conv2_1-dgrad: with one or two chunks per item the
+  //              per-item epilogue + patch DMA land in one long mem phase.)
+  static const int exp3 = [] { const char* e = getenv("DANHIP_HALO_TPS3"); return e ? atoi(e) : 0; }();      // experiment: 64-wide tiles, 3 taps per phase
+  const bool tps3 = exp3 && !a.mask_bits && !a.bits_out && !a.pool_y && a.Co <= 512;
+  const bool t8 = p.th == 8, bn128 = p.bn == 128;
+  // what the 128-wide tiles (which own whole row pairs per wave) can do for this call: decided here, before the instance is picked
+  const bool conv_relu = !dgrad && a.bias && a.relu && !a.resid && !a.out_f32;      // (a forward call carries no mask and does not accumulate)
+  const bool pool = bn128 && conv_relu && a.pool_y && a.Co % 64 == 0;               // fused 2x2 max-pool epilogue: the POOL instances
+  ConvInstance i;
   if (p.head) {
-    if (dgrad) return nullptr;
-    return p.th == 8 ? "conv3x3_halo_kernel<8, 32, 64, 8, 1, 3, 3, false, 1, false>" : "conv3x3_halo_kernel<16, 16, 64, 8, 1, 3, 3, false, 1, false>";
+    i = t8 ? halo_instance<8, 32, 64, 8, 1, 3, 3, false, 1>("conv3x3_halo_kernel<8, 32, 64, 8, 1, 3, 3, false, 1, false>")
+           : halo_instance<16, 16, 64, 8, 1, 3, 3, false, 1>("conv3x3_halo_kernel<16, 16, 64, 8, 1, 3, 3, false, 1, false>");
+  } else if (dgrad) {
+    if (t8 && tps3) i = halo_instance<8, 32, 64, 8, 1, 3, 3, true>("conv3x3_halo_kernel<8, 32, 64, 8, 1, 3, 3, true, 0, false>");
+    else if (t8) i = bn128 ? halo_instance<8, 32, 128, 4, 2, 1, 4, true>("conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, true, 0, false>")
+                           : halo_instance<8, 32, 64, 8, 1, 1, 4, true>("conv3x3_halo_kernel<8, 32, 64, 8, 1, 1, 4, true, 0, false>");
+    else i = bn128 ? halo_instance<16, 16, 128, 4, 2, 1, 4, true>("conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, true, 0, false>")
+                   : halo_instance<16, 16, 64, 8, 1, 1, 4, true>("conv3x3_halo_kernel<16, 16, 64, 8, 1, 1, 4, true, 0, false>");
+  } else {
+    if (pool)
+      i = t8 ? halo_instance<8, 32, 128, 4, 2, 1, 4, false, 0, true>("conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, false, 0, true>")
+             : halo_instance<16, 16, 128, 4, 2, 1, 4, false, 0, true>("conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, false, 0, true>");
+    else if (t8 && tps3) i = halo_instance<8, 32, 64, 8, 1, 3, 3, false>("conv3x3_halo_kernel<8, 32, 64, 8, 1, 3, 3, false, 0, false>");
+    else if (t8) i = bn128 ? halo_instance<8, 32, 128, 4, 2, 1, 4, false>("conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, false, 0, false>")
+                           : halo_instance<8, 32, 64, 8, 1, 1, 4, false>("conv3x3_halo_kernel<8, 32, 64, 8, 1, 1, 4, false, 0, false>");
+    else i = bn128 ? halo_instance<16, 16, 128, 4, 2, 1, 4, false>("conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, false, 0, false>")
+                   : halo_instance<16, 16, 64, 8, 1, 1, 4, false>("conv3x3_halo_kernel<16, 16, 64, 8, 1, 1, 4, false, 0, false>");
   }
-  if (!dgrad && a.pool_y && danhip_conv_halo_pool_fusable(a))
-    return p.th == 8 ? "conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, false, 0, true>" : "conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, false, 0, true>";
-  if (p.th == 8) {
-    if (p.bn == 128) return dgrad ? "conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, true, 0, false>" : "conv3x3_halo_kernel<8, 32, 128, 4, 2, 1, 4, false, 0, false>";
-    return dgrad ? "conv3x3_halo_kernel<8, 32, 64, 8, 1, 1, 4, true, 0, false>" : "conv3x3_halo_kernel<8, 32, 64, 8, 1, 1, 4, false, 0, false>";
-  }
-  if (p.bn == 128) return dgrad ? "conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, true, 0, false>" : "conv3x3_halo_kernel<16, 16, 128, 4, 2, 1, 4, false, 0, false>";
-  return dgrad ? "conv3x3_halo_kernel<16, 16, 64, 8, 1, 1, 4, true, 0, false>" : "conv3x3_halo_kernel<16, 16, 64, 8, 1, 1, 4, false, 0, false>";
+  const bool wide = !p.head && bn128;
+  i.emits_bits = wide && conv_relu && a.Co % 128 == 0;
+  i.takes_bits = wide && dgrad && a.Co % 128 == 0;
+  i.fuses_pool = pool;
+  i.skips_y = pool && halo_lean(a);
+  return i;
 }

@@ -450,16 +450,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   }
 }
 
-int c64_cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
-}
-
 bool c64_eligible(const ConvArgs& a) {
   if (!(a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dstride == 1 && a.pad_t == 1 && a.pad_l == 1)) return false;
   if (a.H != a.Ho || a.W != a.Wo || a.C != 64 || a.Co != 64 || a.out_f32 || a.Kpad != 576) return false;
@@ -484,30 +474,38 @@ int launch_c64(const ConvArgs& a, hipStream_t s) {
   g.sp_items = a.N * g.tiles_x * g.tiles_y;
   g.div_tx = make_fastdiv(g.tiles_x);
   g.div_txy = make_fastdiv(g.tiles_x * g.tiles_y);
-  int G = c64_cu_count();
+  int G = dh_cu_count();
   if (g.sp_items < G) G = g.sp_items;
   hipLaunchKernelGGL((conv3x3_c64_kernel<DGRAD, FUSE8>), dim3(G), dim3(512), LDS, s, a, g);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
 
-}  // namespace
-
-int danhip_launch_conv_c64(const ConvArgs& a, hipStream_t s) {
-  if (!c64_eligible(a)) return 1;
-  const bool dgrad = !a.bias && !a.relu && !a.resid;
-  if (!dgrad && (a.accumulate || a.mask || a.mask_bits)) return 1;
-  if (a.mask && a.mask_bits) return 1;              // one mask form per call (the bits share the 16-bit mask's LDS region)
-  if (a.fuse_dw) {                                  // conv1_1's weight gradient folded into this data gradient (bit-mask form, dense tensors)
-    if (!dgrad || !a.mask_bits || a.accumulate || a.strided() || !a.fuse_x8 || a.fuse_cin_real < 1 || a.fuse_cin_real > 4) return 1;
-    return launch_c64<true, true>(a, s);
-  }
-  return dgrad ? launch_c64<true>(a, s) : launch_c64<false>(a, s);
+template <bool DGRAD, bool FUSE8 = false>
+ConvInstance c64_instance(const char* label) {
+  ConvInstance i;
+  i.label = label;
+  i.launch = &launch_c64<DGRAD, FUSE8>;
+  return i;
 }
 
-bool danhip_conv_c64_eligible(const ConvArgs& a) { return c64_eligible(a); }
+}  // namespace
 
-const char* danhip_conv_c64_label(const ConvArgs& a, bool dgrad) {
-  if (!c64_eligible(a)) return nullptr;
-  return dgrad ? "conv3x3_c64_kernel<true>" : "conv3x3_c64_kernel<false>";
+// data gradient = no bias / relu / residual requested; forward otherwise
+ConvInstance conv_c64_select(const ConvArgs& a) {
+  if (!c64_eligible(a)) return {};
+  const bool dgrad = !a.bias && !a.relu && !a.resid;
+  if (!dgrad && (a.accumulate || a.mask || a.mask_bits)) return {};
+  if (a.mask && a.mask_bits) return {};             // one mask form per call (the bits share the 16-bit mask's LDS region)
+  ConvInstance i;
+  if (a.fuse_dw) {                                  // conv1_1's weight gradient folded into this data gradient (bit-mask form, dense tensors)
+    if (!dgrad || !a.mask_bits || a.accumulate || a.strided() || !a.fuse_x8 || a.fuse_cin_real < 1 || a.fuse_cin_real > 4) return {};
+    i = c64_instance<true, true>("conv3x3_c64_kernel<true, true>");
+    i.folds_first = a.W % 2 == 0 && (int64_t)a.N * a.H * a.W * 16 < (1ll << 31);
+  } else {
+    i = dgrad ? c64_instance<true>("conv3x3_c64_kernel<true>") : c64_instance<false>("conv3x3_c64_kernel<false>");
+  }
+  i.takes_bits = dgrad && a.W % 2 == 0;             // 2 KiB of bits per tile through LDS (pixel pairs)
+  i.fuses_pool = i.skips_y = !dgrad && a.pool_y && a.bias && a.relu && !a.resid;      // forward conv_relu: whole row pairs per wave
+  return i;
 }

@@ -361,17 +361,7 @@ inline int pick_bn(int co) {
   return 64;
 }
 
-int igemm_cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
-}
-
-// Pixel tile of the flat-M configuration launch_conv picks for these args.
+// Pixel tile of the flat-M configuration select_conv picks for these args.
 inline int igemm_bm(const ConvArgs& a) {
   const int bn = pick_bn(a.Co);
   if (bn == 128) return 128;
@@ -387,7 +377,7 @@ int plan_splitk(const ConvArgs& a, int* kt_per_split) {
   if (!danhip_option("splitk") || a.pool_y || a.bits_out || a.mask_bits) return 1;        // (DANHIP_SPLITK=0 / danhip_set_option: A/B)
   const int bm = igemm_bm(a), bn = pick_bn(a.Co);
   const long tiles = (long)cdiv(a.M, bm) * cdiv(a.Co, bn);
-  const int cus = igemm_cu_count();
+  const int cus = dh_cu_count();
   // thin heads (16-channel tiles): a workgroup's K tile is one or two MFMAs per wave, eight workgroups fit a CU and the serial K walk
   // (72-144 tiles at ~0.6 us) is pure latency: aim for 8 workgroups per CU instead of 2
   const long target = (bn == 16 ? 8l : 2l) * cus;
@@ -405,13 +395,14 @@ int plan_splitk(const ConvArgs& a, int* kt_per_split) {
 bool wants_splitk(const ConvArgs& a) {
   int per;
   if (plan_splitk(a, &per) < 2) return false;
-  return (long)cdiv(a.M, 128) * cdiv(a.Co, 128) * 2 <= igemm_cu_count();
+  return (long)cdiv(a.M, 128) * cdiv(a.Co, 128) * 2 <= dh_cu_count();
 }
 bool prefer_splitk(const ConvArgs& a) { return a.splitk_ws && wants_splitk(a); }
 
 template <int BM, int BN, int WN_WAVES>
-int launch_cfg(const ConvArgs& a0, bool fast, hipStream_t s) {
+int launch_cfg(const ConvArgs& a0, hipStream_t s) {
   ConvArgs a = a0;
+  const bool fast = (a.C % 64 == 0);
   int per = a.ktiles;
   const int splits = a.splitk_ws ? plan_splitk(a, &per) : 1;
   if (splits < 2) a.splitk_ws = nullptr;
@@ -437,39 +428,49 @@ int launch_cfg(const ConvArgs& a0, bool fast, hipStream_t s) {
   return DANHIP_OK;
 }
 
-int launch_conv(const ConvArgs& a, hipStream_t s) {
+// the flat-M instance of one tile: FAST (whole 64-channel K tiles) or not
+template <int BM, int BN, int WN_WAVES>
+ConvInstance flat_instance(const ConvArgs& a, const char* fast_label, const char* slow_label) {
+  ConvInstance i;
+  i.label = a.C % 64 == 0 ? fast_label : slow_label;
+  i.launch = &launch_cfg<BM, BN, WN_WAVES>;
+  return i;
+}
+
+int launch_direct_dgrad(const ConvArgs& a, hipStream_t s);
+
+// THE kernel selection of a forward / data-gradient call: the order of precedence between the families, once.
+ConvInstance select_conv(const ConvArgs& a) {
+  if (a.dstride & (a.dstride - 1)) {                   // data gradient of a stride that is no power of two: direct gather form
+    ConvInstance i;
+    i.label = "conv_bwd_data_strided_kernel";
+    i.launch = &launch_direct_dgrad;
+    return i;
+  }
   const bool view = a.strided();                       // channel-slice views / partial ReLU: the streaming GEMM and the flat-M kernel only
   const bool limbs = a.split_out != 0;                 // limb-layout output: the halo kernel's general epilogue or the flat-M kernel (conv_store4)
-  if (!view && !limbs) {
-    const int c8 = danhip_launch_conv_c8(a, s);        // conv1_1: 3 (padded to 8) -> 64 channels, bound by its output write
-    if (c8 <= 0) return c8;
+  if (!view && !limbs)
+    if (ConvInstance i = conv_c8_select(a)) return i;  // conv1_1: 3 (padded to 8) -> 64 channels, bound by its output write
+  if (!limbs)
+    if (ConvInstance i = conv_c64_select(a)) return i; // 3x3 / stride-1, 64 -> 64 channels: register-resident weights (views too)
+  if (!prefer_splitk(a)) {                             // (too few tiles for the persistent kernels: split K over workgroups instead)
+    if (!view)
+      if (ConvInstance i = conv_halo_select(a)) return i;        // 3x3 / stride-1 on large maps: halo-reuse kernel
+    if (!limbs)
+      if (ConvInstance i = conv_pointwise_select(a)) return i;   // 1x1 / stride-1 with 64-multiple channels: streaming GEMM
   }
-  if (!limbs) {
-    const int cr = danhip_launch_conv_c64(a, s);       // 3x3 / stride-1, 64 -> 64 channels: register-resident weights (views too)
-    if (cr <= 0) return cr;
-  }
-  const bool sk = prefer_splitk(a);                    // too few tiles for the persistent kernels: split K over workgroups instead
-  if (!sk) {
-    if (!view) {
-      const int hr = danhip_launch_conv_halo(a, s);    // 3x3 / stride-1 on large maps: halo-reuse kernel
-      if (hr <= 0) return hr;
-    }
-    if (!limbs) {
-      const int pr = danhip_launch_conv_pointwise(a, s); // 1x1 / stride-1 with 64-multiple channels: streaming GEMM
-      if (pr <= 0) return pr;
-    }
-  }
-  const bool fast = (a.C % 64 == 0);
   switch (pick_bn(a.Co)) {
-    case 128: return launch_cfg<128, 128, 2>(a, fast, s);
-    case 64: return launch_cfg<256, 64, 1>(a, fast, s);
-    case 32: return launch_cfg<256, 32, 1>(a, fast, s);
+    case 128: return flat_instance<128, 128, 2>(a, "conv_igemm_kernel<128, 128, 2, true>", "conv_igemm_kernel<128, 128, 2, false>");
+    case 64: return flat_instance<256, 64, 1>(a, "conv_igemm_kernel<256, 64, 1, true>", "conv_igemm_kernel<256, 64, 1, false>");
+    case 32: return flat_instance<256, 32, 1>(a, "conv_igemm_kernel<256, 32, 1, true>", "conv_igemm_kernel<256, 32, 1, false>");
     default:
       // thin heads on small maps: 256-pixel tiles would leave most CUs idle (20x20x16 images = 25 tiles) -> 64-pixel tiles
-      if (a.M <= 256 * 128) return launch_cfg<64, 16, 1>(a, fast, s);
-      return launch_cfg<256, 16, 1>(a, fast, s);
+      if (a.M <= 256 * 128) return flat_instance<64, 16, 1>(a, "conv_igemm_kernel<64, 16, 1, true>", "conv_igemm_kernel<64, 16, 1, false>");
+      return flat_instance<256, 16, 1>(a, "conv_igemm_kernel<256, 16, 1, true>", "conv_igemm_kernel<256, 16, 1, false>");
   }
 }
+
+int launch_conv(const ConvArgs& a, hipStream_t s) { return dh_run_instance(select_conv(a), a, s); }
 
 inline int same_pad_before(int in, int out, int k, int s) {
   int total = (out - 1) * s + k - in;
@@ -626,50 +627,45 @@ ConvArgs bwd_args(const danhip_conv_desc* d) {
   a.ldx = a.C; a.ldy = a.Co; a.ldm = a.Co; a.relu_co = a.Co;
   return a;
 }
+
+// Representative arguments of the calls the label function and the capability queries describe: the pointers only say "present".
+const float g_rep_bias = 1.f;
+bf16_t g_rep_act = 0;
+unsigned char g_rep_bits = 0;
+float g_rep_f32 = 0.f;
+ConvArgs rep_fwd_relu(const danhip_conv_desc* d) {     // forward conv_relu with bias
+  ConvArgs a = fwd_args(d);
+  a.bias = &g_rep_bias; a.relu = 1;
+  return a;
+}
+// conv_relu + 2x2 max-pool (danhip_conv2d_fwd_pool): the pool outputs stay in the arguments only where the selected instance pools in its
+// epilogue - the call runs without them otherwise, and the pool kernel after it.  Returns whether the instance fuses.
+bool keep_fused_pool(ConvArgs& a) {
+  const bool fused = select_conv(a).fuses_pool;
+  if (!fused) a.pool_y = nullptr, a.pool_arg_out = nullptr;
+  return fused;
+}
 }  // namespace
+
+extern "C" const char* danhip_conv_last_launch_label(void) { return dh_last_launch_label(); }
 
 // Label of the kernel instance a forward (which=0) / data-gradient (which=1) call of this descriptor launches
 // (matches the demangled name rocprofv3 reports) — used by bench.py to attribute measured time.
 extern "C" const char* danhip_conv_kernel_label(const danhip_conv_desc* d, int which) {
-  static bf16_t dummy_mask = 0;
   if (!d) return "";
-  const bool noscratch = (which & 16) != 0;            // which | 16: the call without a scratch buffer (danhip_conv2d_fwd / _bwd_data): no split-K
+  const bool scratch = (which & 16) == 0;              // which | 16: the call without a scratch buffer (danhip_conv2d_fwd / _bwd_data): no split-K
   which &= 15;
-  const bool masked = which == 5;                      // which = 5: data gradient with the producer's ReLU mask fused (never the library GEMM)
-  if (which == 5) which = 1;
-  const int cin = (which == 0 || which == 4) ? d->Cin : round_up(d->Cout, 8);
-  const int cout = (which == 0 || which == 4) ? d->Cout : d->Cin;
-  if (which == 1 && d->stride != 1 && (d->stride & (d->stride - 1)) != 0) return "conv_bwd_data_strided_kernel";
-  {
-    ConvArgs a = (which == 0 || which == 4) ? fwd_args(d) : bwd_args(d);
-    if (which == 4) {                                  // forward conv_relu with the fused 2x2 max-pool (danhip_conv2d_fwd_pool)
-      static const float one = 1.f;
-      static bf16_t dummy = 0;
-      a.bias = &one; a.relu = 1; a.pool_y = &dummy;
-      which = 0;
-    }
-    if (which == 0 && danhip_conv_c8_label(a)) return danhip_conv_c8_label(a);
-    const char* cl = danhip_conv_c64_label(a, which == 1);
-    if (cl) return cl;
-    const bool sk = !noscratch && wants_splitk(a);     // (callers that pass the scratch buffer: dan_amd.ops always does)
-    const char* hl = sk ? nullptr : danhip_conv_halo_label(a, which == 1);
-    if (hl) return hl;
-    if (which == 1) { if (masked) a.mask = &dummy_mask; }
-    else { static const float one = 1.f; a.bias = &one; }
-    const char* pl = sk ? nullptr : danhip_conv_pointwise_label(a, which == 1);
-    if (pl) return pl;
+  ConvArgs a;
+  if (which == 0 || which == 4) {
+    a = fwd_args(d);
+    a.bias = &g_rep_bias;
+    if (which == 4) { a.relu = 1; a.pool_y = &g_rep_act; keep_fused_pool(a); }      // danhip_conv2d_fwd_pool: conv_relu + 2x2 max-pool, fused where the kernel can
+  } else {
+    a = bwd_args(d);
+    if (which == 5) a.mask = &g_rep_act;               // which = 5: data gradient with the producer's ReLU mask fused
   }
-  const bool fast = cin % 64 == 0;
-  switch (pick_bn(cout)) {
-    case 128: return fast ? "conv_igemm_kernel<128, 128, 2, true>" : "conv_igemm_kernel<128, 128, 2, false>";
-    case 64: return fast ? "conv_igemm_kernel<256, 64, 1, true>" : "conv_igemm_kernel<256, 64, 1, false>";
-    case 32: return fast ? "conv_igemm_kernel<256, 32, 1, true>" : "conv_igemm_kernel<256, 32, 1, false>";
-    default: {
-      const long M = which == 0 ? (long)d->N * d->Ho * d->Wo : (long)d->N * d->H * d->W;
-      if (M <= 256 * 128) return fast ? "conv_igemm_kernel<64, 16, 1, true>" : "conv_igemm_kernel<64, 16, 1, false>";
-      return fast ? "conv_igemm_kernel<256, 16, 1, true>" : "conv_igemm_kernel<256, 16, 1, false>";
-    }
-  }
+  if (scratch && which != 4) a.splitk_ws = &g_rep_f32; // (callers that pass the scratch buffer: dan_amd.ops always does; the pool call takes none)
+  return select_conv(a).label;
 }
 
 extern "C" int danhip_pack_conv_weight(const danhip_conv_desc* d, const float* w_hwio, int32_t cin_real, uint16_t* wf_packed,
@@ -822,10 +818,8 @@ extern "C" int danhip_conv2d_fwd_concat2_supported(const danhip_conv_desc* d, in
   if (!d || check_desc(d) != DANHIP_OK) return 0;
   ConvArgs a{};
   if (!concat2_args(d, c1, src_pitch, a)) return 0;
-  static const float one = 1.f;
-  static bf16_t dummy = 0;
-  a.bias = &one; a.x2 = &dummy;
-  return danhip_conv_pointwise_label(a, false) != nullptr ? 1 : 0;
+  a.bias = &g_rep_bias; a.x2 = &g_rep_act;
+  return conv_pointwise_select(a) ? 1 : 0;
 }
 
 extern "C" int danhip_conv2d_fwd_concat2(const danhip_conv_desc* d, const uint16_t* x1, const uint16_t* x2, int32_t c1, int32_t src_pitch,
@@ -837,7 +831,7 @@ extern "C" int danhip_conv2d_fwd_concat2(const danhip_conv_desc* d, const uint16
   DH_REQUIRE(concat2_args(d, c1, src_pitch, a), DANHIP_EINVAL,
              "conv2d_fwd_concat2: 1x1 / stride 1 with 64-multiple channel counts (c1, Cin - c1, Cout) and an 8-multiple source pitch only");
   a.x = x1; a.x2 = x2; a.w = wf_packed; a.bias = bias; a.y = y; a.relu = relu ? 1 : 0;
-  rc = danhip_launch_conv_pointwise(a, (hipStream_t)stream);
+  rc = dh_run_instance(conv_pointwise_select(a), a, (hipStream_t)stream);
   DH_REQUIRE(rc <= 0, DANHIP_EINVAL, "conv2d_fwd_concat2: shape not taken by the streaming GEMM (ask danhip_conv2d_fwd_concat2_supported first)");
   return rc;
 }
@@ -863,11 +857,6 @@ extern "C" int danhip_conv2d_bwd_data_strided(const danhip_conv_desc* d, const u
 // conv_relu followed by tf.layers.max_pooling2d([2,2],[2,2],'same') (net/sfd_net.py:128-143: every VGG block): y as
 // danhip_conv2d_fwd(relu = 1) and pool_y = maxpool2x2(y) [N,ceil(Ho/2),ceil(Wo/2),Cout].  The 3x3 kernels that own whole row
 // pairs per wave pool their packed outputs in the epilogue (no second pass over y); other shapes run the pool kernel after.
-bool danhip_conv_pool_fusable(const ConvArgs& a) {
-  if (!(a.bias && a.relu && !a.resid && !a.out_f32 && !a.mask && !a.accumulate)) return false;
-  return danhip_conv_c64_eligible(a) || danhip_conv_halo_pool_fusable(a);
-}
-
 extern "C" int danhip_conv2d_fwd_pool(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* wf_packed, const float* bias, uint16_t* y,
                                       uint16_t* pool_y, void* stream) {
   return danhip_conv2d_fwd_pool_arg(d, x, wf_packed, bias, y, pool_y, nullptr, stream);
@@ -882,12 +871,11 @@ extern "C" int danhip_conv2d_fwd_pool_arg(const danhip_conv_desc* d, const uint1
   ConvArgs a = fwd_args(d);
   a.x = x; a.w = wf_packed; a.bias = bias; a.mask = nullptr; a.resid = nullptr; a.y = y;
   a.relu = 1; a.out_f32 = 0; a.accumulate = 0;
-  const bool fused = danhip_conv_pool_fusable(a);
+  a.pool_y = pool_y; a.pool_arg_out = pool_arg;
+  const bool fused = keep_fused_pool(a);
   // y == NULL: only the pooled map is wanted (inference: nothing reads the full-resolution activation of conv1_2 / conv2_2) - the fusing
   // kernels then skip its stores; ask danhip_conv2d_fwd_pool_only(d) first
   DH_REQUIRE(y || fused, DANHIP_EINVAL, "conv2d_fwd_pool: y == NULL needs a kernel that pools in its epilogue (danhip_conv2d_fwd_pool_only)");
-  a.pool_y = fused ? pool_y : nullptr;
-  a.pool_arg_out = fused ? pool_arg : nullptr;
   rc = launch_conv(a, (hipStream_t)stream);
   if (rc || fused) return rc;
   return danhip_maxpool2x2_fwd_arg(y, pool_y, pool_arg, d->N, d->Ho, d->Wo, d->Cout, stream);
@@ -895,13 +883,10 @@ extern "C" int danhip_conv2d_fwd_pool_arg(const danhip_conv_desc* d, const uint1
 
 extern "C" int danhip_conv2d_fwd_pool_only(const danhip_conv_desc* d) {
   if (!d || check_desc(d) != DANHIP_OK || d->Cout % 8 != 0) return 0;
-  static const float one = 1.f;
-  static bf16_t dummy = 0;
-  ConvArgs a = fwd_args(d);
-  a.bias = &one; a.relu = 1; a.pool_y = &dummy;
-  if (!danhip_conv_pool_fusable(a)) return 0;
-  if (danhip_conv_c64_eligible(a)) return 1;
-  return (int64_t)a.N * a.H * a.W * a.Co * 2 <= (1ll << 31) ? 1 : 0;      // (the halo kernel's lean epilogue: the one with descriptor stores)
+  ConvArgs a = rep_fwd_relu(d);
+  a.pool_y = &g_rep_act;
+  const ConvInstance i = select_conv(a);
+  return i.fuses_pool && i.skips_y ? 1 : 0;
 }
 
 // conv_relu (+ the fused 2x2 max-pool when pool_y is given) that ALSO writes the ReLU bit masks of its outputs (danhip_relu_bits layout) from
@@ -909,15 +894,11 @@ extern "C" int danhip_conv2d_fwd_pool_only(const danhip_conv_desc* d) {
 // 128-wide halo tiles do this: ask danhip_conv2d_fwd_emits_bits first.
 extern "C" int danhip_conv2d_fwd_emits_bits(const danhip_conv_desc* d, int with_pool) {
   if (!d || check_desc(d) != DANHIP_OK || d->Cout % 8 != 0) return 0;
-  static const float one = 1.f;
-  static bf16_t dummy = 0;
-  ConvArgs a = fwd_args(d);
-  a.bias = &one; a.relu = 1;
-  if (danhip_conv_c8_label(a)) return with_pool ? 0 : 1;        // the first layer's store-bound kernel writes the mask beside its output
-  if (danhip_conv_c64_eligible(a)) return 0;
-  if (!danhip_conv_halo_emits_bits(a)) return 0;
-  if (with_pool) { a.pool_y = &dummy; if (!danhip_conv_halo_pool_fusable(a)) return 0; }
-  return 1;
+  ConvArgs a = rep_fwd_relu(d);
+  a.bits_out = &g_rep_bits;
+  if (with_pool) { a.pool_y = &g_rep_act; a.pool_bits_out = &g_rep_bits; }
+  const ConvInstance i = select_conv(a);
+  return i.emits_bits && (!with_pool || i.fuses_pool) ? 1 : 0;
 }
 
 extern "C" int danhip_conv2d_fwd_relu_bits(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* wf_packed, const float* bias, uint16_t* y,
@@ -940,8 +921,8 @@ extern "C" int danhip_conv2d_fwd_relu_bits_arg(const danhip_conv_desc* d, const 
   a.x = x; a.w = wf_packed; a.bias = bias; a.mask = nullptr; a.resid = nullptr; a.y = y;
   a.relu = 1; a.out_f32 = 0; a.accumulate = 0;
   a.pool_y = pool_y; a.bits_out = y_bits; a.pool_bits_out = pool_bits; a.pool_arg_out = pool_y ? pool_arg : nullptr;
-  if (danhip_conv_c8_label(a)) return danhip_launch_conv_c8(a, (hipStream_t)stream);
-  return danhip_launch_conv_halo(a, (hipStream_t)stream);
+  const ConvInstance c8 = conv_c8_select(a);           // (straight to the two families that write bit masks)
+  return dh_run_instance(c8 ? c8 : conv_halo_select(a), a, (hipStream_t)stream);
 }
 
 namespace {
@@ -987,6 +968,17 @@ __global__ void conv_bwd_data_strided_kernel(const bf16_t* __restrict__ dy, cons
     }
   }
 }
+
+// a = bwd_args(d): the forward geometry back from the transposed call's
+int launch_direct_dgrad(const ConvArgs& a, hipStream_t s) {
+  const long total = (long)a.N * a.Ho * a.Wo * (a.Co / 8);
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(conv_bwd_data_strided_kernel, dim3(blocks), dim3(256), 0, s, a.x, a.w, a.mask, reinterpret_cast<bf16_t*>(a.y), a.N, a.Ho, a.Wo, a.Co,
+                     a.H, a.W, a.C, a.kh, a.kw, a.dstride, a.kh - 1 - a.pad_t, a.kw - 1 - a.pad_l, a.Kpad, a.accumulate);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
 }  // namespace
 
 extern "C" int danhip_conv2d_bwd_data(const danhip_conv_desc* d, const uint16_t* dy, const uint16_t* wb_packed, const uint16_t* relu_mask,
@@ -999,19 +991,6 @@ extern "C" int danhip_conv2d_bwd_data_ws(const danhip_conv_desc* d, const uint16
   int rc = check_desc(d);
   if (rc) return rc;
   DH_REQUIRE(dy && wb_packed && dx, DANHIP_EINVAL, "conv2d_bwd_data: null pointer");
-  const int co8 = round_up(d->Cout, 8);
-  const int taps = d->kh * d->kw;
-  const int pad_t = same_pad_before(d->H, d->Ho, d->kh, d->stride), pad_l = same_pad_before(d->W, d->Wo, d->kw, d->stride);
-  const bool pow2 = (d->stride & (d->stride - 1)) == 0;
-  if (d->stride != 1 && !pow2) {
-    const long total = (long)d->N * d->H * d->W * (d->Cin / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(conv_bwd_data_strided_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, wb_packed, relu_mask, dx, d->N,
-                       d->H, d->W, d->Cin, d->Ho, d->Wo, co8, d->kh, d->kw, d->stride, pad_t, pad_l, round_up(taps * co8, 64), accumulate);
-    DH_LAUNCH_CHECK();
-    return DANHIP_OK;
-  }
   ConvArgs a = bwd_args(d);
   a.x = dy; a.w = wb_packed; a.bias = nullptr; a.mask = relu_mask; a.resid = nullptr; a.y = dx;
   a.relu = 0; a.out_f32 = 0; a.accumulate = accumulate;
@@ -1023,18 +1002,17 @@ extern "C" int danhip_conv2d_bwd_data_takes_bits(const danhip_conv_desc* d) {
   if (!d || check_desc(d) != DANHIP_OK) return 0;
   if (d->stride != 1) return 0;
   ConvArgs a = bwd_args(d);
-  a.bias = nullptr; a.relu = 0; a.out_f32 = 0; a.resid = nullptr;
-  if (danhip_conv_c64_eligible(a)) return (a.W % 2 == 0) ? 1 : 0;   // 64 -> 64 register-resident kernel: 2 KiB of bits per tile through LDS (pixel pairs)
-  return danhip_conv_halo_takes_bits(a) ? 1 : 0;
+  a.mask_bits = &g_rep_bits;
+  return select_conv(a).takes_bits ? 1 : 0;
 }
 
 // conv1_2's data gradient with conv1_1's weight / bias gradient folded in (conv_halo_c64.hip FUSE8): dX is never written.
 extern "C" int danhip_conv2d_bwd_data_first_supported(const danhip_conv_desc* d) {
   if (!d || check_desc(d) != DANHIP_OK || d->stride != 1) return 0;
   ConvArgs a = bwd_args(d);
-  static const unsigned char dummy = 0;
-  a.mask_bits = &dummy;
-  return (danhip_conv_c64_eligible(a) && !a.strided() && a.W % 2 == 0 && (int64_t)a.N * a.H * a.W * 16 < (1ll << 31)) ? 1 : 0;
+  a.mask_bits = &g_rep_bits;
+  a.fuse_x8 = &g_rep_act; a.fuse_dw = &g_rep_f32; a.fuse_cin_real = 3;
+  return select_conv(a).folds_first ? 1 : 0;
 }
 
 extern "C" int danhip_conv2d_bwd_data_bits_first(const danhip_conv_desc* d, const uint16_t* dy, const uint16_t* wb_packed, const uint8_t* relu_bits,
@@ -1049,7 +1027,7 @@ extern "C" int danhip_conv2d_bwd_data_bits_first(const danhip_conv_desc* d, cons
   a.x = dy; a.w = wb_packed; a.bias = nullptr; a.mask = nullptr; a.mask_bits = relu_bits; a.resid = nullptr; a.y = nullptr;
   a.relu = 0; a.out_f32 = 0; a.accumulate = 0;
   a.fuse_x8 = x8; a.fuse_dw = dw8; a.fuse_db = db8; a.fuse_cin_real = cin_real;
-  rc = danhip_launch_conv_c64(a, (hipStream_t)stream);
+  rc = dh_run_instance(conv_c64_select(a), a, (hipStream_t)stream);
   DH_REQUIRE(rc <= 0, DANHIP_EINVAL, "conv2d_bwd_data_bits_first: the folded kernel declined the call");
   return rc;
 }
@@ -1064,6 +1042,6 @@ extern "C" int danhip_conv2d_bwd_data_bits(const danhip_conv_desc* d, const uint
   ConvArgs a = bwd_args(d);
   a.x = dy; a.w = wb_packed; a.bias = nullptr; a.mask = nullptr; a.mask_bits = relu_bits; a.resid = nullptr; a.y = dx;
   a.relu = 0; a.out_f32 = 0; a.accumulate = accumulate;
-  if (danhip_conv_c64_eligible(a)) return danhip_launch_conv_c64(a, (hipStream_t)stream);
-  return danhip_launch_conv_halo(a, (hipStream_t)stream);
+  const ConvInstance c64 = conv_c64_select(a);         // (straight to the two families that read bit masks)
+  return dh_run_instance(c64 ? c64 : conv_halo_select(a), a, (hipStream_t)stream);
 }

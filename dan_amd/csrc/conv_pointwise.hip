@@ -419,16 +419,6 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   pw_body<BN, NST, false, true, false, true>(a, g);
 }
 
-int pw_cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
-}
-
 template <int BN, int NST, bool DGRAD, bool LD, bool TAPS>
 int launch_pw_t(const ConvArgs& a, hipStream_t s) {
   constexpr int LDS = NST * (128 * 128 + BN * 128);
@@ -441,7 +431,7 @@ int launch_pw_t(const ConvArgs& a, hipStream_t s) {
   g.items = g.m_tiles * g.NB;
   g.ksteps = a.Kpad / 64;
   g.div_nb = make_fastdiv(g.NB);
-  int G = pw_cu_count();
+  int G = dh_cu_count();
   if (g.items < G) G = g.items;
   g.grouped = (G % 8 == 0 && g.items >= G) ? 1 : 0;
   g.per_xcd = (g.items + 7) / 8;
@@ -462,19 +452,13 @@ int launch_pw_concat2(const ConvArgs& a, hipStream_t s) {
   g.items = g.m_tiles * g.NB;
   g.ksteps = a.Kpad / 64;
   g.div_nb = make_fastdiv(g.NB);
-  int G = pw_cu_count();
+  int G = dh_cu_count();
   if (g.items < G) G = g.items;
   g.grouped = (G % 8 == 0 && g.items >= G) ? 1 : 0;
   g.per_xcd = (g.items + 7) / 8;
   hipLaunchKernelGGL((conv_pointwise_concat2_kernel<BN, NST>), dim3(G), dim3(512), LDS, s, a, g);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
-}
-
-template <int BN, int NST, bool DGRAD, bool LD>
-int launch_pw(const ConvArgs& a, hipStream_t s) {
-  const bool plain = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.H == a.Ho && a.W == a.Wo;
-  return plain ? launch_pw_t<BN, NST, DGRAD, LD, false>(a, s) : launch_pw_t<BN, NST, DGRAD, LD, true>(a, s);
 }
 
 bool pw_eligible(const ConvArgs& a) {
@@ -487,48 +471,55 @@ bool pw_eligible(const ConvArgs& a) {
   return true;
 }
 
-}  // namespace
-
 // tile width: the whole Co where it fits (X read once).  A data gradient WITH epilogue inputs holds them in registers across its last
 // K-step: 128 wide by default; option pw_dgrad_ld_bn = 256 lets it take the 256-wide tile too (32 more registers; measured no faster)
-static int pw_bn(const ConvArgs& a, bool dgrad_ld) {
+int pw_bn(const ConvArgs& a, bool dgrad_ld) {
   const int cap = dgrad_ld ? danhip_option("pw_dgrad_ld_bn") : 256;
   return (a.Co % 256 == 0 && cap >= 256) ? 256 : (a.Co % 128 == 0 ? 128 : 64);
 }
 
-const char* danhip_conv_pointwise_label(const ConvArgs& a, bool dgrad) {
-  if (!pw_eligible(a)) return nullptr;
-  const bool ld = dgrad ? (a.mask || a.accumulate) : true;
-  const int bn = pw_bn(a, dgrad && ld);
-  const bool plain = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.H == a.Ho && a.W == a.Wo;
-  static const char* names[2][2][2][3] = {      // [taps][dgrad][ld][bn 256 / 128 / 64]
-      {{{"conv_pointwise_kernel<256, 3, false, false, false>", "conv_pointwise_kernel<128, 4, false, false, false>", "conv_pointwise_kernel<64, 4, false, false, false>"},
-        {"conv_pointwise_kernel<256, 3, false, true, false>", "conv_pointwise_kernel<128, 4, false, true, false>", "conv_pointwise_kernel<64, 4, false, true, false>"}},
-       {{"conv_pointwise_kernel<256, 3, true, false, false>", "conv_pointwise_kernel<128, 4, true, false, false>", "conv_pointwise_kernel<64, 4, true, false, false>"},
-        {"conv_pointwise_kernel<256, 3, true, true, false>", "conv_pointwise_kernel<128, 4, true, true, false>", "conv_pointwise_kernel<64, 4, true, true, false>"}}},
-      {{{"conv_pointwise_kernel<256, 3, false, false, true>", "conv_pointwise_kernel<128, 4, false, false, true>", "conv_pointwise_kernel<64, 4, false, false, true>"},
-        {"conv_pointwise_kernel<256, 3, false, true, true>", "conv_pointwise_kernel<128, 4, false, true, true>", "conv_pointwise_kernel<64, 4, false, true, true>"}},
-       {{"conv_pointwise_kernel<256, 3, true, false, true>", "conv_pointwise_kernel<128, 4, true, false, true>", "conv_pointwise_kernel<64, 4, true, false, true>"},
-        {"conv_pointwise_kernel<256, 3, true, true, true>", "conv_pointwise_kernel<128, 4, true, true, true>", "conv_pointwise_kernel<64, 4, true, true, true>"}}}};
-  return names[plain ? 0 : 1][dgrad ? 1 : 0][ld ? 1 : 0][bn == 256 ? 0 : bn == 128 ? 1 : 2];
+// the plain (1x1 / stride 1, no taps) or tap form of one tile / direction
+template <int BN, int NST, bool DGRAD, bool LD>
+ConvInstance pw_instance(bool plain, const char* plain_label, const char* taps_label) {
+  ConvInstance i;
+  i.label = plain ? plain_label : taps_label;
+  i.launch = plain ? &launch_pw_t<BN, NST, DGRAD, LD, false> : &launch_pw_t<BN, NST, DGRAD, LD, true>;
+  return i;
+}
+template <int BN, int NST>
+ConvInstance pw_concat2_instance(const char* label) {
+  ConvInstance i;
+  i.label = label;
+  i.launch = &launch_pw_concat2<BN, NST>;
+  return i;
 }
 
-// DANHIP_OK when launched, 1 when the shape is not eligible (caller falls back to the flat-M kernel).
-int danhip_launch_conv_pointwise(const ConvArgs& a, hipStream_t s) {
-  if (!pw_eligible(a)) return 1;
+}  // namespace
+
+// data gradient = no bias / relu requested; forward otherwise.  <BN, NST, DGRAD, LD (epilogue inputs: bias | mask / accumulate), TAPS>
+ConvInstance conv_pointwise_select(const ConvArgs& a) {
+  if (!pw_eligible(a)) return {};
+  const bool plain = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.H == a.Ho && a.W == a.Wo;
   if (a.x2) {                                          // forward over the concatenation of two sources (danhip_conv2d_fwd_concat2)
-    const bool plain = a.kh == 1 && a.kw == 1 && a.stride == 1 && a.H == a.Ho && a.W == a.Wo;
-    if (!plain || a.mask || a.accumulate || a.ksplit <= 0 || a.ksplit >= a.Kpad / 64) return 1;
+    if (!plain || a.mask || a.accumulate || a.ksplit <= 0 || a.ksplit >= a.Kpad / 64) return {};
     const int bn2 = pw_bn(a, false);
-    return bn2 == 256 ? launch_pw_concat2<256, 3>(a, s) : bn2 == 128 ? launch_pw_concat2<128, 4>(a, s) : launch_pw_concat2<64, 4>(a, s);
+    return bn2 == 256 ? pw_concat2_instance<256, 3>("conv_pointwise_concat2_kernel<256, 3>")
+         : bn2 == 128 ? pw_concat2_instance<128, 4>("conv_pointwise_concat2_kernel<128, 4>")
+                      : pw_concat2_instance<64, 4>("conv_pointwise_concat2_kernel<64, 4>");
   }
   const bool dgrad = !a.bias && !a.relu;
-  if (!dgrad && (a.mask || a.accumulate)) return 1;
+  if (!dgrad && (a.mask || a.accumulate)) return {};
   const bool ld = dgrad ? (a.mask || a.accumulate) : true;
   const int bn = pw_bn(a, dgrad && ld);
-  if (dgrad) {
-    if (ld) return bn == 256 ? launch_pw<256, 3, true, true>(a, s) : bn == 128 ? launch_pw<128, 4, true, true>(a, s) : launch_pw<64, 4, true, true>(a, s);
-    return bn == 256 ? launch_pw<256, 3, true, false>(a, s) : bn == 128 ? launch_pw<128, 4, true, false>(a, s) : launch_pw<64, 4, true, false>(a, s);
-  }
-  return bn == 256 ? launch_pw<256, 3, false, true>(a, s) : bn == 128 ? launch_pw<128, 4, false, true>(a, s) : launch_pw<64, 4, false, true>(a, s);
+  if (dgrad && ld)
+    return bn == 256 ? pw_instance<256, 3, true, true>(plain, "conv_pointwise_kernel<256, 3, true, true, false>", "conv_pointwise_kernel<256, 3, true, true, true>")
+         : bn == 128 ? pw_instance<128, 4, true, true>(plain, "conv_pointwise_kernel<128, 4, true, true, false>", "conv_pointwise_kernel<128, 4, true, true, true>")
+                     : pw_instance<64, 4, true, true>(plain, "conv_pointwise_kernel<64, 4, true, true, false>", "conv_pointwise_kernel<64, 4, true, true, true>");
+  if (dgrad)
+    return bn == 256 ? pw_instance<256, 3, true, false>(plain, "conv_pointwise_kernel<256, 3, true, false, false>", "conv_pointwise_kernel<256, 3, true, false, true>")
+         : bn == 128 ? pw_instance<128, 4, true, false>(plain, "conv_pointwise_kernel<128, 4, true, false, false>", "conv_pointwise_kernel<128, 4, true, false, true>")
+                     : pw_instance<64, 4, true, false>(plain, "conv_pointwise_kernel<64, 4, true, false, false>", "conv_pointwise_kernel<64, 4, true, false, true>");
+  return bn == 256 ? pw_instance<256, 3, false, true>(plain, "conv_pointwise_kernel<256, 3, false, true, false>", "conv_pointwise_kernel<256, 3, false, true, true>")
+       : bn == 128 ? pw_instance<128, 4, false, true>(plain, "conv_pointwise_kernel<128, 4, false, true, false>", "conv_pointwise_kernel<128, 4, false, true, true>")
+                   : pw_instance<64, 4, false, true>(plain, "conv_pointwise_kernel<64, 4, false, true, false>", "conv_pointwise_kernel<64, 4, false, true, true>");
 }

@@ -201,8 +201,27 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
   }
 }
 
+// first layer (8-channel image, dense tensors): the taps ride in the tile columns
+bool wgrad_tapcols(const WgradCall& c) {
+  return c.d->Cin == 8 && c.d->kh * c.d->kw <= 16 && c.ldx == c.d->Cin && c.ldy == (c.d->Cout + 7) / 8 * 8;
+}
+
 template <int BCI, int BCO, int WCI_WAVES>
-int launch_wgrad(WgradArgs& a, hipStream_t s) {
+int launch_wgrad(const WgradCall& c, hipStream_t s) {
+  const danhip_conv_desc* d = c.d;
+  WgradArgs a{};
+  a.x = c.x; a.dy = c.dy; a.dw = c.dw; a.db = c.db;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.Co8 = (d->Cout + 7) / 8 * 8;
+  a.ldx = c.ldx; a.ldy = c.ldy;
+  a.cin_real = c.cin_real;
+  a.kh = d->kh; a.kw = d->kw; a.stride = d->stride;
+  int total = (d->Ho - 1) * d->stride + d->kh - d->H; if (total < 0) total = 0; a.pad_t = total / 2;
+  total = (d->Wo - 1) * d->stride + d->kw - d->W; if (total < 0) total = 0; a.pad_l = total / 2;
+  a.M = d->N * d->Ho * d->Wo;
+  a.ktiles = (a.M + 63) / 64;
+  a.div_wo = make_fastdiv(a.Wo); a.div_howo = make_fastdiv(a.Ho * a.Wo);
+  a.tapcols = wgrad_tapcols(c) ? 1 : 0;
+  a.linear = !a.tapcols && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W;
   static const bool attr_ok = (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<BCI, BCO, WCI_WAVES>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * (BCI + BCO) * 2) == hipSuccess);
   (void)attr_ok;
@@ -216,13 +235,7 @@ int launch_wgrad(WgradArgs& a, hipStream_t s) {
   const int lds_block = 2 * 64 * (BCI + BCO) * 2;
   int per_cu = (160 * 1024) / lds_block;
   if (per_cu > 4) per_cu = 4;
-  static const int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  const int slots = per_cu * cus;
+  const int slots = per_cu * dh_cu_count();
   int splits = slots / base_blocks;
   const int max_splits = (a.ktiles + 7) / 8;
   if (splits > max_splits) splits = max_splits;
@@ -235,30 +248,41 @@ int launch_wgrad(WgradArgs& a, hipStream_t s) {
   return DANHIP_OK;
 }
 
+template <int BCI, int BCO, int WCI_WAVES>
+WgradInstance wgrad_instance(const char* label) {
+  WgradInstance i;
+  i.label = label;
+  i.launch = &launch_wgrad<BCI, BCO, WCI_WAVES>;
+  return i;
+}
+
+// THE kernel selection of a weight-gradient call: the order of precedence between the families, once.
+WgradInstance select_wgrad(const WgradCall& c) {
+  if (WgradInstance i = wgrad_rows_select(c)) return i;
+  if (WgradInstance i = wgrad_pw_select(c)) return i;
+  if (WgradInstance i = wgrad_c8_select(c)) return i;
+  const int co8 = (c.d->Cout + 7) / 8 * 8;
+  const bool ci_wide = c.d->Cin > 64 || wgrad_tapcols(c), co_wide = co8 > 64;      // (tap columns: 9 taps x 8 channels in the 128 rows)
+  if (ci_wide && co_wide) return wgrad_instance<128, 128, 2>("conv_wgrad_kernel<128, 128, 2>");
+  if (ci_wide) return wgrad_instance<128, 64, 2>("conv_wgrad_kernel<128, 64, 2>");
+  if (!co_wide) return wgrad_instance<64, 64, 2>("conv_wgrad_kernel<64, 64, 2>");
+  return wgrad_instance<64, 128, 2>("conv_wgrad_kernel<64, 128, 2>");
+}
+
 }  // namespace
 
+// (the label's convention: dense pitches and three real input channels)
 extern "C" const char* danhip_conv_wgrad_kernel_label(const danhip_conv_desc* d) {
   if (!d) return "";
-  const char* rl = danhip_wgrad_rows_label(d);
-  if (rl) return rl;
-  const char* pl = danhip_wgrad_pw_label(d);
-  if (pl) return pl;
-  const int co8 = (d->Cout + 7) / 8 * 8;
-  if (danhip_wgrad_c8_eligible(d, 3, d->Cin, co8)) return "conv_wgrad_c8_kernel";
-  if (d->Cin == 8 && d->kh * d->kw <= 16) return co8 > 64 ? "conv_wgrad_kernel<128, 128, 2>" : "conv_wgrad_kernel<128, 64, 2>";
-  const bool ci_small = d->Cin <= 64, co_small = co8 <= 64;
-  if (ci_small && co_small) return "conv_wgrad_kernel<64, 64, 2>";
-  if (ci_small) return "conv_wgrad_kernel<64, 128, 2>";
-  if (co_small) return "conv_wgrad_kernel<128, 64, 2>";
-  return "conv_wgrad_kernel<128, 128, 2>";
+  const WgradCall c{d, nullptr, nullptr, nullptr, nullptr, 3, d->Cin, (d->Cout + 7) / 8 * 8, nullptr, 0};
+  return select_wgrad(c).label;
 }
 
 extern "C" size_t danhip_conv2d_bwd_weight_workspace_bytes(const danhip_conv_desc* d) {
   if (!d) return 0;
-  const int mode = danhip_option("wgrad_slab");
-  if (!mode) return 0;
-  const size_t r = danhip_wgrad_rows_workspace_bytes(d);
-  return r ? r : danhip_wgrad_pw_workspace_bytes(d);
+  if (!danhip_option("wgrad_slab")) return 0;
+  const size_t r = wgrad_rows_workspace_bytes(d);
+  return r ? r : wgrad_pw_workspace_bytes(d);
 }
 
 static int bwd_weight_impl(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* dy, float* dw_hwio, float* db, int32_t cin_real, int ldx, int ldy,
@@ -267,7 +291,6 @@ static int bwd_weight_impl(const danhip_conv_desc* d, const uint16_t* x, const u
   DH_REQUIRE(d->Cin % 8 == 0, DANHIP_EINVAL, "conv2d_bwd_weight: Cin=%d must be a multiple of 8", d->Cin);
   DH_REQUIRE(cin_real > 0 && cin_real <= d->Cin, DANHIP_EINVAL, "conv2d_bwd_weight: cin_real out of range");
   const int co8 = (d->Cout + 7) / 8 * 8;
-  const bool view = ldx != d->Cin || ldy != co8;
   DH_REQUIRE(ldx >= d->Cin && ldy >= co8 && ((ldx | ldy) & 7) == 0, DANHIP_EINVAL, "conv2d_bwd_weight: pitches must be multiples of 8 and cover the channels");
   // the kernels address both activations through raw buffer descriptors with a 32-bit byte count: 2^31 16-bit elements = 4 GiB would wrap to 0
   DH_REQUIRE((int64_t)d->N * d->H * d->W * ldx < (1ll << 31) && (int64_t)d->N * d->Ho * d->Wo * (int64_t)ldy < (1ll << 31),
@@ -277,39 +300,8 @@ static int bwd_weight_impl(const danhip_conv_desc* d, const uint16_t* x, const u
     const bool valid = d->H >= d->kh && d->W >= d->kw && d->Ho == (d->H - d->kh) / d->stride + 1 && d->Wo == (d->W - d->kw) / d->stride + 1;
     DH_REQUIRE(same || valid, DANHIP_EINVAL, "conv: Ho/Wo (%d,%d) is neither the 'same' nor the 'valid' output size", d->Ho, d->Wo);
   }
-  {
-    {
-      const int hr = danhip_launch_wgrad_rows(d, x, dy, dw_hwio, db, cin_real, (hipStream_t)stream, ws, ws_bytes, ldx, ldy);
-      if (hr <= 0) return hr;
-    }
-    const int pr = danhip_launch_wgrad_pw(d, x, dy, dw_hwio, db, cin_real, (hipStream_t)stream, ws, ws_bytes, ldx, ldy);
-    if (pr <= 0) return pr;
-  }
-  WgradArgs a{};
-  a.x = x; a.dy = dy; a.dw = dw_hwio; a.db = db;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.Co8 = co8;
-  a.ldx = ldx; a.ldy = ldy;
-  a.cin_real = cin_real;
-  a.kh = d->kh; a.kw = d->kw; a.stride = d->stride;
-  int total = (d->Ho - 1) * d->stride + d->kh - d->H; if (total < 0) total = 0; a.pad_t = total / 2;
-  total = (d->Wo - 1) * d->stride + d->kw - d->W; if (total < 0) total = 0; a.pad_l = total / 2;
-  a.M = d->N * d->Ho * d->Wo;
-  a.ktiles = (a.M + 63) / 64;
-  a.div_wo = make_fastdiv(a.Wo); a.div_howo = make_fastdiv(a.Ho * a.Wo);
-  hipStream_t s = (hipStream_t)stream;
-  if (danhip_wgrad_c8_eligible(d, cin_real, ldx, ldy))     // conv1_1: both operands staged once, taps as address offsets (conv_wgrad_c8.hip)
-    return danhip_launch_wgrad_c8(d, x, dy, dw_hwio, db, cin_real, s);
-  if (d->Cin == 8 && d->kh * d->kw <= 16 && !view) {       // first layer: taps ride in the tile columns
-    a.tapcols = 1;
-    return a.Co8 > 64 ? launch_wgrad<128, 128, 2>(a, s) : launch_wgrad<128, 64, 2>(a, s);
-  }
-  a.tapcols = 0;
-  a.linear = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W;
-  const bool ci_small = d->Cin <= 64, co_small = a.Co8 <= 64;
-  if (ci_small && co_small) return launch_wgrad<64, 64, 2>(a, s);
-  if (ci_small) return launch_wgrad<64, 128, 2>(a, s);
-  if (co_small) return launch_wgrad<128, 64, 2>(a, s);
-  return launch_wgrad<128, 128, 2>(a, s);
+  const WgradCall c{d, x, dy, dw_hwio, db, cin_real, ldx, ldy, ws, ws_bytes};
+  return dh_run_instance(select_wgrad(c), c, (hipStream_t)stream);
 }
 
 extern "C" int danhip_conv2d_bwd_weight(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* dy, float* dw_hwio, float* db,

@@ -160,32 +160,36 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_c8_kernel(const WgC8Args a)
   if (a.db && tid < 64) atomicAdd(a.db + tid, red[(9 * 4 + 0) * 64 + tid]);
 }
 
-}  // namespace
-
-bool danhip_wgrad_c8_eligible(const danhip_conv_desc* d, int cin_real, int ldx, int ldy) {
-  return d->Cin == 8 && cin_real >= 1 && cin_real <= 4 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W && d->Cout == 64 &&
-         ldx == 8 && ldy == 64 && (int64_t)d->N * d->H * d->W * 128 < (1ll << 32) && danhip_option("wgrad_c8") != 0;
-}
-
-int danhip_launch_wgrad_c8(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s) {
+int launch_wg_c8(const WgradCall& c, hipStream_t s) {
+  const danhip_conv_desc* d = c.d;
   static const bool attr_ok =
       hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_c8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C8_LDS) == hipSuccess;
   (void)attr_ok;
   WgC8Args a{};
-  a.x = x; a.dy = dy; a.dw = dw; a.db = db;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.cin_real = cin_real;
+  a.x = c.x; a.dy = c.dy; a.dw = c.dw; a.db = c.db;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.cin_real = c.cin_real;
   a.tiles_x = (d->W + C8_TW - 1) / C8_TW;
   a.tiles_y = (d->H + C8_TH - 1) / C8_TH;
   a.items = d->N * a.tiles_x * a.tiles_y;
   a.div_tx = make_fastdiv(a.tiles_x);
   a.div_txy = make_fastdiv(a.tiles_x * a.tiles_y);
-  int G = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) G = v;
-  }
+  int G = dh_cu_count();
   if (a.items < G) G = a.items;
   hipLaunchKernelGGL(conv_wgrad_c8_kernel, dim3(G), dim3(512), C8_LDS, s, a);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
+}
+
+}  // namespace
+
+// conv1_1: both operands staged once, taps as address offsets
+WgradInstance wgrad_c8_select(const WgradCall& c) {
+  const danhip_conv_desc* d = c.d;
+  WgradInstance i;
+  if (d->Cin == 8 && c.cin_real >= 1 && c.cin_real <= 4 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W && d->Cout == 64 &&
+      c.ldx == 8 && c.ldy == 64 && (int64_t)d->N * d->H * d->W * 128 < (1ll << 32) && danhip_option("wgrad_c8") != 0) {
+    i.label = "conv_wgrad_c8_kernel";
+    i.launch = &launch_wg_c8;
+  }
+  return i;
 }

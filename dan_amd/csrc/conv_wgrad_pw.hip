@@ -322,19 +322,7 @@ __global__ __launch_bounds__(256) void wg_pw_reduce_kernel(const WgPwArgs a) {
   }
 }
 
-int wp_cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
-}
-
-}  // namespace
-
-static bool wg_pw_eligible(const danhip_conv_desc* d) {
+bool wg_pw_eligible(const danhip_conv_desc* d) {
   if (!(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W)) return false;
   const int co8 = (d->Cout + 7) / 8 * 8;
   if (d->Cin % 64 != 0 || d->Cin < 128 || co8 < 64) return false;          // thin operands: the generic kernel's 64-wide tiles waste less
@@ -344,61 +332,72 @@ static bool wg_pw_eligible(const danhip_conv_desc* d) {
   return true;
 }
 
-const char* danhip_wgrad_pw_label(const danhip_conv_desc* d) { return wg_pw_eligible(d) ? "conv_wgrad_pw_kernel" : nullptr; }
-
-size_t danhip_wgrad_pw_workspace_bytes(const danhip_conv_desc* d) {
-  if (!wg_pw_eligible(d)) return 0;
-  const int co8 = (d->Cout + 7) / 8 * 8;
-  const int pairs = ((d->Cin + 255) / 256) * ((co8 + 255) / 256);
-  const int ksteps = (d->N * d->H * d->W + 31) / 32;
-  int splits = wp_cu_count() / pairs;
+// The launch geometry of an eligible descriptor, computed once: the workspace query and the launch both read it.
+struct WgPwPlan {
+  int co8, ksteps, ci_tiles, co_tiles, pairs, splits, steps_per_split;
+  bool slab;              // slab form for short launches only (see conv_wgrad_rows.hip: on long ones the atomic tail hides under the other blocks' MFMAs)
+  size_t slab_bytes;
+};
+WgPwPlan plan_wg_pw(const danhip_conv_desc* d) {
+  WgPwPlan p{};
+  p.co8 = (d->Cout + 7) / 8 * 8;
+  p.ksteps = (d->N * d->H * d->W + 31) / 32;
+  p.ci_tiles = (d->Cin + 255) / 256;
+  p.co_tiles = (p.co8 + 255) / 256;
+  p.pairs = p.ci_tiles * p.co_tiles;
+  int splits = dh_cu_count() / p.pairs;
   if (splits < 1) splits = 1;
-  if (splits > ksteps) splits = ksteps;
-  const int steps_per_split = (ksteps + splits - 1) / splits;
-  const int slab_mode = danhip_option("wgrad_slab");
-  if (splits < 2 || (slab_mode != 2 && steps_per_split > 192)) return 0;      // long launches keep the atomic epilogue
-  return (size_t)wp_cu_count() * 32 * 512 * 16;
+  if (splits > p.ksteps) splits = p.ksteps;
+  p.steps_per_split = (p.ksteps + splits - 1) / splits;
+  p.splits = (p.ksteps + p.steps_per_split - 1) / p.steps_per_split;
+  p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.steps_per_split <= 192);
+  p.slab_bytes = (size_t)dh_cu_count() * 32 * 512 * 16;
+  return p;
 }
 
-// Returns DANHIP_OK when launched, 1 when the shape is not eligible (caller falls back to conv_wgrad.hip).
-int danhip_launch_wgrad_pw(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s,
-                           void* ws, size_t ws_bytes, int ldx, int ldy) {
-  if (!wg_pw_eligible(d)) return 1;
-  {   // a channel's 16-byte chunk offset inside a pixel row must keep the row's swizzle: within the 64-channel (X) / 128-channel (dY) sub-tile
-    const long M_ = (long)d->N * d->H * d->W;
-    if (ldx && M_ * ldx >= (1l << 31)) return 1;
-    if (ldy && M_ * ldy >= (1l << 31)) return 1;
-  }
+int launch_wg_pw(const WgradCall& c, hipStream_t s) {
+  const danhip_conv_desc* d = c.d;
+  const WgPwPlan p = plan_wg_pw(d);
   constexpr int LDS = 4 * (16384 + 16384);
   static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_pw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   (void)attr_ok;
   WgPwArgs a{};
-  a.x = x; a.dy = dy; a.dw = dw; a.db = db;
-  a.M = d->N * d->H * d->W; a.C = d->Cin; a.Co8 = (d->Cout + 7) / 8 * 8; a.Cout = d->Cout; a.cin_real = cin_real;
-  a.ldx = ldx ? ldx : a.C; a.ldy = ldy ? ldy : a.Co8;
-  a.ksteps = (a.M + 31) / 32;
-  a.ci_tiles = (a.C + 255) / 256;
-  a.co_tiles = (a.Co8 + 255) / 256;
-  const int pairs = a.ci_tiles * a.co_tiles;
-  int splits = wp_cu_count() / pairs;
-  if (splits < 1) splits = 1;
-  if (splits > a.ksteps) splits = a.ksteps;
-  a.steps_per_split = (a.ksteps + splits - 1) / splits;
-  splits = (a.ksteps + a.steps_per_split - 1) / a.steps_per_split;
+  a.x = c.x; a.dy = c.dy; a.dw = c.dw; a.db = c.db;
+  a.M = d->N * d->H * d->W; a.C = d->Cin; a.Co8 = p.co8; a.Cout = d->Cout; a.cin_real = c.cin_real;
+  a.ldx = c.ldx ? c.ldx : a.C; a.ldy = c.ldy ? c.ldy : a.Co8;
+  a.ksteps = p.ksteps;
+  a.ci_tiles = p.ci_tiles;
+  a.co_tiles = p.co_tiles;
+  a.steps_per_split = p.steps_per_split;
   a.div_ci = make_fastdiv(a.ci_tiles);
-  a.div_pairs = make_fastdiv(pairs);
-  a.xcd_grouped = (splits % 8 == 0 && pairs > 1) ? 1 : 0;
-  a.splits = splits;
+  a.div_pairs = make_fastdiv(p.pairs);
+  a.xcd_grouped = (p.splits % 8 == 0 && p.pairs > 1) ? 1 : 0;
+  a.splits = p.splits;
   a.b2 = danhip_option("wgrad_b2");
-  // slab form for short launches only (see conv_wgrad_rows.hip: on long ones the atomic tail hides under the other blocks' MFMAs)
-  const int slab_mode = danhip_option("wgrad_slab");
-  a.slab = (slab_mode && ws && ws_bytes >= danhip_wgrad_pw_workspace_bytes(d) && splits >= 2 && (slab_mode == 2 || a.steps_per_split <= 192))
-               ? reinterpret_cast<float*>(ws) : nullptr;
-  hipLaunchKernelGGL(conv_wgrad_pw_kernel, dim3(pairs * splits), dim3(512), LDS, s, a);
+  a.slab = (danhip_option("wgrad_slab") && c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
+  hipLaunchKernelGGL(conv_wgrad_pw_kernel, dim3(p.pairs * p.splits), dim3(512), LDS, s, a);
   DH_LAUNCH_CHECK();
   if (a.slab) {
-    hipLaunchKernelGGL(wg_pw_reduce_kernel, dim3(pairs * (32 * 512 / 64)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(wg_pw_reduce_kernel, dim3(p.pairs * (32 * 512 / 64)), dim3(256), 0, s, a);
     DH_LAUNCH_CHECK();
   }
   return DANHIP_OK;
+}
+
+}  // namespace
+
+size_t wgrad_pw_workspace_bytes(const danhip_conv_desc* d) {
+  if (!wg_pw_eligible(d)) return 0;
+  const WgPwPlan p = plan_wg_pw(d);
+  return p.slab ? p.slab_bytes : 0;
+}
+
+WgradInstance wgrad_pw_select(const WgradCall& c) {
+  if (!wg_pw_eligible(c.d)) return {};
+  const long M = (long)c.d->N * c.d->H * c.d->W;       // (32-bit element offsets with the caller's pitches too)
+  if ((c.ldx && M * c.ldx >= (1l << 31)) || (c.ldy && M * c.ldy >= (1l << 31))) return {};
+  WgradInstance i;
+  i.label = "conv_wgrad_pw_kernel";
+  i.launch = &launch_wg_pw;
+  return i;
 }

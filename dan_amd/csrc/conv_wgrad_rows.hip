@@ -501,18 +501,58 @@ unsigned* wr_trace_buffer() {
 }
 #endif
 
-int wr_cu_count() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-    return v;
-  }();
-  return n;
+// output-channel tile: 128 when the 64-padded channel count is a multiple of 128 (72 -> 128: one tile, 56 zero-filled columns)
+int wg_rows_cot(const danhip_conv_desc* d) { return ((d->Cout + 63) / 64 * 64) % 128 == 0 ? 128 : 64; }
+
+bool wg_rows_eligible(const danhip_conv_desc* d) {
+  if (!(d->kh == 3 && d->kw == 3 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W)) return false;      // 'same' 3x3 only
+  if (d->Cin % 64 != 0) return false;      // any Cout: channel chunks beyond Co8 are zero-filled (thin heads: one 64-wide tile; 72 -> one 128-wide tile)
+  const int tw = 32;
+  const double util = (double)d->W / (double)((d->W + tw - 1) / tw * tw);
+  return util >= 0.6;       // 40- and 20-wide maps (0.625) still beat the per-tap kernel
+}
+
+// The launch geometry of an eligible descriptor, computed once: the workspace query and the launch both read it.
+struct WgRowsPlan {
+  int co8, ci_tiles, co_tiles, pairs, tiles_x, total_rows, splits, rows_per_split;
+  bool slab;              // the slab form (partial tiles as plain stores + a combine pass) is worth taking ...
+  size_t slab_bytes;      // ... and needs this much scratch (one register tile per workgroup, at most one workgroup per CU)
+};
+WgRowsPlan plan_wg_rows(const danhip_conv_desc* d) {
+  WgRowsPlan p{};
+  const int cot = wg_rows_cot(d);
+  p.co8 = (d->Cout + 7) / 8 * 8;
+  p.ci_tiles = d->Cin / 64;
+  p.co_tiles = (p.co8 + cot - 1) / cot;
+  p.pairs = p.ci_tiles * p.co_tiles;
+  p.tiles_x = (d->W + 31) / 32;
+  p.total_rows = d->N * p.tiles_x * d->H;
+  int splits = dh_cu_count() / p.pairs;
+  if (splits < 1) splits = 1;
+  if (splits > p.total_rows) splits = p.total_rows;
+  p.rows_per_split = (p.total_rows + splits - 1) / splits;
+  p.splits = (p.total_rows + p.rows_per_split - 1) / p.rows_per_split;
+  // The slab form pays when the launch is short (every block reaches its epilogue together and nothing hides the tail: 2-4 images per
+  // GPU, the 40x40 / 20x20 levels); on long launches the blocks drift apart, the atomic tail hides under other blocks' MFMAs and the
+  // extra pass costs more than it saves (batch 16: conv3_2 0.426 against 0.428 ms, conv2_2 0.479 against 0.455; profiles/r3).
+  p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.rows_per_split <= 192);
+  p.slab_bytes = (size_t)dh_cu_count() * 9 * (cot / 32) * 512 * 16;
+  return p;
 }
 
 template <int COT>
-int launch_wg_rows(WgRowsArgs& a, hipStream_t s) {
+int launch_wg_rows(const WgradCall& c, hipStream_t s) {
+  const danhip_conv_desc* d = c.d;
+  const WgRowsPlan p = plan_wg_rows(d);
+  WgRowsArgs a{};
+  a.x = c.x; a.dy = c.dy; a.dw = c.dw; a.db = c.db;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Co8 = p.co8; a.Cout = d->Cout; a.cin_real = c.cin_real;
+  a.ldx = c.ldx ? c.ldx : d->Cin; a.ldy = c.ldy ? c.ldy : p.co8;
+  a.tiles_x = p.tiles_x;
+  a.total_rows = p.total_rows;
+  a.div_tx = make_fastdiv(a.tiles_x);
+  a.div_h = make_fastdiv(d->H);
+  a.slab = (c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
 #ifdef WR_TRACE
   constexpr int LDS = 6 * (32 * COT * 2) + 6 * 40 * 128 + 4096;
   a.trace = wr_trace_buffer();
@@ -522,14 +562,10 @@ int launch_wg_rows(WgRowsArgs& a, hipStream_t s) {
   static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rows_kernel<COT>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   (void)attr_ok;
-  a.ci_tiles = a.C / 64;
-  a.co_tiles = (a.Co8 + COT - 1) / COT;
-  const int pairs = a.ci_tiles * a.co_tiles;
-  int splits = wr_cu_count() / pairs;
-  if (splits < 1) splits = 1;
-  if (splits > a.total_rows) splits = a.total_rows;
-  a.rows_per_split = (a.total_rows + splits - 1) / splits;
-  splits = (a.total_rows + a.rows_per_split - 1) / a.rows_per_split;
+  a.ci_tiles = p.ci_tiles;
+  a.co_tiles = p.co_tiles;
+  const int pairs = p.pairs, splits = p.splits;
+  a.rows_per_split = p.rows_per_split;
   a.div_ci = make_fastdiv(a.ci_tiles);
   a.div_pairs = make_fastdiv(pairs);
   a.xcd_grouped = (splits % 8 == 0 && pairs > 1) ? 1 : 0;
@@ -537,11 +573,6 @@ int launch_wg_rows(WgRowsArgs& a, hipStream_t s) {
   a.ablate = ablate;
   a.b2 = danhip_option("wgrad_b2");
   a.splits = splits;
-  // The slab form pays when the launch is short (every block reaches its epilogue together and nothing hides the tail: 2-4 images per
-  // GPU, the 40x40 / 20x20 levels); on long launches the blocks drift apart, the atomic tail hides under other blocks' MFMAs and the
-  // extra pass costs more than it saves (batch 16: conv3_2 0.426 against 0.428 ms, conv2_2 0.479 against 0.455; profiles/r3).
-  const int slab_mode = danhip_option("wgrad_slab");
-  if (a.slab && (splits < 2 || (slab_mode != 2 && a.rows_per_split > 192))) a.slab = nullptr;
 #ifdef WR_CLOCK
   a.clk = wr_clock_buffer();
   g_wr_clock_blocks = pairs * splits;
@@ -559,54 +590,17 @@ int launch_wg_rows(WgRowsArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// output-channel tile: 128 when the 64-padded channel count is a multiple of 128 (72 -> 128: one tile, 56 zero-filled columns)
-static int wg_rows_cot(const danhip_conv_desc* d) { return ((d->Cout + 63) / 64 * 64) % 128 == 0 ? 128 : 64; }
-
-static bool wg_rows_eligible(const danhip_conv_desc* d) {
-  if (!(d->kh == 3 && d->kw == 3 && d->stride == 1 && d->Ho == d->H && d->Wo == d->W)) return false;      // 'same' 3x3 only
-  if (d->Cin % 64 != 0) return false;      // any Cout: channel chunks beyond Co8 are zero-filled (thin heads: one 64-wide tile; 72 -> one 128-wide tile)
-  const int tw = 32;
-  const double util = (double)d->W / (double)((d->W + tw - 1) / tw * tw);
-  return util >= 0.6;       // 40- and 20-wide maps (0.625) still beat the per-tap kernel
-}
-
-const char* danhip_wgrad_rows_label(const danhip_conv_desc* d) {
-  if (!wg_rows_eligible(d)) return nullptr;
-  return wg_rows_cot(d) == 128 ? "conv_wgrad_rows_kernel<128>" : "conv_wgrad_rows_kernel<64>";
-}
-
-// Bytes of the partial-tile workspace the slab form needs for this descriptor (one register tile per workgroup, at most one workgroup
-// per CU); 0 when the row-streaming kernel does not take the shape.
-size_t danhip_wgrad_rows_workspace_bytes(const danhip_conv_desc* d) {
+size_t wgrad_rows_workspace_bytes(const danhip_conv_desc* d) {
   if (!wg_rows_eligible(d)) return 0;
-  const int cot = wg_rows_cot(d);
-  // the launch geometry of launch_wg_rows: the slab form is taken for short launches only (rows_per_split <= 192)
-  const int co8 = (d->Cout + 7) / 8 * 8;
-  const int pairs = (d->Cin / 64) * ((co8 + cot - 1) / cot);
-  const int total_rows = d->N * ((d->W + 31) / 32) * d->H;
-  int splits = wr_cu_count() / pairs;
-  if (splits < 1) splits = 1;
-  if (splits > total_rows) splits = total_rows;
-  const int rows_per_split = (total_rows + splits - 1) / splits;
-  const int slab_mode = danhip_option("wgrad_slab");
-  if (splits < 2 || (slab_mode != 2 && rows_per_split > 192)) return 0;
-  return (size_t)wr_cu_count() * 9 * (cot / 32) * 512 * 16;
+  const WgRowsPlan p = plan_wg_rows(d);
+  return p.slab ? p.slab_bytes : 0;
 }
 
-// Returns DANHIP_OK when launched, 1 when the shape is not eligible (caller falls back to conv_wgrad.hip).
-int danhip_launch_wgrad_rows(const danhip_conv_desc* d, const bf16_t* x, const bf16_t* dy, float* dw, float* db, int cin_real, hipStream_t s,
-                             void* ws, size_t ws_bytes, int ldx, int ldy) {
-  if (!wg_rows_eligible(d)) return 1;
-  const int co8 = (d->Cout + 7) / 8 * 8;
-  if (ldx > 0xFFFF || ldy > 0xFFFF) return 1;       // (the lane offsets are 24-bit products)
-  WgRowsArgs a{};
-  a.x = x; a.dy = dy; a.dw = dw; a.db = db;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Co8 = co8; a.Cout = d->Cout; a.cin_real = cin_real;
-  a.ldx = ldx ? ldx : d->Cin; a.ldy = ldy ? ldy : co8;
-  a.tiles_x = (d->W + 31) / 32;
-  a.total_rows = d->N * a.tiles_x * d->H;
-  a.div_tx = make_fastdiv(a.tiles_x);
-  a.div_h = make_fastdiv(d->H);
-  a.slab = (ws && ws_bytes >= danhip_wgrad_rows_workspace_bytes(d)) ? reinterpret_cast<float*>(ws) : nullptr;
-  return wg_rows_cot(d) == 128 ? launch_wg_rows<128>(a, s) : launch_wg_rows<64>(a, s);
+WgradInstance wgrad_rows_select(const WgradCall& c) {
+  if (!wg_rows_eligible(c.d)) return {};
+  if (c.ldx > 0xFFFF || c.ldy > 0xFFFF) return {};       // (the lane offsets are 24-bit products)
+  WgradInstance i;
+  if (wg_rows_cot(c.d) == 128) { i.label = "conv_wgrad_rows_kernel<128>"; i.launch = &launch_wg_rows<128>; }
+  else { i.label = "conv_wgrad_rows_kernel<64>"; i.launch = &launch_wg_rows<64>; }
+  return i;
 }

@@ -216,6 +216,9 @@ int danhip_relu_bwd_bias_grad(uint16_t* dy, const uint16_t* y, float* db, int64_
 const char* danhip_conv_kernel_label(const danhip_conv_desc* d, int which);
 /* Same for the weight-gradient call of this descriptor. */
 const char* danhip_conv_wgrad_kernel_label(const danhip_conv_desc* d);
+/* Label of the convolution kernel instance (forward, data gradient or weight gradient) most recently launched on the calling thread;
+ * "" before the first launch.  The two functions above predict it from a descriptor; this one reports what ran. */
+const char* danhip_conv_last_launch_label(void);
 
 /* ------------------------------------------------------------------------------------------------
  * HBM-bound layer kernels (bf16 NHWC, 16-byte vectors, wave reductions).

@@ -25,6 +25,10 @@ void danhip_set_error(const char* fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+int dh_cu_count() {
+  int v = 0;
+  return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0) == hipSuccess && v > 0) ? v : 256;
+}
 int danhip_option(const char* name) {
   if (!strcmp(name, "wgrad_b2")) { const char* e = getenv("DANHIP_WGRAD_B2"); return e ? atoi(e) : 0; }
   if (!strcmp(name, "wgrad_slab")) { const char* e = getenv("DANHIP_WGRAD_SLAB"); return e ? atoi(e) : 1; }
@@ -57,7 +61,8 @@ int main(int argc, char** argv) {
   dd.N = N; dd.H = H; dd.W = W; dd.Cin = C; dd.Ho = H; dd.Wo = W; dd.Cout = Co; dd.kh = dd.kw = 3; dd.stride = 1;
   hipStream_t s;
   hipStreamCreate(&s);
-  auto launch = [&]() { return danhip_launch_wgrad_rows(&dd, dx, dy, ddw, nullptr, C, s, nullptr, 0); };
+  const WgradCall wc{&dd, dx, dy, ddw, nullptr, C, 0, 0, nullptr, 0};      // (pitches 0 = dense)
+  auto launch = [&]() { return dh_run_instance(wgrad_rows_select(wc), wc, s); };
   if (launch() != 0) { fprintf(stderr, "not eligible / launch failed\n"); return 1; }
   hipStreamSynchronize(s);
   hipEvent_t e0, e1;

@@ -21,7 +21,7 @@
 #elif defined(TRACE_HALO1)      // the production kernel (conv_halo.hip, 8 x 32 pixel tiles, 64-channel chunks) instead of conv_halo2.hip
 #define H_TRACE 1
 #include "../dan_amd/csrc/conv_halo.hip"
-#define TRACE_LAUNCH danhip_launch_conv_halo
+#define TRACE_LAUNCH(a, s) dh_run_instance(conv_halo_select(a), a, s)
 #define TRACE_BUFFER h_trace_buffer
 #else
 #error "build with -DTRACE_HALO1 (conv_halo.hip) or -DTRACE_WGRAD (conv_wgrad_rows.hip): the 512-pixel-tile experiment conv_halo2.hip was removed in round 4"
@@ -34,6 +34,11 @@ void danhip_set_error(const char* fmt, ...) {
   vfprintf(stderr, fmt, ap);
   va_end(ap);
   fputc('\n', stderr);
+}
+
+int dh_cu_count() {
+  int v = 0;
+  return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0) == hipSuccess && v > 0) ? v : 256;
 }
 
 int danhip_option(const char* name) {
@@ -89,7 +94,8 @@ int main(int argc, char** argv) {
   hipMalloc(&ddw, (size_t)9 * C * Co * 4);
   danhip_conv_desc dd{};
   dd.N = N; dd.H = H; dd.W = W; dd.Cin = C; dd.Ho = H; dd.Wo = W; dd.Cout = Co; dd.kh = dd.kw = 3; dd.stride = 1;
-  auto launch = [&]() { hipMemsetAsync(ddw, 0, (size_t)9 * C * Co * 4, s); return danhip_launch_wgrad_rows(&dd, dx, dy, ddw, nullptr, C, s, nullptr, 0); };
+  const WgradCall wc{&dd, dx, dy, ddw, nullptr, C, 0, 0, nullptr, 0};      // (pitches 0 = dense)
+  auto launch = [&]() { hipMemsetAsync(ddw, 0, (size_t)9 * C * Co * 4, s); return dh_run_instance(wgrad_rows_select(wc), wc, s); };
 #else
   auto launch = [&]() { return TRACE_LAUNCH(a, s); };
 #endif
