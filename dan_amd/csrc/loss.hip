@@ -289,8 +289,8 @@ __global__ void grad_nonfinite_kernel(const float* __restrict__ g, long total, f
   const long n4 = total >> 2;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (long)gridDim.x * blockDim.x) {
     const float4 gi = reinterpret_cast<const float4*>(g)[q];
-    const float t = gi.x + gi.y + gi.z + gi.w;            // inf - inf and NaN both end up non-finite
-    bad = bad || !(fabsf(t) <= 3.4028234663852886e+38f) || !(fabsf(gi.x) <= 3.4028234663852886e+38f) || !(fabsf(gi.y) <= 3.4028234663852886e+38f) ||
+    // per element, as GradScaler does (NaN fails the comparison too): the sum of a float4 of FINITE gradients can overflow, and is no reason to skip
+    bad = bad || !(fabsf(gi.x) <= 3.4028234663852886e+38f) || !(fabsf(gi.y) <= 3.4028234663852886e+38f) ||
           !(fabsf(gi.z) <= 3.4028234663852886e+38f) || !(fabsf(gi.w) <= 3.4028234663852886e+38f);
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) dyn[3] = 1.f;  // benign race: every writer stores the same value
