@@ -80,6 +80,16 @@ def main():
     hbm_seconds = time.time() - t0
     n += 1
 
+    # the convolution kernels on integer-valued operands, equal to a float64 reference (tests/conv_exact.py; every value stays within +-256,
+    # exact in IEEE half as in bf16): the bf16 suite's whole table
+    import conv_exact as CE
+    t0 = time.time()
+    conv_cases = CE.all_cases()
+    for case in conv_cases:
+        CE.run_case(case, dev)
+    conv_seconds = time.time() - t0
+    n += 1
+
     # S3FD forward against the oracle in fp16-storage emulation
     from dan_amd.train_sfd import AnchorConfig, SFDModel
     P = ON.Params(create=True, seed=1234)
@@ -158,7 +168,8 @@ def main():
     checked = GC.train_step_case("dan_deform", 1024, 1024, dev, H, grad_tol=0.05)
     assert checked > 100
     n += 1
-    print("FP16-OK", n, "groups; DAN-Deform losses", ["%.4f" % t for t in totals], "; hbm_layers group: %d cases in %.0f s" % (len(HL.FP16_IDS), hbm_seconds))
+    print("FP16-OK", n, "groups; DAN-Deform losses", ["%.4f" % t for t in totals], "; hbm_layers group: %d cases in %.0f s" % (len(HL.FP16_IDS), hbm_seconds),
+          "; conv_exact group: %d cases in %.0f s" % (len(conv_cases), conv_seconds))
 
 
 if __name__ == "__main__":

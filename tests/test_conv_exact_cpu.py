@@ -1,0 +1,176 @@
+"""Pins tests/conv_exact.py itself (no GPU): the float64 reference against the float32 oracle convolution and its autograd gradients, the
+pool / arg-code / bit-mask restatements against the oracle pool and hand-written windows, the conditions every listed case must meet on its
+reference (16-bit exact range, exact zeros, late ties, the cut a case is there for) and the launch-plan restatements against descriptors
+worked out by hand from the .hip sources and against the library's own workspace queries."""
+import ctypes
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_exact as CE  # noqa: E402
+from oracle import tf_ops as T  # noqa: E402
+
+F64 = torch.float64
+
+
+@pytest.mark.parametrize("shape", [(2, 9, 7, 5, 6, 3, 3, 1), (1, 10, 8, 4, 3, 3, 3, 2), (1, 11, 7, 4, 3, 3, 3, 2), (2, 6, 9, 8, 5, 3, 1, 1), (1, 7, 12, 8, 5, 1, 3, 1),
+                                   (3, 5, 5, 16, 7, 1, 1, 1), (1, 5, 1, 3, 4, 3, 3, 1), (1, 9, 9, 8, 8, 3, 3, 3)])
+def test_reference_is_the_oracle_convolution_and_its_gradients(shape):
+    N, H, W, Cin, Cout, kh, kw, s = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    x, w, b = torch.randn((N, H, W, Cin), generator=g), torch.randn((kh, kw, Cin, Cout), generator=g), torch.randn((Cout,), generator=g)
+    xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    want = T.conv2d_same(xr, wr, br, stride=s)
+    got = CE.conv_ref(x.double(), w.double(), b.double(), s)
+    assert got.dtype == F64 and got.shape == want.shape
+    assert (got - want.detach().double()).abs().max().item() <= 1e-5 * max(1.0, want.abs().max().item())          # test_oracle_cpu.py's tolerance
+    dy = torch.randn(want.shape, generator=g)
+    want.backward(dy)
+    dx = CE.dgrad_ref(dy.double(), w.double(), H, W, s)
+    dw, db = CE.wgrad_ref(x.double(), dy.double(), kh, kw, s)
+    for a, r in ((dx, xr.grad), (dw, wr.grad), (db, br.grad)):
+        assert a.shape == r.shape and (a - r.double()).abs().max().item() <= 1e-5 * max(1.0, r.abs().max().item())
+
+
+def test_stride_two_puts_the_odd_pad_pixel_at_the_bottom_right():
+    assert CE.same_pad(10, 3, 2) == (0, 1, 5) and CE.same_pad(11, 3, 2) == (1, 1, 6) and CE.same_pad(7, 3, 1) == (1, 1, 7) and CE.same_pad(7, 1, 1) == (0, 0, 7)
+    # 4 x 4 map, 3 x 3 window, stride 2: pad (0, 1) -> windows cover rows 0..2 and 2..4, their centres are the pixels (1,1), (1,3), (3,1), (3,3);
+    # with the pad on the top / left the centres would be (0,0), (0,2), (2,0), (2,2)
+    x = torch.zeros((1, 4, 4, 1), dtype=F64)
+    x[0, 3, 3, 0] = 1.0
+    w = torch.zeros((3, 3, 1, 1), dtype=F64)
+    w[1, 1] = 1.0
+    y = CE.conv_ref(x, w, None, 2)
+    assert y.shape == (1, 2, 2, 1) and y[0, :, :, 0].tolist() == [[0, 0], [0, 1]]
+    x[0, 3, 3, 0], x[0, 2, 2, 0] = 0.0, 1.0
+    assert CE.conv_ref(x, w, None, 2).abs().sum().item() == 0
+
+
+def test_pool_codes_and_bit_masks_follow_their_rules():
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn((2, 7, 9, 8), generator=g).double()
+    p, code = CE.pool_ref(x)
+    assert torch.equal(p, T.max_pool_2x2_same(x))
+    xr = x.clone().requires_grad_(True)                           # without ties: the scatter is autograd's gradient of the oracle pool
+    y = T.max_pool_2x2_same(xr)
+    dy = torch.randn(y.shape, generator=g).double()
+    y.backward(dy)
+    assert torch.equal(CE.pool_scatter(code, dy, 7, 9), xr.grad)
+    # hand-written windows, one channel each: [a b / c d] -> code of the first maximum in row-major order
+    wins = [([0, 0, 0, 0], 0), ([1, 3, 3, 2], 1), ([0, 2, 1, 2], 1), ([0, 1, 5, 5], 2), ([0, 0, 0, 4], 3), ([2, 2, 1, 0], 0), ([0, 1, 1, 1], 1), ([0, 0, 7, 0], 2)]
+    y = torch.tensor([[[w[0], w[1]] for w, _ in wins], [[w[2], w[3]] for w, _ in wins]], dtype=F64).permute(0, 2, 1).reshape(1, 2, 2, 8)
+    p, code = CE.pool_ref(y)
+    assert code[0, 0, 0].tolist() == [c for _, c in wins] and p[0, 0, 0].tolist() == [max(w) for w, _ in wins]
+    assert CE.pack_codes(code).tolist() == [[0 | 1 << 2 | 1 << 4 | 2 << 6, 3 | 0 << 2 | 1 << 4 | 2 << 6]]
+    assert CE.late_ties(y) == 4                                    # windows 1, 2, 3 and 6: a repeated maximum that does not start at code 0
+    # odd sizes: the last window has one column / one row, and elements outside the map never win
+    y = torch.tensor([[-1.0, -2.0, -3.0], [-4.0, -0.5, -6.0], [-7.0, -8.0, -9.0]], dtype=F64).reshape(1, 3, 3, 1)
+    p, code = CE.pool_ref(y)
+    assert p[0, :, :, 0].tolist() == [[-0.5, -3.0], [-7.0, -9.0]] and code[0, :, :, 0].tolist() == [[3, 0], [0, 0]]
+    # bit mask: bit r of byte k = channel 8 k + r, set where y > 0 (not >= 0, and -0.0 is not positive)
+    v = torch.tensor([[1, 0, -1, 2, -0.0, 0.5, 0, 3, 0, 0, 0, 0, 0, 0, 0, 9]], dtype=F64)
+    assert CE.relu_bits(v).tolist() == [[0b10101001, 0b10000000]]
+
+
+def test_generators_are_integer_valued_and_dense_where_stated():
+    g = CE.gen(0)
+    w = CE.signs((3, 3, 16, 8), g)
+    assert set(w.unique().tolist()) == {-1.0, 1.0}
+    t = CE.ternary((4000,), 0.25, g)
+    assert set(t.unique().tolist()) == {-1.0, 0.0, 1.0} and 0.2 < (t != 0).double().mean().item() < 0.3
+    s = CE.small((4000,), g)
+    assert s.min().item() == -8 and s.max().item() == 8 and torch.equal(s, s.round())
+    assert CE.density(9 * 512) == 1024 / 4608 and CE.density(27) == 1.0
+    inp = CE.forward_inputs((2, 17, 45, 8, 64, 3, 3, 1))
+    assert inp["cin_real"] == 3 and inp["x"][..., 3:].abs().sum().item() == 0 and tuple(inp["w"].shape) == (3, 3, 3, 64)
+    inp = CE.dgrad_inputs((1, 12, 12, 64, 30, 3, 3, 1))
+    assert inp["dy"].shape[-1] == 32 and inp["dy"][..., 30:].abs().sum().item() == 0
+    for dt in (torch.bfloat16, torch.float16):                     # every integer up to the limit is a value of both 16-bit types
+        v = torch.arange(-CE.LIMIT16, CE.LIMIT16 + 1, dtype=F64)
+        assert torch.equal(v.to(dt).double(), v)
+
+
+CASES = CE.all_cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_case_meets_its_conditions_on_the_reference(case):
+    """|value| <= 256 wherever the output is stored in 16 bits, an exact zero before every ReLU, a late tie in every pool case, the cut a
+    weight-gradient / split-K case is there for (256 CUs: the MI355X, and what the library assumes without a device)."""
+    figs = CE.check_case_inputs(case, cus=256)
+    print(case[0], figs)
+
+
+def test_tables_cover_every_dispatch_row_and_family():
+    import test_conv_dispatch_gpu as D
+    rows = [c for c in CASES if c[4].get("row")]
+    assert len(D.CASES) == 30 and len(rows) == len(D.CASES)
+    assert [c[0] for c in rows] == ["row_" + r[0] for r in D.CASES]
+    assert {r[3] for r in D.CASES} == {c[3] for c in rows}          # (30 rows, 29 kernel instances: pointwise and pointwise_pool_not_fused share one)
+    for (name, shp, call, family), c in zip(D.CASES, rows):
+        assert c[2] == (shp[0], shp[1], shp[2], shp[3], shp[4], shp[5], shp[5], shp[6]) and c[4]["row"] == call
+    ids = [c[0] for c in CASES]
+    assert len(set(ids)) == len(ids)
+
+
+def test_launch_plans_restate_the_sources_by_hand():
+    # conv_wgrad_rows.hip: (3,37,40,256 -> 128): 128-wide co tile, 4 ci tiles x 1 co tile, 2 strips per image, 3 * 2 * 37 = 222 rows, 256 / 4 = 64
+    # splits -> ceil(222 / 64) = 4 rows per split -> 56 splits; the slab holds one 9 x 4 x 512 float4 register tile per CU
+    p = CE.plan_wg_rows((3, 37, 40, 256, 128, 3, 3, 1), 256)
+    assert (p["cot"], p["pairs"], p["tiles_x"], p["total_rows"], p["rows_per_split"], p["splits"], p["slab"]) == (128, 4, 2, 222, 4, 56, True)
+    assert p["slab_bytes"] == 256 * 9 * 4 * 512 * 16
+    c = CE.wg_rows_cuts((3, 37, 40, 256, 128, 3, 3, 1), 256)
+    # split 9 owns rows 36..39: row 36 of strip 0 and rows 0..2 of strip 1 (a second pair of warm-up steps); of the five strip changes at rows
+    # 37, 74, 111, 148, 185 only 148 = 4 * 37 falls on a split boundary; the last split has 2 rows
+    assert c["crossing"] == 4 and c["mid_strip"] >= 1 and c["last_rows"] == 2 and c["last_strip_width"] == 8
+    # 72 output channels: padded to 128 -> one 128-wide tile; 8 channels: one 64-wide tile
+    assert CE.plan_wg_rows((2, 32, 64, 256, 72, 3, 3, 1), 256)["cot"] == 128 and CE.plan_wg_rows((2, 16, 32, 256, 8, 3, 3, 1), 256)["cot"] == 64
+    p = CE.plan_wg_rows((1, 33, 47, 64, 64, 3, 3, 1), 256)
+    assert (p["pairs"], p["total_rows"], p["rows_per_split"], p["splits"]) == (1, 66, 1, 66)
+    # (3,37,40,128 -> 64): 64-wide co tile, 2 ci tiles x 1 co tile, 222 rows on 256 / 2 = 128 splits -> 2 rows per split -> 111 splits; split 18 owns
+    # rows 36 and 37: the last row of strip 0 and the first of strip 1
+    p = CE.plan_wg_rows((3, 37, 40, 128, 64, 3, 3, 1), 256)
+    assert (p["cot"], p["pairs"], p["total_rows"], p["rows_per_split"], p["splits"], p["slab"]) == (64, 2, 222, 2, 111, True)
+    assert CE.wg_rows_cuts((3, 37, 40, 128, 64, 3, 3, 1), 256)["crossing"] == 3          # strip changes at the odd rows 37, 111, 185
+    # a long launch keeps the atomic form: 16 images of 160 x 160, 256 -> 256: 8 pairs, 32 splits of 400 rows
+    p = CE.plan_wg_rows((16, 160, 160, 256, 256, 3, 3, 1), 256)
+    assert (p["pairs"], p["total_rows"], p["rows_per_split"], p["splits"], p["slab"]) == (8, 12800, 400, 32, False)
+    assert not CE.wg_rows_eligible((1, 16, 16, 256, 256, 3, 3, 1)) and CE.wg_rows_eligible((1, 20, 20, 64, 64, 3, 3, 1))          # 16 / 32 < 0.6 <= 20 / 32
+    # conv_wgrad_pw.hip: (1,64,72,2304 -> 256): 144 K-steps of 32 pixels, 9 x 1 tiles of 256 x 256, 28 splits -> 6 steps per split -> 24 splits
+    p = CE.plan_wg_pw((1, 64, 72, 2304, 256, 1, 1, 1), 256)
+    assert (p["ksteps"], p["pairs"], p["steps_per_split"], p["splits"], p["slab"], p["slab_bytes"]) == (144, 9, 6, 24, True, 256 * 32 * 512 * 16)
+    assert not CE.wg_pw_eligible((1, 8, 8, 128, 64, 1, 1, 1)) and not CE.wg_pw_eligible((1, 64, 64, 64, 64, 1, 1, 1)) and CE.wg_pw_eligible((1, 64, 64, 128, 64, 1, 1, 1))
+    # conv_igemm.hip plan_splitk: (1,10,10,512 -> 512) forward: 128 x 128 tiles: 1 x 4 tiles, 72 K tiles; target 512 -> 128 splits, capped at 72 / 4 = 18,
+    # 4 K tiles each
+    assert CE.plan_splitk((1, 10, 10, 512, 512, 3, 3, 1), 0, 256) == (18, 4, 100, 512)
+    assert CE.conv_workspace_bytes((1, 10, 10, 512, 512, 3, 3, 1), 0, 256) == 18 * 100 * 512 * 4
+    # stride 2, data gradient: M = 2 * 20 * 20 pixels of dx, Co = 256 input channels, K = 9 * 512: 7 x 2 tiles -> ceil(512 / 14) = 37 -> capped at 18
+    assert CE.plan_splitk((2, 20, 20, 256, 512, 3, 3, 2), 1, 256) == (18, 4, 800, 256)
+    # thin head: 16-wide tiles of 64 pixels, target 8 per CU: (2,16,32,256 -> 8): 16 tiles, 36 K tiles -> min(128, 9) = 9 splits of 4
+    assert CE.plan_splitk((2, 16, 32, 256, 8, 3, 3, 1), 0, 256) == (9, 4, 1024, 8)
+    # a stride that is no power of two has no split data gradient; a large map does not split
+    assert CE.plan_splitk((1, 9, 9, 8, 8, 3, 3, 3), 1, 256)[0] == 1 and CE.plan_splitk((4, 136, 128, 64, 64, 3, 3, 1), 0, 256)[0] == 1
+
+
+def test_launch_plans_equal_the_library_queries():
+    """Without a device the library plans for 256 CUs (dh_cu_count), the MI355X's count: every listed shape, both directions."""
+    from dan_amd import build as B
+    from dan_amd._lib import ConvDesc
+    B.build()
+    L = ctypes.CDLL(B.OUT)
+    L.danhip_conv2d_workspace_bytes.restype = ctypes.c_size_t
+    L.danhip_conv2d_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), ctypes.c_int]
+    L.danhip_conv2d_bwd_weight_workspace_bytes.restype = ctypes.c_size_t
+    L.danhip_conv2d_bwd_weight_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
+    shapes = sorted({c[2] for c in CASES} | {(16, 160, 160, 256, 256, 3, 3, 1), (2, 80, 80, 512, 64, 1, 1, 1), (4, 40, 40, 1024, 1024, 1, 1, 1)})
+    for shp in shapes:
+        N, H, W, Cin, Cout, kh, kw, s = shp
+        d = ConvDesc()
+        d.N, d.H, d.W, d.Cin, d.Cout, d.kh, d.kw, d.stride = N, H, W, Cin, Cout, kh, kw, s
+        d.Ho, d.Wo = -(-H // s), -(-W // s)
+        for which in (0, 1):
+            assert L.danhip_conv2d_workspace_bytes(ctypes.byref(d), which) == CE.conv_workspace_bytes(shp, which, 256), (shp, which)
+        assert L.danhip_conv2d_bwd_weight_workspace_bytes(ctypes.byref(d)) == CE.wgrad_workspace_bytes(shp, 256), shp
