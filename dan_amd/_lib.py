@@ -163,6 +163,8 @@ SIGNATURES = {
     "danhip_comm_reduce_scatter_sum": [P, P, P, I64, ctypes.c_int, P],
     "danhip_comm_allgather": [P, P, P, I64, ctypes.c_int, P],
     "danhip_jpeg_entropy_decode_batch": [P, P, I32, I32, P, I64, P, P],
+    "danhip_jpeg_entropy_decode_batch_ex": [P, P, I32, I32, ctypes.c_uint32, P, I64, P, P],
+    "danhip_jpeg_scan_prepare_batch_ex": [P, P, I32, ctypes.c_uint32, P, ctypes.c_size_t, I64, P, P],
     "danhip_jpeg_reconstruct_batch": [P, I64, P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
     "danhip_jpeg_scan_prepare_batch": [P, P, I32, P, ctypes.c_size_t, I64, P, P],
     "danhip_jpeg_huffman_decode_batch": [P, P, ctypes.c_size_t, I32, P, I64, P, P, P, ctypes.c_size_t, P, P, P],
@@ -265,6 +267,8 @@ def _load(so_path, act_name):
         L.danhip_wider_eval_workspace_bytes.argtypes = [I32, I32, I32]
         L.danhip_jpeg_inspect.restype = ctypes.c_int           # a reason code (>= 0), not a status
         L.danhip_jpeg_inspect.argtypes = [P, I64, ctypes.POINTER(JpegInfo)]
+        L.danhip_jpeg_inspect_ex.restype = ctypes.c_int        # likewise (DANHIP_EINVAL for unknown flag bits)
+        L.danhip_jpeg_inspect_ex.argtypes = [P, I64, ctypes.c_uint32, ctypes.POINTER(JpegInfo)]
         L.danhip_jpeg_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_jpeg_workspace_bytes.argtypes = [P, I32]
         L.danhip_jpeg_output_bytes.restype = I64

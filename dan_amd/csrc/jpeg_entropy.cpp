@@ -1,6 +1,7 @@
 // Host half of the JPEG decoder (include/danhip.h, "Baseline JPEG decode"): marker parsing, validation and Huffman decoding of baseline
-// streams into de-zigzagged, column-major int16 coefficient blocks plus one descriptor per image for the two device launches of
-// jpeg_exact.hip.  Plain C++: no HIP call, usable in a process without a GPU.  A malformed stream ends here as a reason code; nothing
+// streams - and, where the caller allows them, of complete progressive streams ("Progressive streams") - into de-zigzagged, column-major
+// int16 coefficient blocks plus one descriptor per image for the two device launches of jpeg_exact.hip.  Plain C++: no HIP call, usable
+// in a process without a GPU.  A malformed stream ends here as a reason code; nothing
 // read from a file becomes an index on the device - the descriptors carry geometry derived from (width, height, mode) by jpeg_layout.h.
 #include <string.h>
 
@@ -17,6 +18,9 @@ namespace {
 const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};   // k-th coded -> row * 8 + col
+const uint8_t kZigColMajor[64] = {0,  8,  1,  2,  9,  16, 24, 17, 10, 3,  4,  11, 18, 25, 32, 40, 33, 26, 19, 12, 5,  6,
+                                  13, 20, 27, 34, 41, 48, 56, 49, 42, 35, 28, 21, 14, 7,  15, 22, 29, 36, 43, 50, 57, 58,
+                                  51, 44, 37, 30, 23, 31, 38, 45, 52, 59, 60, 53, 46, 39, 47, 54, 61, 62, 55, 63};   // (kZigzag[k] & 7) * 8 + (kZigzag[k] >> 3)
 
 struct Huff {
   bool defined = false;
@@ -33,7 +37,9 @@ struct Header {
   uint16_t quant[4][64];
   bool quant_defined[4] = {false, false, false, false};
   Huff dc[4], ac[4];
-  int64_t scan = 0;          // first byte of the entropy-coded segment
+  int64_t scan = 0;          // first byte of the entropy-coded segment; of a progressive frame: the FF of its first SOS marker
+  bool progressive = false;  // SOF2 (only with DANHIP_JPEG_ALLOW_PROGRESSIVE): dc / ac / restart are the state at the first SOS
+  int32_t ids[3] = {0, 0, 0};
 };
 
 bool build_huff(const uint8_t* counts, const uint8_t* syms, int n, bool is_dc, Huff* h) {
@@ -58,15 +64,32 @@ bool build_huff(const uint8_t* counts, const uint8_t* syms, int n, bool is_dc, H
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
-// Markers up to and including SOS.  0 = a stream the device path decodes.
-int parse_header(const uint8_t* d, int64_t n, Header* H) {
+int parse_dht(const uint8_t* s, int L, Header* H) {
+  int q = 0;
+  while (q < L) {
+    if (q + 17 > L) return DANHIP_JPEG_ETABLE;
+    const int tc = s[q] >> 4, t = s[q] & 15;
+    int cnt = 0;
+    for (int i = 0; i < 16; ++i) cnt += s[q + 1 + i];
+    if (tc > 1 || t > 3 || cnt > 256 || q + 17 + cnt > L) return DANHIP_JPEG_ETABLE;
+    if (!build_huff(s + q + 1, s + q + 17, cnt, tc == 0, tc ? &H->ac[t] : &H->dc[t])) return DANHIP_JPEG_ETABLE;
+    q += 17 + cnt;
+  }
+  return 0;
+}
+
+// Markers up to and including SOS (of a progressive frame: up to its first SOS; prog_walk goes on from there).  0 = a stream the device
+// path decodes.  flags: DANHIP_JPEG_ALLOW_PROGRESSIVE or 0.
+int parse_header(const uint8_t* d, int64_t n, Header* H, uint32_t flags = 0) {
   if (!d || n < 2 || d[0] != 0xFF || d[1] != 0xD8) return DANHIP_JPEG_ENOTJPEG;
   int64_t p = 2;
   bool have_sof = false;
-  int adobe_transform = -1, ids[3] = {0, 0, 0}, hv[3] = {0, 0, 0};
+  int adobe_transform = -1, hv[3] = {0, 0, 0};
+  int32_t* ids = H->ids;
   for (;;) {
     if (p >= n) return DANHIP_JPEG_ETRUNCATED;
     if (d[p] != 0xFF) return DANHIP_JPEG_ENOTJPEG;
+    const int64_t mark = p;
     while (p < n && d[p] == 0xFF) ++p;                          // fill bytes
     if (p >= n) return DANHIP_JPEG_ETRUNCATED;
     const int m = d[p++];
@@ -81,10 +104,10 @@ int parse_header(const uint8_t* d, int64_t n, Header* H) {
     const uint8_t* s = d + p + 2;
     const int L = len - 2;
     p += len;
-    if (m == 0xC2) return DANHIP_JPEG_EPROGRESSIVE;
+    if (m == 0xC2 && !(flags & DANHIP_JPEG_ALLOW_PROGRESSIVE)) return DANHIP_JPEG_EPROGRESSIVE;
     if (m >= 0xC9 && m <= 0xCF) return DANHIP_JPEG_EARITHMETIC;
     if (m == 0xC3 || (m >= 0xC5 && m <= 0xC8) || m == 0xDC || m == 0xDE || m == 0xDF) return DANHIP_JPEG_EUNSUPPORTED;
-    if (m == 0xC0 || m == 0xC1) {
+    if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
       if (have_sof) return DANHIP_JPEG_EUNSUPPORTED;
       if (L < 6) return DANHIP_JPEG_ETABLE;
       if (s[0] != 8) return DANHIP_JPEG_EPRECISION;
@@ -113,6 +136,7 @@ int parse_header(const uint8_t* d, int64_t n, Header* H) {
         else return DANHIP_JPEG_ESAMPLING;
       }
       H->width = w; H->height = h; H->ncomp = nc;
+      H->progressive = m == 0xC2;
       have_sof = true;
     } else if (m == 0xDB) {
       int q = 0;
@@ -128,16 +152,8 @@ int parse_header(const uint8_t* d, int64_t n, Header* H) {
         q += 1 + 64 * (pq + 1);
       }
     } else if (m == 0xC4) {
-      int q = 0;
-      while (q < L) {
-        if (q + 17 > L) return DANHIP_JPEG_ETABLE;
-        const int tc = s[q] >> 4, t = s[q] & 15;
-        int cnt = 0;
-        for (int i = 0; i < 16; ++i) cnt += s[q + 1 + i];
-        if (tc > 1 || t > 3 || cnt > 256 || q + 17 + cnt > L) return DANHIP_JPEG_ETABLE;
-        if (!build_huff(s + q + 1, s + q + 17, cnt, tc == 0, tc ? &H->ac[t] : &H->dc[t])) return DANHIP_JPEG_ETABLE;
-        q += 17 + cnt;
-      }
+      const int rc = parse_dht(s, L, H);
+      if (rc) return rc;
     } else if (m == 0xDD) {
       if (L != 2) return DANHIP_JPEG_ETABLE;
       H->restart = be16(s);
@@ -145,6 +161,13 @@ int parse_header(const uint8_t* d, int64_t n, Header* H) {
       if (L >= 12 && memcmp(s, "Adobe", 5) == 0) adobe_transform = s[11];
     } else if (m == 0xDA) {
       if (!have_sof) return DANHIP_JPEG_ETABLE;
+      if (H->progressive) {                                       // the scans themselves: prog_walk
+        for (int c = 0; c < H->ncomp; ++c)
+          if (!H->quant_defined[H->tq[c]]) return DANHIP_JPEG_ETABLE;
+        if (adobe_transform >= 0 && adobe_transform != 1) return DANHIP_JPEG_EADOBE;
+        H->scan = mark;
+        return 0;
+      }
       if (L < 1) return DANHIP_JPEG_ETABLE;
       const int ns = s[0];
       if (ns < 1 || ns > 4 || L != 4 + 2 * ns) return DANHIP_JPEG_ETABLE;
@@ -278,6 +301,286 @@ int decode_scan(const uint8_t* d, int64_t n, const Header& H, const DhJpegGeom& 
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Progressive frames (include/danhip.h, "Progressive streams"): the scans of T.81 G.2 as jdphuff.c decodes them, into the same coefficient
+// layout.  One walk over the markers behind the frame header does both jobs: without a coefficient buffer it validates the scan script
+// (every SOS against G.1.1.1.1, completeness at EOI) and finds where each scan's data end - this is the "header" of a progressive stream,
+// and a stream refused here owns no slot; with one it decodes every scan on the way.
+struct ProgScan {
+  int32_t ns, comp[3], td[3], ta, ss, se, ah, al;
+};
+
+enum { PROG_DC_FIRST, PROG_DC_REFINE, PROG_AC_FIRST, PROG_AC_REFINE };
+
+// one SOS of a progressive frame against the tables and the progression state so far; on success bits[c][k] (the Al a coefficient has
+// been sent down to, -1 = never) has advanced for every coefficient of the scan
+int prog_scan_header(const uint8_t* s, int L, const Header& H, int8_t bits[3][64], ProgScan* S) {
+  if (L < 1) return DANHIP_JPEG_ETABLE;
+  const int ns = s[0];
+  if (ns < 1 || ns > 4 || L != 4 + 2 * ns || ns > H.ncomp) return DANHIP_JPEG_ETABLE;
+  S->ns = ns;
+  int prev = -1;
+  for (int i = 0; i < ns; ++i) {
+    int c = -1;
+    for (int k = 0; k < H.ncomp; ++k)
+      if (H.ids[k] == s[1 + 2 * i]) c = k;
+    if (c < 0) return DANHIP_JPEG_ETABLE;
+    if (c <= prev) return DANHIP_JPEG_EUNSUPPORTED;             // components in another order than the frame's
+    prev = c;
+    S->comp[i] = c;
+    S->td[i] = s[2 + 2 * i] >> 4;
+    if (S->td[i] > 3 || (s[2 + 2 * i] & 15) > 3) return DANHIP_JPEG_ETABLE;
+  }
+  S->ta = s[2] & 15;
+  S->ss = s[1 + 2 * ns]; S->se = s[2 + 2 * ns]; S->ah = s[3 + 2 * ns] >> 4; S->al = s[3 + 2 * ns] & 15;
+  if (S->ss == 0) {
+    if (S->se != 0) return DANHIP_JPEG_EPROGRESSION;
+  } else if (ns != 1 || S->ss > S->se || S->se > 63) {
+    return DANHIP_JPEG_EPROGRESSION;
+  }
+  if (S->al > 13 || (S->ah != 0 && S->al != S->ah - 1)) return DANHIP_JPEG_EPROGRESSION;
+  for (int i = 0; i < ns; ++i) {
+    const int8_t* b = bits[S->comp[i]];
+    if (S->ss > 0 && b[0] < 0) return DANHIP_JPEG_EPROGRESSION;                 // a component's DC comes before its AC bands
+    for (int k = S->ss; k <= S->se; ++k) {
+      if (b[k] < 0 ? S->ah != 0 : (S->ah == 0 || S->ah != b[k])) return DANHIP_JPEG_EPROGRESSION;   // first scan: Ah = 0; later: Ah = previous Al, never twice
+    }
+  }
+  if (S->ss == 0) {
+    if (S->ah == 0)
+      for (int i = 0; i < ns; ++i)
+        if (!H.dc[S->td[i]].defined) return DANHIP_JPEG_ETABLE;
+  } else if (!H.ac[S->ta].defined) {
+    return DANHIP_JPEG_ETABLE;
+  }
+  for (int i = 0; i < ns; ++i)
+    for (int k = S->ss; k <= S->se; ++k) bits[S->comp[i]][k] = (int8_t)S->al;
+  return 0;
+}
+
+inline int prog_bit(Bits& b) {
+  if (b.cnt < 1) b.fill();
+  const int v = (int)b.peek(1);
+  b.skip(1);
+  return v;
+}
+
+// a correction bit for a coefficient that is already non-zero (G.1.2.3): the bit of this scan is added away from zero
+inline void prog_correct(Bits& b, int16_t* c, int p1) {
+  if (prog_bit(b) && (*c & p1) == 0) *c = (int16_t)(*c >= 0 ? *c + p1 : *c - p1);
+}
+
+// The entropy-coded data d[begin, end) of one scan.  An interleaved scan walks the frame's MCUs; a single-component scan walks that
+// component's own ceil(comp_w / 8) x ceil(comp_h / 8) blocks (not the padded grid), and there the restart interval counts those blocks.
+template <int KIND>
+int prog_decode_scan(const uint8_t* d, int64_t begin, int64_t end, const Header& H, const DhJpegGeom& g, const ProgScan& S, int16_t* coef) {
+  Bits b(d, end, begin);
+  int64_t plane[3] = {0, 0, 0};
+  for (int c = 1; c < g.ncomp; ++c) plane[c] = plane[c - 1] + (int64_t)g.blocks_w[c - 1] * g.blocks_h[c - 1];
+  const bool inter = S.ns > 1;
+  const int c0 = S.comp[0];
+  const int32_t ux = inter ? g.blocks_w[0] / g.hs : (g.comp_w[c0] + 7) / 8, uy = inter ? g.blocks_h[0] / g.vs : (g.comp_h[c0] + 7) / 8;
+  const int p1 = 1 << S.al;
+  const Huff& ha = H.ac[S.ta];
+  int pred[3] = {0, 0, 0};
+  int32_t eobrun = 0;
+  int64_t unit = 0;
+  int next_rst = 0;
+  for (int32_t y = 0; y < uy; ++y) {
+    for (int32_t x = 0; x < ux; ++x, ++unit) {
+      if (H.restart && unit && unit % H.restart == 0) {
+        if (!b.restart(next_rst)) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_ERESTART;
+        next_rst = (next_rst + 1) & 7;
+        pred[0] = pred[1] = pred[2] = 0;
+        eobrun = 0;
+      }
+      for (int i = 0; i < S.ns; ++i) {
+        const int c = S.comp[i];
+        const int ch = inter && c == 0 ? g.hs : 1, cv = inter && c == 0 ? g.vs : 1;
+        for (int v = 0; v < cv; ++v) {
+          for (int h = 0; h < ch; ++h) {
+            int16_t* blk = coef + 64 * (plane[c] + (int64_t)(y * cv + v) * g.blocks_w[c] + (x * ch + h));
+            if (KIND == PROG_DC_FIRST) {
+              b.fill();
+              const int s = decode_sym(b, H.dc[S.td[i]]);
+              if (s < 0 || s > 11) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;
+              if (s) { const int r = (int)b.peek(s); b.skip(s); pred[i] += extend(r, s); }
+              const int64_t val = (int64_t)pred[i] * p1;
+              if (val < -32768 || val > 32767) return DANHIP_JPEG_EHUFFMAN;
+              blk[0] = (int16_t)val;
+            } else if (KIND == PROG_DC_REFINE) {
+              if (prog_bit(b)) blk[0] = (int16_t)(blk[0] | p1);
+            } else if (KIND == PROG_AC_FIRST) {
+              if (eobrun > 0) {
+                --eobrun;
+              } else {
+                for (int k = S.ss; k <= S.se; ++k) {
+                  if (b.cnt < 32) b.fill();                                   // a symbol and its value take at most 16 + 15 bits
+                  const int rs = decode_sym(b, ha);
+                  if (rs < 0) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;
+                  const int r = rs >> 4, s = rs & 15;
+                  if (s) {
+                    k += r;
+                    if (k > S.se) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;
+                    const int64_t val = (int64_t)extend((int)b.peek(s), s) * p1;
+                    b.skip(s);
+                    if (val < -32768 || val > 32767) return DANHIP_JPEG_EHUFFMAN;
+                    blk[kZigColMajor[k]] = (int16_t)val;
+                  } else if (r == 15) {
+                    k += 15;
+                  } else {                                                    // EOBr: this band of this block and of the next run - 1 is over
+                    eobrun = 1 << r;
+                    if (r) { eobrun += (int32_t)b.peek(r); b.skip(r); }
+                    --eobrun;
+                    break;
+                  }
+                }
+              }
+            } else {
+              int k = S.ss;
+              if (eobrun == 0) {
+                for (; k <= S.se; ++k) {
+                  if (b.cnt < 32) b.fill();
+                  const int rs = decode_sym(b, ha);
+                  if (rs < 0) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;
+                  int r = rs >> 4, s = rs & 15;
+                  if (s) {
+                    if (s != 1) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;      // a new coefficient is +-1 at this precision
+                    s = prog_bit(b) ? p1 : -p1;
+                  } else if (r != 15) {
+                    eobrun = 1 << r;
+                    if (r) { eobrun += (int32_t)b.peek(r); b.skip(r); }
+                    break;                                                    // the rest of the band: correction bits only, below
+                  }
+                  // over r coefficients that are still zero, and every non-zero one on the way takes a correction bit
+                  do {
+                    int16_t* cf = blk + kZigColMajor[k];
+                    if (*cf != 0) prog_correct(b, cf, p1);
+                    else if (--r < 0) break;
+                    ++k;
+                  } while (k <= S.se);
+                  if (s) {
+                    if (k > S.se) return b.overrun() ? DANHIP_JPEG_ETRUNCATED : DANHIP_JPEG_EHUFFMAN;    // the run leaves the band
+                    blk[kZigColMajor[k]] = (int16_t)s;
+                  }
+                }
+              }
+              if (eobrun > 0) {
+                for (; k <= S.se; ++k) {
+                  int16_t* cf = blk + kZigColMajor[k];
+                  if (*cf != 0) prog_correct(b, cf, p1);
+                }
+                --eobrun;
+              }
+            }
+            if (b.overrun()) return DANHIP_JPEG_ETRUNCATED;
+          }
+        }
+      }
+    }
+  }
+  return 0;
+}
+
+// The DC value and every first AC value are range-checked where they are written; the +-p1 corrections of the refinement scans are not (on
+// a hostile stream one may wrap in the int16 it is stored in), so AC magnitudes are bounded here, by the block energy of the finished
+// coefficients as the baseline path checks it: a block that passes has every dequantised coefficient within +-1440.
+int prog_post_check(const Header& H, const DhJpegGeom& g, const int16_t* coef) {
+  const int16_t* blk = coef;
+  for (int c = 0; c < g.ncomp; ++c) {
+    const uint16_t* q = H.quant[H.tq[c]];
+    const int64_t nb = (int64_t)g.blocks_w[c] * g.blocks_h[c];
+    for (int64_t i = 0; i < nb; ++i, blk += 64) {
+      int64_t energy = 0;
+      for (int e = 0; e < 64; ++e) {
+        const int64_t dq = (int64_t)blk[e] * q[(e & 7) * 8 + (e >> 3)];
+        energy += dq * dq;
+      }
+      if (energy > DANHIP_JPEG_MAX_BLOCK_ENERGY) return DANHIP_JPEG_ECOEFRANGE;
+    }
+  }
+  return 0;
+}
+
+// The markers of a progressive frame from its first SOS to EOI.  coef == nullptr: validation alone (what the header phase runs);
+// else the slot is zeroed first - padding blocks that no single-component scan visits must read as zero - and every scan decoded.
+int prog_walk(const uint8_t* d, int64_t n, const Header& H0, const DhJpegGeom& g, int16_t* coef) {
+  Header H = H0;                                                 // DHT and DRI between scans change the copy
+  int8_t bits[3][64];
+  memset(bits, -1, sizeof(bits));
+  if (coef) memset(coef, 0, (size_t)g.coef_count * 2);
+  int64_t p = H0.scan;
+  for (;;) {
+    if (p >= n) return DANHIP_JPEG_ETRUNCATED;
+    if (d[p] != 0xFF) return DANHIP_JPEG_ENOTJPEG;
+    while (p < n && d[p] == 0xFF) ++p;                          // fill bytes
+    if (p >= n) return DANHIP_JPEG_ETRUNCATED;
+    const int m = d[p++];
+    if (m == 0x00) return DANHIP_JPEG_ENOTJPEG;
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+    if (m == 0xD8) return DANHIP_JPEG_ENOTJPEG;
+    if (m == 0xD9) break;
+    if (p + 2 > n) return DANHIP_JPEG_ETRUNCATED;
+    const int len = be16(d + p);
+    if (len < 2) return DANHIP_JPEG_ETABLE;
+    if (p + len > n) return DANHIP_JPEG_ETRUNCATED;
+    const uint8_t* s = d + p + 2;
+    const int L = len - 2;
+    p += len;
+    if (m == 0xC0 || m == 0xC1 || m == 0xC2) return DANHIP_JPEG_EUNSUPPORTED;           // a second frame
+    if (m >= 0xC9 && m <= 0xCF) return DANHIP_JPEG_EARITHMETIC;
+    if (m == 0xC3 || (m >= 0xC5 && m <= 0xC8) || m == 0xDC || m == 0xDE || m == 0xDF) return DANHIP_JPEG_EUNSUPPORTED;
+    if (m == 0xDB) return DANHIP_JPEG_ETABLE;                   // libjpeg latched the quantisation tables at a component's first scan
+    if (m == 0xC4) {
+      const int rc = parse_dht(s, L, &H);
+      if (rc) return rc;
+    } else if (m == 0xDD) {
+      if (L != 2) return DANHIP_JPEG_ETABLE;
+      H.restart = be16(s);
+    } else if (m == 0xDA) {
+      ProgScan S;
+      int rc = prog_scan_header(s, L, H, bits, &S);
+      if (rc) return rc;
+      int64_t q = p;                                             // the data end at the first marker that is no RSTn
+      for (;;) {
+        const void* f = q < n ? memchr(d + q, 0xFF, (size_t)(n - q)) : nullptr;
+        if (!f) return DANHIP_JPEG_ETRUNCATED;                  // no EOI
+        q = (const uint8_t*)f - d;
+        if (q + 1 >= n) return DANHIP_JPEG_ETRUNCATED;
+        const int x = d[q + 1];
+        if (x == 0x00 || (x >= 0xD0 && x <= 0xD7)) { q += 2; continue; }
+        if (x == 0xFF) { q += 1; continue; }
+        break;
+      }
+      if (coef) {
+        if (S.ss == 0) rc = S.ah == 0 ? prog_decode_scan<PROG_DC_FIRST>(d, p, q, H, g, S, coef) : prog_decode_scan<PROG_DC_REFINE>(d, p, q, H, g, S, coef);
+        else rc = S.ah == 0 ? prog_decode_scan<PROG_AC_FIRST>(d, p, q, H, g, S, coef) : prog_decode_scan<PROG_AC_REFINE>(d, p, q, H, g, S, coef);
+        if (rc) return rc;
+      }
+      p = q;
+    }
+    // APPn, COM and the remaining markers with a length: skipped
+  }
+  for (int c = 0; c < H.ncomp; ++c)                             // complete: every coefficient of every component down to Al = 0
+    for (int k = 0; k < 64; ++k)
+      if (bits[c][k] != 0) return DANHIP_JPEG_EPROGRESSION;
+  return coef ? prog_post_check(H, g, coef) : 0;
+}
+
+// header and geometry of one stream; for a progressive frame the header is the whole scan script
+int accept_stream(const uint8_t* d, int64_t n, uint32_t flags, Header* H, DhJpegGeom* g) {
+  int rc = parse_header(d, n, H, flags);
+  if (rc == 0 && !dh_jpeg_geometry(H->width, H->height, H->mode, g)) rc = DANHIP_JPEG_ETOOLARGE;
+  if (rc == 0 && H->progressive) rc = prog_walk(d, n, *H, *g, nullptr);
+  return rc;
+}
+
+bool bad_flags(const char* who, uint32_t flags) {
+  if (!(flags & ~(uint32_t)DANHIP_JPEG_ALLOW_PROGRESSIVE)) return false;
+  danhip_set_error("%s: unknown bits in flags 0x%x (DANHIP_JPEG_ALLOW_PROGRESSIVE is the one flag)", who, flags);
+  return true;
+}
+
 void clear_desc(danhip_jpeg_desc* d, int status) {
   memset(d, 0, sizeof(*d));
   d->status = status;
@@ -297,38 +600,42 @@ void fill_device_fields(danhip_jpeg_desc* d, const Header& H, const DhJpegGeom& 
   *out += dh_jpeg_align(g.out_bytes, 256);
   for (int t = 0; t < 4; ++t)
     for (int k = 0; k < 64; ++k) d->quant[t][k] = H.quant_defined[t] ? H.quant[t][k] : 1;
+  d->reserved[0] = H.progressive ? 1 : 0;                        // informational: the launcher does not look at it
 }
 
 }  // namespace
 
-extern "C" int danhip_jpeg_inspect(const uint8_t* data, int64_t n, danhip_jpeg_info* info) {
+extern "C" int danhip_jpeg_inspect_ex(const uint8_t* data, int64_t n, uint32_t flags, danhip_jpeg_info* info) {
   if (!info) { danhip_set_error("jpeg_inspect: info is NULL"); return DANHIP_EINVAL; }
   memset(info, 0, sizeof(*info));
+  if (bad_flags("jpeg_inspect_ex", flags)) return DANHIP_EINVAL;
   Header* H = new Header();
-  int rc = parse_header(data, n, H);
   DhJpegGeom g;
-  if (rc == 0 && !dh_jpeg_geometry(H->width, H->height, H->mode, &g)) rc = DANHIP_JPEG_ETOOLARGE;
+  const int rc = accept_stream(data, n, flags, H, &g);
   info->reason = rc;
   if (rc == 0) {
     info->width = H->width; info->height = H->height; info->ncomp = H->ncomp; info->mode = H->mode;
+    info->reserved = H->progressive ? 1 : 0;
     info->coef_count = g.coef_count;
   }
   delete H;
   return rc;
 }
 
-extern "C" int danhip_jpeg_entropy_decode_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, int32_t threads, int16_t* coef_out,
-                                                int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
+extern "C" int danhip_jpeg_inspect(const uint8_t* data, int64_t n, danhip_jpeg_info* info) { return danhip_jpeg_inspect_ex(data, n, 0, info); }
+
+extern "C" int danhip_jpeg_entropy_decode_batch_ex(const uint8_t* const* datas, const int64_t* sizes, int32_t B, int32_t threads, uint32_t flags,
+                                                   int16_t* coef_out, int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
   if (!datas || !sizes || B < 1 || B > 65535 || !descs_out || !status_out || coef_capacity < 0 || (coef_capacity > 0 && !coef_out)) {
     danhip_set_error("jpeg_entropy_decode_batch: bad arguments (1 <= B <= 65535, no NULL table)");
     return DANHIP_EINVAL;
   }
+  if (bad_flags("jpeg_entropy_decode_batch_ex", flags)) return DANHIP_EINVAL;
   std::vector<Header> hdr((size_t)B);
   std::vector<DhJpegGeom> geom((size_t)B);
   int64_t next = 0;
   for (int32_t i = 0; i < B; ++i) {                              // headers in order: the coefficient slots
-    int rc = parse_header(datas[i], sizes[i], &hdr[i]);
-    if (rc == 0 && !dh_jpeg_geometry(hdr[i].width, hdr[i].height, hdr[i].mode, &geom[i])) rc = DANHIP_JPEG_ETOOLARGE;
+    int rc = accept_stream(datas[i], sizes[i], flags, &hdr[i], &geom[i]);
     if (rc == 0 && geom[i].coef_count > coef_capacity - next) rc = DANHIP_JPEG_ECAPACITY;
     clear_desc(&descs_out[i], rc);
     status_out[i] = rc;
@@ -346,7 +653,8 @@ extern "C" int danhip_jpeg_entropy_decode_batch(const uint8_t* const* datas, con
       const int32_t i = cursor.fetch_add(1);
       if (i >= B) return;
       if (status_out[i]) continue;
-      status_out[i] = decode_scan(datas[i], sizes[i], hdr[i], geom[i], coef_out + descs_out[i].coef_offset);
+      int16_t* slot = coef_out + descs_out[i].coef_offset;
+      status_out[i] = hdr[i].progressive ? prog_walk(datas[i], sizes[i], hdr[i], geom[i], slot) : decode_scan(datas[i], sizes[i], hdr[i], geom[i], slot);
     }
   };
   if (T == 1) {
@@ -364,6 +672,11 @@ extern "C" int danhip_jpeg_entropy_decode_batch(const uint8_t* const* datas, con
     fill_device_fields(d, hdr[i], geom[i], &ws, &out);
   }
   return DANHIP_OK;
+}
+
+extern "C" int danhip_jpeg_entropy_decode_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, int32_t threads, int16_t* coef_out,
+                                                int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
+  return danhip_jpeg_entropy_decode_batch_ex(datas, sizes, B, threads, 0, coef_out, coef_capacity, descs_out, status_out);
 }
 
 namespace {
@@ -679,13 +992,14 @@ extern "C" size_t danhip_jpeg_scan_staging_bytes(const uint8_t* const* datas, co
   return (size_t)total;
 }
 
-extern "C" int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, void* staging, size_t staging_bytes,
-                                              int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
+extern "C" int danhip_jpeg_scan_prepare_batch_ex(const uint8_t* const* datas, const int64_t* sizes, int32_t B, uint32_t flags, void* staging,
+                                                 size_t staging_bytes, int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
   if (!datas || !sizes || B < 1 || B > 65535 || !descs_out || !status_out || coef_capacity < 0 || !staging || ((uintptr_t)staging & 15) ||
       staging_bytes < sizeof(DhScanHeader)) {
     danhip_set_error("jpeg_scan_prepare_batch: bad arguments (1 <= B <= 65535, no NULL table, staging 16-byte aligned)");
     return DANHIP_EINVAL;
   }
+  if (bad_flags("jpeg_scan_prepare_batch_ex", flags)) return DANHIP_EINVAL;
   std::vector<Header> hdr((size_t)B);
   std::vector<DhJpegGeom> geom((size_t)B);
   ScanPlan plan;
@@ -695,8 +1009,7 @@ extern "C" int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const
   for (int32_t i = 0; i < B; ++i) {
     DhScanImage& im = plan.images[(size_t)i];
     memset(&im, 0, sizeof(im));
-    int rc = parse_header(datas[i], sizes[i], &hdr[i]);
-    if (rc == 0 && !dh_jpeg_geometry(hdr[i].width, hdr[i].height, hdr[i].mode, &geom[i])) rc = DANHIP_JPEG_ETOOLARGE;
+    int rc = accept_stream(datas[i], sizes[i], flags, &hdr[i], &geom[i]);
     if (rc == 0 && geom[i].coef_count > coef_capacity - next) rc = DANHIP_JPEG_ECAPACITY;
     clear_desc(&descs_out[i], rc);
     status_out[i] = rc;
@@ -705,7 +1018,7 @@ extern "C" int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const
     const DhJpegGeom& g = geom[i];
     const int64_t coef_offset = next;                            // the slot belongs to the image whatever happens to it below
     next += g.coef_count;
-    if (sizes[i] - H.scan >= DH_HUFF_MAX_SCAN) {
+    if (H.progressive || sizes[i] - H.scan >= DH_HUFF_MAX_SCAN) {   // the device stage decodes one interleaved baseline scan
       rc = DANHIP_JPEG_HOSTONLY;
     } else {
       im.scan_offset = a16(plan.scan_bytes);
@@ -786,6 +1099,11 @@ extern "C" int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const
   return DANHIP_OK;
 }
 
+extern "C" int danhip_jpeg_scan_prepare_batch(const uint8_t* const* datas, const int64_t* sizes, int32_t B, void* staging, size_t staging_bytes,
+                                              int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out) {
+  return danhip_jpeg_scan_prepare_batch_ex(datas, sizes, B, 0, staging, staging_bytes, coef_capacity, descs_out, status_out);
+}
+
 extern "C" size_t danhip_jpeg_scan_device_bytes(const void* staging) {
   const DhScanHeader* h = (const DhScanHeader*)staging;
   return (!h || h->magic != DH_HUFF_MAGIC || h->used_bytes < 0) ? 0 : (size_t)h->used_bytes;
@@ -799,10 +1117,6 @@ extern "C" size_t danhip_jpeg_scan_workspace_bytes(const void* staging) {
 }
 
 namespace {
-
-const uint8_t kZigColMajor[64] = {0,  8,  1,  2,  9,  16, 24, 17, 10, 3,  4,  11, 18, 25, 32, 40, 33, 26, 19, 12, 5,  6,
-                                  13, 20, 27, 34, 41, 48, 56, 49, 42, 35, 28, 21, 14, 7,  15, 22, 29, 36, 43, 50, 57, 58,
-                                  51, 44, 37, 30, 23, 31, 38, 45, 52, 59, 60, 53, 46, 39, 47, 54, 61, 62, 55, 63};   // (kZigzag[k] & 7) * 8 + (kZigzag[k] >> 3)
 
 struct EmuCtx {                    // the context of jpeg_huffman.h with every index checked: a refused one is counted and reads as 0
   const uint8_t* scan; int64_t scan_bytes;

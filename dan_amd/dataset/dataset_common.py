@@ -247,7 +247,8 @@ def decode_record(payload, decode=True):
 
 # ---------------------------------------------------------------------------------------------------------- the batch generator
 def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_readers, num_preprocessing_threads, image_preprocessing_fn,
-                   anchor_encoder, num_epochs=None, is_training=True, seed=None, decode_device=None, decode_entropy="host"):
+                   anchor_encoder, num_epochs=None, is_training=True, seed=None, decode_device=None, decode_entropy="host",
+                   decode_progressive=False):
     """dataset_common.py:33-193 as a generator of batches (lists of per-image entries; stacking is the caller's, the anchor encoder's
     outputs have fixed shapes).
 
@@ -260,7 +261,9 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
     decode_device: None = images are decoded on the host with Pillow, one by one (image_preprocessing_fn gets numpy uint8 [H,W,3]); a
     device = the same records, selected by the same draws of the same generator, are decoded in groups of batch_size by
     dataset.jpeg.JpegDecoder and image_preprocessing_fn gets uint8 [H,W,3] tensors on that device (what preprocess_for_train takes).
-    decode_entropy: "host" | "device", JpegDecoder's entropy argument (where the Huffman stage of that decoder runs)."""
+    decode_entropy: "host" | "device", JpegDecoder's entropy argument (where the Huffman stage of that decoder runs).
+    decode_progressive: JpegDecoder's progressive argument (True: complete progressive records are decoded on the device as well, not by
+    the Pillow fallback)."""
     if split_name not in data_splits_num:
         raise ValueError('split name %s was not recognized.' % split_name)
     files = sorted(glob.glob(file_pattern.format(split_name)))
@@ -318,7 +321,7 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
                 yield entry(payload)
             return
         from .jpeg import JpegDecoder                                    # needs torch and libdanhip: only on this path
-        decoder = JpegDecoder(decode_device, entropy=decode_entropy)
+        decoder = JpegDecoder(decode_device, entropy=decode_entropy, progressive=decode_progressive)
         group = []
 
         def flush():

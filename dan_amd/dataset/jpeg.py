@@ -1,4 +1,5 @@
-"""Baseline JPEG records decoded on the device, bit for bit what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy upsampling) gives.
+"""Baseline - and, opt-in, complete progressive - JPEG records decoded on the device, bit for bit what Pillow (libjpeg-turbo, JDCT_ISLOW,
+fancy upsampling) gives.
 
 By default the serial half (markers, Huffman) runs in libdanhip on a few host threads (csrc/jpeg_entropy.cpp) and leaves quantised
 coefficients in a pinned buffer; dequantisation, inverse DCT, chroma upsampling and colour conversion are two launches per BATCH
@@ -8,6 +9,16 @@ launches per BATCH) writes the same coefficient buffer, bit for bit, on the devi
 image the device stage gave up on goes through the host stage, which stays the authority (stats["entropy_retry"]).
 A stream the host validator refuses (progressive, CMYK, 4:1:1, truncated, ... - include/danhip.h lists the reason codes) never reaches
 the device: it goes through dataset_common.decode_image (Pillow) and is counted in `stats`.
+
+progressive=True also takes SOF2 frames (stats["progressive"] counts them): 8 bit, Huffman, the same component counts and sampling modes,
+any number of scans whose script obeys T.81 G.1.1.1.1 (Ss = 0 implies Se = 0; AC scans carry one component; Al <= 13; Ah = 0 on a
+coefficient's first scan, afterwards Ah = its previous Al and Al = Ah - 1; DC before AC; nothing twice at the same precision), DHT and DRI
+between scans - and COMPLETE at EOI: every coefficient of every component sent down to Al = 0.  Their entropy stage is the host's whatever
+`entropy` says (with entropy="device" they are counted in stats["entropy_retry"], as any host-only image); behind the coefficient buffer
+the same two launches run, unchanged.  The completion rule exists because libjpeg decodes an incomplete progression through another path
+(inter-block smoothing, coarse coefficients left as they are) that the kernels have no counterpart for: such a file, like any other
+script the validator does not take, is refused with reason "progression" and goes to Pillow.  The default stays False: a progressive
+record then takes the fallback as before (reason "progressive").
 
     dec = JpegDecoder(torch.device("cuda:0"))
     images = dec.decode_batch([record_bytes, ...])        # uint8 [H,W,3] device tensors: what preprocess_for_train takes"""
@@ -22,7 +33,8 @@ from . import dataset_common
 MAX_THREADS = 16                                          # DANHIP_JPEG_MAX_THREADS
 REASONS = {1: "not_jpeg", 2: "truncated", 3: "progressive", 4: "arithmetic", 5: "precision", 6: "multiscan", 7: "components", 8: "adobe",
            9: "rgb_ids", 10: "sampling", 11: "huffman", 12: "too_large", 13: "table", 14: "unsupported", 15: "restart", 16: "coef_range",
-           17: "capacity"}
+           17: "capacity", 18: "progression"}
+ALLOW_PROGRESSIVE = 1                                     # DANHIP_JPEG_ALLOW_PROGRESSIVE
 _DESC_BYTES = ctypes.sizeof(JpegDesc)
 
 
@@ -31,7 +43,7 @@ def _align(v, a=256):
 
 
 class JpegDecoder(object):
-    def __init__(self, device, threads=4, entropy="host"):
+    def __init__(self, device, threads=4, entropy="host", progressive=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("JpegDecoder decodes on the GPU; use dataset_common.decode_image on the host")
@@ -39,9 +51,11 @@ class JpegDecoder(object):
             raise ValueError("entropy must be 'host' or 'device', got %r" % (entropy,))
         self.entropy = entropy
         self.threads = max(1, min(int(threads), MAX_THREADS))
-        # entropy_device: images whose coefficients came from the device; entropy_retry: images the device stage handed back to the host stage
+        self.flags = ALLOW_PROGRESSIVE if progressive else 0
+        # entropy_device: images whose coefficients came from the device; entropy_retry: images the device stage handed back to the host stage;
+        # progressive: progressive images the host stage decoded (progressive=True)
         self.stats = {"device": 0, "fallback": {}, "launches": 0, "entropy_seconds": 0.0, "entropy_device": 0, "entropy_retry": 0,
-                      "upload_bytes": 0, "huffman_ms": None}
+                      "upload_bytes": 0, "huffman_ms": None, "progressive": 0}
         self.time_huffman = False                         # diagnosis (tools/bench_jpeg_entropy.py): device-event time of the Huffman launches
         self._pinned = None                               # [descriptors | coefficients] of the batch in flight
         self._uploaded = None                             # event after the upload that reads _pinned
@@ -80,8 +94,12 @@ class JpegDecoder(object):
         L = lib()
         info = JpegInfo()
         capacity = 0
-        for d in datas:                                   # headers only: the size of the coefficient buffer
-            if L.danhip_jpeg_inspect(d, len(d), ctypes.byref(info)) == 0:
+        # headers only: the size of the coefficient buffer.  A progressive stream's header is its scan script, so with progressive=True its
+        # markers are walked to EOI here and again in the batch call's serial header loop (and once more by the prepare call with
+        # entropy="device") before the threaded decode: memchr passes, small next to the entropy stage, but serial work per image that a
+        # baseline stream does not have.  A batch call that reports the capacity itself would save them.
+        for d in datas:
+            if L.danhip_jpeg_inspect_ex(d, len(d), self.flags, ctypes.byref(info)) == 0:
                 capacity += info.coef_count
         head = _align(B * _DESC_BYTES)
         pinned = self._staging(head + 2 * capacity)
@@ -91,7 +109,7 @@ class JpegDecoder(object):
         ptrs = (ctypes.c_char_p * B)(*datas)
         sizes = (ctypes.c_int64 * B)(*[len(d) for d in datas])
         t0 = time.perf_counter()
-        call("danhip_jpeg_entropy_decode_batch", ptrs, sizes, B, self.threads, ctypes.c_void_p(base + head), capacity, descs, status)
+        call("danhip_jpeg_entropy_decode_batch_ex", ptrs, sizes, B, self.threads, self.flags, ctypes.c_void_p(base + head), capacity, descs, status)
         self.stats["entropy_seconds"] += time.perf_counter() - t0
         out_bytes = L.danhip_jpeg_output_bytes(descs, B)
         results = [None] * B
@@ -114,6 +132,7 @@ class JpegDecoder(object):
                     d = descs[i]
                     results[i] = out[d.out_offset:d.out_offset + d.height * d.width * 3].view(d.height, d.width, 3)
                     self.stats["device"] += 1
+                    self.stats["progressive"] += d.reserved[0]            # 1: a progressive frame
         return self._fallback(datas, status, results)
 
     def _decode_device_entropy(self, datas):
@@ -123,7 +142,7 @@ class JpegDecoder(object):
         info = JpegInfo()
         capacity = 0
         for d in datas:
-            if L.danhip_jpeg_inspect(d, len(d), ctypes.byref(info)) == 0:
+            if L.danhip_jpeg_inspect_ex(d, len(d), self.flags, ctypes.byref(info)) == 0:
                 capacity += info.coef_count
         ptrs = (ctypes.c_char_p * B)(*datas)
         sizes = (ctypes.c_int64 * B)(*[len(d) for d in datas])
@@ -135,12 +154,12 @@ class JpegDecoder(object):
         status = (ctypes.c_int32 * B)()
         staging = ctypes.c_void_p(base + head)
         t0 = time.perf_counter()
-        call("danhip_jpeg_scan_prepare_batch", ptrs, sizes, B, staging, need, capacity, descs, status)
+        call("danhip_jpeg_scan_prepare_batch_ex", ptrs, sizes, B, self.flags, staging, need, capacity, descs, status)
         self.stats["entropy_seconds"] += time.perf_counter() - t0
         used = L.danhip_jpeg_scan_device_bytes(staging)
         out_bytes = L.danhip_jpeg_output_bytes(descs, B)
         results = [None] * B
-        retry = [i for i in range(B) if status[i] < 0]    # DANHIP_JPEG_HOSTONLY
+        retry = [i for i in range(B) if status[i] < 0]    # DANHIP_JPEG_HOSTONLY (a progressive frame among them)
         if out_bytes > 0:                                 # at least one image for the device
             with torch.cuda.device(self.device):
                 dev_in = torch.empty(head + used, dtype=torch.uint8, device=self.device)

@@ -706,6 +706,37 @@ int danhip_jpeg_huffman_decode_batch(const void* staging_host, const void* stagi
 int danhip_jpeg_entropy_emulate_batch(const void* staging, size_t staging_bytes, int32_t B, const danhip_jpeg_desc* descs, int16_t* coef_out,
                                       int64_t coef_count, int32_t sync_rounds, int32_t* status_out, int64_t* range_errors);
 
+/* --------------------------------------------------------------------------------------------------
+ * Progressive streams (ABI version 8), opt-in: with DANHIP_JPEG_ALLOW_PROGRESSIVE in `flags` the host entropy stage also takes SOF2 frames
+ * (8 bit, Huffman, the component counts and sampling factors of the baseline path) and leaves the SAME coefficient array and descriptors
+ * behind, so that danhip_jpeg_reconstruct_batch - which re-derives everything from (width, height, mode) - runs unchanged: a progressive
+ * file that is complete gives libjpeg the same kind of coefficient array as a baseline file, and the same dequantisation, islow IDCT, fancy
+ * upsampling and colour conversion follow.  Without the flag (and through the entry points above, which pass flags = 0) SOF2 stays
+ * DANHIP_JPEG_EPROGRESSIVE.
+ * Accepted: any number of scans, DHT between scans (tables are latched per scan), DRI between scans, every scan obeying T.81 G.1.1.1.1 as
+ * libjpeg's start_pass_phuff_decoder checks it - Ss = 0 implies Se = 0; an AC scan has ONE component and 1 <= Ss <= Se <= 63; Al <= 13;
+ * Ah = 0 on the first scan of a coefficient, afterwards Ah = that coefficient's previous Al and Al = Ah - 1; a component's DC before any of
+ * its AC bands; no coefficient twice at the same precision - and, at EOI, COMPLETE: every coefficient 0..63 of every component sent down to
+ * Al = 0.  Anything else is DANHIP_JPEG_EPROGRESSION (libjpeg's "warn and go on" is not reproduced).  The completion rule exists because
+ * libjpeg decodes an incomplete progression through another path - inter-block smoothing of the coefficients not yet refined, coarse
+ * coefficients left as they are - for which the device kernels have no counterpart: such a file differs from its complete version by tens
+ * of grey levels and stays with the caller's fallback.  A DQT after the first SOS is DANHIP_JPEG_ETABLE (libjpeg latches a component's
+ * quantisation table at its first scan); a stream that ends before EOI or meets a marker inside a scan's data is DANHIP_JPEG_ETRUNCATED.
+ * The DC range and block energy checks of the baseline path are applied to the finished coefficients, with the same reason codes.
+ * The device Huffman stage does not take progressive scans: danhip_jpeg_scan_prepare_batch_ex hands an accepted progressive header its
+ * coefficient slot, no device segments and the status DANHIP_JPEG_HOSTONLY (the caller sends it through the host stage), or the reason
+ * code the host stage gives.
+ * An accepted progressive frame is marked by info.reserved = 1 and desc.reserved[0] = 1 (0 otherwise); the launcher does not read them.
+ * Unknown bits in flags: DANHIP_EINVAL.  flags = 0: exactly the entry point without _ex.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_ALLOW_PROGRESSIVE 1
+#define DANHIP_JPEG_EPROGRESSION 18  /* a progressive frame whose scan script is not taken: a scan against T.81 G.1.1.1.1, or incomplete at EOI */
+int danhip_jpeg_inspect_ex(const uint8_t* data, int64_t n, uint32_t flags, danhip_jpeg_info* info);
+int danhip_jpeg_entropy_decode_batch_ex(const uint8_t* const* datas, const int64_t* sizes, int32_t B, int32_t threads, uint32_t flags,
+                                        int16_t* coef_out, int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out);
+int danhip_jpeg_scan_prepare_batch_ex(const uint8_t* const* datas, const int64_t* sizes, int32_t B, uint32_t flags, void* staging,
+                                      size_t staging_bytes, int64_t coef_capacity, danhip_jpeg_desc* descs_out, int32_t* status_out);
+
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange (csrc/comm.cpp): the all-reduce(sum) of tf_replicate_model_fn.py:633-645
  * (_compute_sum_on_device: add_n over the towers' gradients, after _scale_loss :615-631 put 1/N into every tower's loss) issued

@@ -4,8 +4,11 @@ dataset.jpeg.JpegDecoder.decode_batch at 1 / 4 / 8 / 16 host threads, batch 16, 
 paths alternating in the same run.  Also: host entropy ms per image, the two launches' time (device events around
 danhip_jpeg_reconstruct_batch; per-kernel times come from a rocprofv3 --kernel-trace --stats run of this script with --kernels-only),
 their algorithmic bytes/s, and the box's copy rate measured the way tools/calibrate_peaks.py measures it.  Prints one JSON object.
+--progressive: the same images encoded as progressive streams; JpegDecoder(progressive=True) at 1 / 4 / 8 / 16 host threads against
+JpegDecoder(progressive=False) - every image through the Pillow fallback and its own upload, what a progressive record costs by default -
+the arms alternating inside every round: seconds per batch of 16 (median, min, max over rounds x batches) and the host entropy stage's share.
 
-    python tools/bench_jpeg.py [--images 64] [--rounds 3] [--kernels-only]"""
+    python tools/bench_jpeg.py [--images 64] [--rounds 3] [--kernels-only | --progressive]"""
 import argparse
 import ctypes
 import io
@@ -28,7 +31,9 @@ H, W, BATCH = 768, 1024, 16
 
 
 def encode_set(n, kw, seed):
-    from PIL import Image
+    from PIL import Image, ImageFile
+    if kw.get("progressive"):
+        ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 4 * H * W)               # a progressive encode needs the whole stream in one buffer
     out = []
     for i in range(n):
         r = np.random.RandomState(seed + i)
@@ -91,6 +96,45 @@ def launches_time(datas, dev, it=20):
             "two_launches_GBps_algorithmic": round((idct_bytes + rgb_bytes) / ms / 1e6, 1)}
 
 
+def batch_times(dec, datas):
+    """seconds of every batch of 16, each timed to the end of its device work"""
+    out = []
+    for i in range(0, len(datas), BATCH):
+        t0 = time.perf_counter()
+        keep = dec.decode_batch(datas[i:i + BATCH])
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+        del keep
+    return out
+
+
+def progressive_mode(a, dev):
+    res = {"device": torch.cuda.get_device_name(0), "image": [H, W], "batch": BATCH, "images_per_mode": a.images, "rounds": a.rounds, "modes": {}}
+    for m, (name, kw) in enumerate(MODES):
+        datas = encode_set(a.images, dict(kw, progressive=True), 1000 * m)
+        arms = {"fallback": JpegDecoder(dev, progressive=False)}
+        arms.update({"threads_%d" % t: JpegDecoder(dev, threads=t, progressive=True) for t in (1, 4, 8, 16)})
+        for dec in arms.values():
+            batch_times(dec, datas[:BATCH])                                   # warm-up: code objects, pinned buffer, allocator
+            dec.stats["entropy_seconds"] = 0.0
+        times = {k: [] for k in arms}
+        for _ in range(a.rounds):                                             # alternate the arms inside every round
+            for k, dec in arms.items():
+                times[k] += batch_times(dec, datas)
+        row = {"jpeg_bytes_per_image": int(np.mean([len(d) for d in datas])), "ms_per_batch16": {}, "entropy_ms_per_batch16": {}}
+        for k, v in times.items():
+            row["ms_per_batch16"][k] = {"median": round(1e3 * float(np.median(v)), 2), "min": round(1e3 * min(v), 2), "max": round(1e3 * max(v), 2), "n": len(v)}
+            if k != "fallback":
+                row["entropy_ms_per_batch16"][k] = round(1e3 * arms[k].stats["entropy_seconds"] / len(v), 2)
+        row["fallback_over_threads_4"] = round(row["ms_per_batch16"]["fallback"]["median"] / row["ms_per_batch16"]["threads_4"]["median"], 2)
+        row["fallbacks_with_progressive_on"] = sum(sum(d.stats["fallback"].values()) for k, d in arms.items() if k != "fallback")
+        row["launches_per_batch_threads_4"] = arms["threads_4"].stats["launches"] / (len(times["threads_4"]) + 1)
+        got = arms["threads_4"].decode_batch(datas[:BATCH])
+        row["equal_to_pillow"] = all(torch.equal(g.cpu(), torch.from_numpy(DC.decode_image(d))) for g, d in zip(got, datas[:BATCH]))
+        res["modes"][name] = row
+    print(json.dumps(res))
+
+
 def copy_rate(dev):
     n = 16 * 640 * 640 * 64                                                   # as tools/calibrate_peaks.py: 839 MB of bf16, read + write
     x = torch.zeros(n, device=dev, dtype=torch.bfloat16)
@@ -112,10 +156,13 @@ def main():
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kernels-only", action="store_true", help="only the two launches (for a rocprofv3 --kernel-trace --stats run)")
+    ap.add_argument("--progressive", action="store_true", help="progressive streams: JpegDecoder(progressive=True) against the Pillow fallback")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_jpeg.py measures on the GPU; none is visible")
     dev = torch.device("cuda:0")
+    if a.progressive:
+        return progressive_mode(a, dev)
     res = {"device": torch.cuda.get_device_name(0), "image": [H, W], "batch": BATCH, "images_per_mode": a.images, "modes": {}}
     if not a.kernels_only:
         res["copy_GBps_read_plus_write"] = copy_rate(dev)
