@@ -35,6 +35,14 @@ class PackEntry(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("kh", "kw", "cin", "cin_real", "cout", "rows_f", "cols_f", "rows_b", "cols_b", "co8", "first_block", "pad_")]
 
 
+HEADS_MAX_LEVELS = 8
+
+
+class HeadLevel(ctypes.Structure):
+    """danhip_head_level: one pyramid level of danhip_heads_split_fwd / danhip_heads_grad_pad."""
+    _fields_ = [("h", ctypes.c_void_p), ("dy", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in ("HW", "Ch", "nneg", "npos", "off", "co_pad")]
+
+
 class JpegInfo(ctypes.Structure):
     """danhip_jpeg_info"""
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "ncomp", "mode", "reason", "reserved")] + [("coef_count", ctypes.c_int64)]
@@ -139,6 +147,8 @@ SIGNATURES = {
     "danhip_cast_pad_f32_to_bf16": [P, P, P, I64, I32, I32, P],
     "danhip_head_split_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, I32, P],
     "danhip_head_split_bwd": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P],
+    "danhip_heads_split_fwd": [ctypes.POINTER(HeadLevel), I32, P, P, I32, I32, P],
+    "danhip_heads_grad_pad": [ctypes.POINTER(HeadLevel), I32, P, P, I32, I32, P],
     "danhip_hard_neg_select": [P, P, P, P, P, P, I32, I32, FL, ctypes.c_int, P],
     "danhip_detection_loss_fwd": [P, P, P, P, P, P, P, P, I32, I32, P],
     "danhip_detection_loss_bwd": [P, P, P, P, P, P, P, FL, FL, I32, I32, P],

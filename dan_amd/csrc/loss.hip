@@ -61,6 +61,128 @@ __global__ void head_split_bwd_kernel(const float* __restrict__ h, const float* 
   }
 }
 
+// ---------------------------------------------------------------- all levels of the heads in one launch
+// The level table is a kernel ARGUMENT (by value): nothing is copied to the device per call.  row0[l] = first flat row of level l
+// (rows of a level = B * HW), row0[n] = all rows; a thread finds the level of its flat row by a scan of at most 8 entries.
+struct HeadsTable {
+  const float* h[DANHIP_HEADS_MAX_LEVELS];
+  bf16_t* dy[DANHIP_HEADS_MAX_LEVELS];
+  long row0[DANHIP_HEADS_MAX_LEVELS + 1];
+  int HW[DANHIP_HEADS_MAX_LEVELS], Ch[DANHIP_HEADS_MAX_LEVELS], nneg[DANHIP_HEADS_MAX_LEVELS], off[DANHIP_HEADS_MAX_LEVELS],
+      co_pad[DANHIP_HEADS_MAX_LEVELS];
+  int n;
+};
+
+// per level exactly head_split_fwd_kernel
+__global__ void heads_split_fwd_kernel(const HeadsTable t, float* __restrict__ loc, float* __restrict__ cls, int A) {
+  const long total = t.row0[t.n];
+  for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (long)gridDim.x * blockDim.x) {
+    int l = 0;
+    while (l + 1 < t.n && m >= t.row0[l + 1]) ++l;
+    const long ml = m - t.row0[l];
+    const int HW = t.HW[l], Ch = t.Ch[l], nneg = t.nneg[l], npos = Ch - 4 - nneg;
+    const int b = (int)(ml / HW), p = (int)(ml % HW);
+    const float* r = t.h[l] + ml * Ch;
+    const long a = (long)b * A + t.off[l] + p;
+    *reinterpret_cast<float4*>(loc + a * 4) = make_float4(r[0], r[1], r[2], r[3]);
+    float ng = r[4];
+    for (int i = 1; i < nneg; ++i) ng = fmaxf(ng, r[4 + i]);
+    float ps = r[4 + nneg];
+    for (int i = 1; i < npos; ++i) ps = fmaxf(ps, r[4 + nneg + i]);
+    *reinterpret_cast<float2*>(cls + a * 2) = make_float2(ng, ps);
+  }
+}
+
+__device__ __forceinline__ uint4 pack8_rne(const float* f) {  // eight conversions as cast_pad_kernel makes them (f2bf each)
+  uint4 o;
+  o.x = (unsigned)f2bf(f[0]) | ((unsigned)f2bf(f[1]) << 16);
+  o.y = (unsigned)f2bf(f[2]) | ((unsigned)f2bf(f[3]) << 16);
+  o.z = (unsigned)f2bf(f[4]) | ((unsigned)f2bf(f[5]) << 16);
+  o.w = (unsigned)f2bf(f[6]) | ((unsigned)f2bf(f[7]) << 16);
+  return o;
+}
+
+// per level head_split_bwd_kernel -> cast_pad_kernel (no ReLU operand) without the fp32 dY in between: one thread per row forms the row's
+// gradient in registers with the same operations in the same order, rounds it with the same conversion and stores the channel-padded
+// 16-bit row with 16-byte stores (a dY row is 16 or 32 bytes).  Rows of at most 8 channels (every reference configuration: 4 + 1 + 1 or
+// 4 + 3 + 1) are loaded whole with 16- or 8-byte loads; wider rows walk their channels as the per-level kernel does.
+__global__ void heads_grad_pad_kernel(const HeadsTable t, const float* __restrict__ dloc, const float* __restrict__ dcls, int A) {
+  const long total = t.row0[t.n];
+  for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < total; m += (long)gridDim.x * blockDim.x) {
+    int l = 0;
+    while (l + 1 < t.n && m >= t.row0[l + 1]) ++l;
+    const long ml = m - t.row0[l];
+    const int HW = t.HW[l], Ch = t.Ch[l], nneg = t.nneg[l], co_pad = t.co_pad[l];
+    const int b = (int)(ml / HW), p = (int)(ml % HW);
+    const float* r = t.h[l] + ml * Ch;
+    const long a = (long)b * A + t.off[l] + p;
+    const float4 dl = *reinterpret_cast<const float4*>(dloc + a * 4);
+    const float2 dc = *reinterpret_cast<const float2*>(dcls + a * 2);
+    uint4* o = reinterpret_cast<uint4*>(t.dy[l] + ml * co_pad);
+    const int pos0 = 4 + nneg;                          // first channel of the positive group
+    if (Ch <= 8) {
+      float v[8];
+      if (Ch == 8) {                                    // 32-byte rows
+        const float4 lo = reinterpret_cast<const float4*>(r)[0], hi = reinterpret_cast<const float4*>(r)[1];
+        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+      } else if (Ch == 6) {                             // 24-byte rows
+        const float2 c0 = reinterpret_cast<const float2*>(r)[0], c1 = reinterpret_cast<const float2*>(r)[1], c2 = reinterpret_cast<const float2*>(r)[2];
+        v[0] = c0.x; v[1] = c0.y; v[2] = c1.x; v[3] = c1.y; v[4] = c2.x; v[5] = c2.y; v[6] = 0.f; v[7] = 0.f;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = i < Ch ? r[i] : 0.f;
+      }
+      // the two running maxima, folded in ascending channel order from each group's first channel
+      float mxn = v[4], mxp = 0.f;
+#pragma unroll
+      for (int j = 5; j < 8; ++j) {
+        if (j < pos0) mxn = fmaxf(mxn, v[j]);
+        else if (j == pos0) mxp = v[j];
+        else if (j < Ch) mxp = fmaxf(mxp, v[j]);
+      }
+      int cn = 0, cp = 0;
+#pragma unroll
+      for (int j = 4; j < 8; ++j) {
+        if (j < pos0) cn += (v[j] == mxn);
+        else if (j < Ch) cp += (v[j] == mxp);
+      }
+      const float gn = dc.x / (float)cn, gp = dc.y / (float)cp;
+      float g[8] = {dl.x, dl.y, dl.z, dl.w, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 4; j < 8; ++j) {
+        if (j < pos0) g[j] = v[j] == mxn ? gn : 0.f;
+        else if (j < Ch) g[j] = v[j] == mxp ? gp : 0.f;
+      }
+      o[0] = pack8_rne(g);
+      for (int c = 8; c < co_pad; c += 8) o[c >> 3] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+      float mx[2], gg[2];
+      for (int grp = 0; grp < 2; ++grp) {
+        const int s = grp == 0 ? 4 : pos0, n = grp == 0 ? nneg : Ch - pos0;
+        float q = r[s];
+        for (int i = 1; i < n; ++i) q = fmaxf(q, r[s + i]);
+        int cnt = 0;
+        for (int i = 0; i < n; ++i) cnt += (r[s + i] == q);
+        mx[grp] = q;
+        gg[grp] = (grp == 0 ? dc.x : dc.y) / (float)cnt;
+      }
+      for (int c = 0; c < co_pad; c += 8) {
+        float g[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const int j = c + k;
+          float x = 0.f;
+          if (j < 4) x = j == 0 ? dl.x : j == 1 ? dl.y : j == 2 ? dl.z : dl.w;
+          else if (j < pos0) x = r[j] == mx[0] ? gg[0] : 0.f;
+          else if (j < Ch) x = r[j] == mx[1] ? gg[1] : 0.f;
+          g[k] = x;
+        }
+        o[c >> 3] = pack8_rne(g);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- hard-negative mining
 // score = label==0 ? -softmax(cls)[0] : -1 ;  counts[b*2+0] += (label>0), counts[b*2+1] += (label==0)
 __global__ void hard_neg_scores_kernel(const float* __restrict__ cls, const int* __restrict__ labels, float* __restrict__ score,
@@ -333,6 +455,67 @@ extern "C" int danhip_head_split_bwd(const float* h, const float* dloc, const fl
   DH_REQUIRE(anchor_offset >= 0 && anchor_offset + HW <= A, DANHIP_EINVAL, "head_split_bwd: anchor range out of bounds");
   hipLaunchKernelGGL(head_split_bwd_kernel, dim3(grid_for((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, h, dloc, dcls, dy, B, HW, Ch,
                      nneg, npos, A, anchor_offset);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
+
+// Checks a level table and lays it out for the kernels.  -> 0, or DANHIP_EINVAL with the message set.
+static int heads_table(const danhip_head_level* lv, int32_t n, int32_t B, int32_t A, bool grad, const char* who, HeadsTable* t) {
+  DH_REQUIRE(lv && B > 0 && A > 0, DANHIP_EINVAL, "%s: bad arguments", who);
+  DH_REQUIRE(n >= 1 && n <= DANHIP_HEADS_MAX_LEVELS, DANHIP_EINVAL, "%s: %d levels (1 .. %d fit the table)", who, n, DANHIP_HEADS_MAX_LEVELS);
+  int order[DANHIP_HEADS_MAX_LEVELS];
+  t->n = n;
+  t->row0[0] = 0;
+  for (int l = 0; l < n; ++l) {
+    const danhip_head_level& e = lv[l];
+    DH_REQUIRE(e.h && (!grad || e.dy), DANHIP_EINVAL, "%s: level %d: null pointer", who, l);
+    DH_REQUIRE(((uintptr_t)e.h & 15) == 0 && (!grad || ((uintptr_t)e.dy & 15) == 0), DANHIP_EINVAL, "%s: level %d: pointers must be 16-byte aligned", who, l);
+    DH_REQUIRE(e.HW > 0 && e.nneg >= 1 && e.npos >= 1 && e.Ch == 4 + e.nneg + e.npos, DANHIP_EINVAL,
+               "%s: level %d: Ch=%d must be 4 + nneg + npos (nneg=%d, npos=%d, depth 1)", who, l, e.Ch, e.nneg, e.npos);
+    DH_REQUIRE(!grad || (e.co_pad >= e.Ch && e.co_pad % 8 == 0), DANHIP_EINVAL, "%s: level %d: co_pad=%d must be a multiple of 8 and >= Ch=%d", who, l,
+               e.co_pad, e.Ch);
+    DH_REQUIRE(e.off >= 0 && (long)e.off + e.HW <= A, DANHIP_EINVAL, "%s: level %d: anchor range [%d, %ld) outside [0, %d)", who, l, e.off,
+               (long)e.off + e.HW, A);
+    t->h[l] = e.h; t->dy[l] = grad ? e.dy : nullptr;
+    t->HW[l] = e.HW; t->Ch[l] = e.Ch; t->nneg[l] = e.nneg; t->off[l] = e.off; t->co_pad[l] = grad ? e.co_pad : 0;
+    t->row0[l + 1] = t->row0[l] + (long)B * e.HW;
+    int i = l;                                           // insertion by anchor offset
+    for (; i > 0 && lv[order[i - 1]].off > e.off; --i) order[i] = order[i - 1];
+    order[i] = l;
+  }
+  long next = 0;
+  for (int i = 0; i < n; ++i) {
+    DH_REQUIRE(lv[order[i]].off == next, DANHIP_EINVAL, "%s: the levels' anchor ranges must tile [0, %d) without gap or overlap (level %d starts at %d, expected %ld)",
+               who, A, order[i], lv[order[i]].off, next);
+    next += lv[order[i]].HW;
+  }
+  DH_REQUIRE(next == A, DANHIP_EINVAL, "%s: the levels' anchor ranges end at %ld, not at A=%d", who, next, A);
+  for (int l = n; l < DANHIP_HEADS_MAX_LEVELS; ++l) {
+    t->h[l] = nullptr; t->dy[l] = nullptr; t->HW[l] = 1; t->Ch[l] = 0; t->nneg[l] = 0; t->off[l] = 0; t->co_pad[l] = 0;
+    t->row0[l + 1] = t->row0[n];
+  }
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_heads_split_fwd(const danhip_head_level* levels, int32_t nlevels, float* loc, float* cls, int32_t B, int32_t A, void* stream) {
+  DH_REQUIRE(loc && cls && ((uintptr_t)loc & 15) == 0 && ((uintptr_t)cls & 7) == 0, DANHIP_EINVAL,
+             "heads_split_fwd: loc / cls must be non-null and 16- / 8-byte aligned");
+  HeadsTable t;
+  if (int rc = heads_table(levels, nlevels, B, A, false, "heads_split_fwd", &t)) return rc;
+  const long rows = t.row0[t.n];
+  hipLaunchKernelGGL(heads_split_fwd_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, t, loc, cls, A);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_heads_grad_pad(const danhip_head_level* levels, int32_t nlevels, const float* dloc, const float* dcls, int32_t B, int32_t A,
+                                     void* stream) {
+  DH_REQUIRE(dloc && dcls && ((uintptr_t)dloc & 15) == 0 && ((uintptr_t)dcls & 7) == 0, DANHIP_EINVAL,
+             "heads_grad_pad: dloc / dcls must be non-null and 16- / 8-byte aligned");
+  HeadsTable t;
+  if (int rc = heads_table(levels, nlevels, B, A, true, "heads_grad_pad", &t)) return rc;
+  const long rows = t.row0[t.n];
+  hipLaunchKernelGGL(heads_grad_pad_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, t, dloc, dcls, A);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

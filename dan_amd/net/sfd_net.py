@@ -121,14 +121,10 @@ class VGG16Backbone(object):
         """Shared body of multibox_head (net/sfd_net.py:159-219), pb_net.get_predict_module (:230-290) and
         danet.get_predict_module (:469-532).  loc_i and cls_i stay separate TF variables but run as ONE 3x3 conv
         (their HWIO kernels concatenated on Cout: the feature map is read once — HBM-bound head), then
-        max-out + reshape_pred write straight into the level-concatenated [B, A, 4] / [B, A, 2] buffers."""
-        B = feature_layers[0].shape[0]
+        max-out + reshape_pred write straight into the level-concatenated [B, A, 4] / [B, A, 2] buffers - all levels in one launch
+        (ops.heads_split), whose backward also leaves every head convolution its channel-padded 16-bit dY."""
         assert all(d == 1 for d in num_anchors_depth_per_layer), "one anchor per cell (all reference configs)"
-        A = sum(f.shape[1] * f.shape[2] for f in feature_layers)
-        dev = feature_layers[0].device
-        loc = torch.zeros((B, A, 4), dtype=torch.float32, device=dev)
-        cls = torch.zeros((B, A, 2), dtype=torch.float32, device=dev)
-        off = 0
+        hs = []
         for ind, feat in enumerate(feature_layers):
             if shared_conv:
                 feat = self.conv_relu(feat, feat.shape[-1], (3, 3), (1, 1), "{}/shared_conv_{}".format(name, ind))
@@ -143,12 +139,11 @@ class VGG16Backbone(object):
             bf = self.vs.fuse((pre[0] + "bias", pre[1] + "bias"), axis=0)
             if wf is None or bf is None:
                 wf, bf = ops.cat_static([wl, wc], 3), ops.cat_static([bl, bc], 0)
-            h = ops.conv2d(feat, wf, bf, stride=1, relu=False, out_f32=True)
+            h = ops.conv2d(feat, wf, bf, stride=1, relu=False, out_f32=True, dy_slot=ops.context().HEADS_BATCHED)
             if ops.TRACE is not None and ncls > 2:           # the max-out decision of this level (tests: imposed on the oracle graph)
                 ops.TRACE.setdefault("maxout", {})[id(wc)] = h.detach()[..., 4:]
-            loc, cls = ops.head_split(h, loc, cls, neg_maxout[ind], pos_maxout[ind], off)
-            off += feat.shape[1] * feat.shape[2]
-        return loc, cls
+            hs.append(h)
+        return ops.heads_split(hs, list(zip(neg_maxout, pos_maxout)))
 
     def multibox_head(self, feature_layers, pos_maxout, neg_maxout, num_anchors_depth_per_layer):
         """net/sfd_net.py:159-219 + reshape/concat of train_sfd.py:293-304: returns (location_pred [B,A,4],

@@ -45,13 +45,17 @@ class OpsContext(object):
       FUSE_FIRST_WGRAD [DANHIP_FUSE_FIRST_WGRAD, 1]  0: conv1_2's data gradient stores its output and conv1_1's weight gradient is a launch of its own
                        (rounds 1-5); 1: the first layer's weight / bias gradient is folded into the second layer's data gradient
                        (danhip_conv2d_bwd_data_bits_first: conv1_1's dY never reaches HBM) where a trainer's gradient sinks exist
+      HEADS_BATCHED    [DANHIP_HEADS_BATCHED, 1]  0: the detection heads split their maps (forward) and form the head convolutions' dY
+                       (backward) level by level: one head_split launch per level each way plus a cast_pad launch per level, through an
+                       fp32 dY, into zero-filled prediction buffers (rounds 1-11); 1: one danhip_heads_split_fwd and one
+                       danhip_heads_grad_pad for all levels (heads_split; values bit-identical)
       SPLIT_EVAL       True: convolutions of the fp32 inference path run as split-operand products on the fp16 MFMA (csrc/split_infer.hip;
                        models set it for precision "split"): fp32-accurate boxes at a third of the 16-bit rate instead of a tenth
     Diagnostic sinks (None = off): TRACE (tests: activations / decisions by variable id), PROFILE / PROFILE_BYTES (bench.py: HIP events
     and algorithmic bytes per convolution launch).
     Per-step state a trainer arms: GRAD_READY_HOOK (a parameter's gradient is final), LOSS_SCALE_DEV (device scalar of the dynamic loss
     scale), wgrad (the second backward stream: {"on", "side", "main", "keep"})."""
-    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "SPLIT_EVAL", "TRACE",
+    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "HEADS_BATCHED", "SPLIT_EVAL", "TRACE",
                  "PROFILE", "PROFILE_BYTES", "GRAD_READY_HOOK", "LOSS_SCALE_DEV", "wgrad")
 
     def __init__(self, **overrides):
@@ -66,6 +70,7 @@ class OpsContext(object):
         self.WGRAD_STREAM = env("DANHIP_WGRAD_STREAM", "1") == "1"
         self.WGRAD_FIRST = env("DANHIP_WGRAD_FIRST", "0") == "1"
         self.FUSE_FIRST_WGRAD = env("DANHIP_FUSE_FIRST_WGRAD", "1") == "1"
+        self.HEADS_BATCHED = env("DANHIP_HEADS_BATCHED", "1") == "1"
         self.SPLIT_EVAL = False
         self.TRACE = self.PROFILE = self.PROFILE_BYTES = None
         self.GRAD_READY_HOOK = self.LOSS_SCALE_DEV = None
@@ -518,6 +523,7 @@ class _Conv2d(torch.autograd.Function):
                  F32 if out_f32 else BF16, int(relu), ptr(residual), ptr(ws), nws, stream())
         _prof_end(e0, d, 4 if pool_out is not None else 0, wrote_y=not skip_y, pooled=pool_out is not None)
         ctx.d, ctx.relu, ctx.cin_real = d, relu, cin_real
+        ctx.out_f32 = out_f32
         ctx.xslot, ctx.yslot, ctx.xbits = xslot, yslot, xbits
         ctx.set_materialize_grads(False)
         ctx.has_res = residual is not None
@@ -568,6 +574,8 @@ class _Conv2d(torch.autograd.Function):
             g = dy if g is None else g.add_(dy)
         if g is None:                                    # no gradient reached this layer
             return (None,) * 19
+        if _CTX.TRACE is not None and ctx.out_f32:       # tests: the 16-bit dY of every head convolution, in backward order
+            _CTX.TRACE.setdefault("head_dy", []).append(g)
         db_in_wgrad = need_db and need_dw                        # the weight-gradient kernel also emits the bias gradient
         if need_db and not db_in_wgrad:
             if co8 == d.Cout:
@@ -903,8 +911,10 @@ def _conv2d_split(x, w, b, stride, relu, residual, padding, want_f32=False):
     return y
 
 
-def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, pool=False, padding="same", pool_only=False):
-    """pool=True: also computes max_pool_2x2(y) (danhip_conv2d_fwd_pool); the next ops.max_pool_2x2(y) call picks it up.
+def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, pool=False, padding="same", pool_only=False, dy_slot=False):
+    """dy_slot=True (with out_f32, a head convolution): the fp32 output carries a slot (`_dh_hslot`) through which heads_split hands this
+    layer's channel-padded 16-bit dY over in backward, ready for the data and weight gradients.
+    pool=True: also computes max_pool_2x2(y) (danhip_conv2d_fwd_pool); the next ops.max_pool_2x2(y) call picks it up.
     pool_only=True (with pool, no gradient tracked): the caller promises that ONLY the pooled map is used - where the kernel pools in its
     epilogue the full-resolution activation is never written and the POOLED tensor is returned (ops.max_pool_2x2 passes it through)."""
     if _is_limbs(x) or (_CTX.SPLIT_EVAL and _f32_infer(x)):
@@ -918,6 +928,9 @@ def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, poo
     if track and relu and residual is not None:
         raise NotImplementedError("relu + fused residual needs a separate ReLU mask in backward (y > 0 is not the mask)")
     yslot = _new_slot(track and not out_f32)
+    hslot = None
+    if dy_slot and out_f32 and not relu and residual is None:
+        yslot = hslot = _new_slot(track)
     pool_out = [] if (pool and relu and not out_f32 and residual is None and b is not None and w.shape[-1] % 8 == 0) else None
     if padding not in ("same", "valid"):
         raise ValueError("padding must be 'same' or 'valid'")
@@ -941,7 +954,11 @@ def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, poo
         _CTX.TRACE[id(wp)] = y.detach()
     if bits_out:                                         # the forward kernel wrote the masks: the holders of y (and its pooled map) start filled
         y._dh_bits = [bits_out[0]]
-    if yslot is not None:
+    if hslot is not None:                                # (the slot's buffer is the 16-bit dY, not a gradient of y's own type and width)
+        hslot.__init__(y, False, (w.shape[-1] + 7) // 8 * 8)
+        hslot.dtype = ACT
+        y._dh_hslot = hslot
+    elif yslot is not None:
         cout = w.shape[-1]
         if cout % 8 == 0:
             yslot.__init__(y, relu)
@@ -1181,6 +1198,70 @@ class _HeadSplit(torch.autograd.Function):
 
 def head_split(h, loc, cls, nneg, npos, off):
     return _HeadSplit.apply(h, loc, cls, nneg, npos, off)
+
+
+class _HeadsSplit(torch.autograd.Function):
+    """Max-out + reshape_pred for ALL pyramid levels in one launch each way (OpsContext.HEADS_BATCHED): the head maps h_i fp32
+    [B,H_i,W_i,4+nneg_i+npos_i] -> loc [B,A,4], cls [B,A,2], level after level along A (what a chain of _HeadSplit nodes writes).
+    Backward forms every level's gradient, rounds it to 16 bits and stores it channel-padded into the slot of the level's head
+    convolution (conv2d(dy_slot=True)) - what head_split_bwd + the convolution's cast_pad produced per level through an fp32 dY - and
+    hands autograd nothing: each convolution's backward finds its dY in its slot.  One node per forward call receives dloc / dcls once,
+    so several forwards per step (train_step_towers) never share state."""
+
+    @staticmethod
+    def forward(ctx, cfg, slots, *hs):
+        B = hs[0].shape[0]
+        levels = (_lib.HeadLevel * len(hs))()
+        off = 0
+        for e, h, (nneg, npos) in zip(levels, hs, cfg):
+            assert h.dtype == torch.float32 and h.is_contiguous() and h.dim() == 4 and h.shape[0] == B, "heads_split: fp32 NHWC head maps of one batch"
+            e.h, e.dy = h.data_ptr(), None
+            e.HW, e.Ch, e.nneg, e.npos, e.off, e.co_pad = h.shape[1] * h.shape[2], h.shape[3], nneg, npos, off, 0
+            off += e.HW
+        loc = torch.empty((B, off, 4), dtype=torch.float32, device=hs[0].device)         # (every element is written: the levels tile [0, A))
+        cls = torch.empty((B, off, 2), dtype=torch.float32, device=hs[0].device)
+        call("danhip_heads_split_fwd", levels, len(hs), ptr(loc), ptr(cls), B, off, stream())
+        ctx.save_for_backward(*hs)
+        ctx.levels, ctx.slots, ctx.dims = levels, slots, (B, off)
+        return loc, cls
+
+    @staticmethod
+    def backward(ctx, dloc, dcls):
+        hs = ctx.saved_tensors
+        B, A = ctx.dims
+        assert dloc.dtype == torch.float32 and dcls.dtype == torch.float32 and dloc.shape == (B, A, 4) and dcls.shape == (B, A, 2)
+        dloc, dcls = dloc.contiguous(), dcls.contiguous()
+        if dloc.data_ptr() % 16:                         # (a view at an odd element offset: the kernel loads float4 / float2)
+            dloc = dloc.clone()
+        if dcls.data_ptr() % 8:
+            dcls = dcls.clone()
+        levels = ctx.levels
+        for e, h, slot in zip(levels, hs, ctx.slots):
+            buf, acc = slot.target()
+            if acc:
+                raise RuntimeError("heads_split: a head convolution's dY slot was filled before the heads' backward ran")
+            e.h, e.dy, e.co_pad = h.data_ptr(), buf.data_ptr(), buf.shape[-1]
+        call("danhip_heads_grad_pad", levels, len(hs), ptr(dloc), ptr(dcls), B, A, stream())
+        return (None, None) + (None,) * len(hs)
+
+
+def heads_split(hs, cfg):
+    """Head maps of all levels (conv2d(out_f32=True, dy_slot=True)) + their (nneg, npos) -> (loc [B,A,4], cls [B,A,2]).
+    HEADS_BATCHED: one launch for all levels each way; else, and where the batched form does not apply (more levels than the kernels'
+    table holds, or gradients tracked without the direct hand-off), the per-level launches into zero-filled buffers."""
+    track = torch.is_grad_enabled() and any(h.requires_grad for h in hs)
+    slots = [getattr(h, "_dh_hslot", None) for h in hs]
+    if _CTX.HEADS_BATCHED and len(hs) <= _lib.HEADS_MAX_LEVELS and (not track or all(s is not None for s in slots)):
+        return _HeadsSplit.apply([tuple(c) for c in cfg], slots, *hs)
+    B, dev = hs[0].shape[0], hs[0].device
+    A = sum(h.shape[1] * h.shape[2] for h in hs)
+    loc = torch.zeros((B, A, 4), dtype=torch.float32, device=dev)
+    cls = torch.zeros((B, A, 2), dtype=torch.float32, device=dev)
+    off = 0
+    for h, (nneg, npos) in zip(hs, cfg):
+        loc, cls = head_split(h, loc, cls, nneg, npos, off)
+        off += h.shape[1] * h.shape[2]
+    return loc, cls
 
 
 # 1-element device tensor holding the current dynamic loss scale (set by the trainer around its backward pass), or None

@@ -305,6 +305,26 @@ int danhip_head_split_fwd(const float* h, float* loc, float* cls, int32_t B, int
                           int32_t A, int32_t anchor_offset, void* stream);
 int danhip_head_split_bwd(const float* h, const float* dloc, const float* dcls, float* dy, int32_t B, int32_t HW, int32_t Ch,
                           int32_t nneg, int32_t npos, int32_t A, int32_t anchor_offset, void* stream);
+/* ABI version 9: all pyramid levels of the detection heads in ONE launch each way.  The level table travels by value as a kernel
+ * argument (nothing is copied to the device per call), at most DANHIP_HEADS_MAX_LEVELS entries.  The launchers refuse
+ * (DANHIP_EINVAL) more levels than that, Ch != 4 + nneg + npos, anchor ranges [off, off + HW) that do not tile [0, A) without
+ * overlap, a null or misaligned pointer (h, dy, loc, dloc: 16 bytes; cls, dcls: 8 bytes - what a batch slice of them keeps) and, for
+ * the gradient, co_pad < Ch or co_pad % 8 != 0.
+ *   danhip_heads_split_fwd: per level exactly danhip_head_split_fwd (same max-out arithmetic, same destinations).
+ *   danhip_heads_grad_pad:  per level the composition danhip_head_split_bwd -> danhip_cast_pad_f32_to_bf16 (no ReLU operand):
+ *     reads h, dloc [B,A,4], dcls [B,A,2]; writes the level's channel-padded 16-bit dY [B*HW, co_pad] (pad columns zero),
+ *     bit-identical to the two calls; the fp32 dY exists in registers only. */
+#define DANHIP_HEADS_MAX_LEVELS 8
+typedef struct danhip_head_level {
+  const float* h;  /* head map of the level, fp32 [B*HW, Ch] */
+  uint16_t* dy;    /* danhip_heads_grad_pad: destination, 16 bit [B*HW, co_pad]; ignored by danhip_heads_split_fwd */
+  int32_t HW, Ch, nneg, npos;
+  int32_t off;     /* anchor offset of the level in [0, A) */
+  int32_t co_pad;  /* danhip_heads_grad_pad: channels per row of dy */
+} danhip_head_level;
+int danhip_heads_split_fwd(const danhip_head_level* levels, int32_t nlevels, float* loc, float* cls, int32_t B, int32_t A, void* stream);
+int danhip_heads_grad_pad(const danhip_head_level* levels, int32_t nlevels, const float* dloc, const float* dcls, int32_t B, int32_t A,
+                          void* stream);
 /* Per-image hard-negative mining (train_sfd.py:350-384, train_dan.py:286-324): score = label==0 ? -softmax(cls)[0] : -1;
  * k = min(int(ratio*n_pos), n_neg) (at_least_one: max(k,1)); thr[b] = exact k-th largest score of row b (radix select),
  * +inf when k == 0.  cls fp32 [B,A,2], labels int32 [B,A] in {1,0,-1}; score [B,A], counts int32 [B,2], thr [B], k_out [B]. */
