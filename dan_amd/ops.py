@@ -30,15 +30,25 @@ class OpsContext(object):
 
     Kernel-form switches (results agree up to fp32 summation order whatever they say):
       USE_SPLITK       False: never pass the split-K scratch buffer (every shape on its single-pass kernel)
-      USE_SLOTS        False: activation gradients travel through autograd's own edges instead of the direct hand-off (GradSlot)
-      USE_RELU_BITS    [DANHIP_RELU_BITS, 1]  0: ReLU masks read as 16-bit activations instead of bit masks
-      USE_POOL_ARG     [DANHIP_POOL_ARG, 1]   0: max-pool backward re-reads the activation instead of the 2-bit arg-max codes
+      USE_SLOTS        False: activation gradients travel through autograd's own edges instead of the direct hand-off (GradSlot), which
+                       gives the parity tests a second, independent route through the same kernels (tests/test_grad_parity_gpu.py)
+      USE_RELU_BITS    [DANHIP_RELU_BITS, 1]  0: ReLU masks read as 16-bit activations instead of bit masks (danhip_relu_bits: for the
+                       data-gradient kernels that stage them in LDS; every consumer of an activation shares ONE holder hung on the
+                       tensor, which the first backward that needs the bits fills)
+      USE_POOL_ARG     [DANHIP_POOL_ARG, 1]   0: max-pool backward re-reads the activation to find each window's maximum (round 3) instead
+                       of scattering through the 2-bit arg-max codes its forward kept (round 4, danhip_maxpool2x2_bwd_arg: 1.28 instead of
+                       2.25 map-sized HBM passes)
       USE_JUNCTION     [DANHIP_JUNCTION, 1]   0: a map that feeds an L2 norm and a 2 x 2 max-pool gets their two gradients by two launches
                        (l2norm_bwd, then maxpool2x2_bwd_arg accumulating) instead of one danhip_l2norm_bwd_pool_scatter (dx bit-identical)
       POOL_ONLY_TRAIN  [DANHIP_POOL_ONLY_TRAIN, 1]  0: the training forward of a conv whose only consumer is a fused pool still writes its map
+                       (conv1_2 / conv2_2; round 4's behaviour)
       KEEP_DEFORM_COL  False: the deformable backward re-samples the im2col buffer as the reference does instead of keeping the forward's
-      WGRAD_STREAM     [DANHIP_WGRAD_STREAM, 1]  0: weight gradients on the data gradients' stream
-      WGRAD_FIRST      [DANHIP_WGRAD_FIRST, 0]   1: a convolution's backward issues its weight gradient (side stream) BEFORE its data gradient, so the
+      WGRAD_STREAM     [DANHIP_WGRAD_STREAM, 1]  0: weight gradients on the data gradients' stream.  The environment is read ONCE, when the
+                       context is made; a process that wants to switch mid-run (bench.py's serialized roofline leg, tests) assigns
+                       ops.WGRAD_STREAM.  dgrad(L) and wgrad(L) both consume dY_L and are independent: on one stream each kernel's ramp-up
+                       and tail (and, on the 40x40 / 20x20 maps, its under-filled grid) leave CUs idle that the other can use
+                       (tools/probe_concurrent_bwd.py: conv4_2 0.95 -> 0.84 ms, conv5_1 0.37 -> 0.31, fc6 0.25 -> 0.18 for the pair)
+      WGRAD_FIRST     [DANHIP_WGRAD_FIRST, 0]   1: a convolution's backward issues its weight gradient (side stream) BEFORE its data gradient, so the
                        side stream waits for dY only, not for the data gradient.  Measured slower (round 6, same box, alternating: 12.81 against
                        12.73 ms): both kernels are full-chip persistent grids, "beside each other" means taking turns, and the data gradient —
                        the critical path — then queues behind the weight gradient's workgroups
@@ -51,10 +61,15 @@ class OpsContext(object):
                        danhip_heads_grad_pad for all levels (heads_split; values bit-identical)
       SPLIT_EVAL       True: convolutions of the fp32 inference path run as split-operand products on the fp16 MFMA (csrc/split_infer.hip;
                        models set it for precision "split"): fp32-accurate boxes at a third of the 16-bit rate instead of a tenth
-    Diagnostic sinks (None = off): TRACE (tests: activations / decisions by variable id), PROFILE / PROFILE_BYTES (bench.py: HIP events
-    and algorithmic bytes per convolution launch).
-    Per-step state a trainer arms: GRAD_READY_HOOK (a parameter's gradient is final), LOSS_SCALE_DEV (device scalar of the dynamic loss
-    scale), wgrad (the second backward stream: {"on", "side", "main", "keep"})."""
+    Diagnostic sinks (None = off): TRACE (tests: a dict in which every ReLU layer files its output under id(weight variable) and every
+    2 x 2 max-pool its input under "pools", in call order - the discrete decisions of a forward pass, which the gradient-parity tests
+    impose on the oracle graph), PROFILE / PROFILE_BYTES (bench.py: dicts; every conv forward / data-gradient / weight-gradient launch is
+    bracketed by events on its stream and filed under its kernel-instance label with its algorithmic FLOPs / bytes).
+    Per-step state a trainer arms: GRAD_READY_HOOK (callback(param) right after a layer's weight / bias gradients have been issued in
+    backward: the data-parallel trainer launches its bucketed all-reduce from it while backward continues), LOSS_SCALE_DEV (1-element
+    device tensor of the dynamic loss scale, set around the backward pass), wgrad (the second backward stream: {"on", "side", "main",
+    "keep"}; switched on around the backward pass and joined before the gradients are consumed; "keep" holds the tensors the side
+    stream still reads until that join: no allocator reuse while in flight, also valid inside a hipGraph capture)."""
     __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "HEADS_BATCHED", "SPLIT_EVAL", "TRACE",
                  "PROFILE", "PROFILE_BYTES", "GRAD_READY_HOOK", "LOSS_SCALE_DEV", "wgrad")
 
@@ -226,12 +241,7 @@ def _sink_trainable(t):
     return ms is not None and any(m.requires_grad for m in ms)
 
 
-# Optional per-kernel timing (bench.py): when PROFILE is a dict, every conv forward / stride-1 data-gradient launch is
-# bracketed by events on the launch stream and recorded under its kernel-instance label with its algorithmic FLOPs.
-# (PROFILE: a field of OpsContext, see the top of the module)
-# (PROFILE_BYTES: a field of OpsContext, see the top of the module)
-
-
+# ---- optional per-kernel timing (OpsContext.PROFILE / PROFILE_BYTES)
 def _prof_begin(st=None):
     if _CTX.PROFILE is None:
         return None
@@ -262,17 +272,7 @@ def _prof_end(e0, d, which, st=None, wrote_y=True, pooled=False):
         _CTX.PROFILE_BYTES.setdefault(label, []).append(nbytes)
 
 
-# ---- weight gradients on a second stream.  dgrad(L) and wgrad(L) both consume dY_L and are independent of each other; on one stream
-# each kernel's ramp-up and tail (and, on the 40x40 / 20x20 maps, its under-filled grid) leave CUs idle that the other kernel can use
-# (tools/probe_concurrent_bwd.py: conv4_2 0.95 -> 0.84 ms, conv5_1 0.37 -> 0.31, fc6 0.25 -> 0.18 for the pair).  The trainer switches
-# this on around its backward pass and joins before the gradients are consumed; tensors the side stream still reads are kept alive
-# until that join (no allocator reuse while in flight, also valid inside a hipGraph capture).
-# (_WGRAD: a field of OpsContext, see the top of the module)
-# read ONCE at import (DANHIP_WGRAD_STREAM=0: A/B on one stream); a process that wants to switch mid-run (bench.py's serialized
-# roofline leg, tests) assigns ops.WGRAD_STREAM - the environment is never re-read or written
-# (WGRAD_STREAM: a field of OpsContext, see the top of the module)
-
-
+# ---- weight gradients on a second stream (OpsContext.WGRAD_STREAM / wgrad)
 def wgrad_overlap_begin():
     if not torch.cuda.is_available():
         return
@@ -297,11 +297,6 @@ def wgrad_streams():
     return [_CTX.wgrad["main"], _CTX.wgrad["side"]] if _CTX.wgrad["on"] else []
 
 
-# Optional callback(param) invoked right after a layer's weight/bias gradients have been produced in backward
-# (the data-parallel trainer uses it to launch the bucketed gradient all-reduce while backward continues).
-# (GRAD_READY_HOOK: a field of OpsContext, see the top of the module)
-
-
 
 class GradSlot(object):
     """Direct gradient hand-off between this package's ops, bypassing autograd's per-edge tensors.
@@ -310,16 +305,25 @@ class GradSlot(object):
     or accumulates (later deliveries) its input-gradient contribution straight into the slot's buffer — already
     multiplied by (x > 0) when x is a ReLU output, which folds the producer's ReLU backward into the consumer's
     epilogue — and returns None to autograd.  The producer's backward then takes the buffer.  Consumers that do not
-    know about slots (plain torch ops) still work: their gradient arrives through autograd and is merged in."""
+    know about slots (plain torch ops) still work: their gradient arrives through autograd and is merged in.
+
+    An op's wrapper makes the slot UNBOUND (_new_slot), hands it to the autograd function, which keeps it for its backward, and binds it
+    to the output once that exists (_publish); GradSlot(t, is_relu, channels) makes and binds in one step."""
 
     __slots__ = ("shape", "dtype", "device", "is_relu", "buf", "count", "taps", "pending")
 
-    def __init__(self, t, is_relu, channels=None):
-        self.shape, self.dtype, self.device, self.is_relu = t.shape, t.dtype, t.device, is_relu
-        if channels is not None:                         # ragged Cout: the buffer carries the channel-padded gradient layout
-            self.shape = tuple(t.shape[:-1]) + (channels,)
+    def __init__(self, t=None, is_relu=False, channels=None):
         self.buf, self.count = None, 0
         self.taps, self.pending = 0, None                # gradient junction (USE_JUNCTION): see defer()
+        if t is not None:
+            self.bind(t, is_relu, channels)
+
+    def bind(self, t, is_relu, channels=None, dtype=None):
+        """The buffer is a gradient of t: its shape, dtype and device - except `channels` (ragged Cout: the buffer carries the
+        channel-padded gradient layout) and `dtype` (a head convolution's slot holds the 16-bit dY of its fp32 output)."""
+        self.shape, self.dtype, self.device, self.is_relu = t.shape, (t.dtype if dtype is None else dtype), t.device, is_relu
+        if channels is not None:
+            self.shape = tuple(t.shape[:-1]) + (channels,)
 
     def defer(self, kind, alone, payload):
         """A delivery of a gradient junction (kind: TAP_L2NORM / TAP_POOL) takes its turn - buffer and accumulate flag exactly as
@@ -359,11 +363,6 @@ class GradSlot(object):
         return b if n > 0 else None
 
 
-# USE_SLOTS = False (tests): every activation gradient travels through autograd's own edges instead of the direct hand-off, which gives
-# the parity tests a second, independent route through the same kernels (tests/test_grad_parity_gpu.py)
-# (USE_SLOTS: a field of OpsContext, see the top of the module)
-
-
 TAP_L2NORM, TAP_POOL = 1, 2      # GradSlot.taps: the consumers of a gradient junction, registered by their forward passes
 
 
@@ -377,20 +376,103 @@ def _slot_of(t):
 
 
 def _new_slot(track):
-    return GradSlot.__new__(GradSlot) if (track and _CTX.USE_SLOTS) else None
+    return GradSlot() if (track and _CTX.USE_SLOTS) else None
 
 
-def _attach_slot(t, is_relu):
-    s = GradSlot(t, is_relu)
-    t._dh_slot = s
-    return s
+# ---- the hand-off protocol, once.  Forward: the wrapper makes an unbound slot, the autograd function keeps it, _publish binds it to the
+# output.  Backward: _incoming gathers the output gradient, _deliver hands the input gradient to the producer's slot or to autograd,
+# _grad_target picks a parameter's gradient sink or a fresh tensor for autograd, _launch_wgrad issues a weight gradient on its stream.
+def _pad8(c):
+    return (c + 7) // 8 * 8
 
 
-# ReLU masks as bits for the data-gradient kernels that stage them in LDS (danhip_relu_bits).  One activation may feed several convolutions:
-# every consumer's forward shares ONE holder hung on the activation tensor, the first backward that needs the bits fills it.
-# (USE_RELU_BITS: a field of OpsContext, see the top of the module)
+def _ragged(c):
+    """The channel-padded width the slot of a c-wide output carries, None when c needs no padding."""
+    return None if c % 8 == 0 else _pad8(c)
 
 
+def _publish(y, slot, is_relu, channels=None, dtype=None):
+    """Binds the slot (or None) to the output y and hangs it on the tensor, where y's consumers find it: `_dh_slot`; `_dh_pslot` when
+    the buffer is channel-padded (`channels`: only ops.concat knows that layout, a ragged tensor feeds no conv directly); `_dh_hslot`
+    for a head convolution, whose buffer is the 16-bit dY (`dtype`, `channels`), not a gradient of y's own type and width.  -> y"""
+    if slot is not None:
+        slot.bind(y, is_relu, channels, dtype)
+        if dtype is not None:
+            y._dh_hslot = slot
+        elif channels is not None:
+            y._dh_pslot = slot
+        else:
+            y._dh_slot = slot
+    return y
+
+
+def _incoming(slot, dy, prepare=None, ragged=False):
+    """-> the output gradient of a backward node, or None when none reached it: what the consumers delivered into its slot (already
+    ReLU-masked where the output is a ReLU's) merged with autograd's dy.  prepare(dy): a producer that must cast, pad or mask the raw
+    autograd gradient first returns a contiguous tensor of its own.  dy is ADDED INTO THE SLOT'S BUFFER, never the other way round: the
+    incoming tensor may be shared with other consumers.  ragged: the buffer may be channel-padded and wider than dy (ops.concat)."""
+    g = slot.take() if slot is not None else None
+    if dy is not None:
+        if prepare is not None:
+            dy = prepare(dy)
+        if g is None:
+            g = dy.contiguous()
+        elif ragged and g.shape[-1] != dy.shape[-1]:
+            g[..., :dy.shape[-1]].add_(dy)
+        else:
+            g.add_(dy)
+    return g
+
+
+def _deliver(slot, shape, like, launch):
+    """The input gradient of a backward node goes straight into the producer's slot (launch(buffer, accumulate flag); -> None for
+    autograd) or, without a slot, into a fresh tensor of `shape` and `like`'s type that autograd gets (launch(tensor, 0); -> it)."""
+    if slot is not None:
+        launch(*slot.target())
+        return None
+    dx = like.new_empty(shape)
+    launch(dx, 0)
+    return dx
+
+
+def _param_handle(t):
+    """t itself when it is a variable with state of its own here (cached packings, a gradient sink): an nn.Parameter, or a plain tensor
+    carrying a gradient sink - a fused block of parameters (FlatParams); else None."""
+    return t if (isinstance(t, torch.nn.Parameter) or hasattr(t, "_danhip_grad")) else None
+
+
+def _grad_target(p, shape, device):
+    """-> (fp32 tensor the kernels accumulate a parameter's gradient into, what autograd gets back): the gradient sink of handle p and
+    None, or a fresh zero tensor twice."""
+    sink = _grad_sink(p) if p is not None else None
+    if sink is not None:
+        return sink, None
+    z = torch.zeros(shape, dtype=torch.float32, device=device)
+    return z, z
+
+
+def _launch_wgrad(d, on_side, issue, keep):
+    """Issues a weight gradient of descriptor d - issue(stream handle) makes the library call - with its profiling bracket.  on_side and
+    the trainer's second stream on: on that stream, ordered behind everything issued so far on the current one (dY is final there, and
+    the sinks are zeroed), with explicit stream handles (no stream-context switch per layer on the host) and `keep` (what the call
+    reads) alive until the join.  -> went to the side stream"""
+    if on_side and _CTX.wgrad["on"]:
+        side = _CTX.wgrad["side"]
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        side.wait_event(ev)
+        e0 = _prof_begin(side)
+        issue(ctypes.c_void_p(side.cuda_stream))
+        _prof_end(e0, d, 2, side)
+        _CTX.wgrad["keep"].append(keep)
+        return True
+    e0 = _prof_begin()
+    issue(stream())
+    _prof_end(e0, d, 2)
+    return False
+
+
+# ---- ReLU masks as bits (OpsContext.USE_RELU_BITS): one holder per activation, shared by all its consumers
 def _bits_holder(x):
     h = getattr(x, "_dh_bits", None)
     if h is None:
@@ -408,12 +490,6 @@ def relu_bits(x, holder):
         holder[0] = b
     return holder[0]
 
-
-# TRACE (tests): when a dict, every ReLU layer records its output under id(weight variable) and every 2x2 max-pool its input under
-# "pools" (call order) — the discrete decisions of this forward pass, which the gradient-parity tests impose on the oracle graph
-# (TRACE: a field of OpsContext, see the top of the module)
-
-# (USE_SPLITK: a field of OpsContext, see the top of the module)
 
 
 def _conv_scratch(d, which, dev):
@@ -438,16 +514,6 @@ def _wgrad_scratch(d, dev):
     if n is None:
         n = _SCRATCH_BYTES[key] = _lib.lib().danhip_conv2d_bwd_weight_workspace_bytes(ctypes.byref(d))
     return (torch.empty(n, dtype=torch.uint8, device=dev), n) if n else (None, 0)
-
-
-# USE_POOL_ARG (round 4): the 2 x 2 max-pool keeps 2-bit arg-max codes from its forward pass (written by the pooling conv epilogues / the pool
-# kernel) and its backward scatters the pooled gradient through them instead of re-reading the full-resolution activation to find each
-# window's maximum (danhip_maxpool2x2_bwd_arg: 1.28 instead of 2.25 map-sized HBM passes).  DANHIP_POOL_ARG=0: the round-3 form (A/B).
-# (USE_POOL_ARG: a field of OpsContext, see the top of the module)
-
-
-# DANHIP_POOL_ONLY_TRAIN=0: conv1_2 / conv2_2 write their full-resolution outputs in training too (A/B; round 4's behaviour)
-# (POOL_ONLY_TRAIN: a field of OpsContext, see the top of the module)
 
 
 def _pool_arg_buffer(pooled, need_bwd):
@@ -543,19 +609,13 @@ class _Conv2d(torch.autograd.Function):
         wp, bp = ctx.w_param, ctx.b_param
         need_dw = ctx.needs_input_grad[1] or ctx.block_w
         need_db = ctx.has_bias and (ctx.needs_input_grad[2] or ctx.block_b)
-        db_sink = _grad_sink(bp) if bp is not None else None
-        db = None
-        if need_db:
-            db = db_sink if db_sink is not None else torch.zeros(d.Cout, dtype=torch.float32, device=x.device)
-        # ---- gather the output gradient: slot deliveries (already ReLU-masked) and/or the autograd tensor
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        dres = None
+        db, db_ret = _grad_target(bp, (d.Cout,), x.device) if need_db else (None, None)
         if dy is not None and ctx.y_unwritten:
             raise RuntimeError("conv2d(pool_only=True): the full-resolution activation was never written, but a gradient reached it outside the "
                                "fused pool's direct hand-off (some op other than max_pool_2x2 consumed it)")
-        if dy is not None:
-            if ctx.has_res:
-                dres = dy                                # residual is added after the activation
+        dres = dy if ctx.has_res else None               # residual is added after the activation
+
+        def prepare(dy):                                 # the autograd tensor: to the slot's layout, times this layer's own ReLU mask
             if dy.dtype != ACT or dy.shape[-1] != co8:
                 # fp32 / unpadded upstream gradient (head convs): cast + pad channels to a multiple of 8
                 src = dy.contiguous().to(torch.float32)
@@ -571,7 +631,9 @@ class _Conv2d(torch.autograd.Function):
                 if not owned:
                     dy = dy.clone()                      # the incoming gradient tensor may be shared with other consumers
                 call("danhip_relu_bwd_bias_grad", ptr(dy), ptr(y), None, M, co8, stream())
-            g = dy if g is None else g.add_(dy)
+            return dy
+
+        g = _incoming(ctx.yslot, dy, prepare)            # slot deliveries (already ReLU-masked) and / or the autograd tensor
         if g is None:                                    # no gradient reached this layer
             return (None,) * 19
         if _CTX.TRACE is not None and ctx.out_f32:       # tests: the 16-bit dY of every head convolution, in backward order
@@ -612,51 +674,37 @@ class _Conv2d(torch.autograd.Function):
                     _prof_end(e0, d, 5, wrote_y=False)       # (dX is never stored: algorithmic bytes = dY + bit mask + image + weights)
                     fused_first = True
                     return
-                if xs is not None:                           # deliver straight into the producer's slot (+ its ReLU backward)
-                    buf, acc = xs.target()
+                relu_x = xs is not None and xs.is_relu
+
+                def data_grad(buf, acc):                     # into the producer's slot (+ its ReLU backward), or a tensor for autograd
                     e0 = _prof_begin()
-                    if xs.is_relu and ctx.xbits is not None and _lib.lib().danhip_conv2d_bwd_data_takes_bits(ctypes.byref(d)):
+                    if relu_x and ctx.xbits is not None and _lib.lib().danhip_conv2d_bwd_data_takes_bits(ctypes.byref(d)):
                         # the kernel keeps its tile's mask in LDS as bits: 1/16 of the bytes, and not a load in its epilogue
                         call("danhip_conv2d_bwd_data_bits", ctypes.byref(d), ptr(g), ptr(wb), ptr(relu_bits(x, ctx.xbits)), ptr(buf), acc, stream())
                     else:
                         ws, nws = _conv_scratch(d, 1, g.device)
-                        call("danhip_conv2d_bwd_data_ws", ctypes.byref(d), ptr(g), ptr(wb), ptr(x) if xs.is_relu else None, ptr(buf), acc, ptr(ws), nws,
+                        call("danhip_conv2d_bwd_data_ws", ctypes.byref(d), ptr(g), ptr(wb), ptr(x) if relu_x else None, ptr(buf), acc, ptr(ws), nws,
                              stream())
-                    _prof_end(e0, d, 5 if xs.is_relu else 1)
-                else:
-                    dx = torch.empty_like(x)
-                    e0 = _prof_begin()
-                    ws, nws = _conv_scratch(d, 1, g.device)
-                    call("danhip_conv2d_bwd_data_ws", ctypes.byref(d), ptr(g), ptr(wb), None, ptr(dx), 0, ptr(ws), nws, stream())
-                    _prof_end(e0, d, 1)
+                    _prof_end(e0, d, 5 if relu_x else 1)
+
+                dx = _deliver(xs, x.shape, x, data_grad)
 
         def launch_dw():
             nonlocal dw, hooked
             if need_dw:
-                sink = _grad_sink(wp) if wp is not None else None
-                dw = sink if sink is not None else torch.zeros((d.kh, d.kw, ctx.cin_real, d.Cout), dtype=torch.float32, device=g.device)
+                dw_to, dw = _grad_target(wp, (d.kh, d.kw, ctx.cin_real, d.Cout), g.device)
                 # split partial sums as plain stores into a scratch slab + a combine pass, where the library's kernel for this shape offers it
                 ws, nws = _wgrad_scratch(d, g.device)
-                if _CTX.wgrad["on"] and sink is not None:      # side stream: needs dY (final now) and the zeroed sinks, both ordered on this stream
-                    side = _CTX.wgrad["side"]
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream())
-                    side.wait_event(ev)
-                    e0 = _prof_begin(side)                  # (explicit stream handle: no stream-context switch per layer on the host)
-                    call("danhip_conv2d_bwd_weight_ws", ctypes.byref(d), ptr(x), ptr(g), ptr(dw), ptr(db) if db_in_wgrad else None, ctx.cin_real,
-                         ptr(ws), nws, ctypes.c_void_p(side.cuda_stream))
-                    _prof_end(e0, d, 2, side)
+
+                def issue(st):
+                    call("danhip_conv2d_bwd_weight_ws", ctypes.byref(d), ptr(x), ptr(g), ptr(dw_to), ptr(db) if db_in_wgrad else None, ctx.cin_real,
+                         ptr(ws), nws, st)
+
+                # (the side stream only with a gradient sink: a gradient handed back to autograd is consumed on this stream)
+                if _launch_wgrad(d, dw is None, issue, (g, x, ws)):
                     if _CTX.GRAD_READY_HOOK is not None and wp is not None:
                         _CTX.GRAD_READY_HOOK(wp)                 # the buckets wait for both gradient streams (trainer.GradBuckets._launch_ready)
-                    _CTX.wgrad["keep"].append((g, x, ws))
                     hooked = True
-                else:
-                    e0 = _prof_begin()
-                    call("danhip_conv2d_bwd_weight_ws", ctypes.byref(d), ptr(x), ptr(g), ptr(dw), ptr(db) if db_in_wgrad else None, ctx.cin_real,
-                         ptr(ws), nws, stream())
-                    _prof_end(e0, d, 2)
-                if sink is not None:
-                    dw = None
 
         if _CTX.WGRAD_FIRST:
             launch_dw()
@@ -664,13 +712,11 @@ class _Conv2d(torch.autograd.Function):
         else:
             launch_dx()
             launch_dw()
-        if db_sink is not None:
-            db = None
         if _CTX.GRAD_READY_HOOK is not None and wp is not None and not hooked:
             _CTX.GRAD_READY_HOOK(wp)
         if fused_first and _CTX.GRAD_READY_HOOK is not None:
             _CTX.GRAD_READY_HOOK(ctx.first[1])           # the first layer's gradients are final too (its own backward will find nothing to do)
-        return dx, dw, db, None, None, None, dres, None, None, None, None, None, None, None, None, None, None, None, None
+        return (dx, dw, db_ret, None, None, None, dres) + (None,) * 12
 
 
 # ---- fp32 inference path (csrc/f32_infer.hip): every op below accepts fp32 NHWC activations and then runs the fp32 kernels — forward
@@ -921,9 +967,7 @@ def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, poo
         return _conv2d_split(x, w, b, stride, relu, residual, padding, want_f32=out_f32)
     if _f32_infer(x):
         return _conv2d_f32(x, w, b, stride, relu, _f32_in(residual), padding)
-    # a plain tensor carrying a gradient sink is a fused block of parameters (FlatParams): cached packing, gradients written in place
-    wp = w if (isinstance(w, torch.nn.Parameter) or hasattr(w, "_danhip_grad")) else None
-    bp = b if (isinstance(b, torch.nn.Parameter) or hasattr(b, "_danhip_grad")) else None
+    wp, bp = _param_handle(w), _param_handle(b)
     track = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or _sink_trainable(w))
     if track and relu and residual is not None:
         raise NotImplementedError("relu + fused residual needs a separate ReLU mask in backward (y > 0 is not the mask)")
@@ -954,18 +998,10 @@ def conv2d(x, w, b=None, stride=1, relu=False, out_f32=False, residual=None, poo
         _CTX.TRACE[id(wp)] = y.detach()
     if bits_out:                                         # the forward kernel wrote the masks: the holders of y (and its pooled map) start filled
         y._dh_bits = [bits_out[0]]
-    if hslot is not None:                                # (the slot's buffer is the 16-bit dY, not a gradient of y's own type and width)
-        hslot.__init__(y, False, (w.shape[-1] + 7) // 8 * 8)
-        hslot.dtype = ACT
-        y._dh_hslot = hslot
-    elif yslot is not None:
-        cout = w.shape[-1]
-        if cout % 8 == 0:
-            yslot.__init__(y, relu)
-            y._dh_slot = yslot
-        else:                                            # only ops.concat knows the padded layout (a ragged tensor feeds no conv directly)
-            yslot.__init__(y, relu, (cout + 7) // 8 * 8)
-            y._dh_pslot = yslot
+    if hslot is not None:
+        _publish(y, hslot, False, _pad8(w.shape[-1]), ACT)
+    else:
+        _publish(y, yslot, relu, _ragged(w.shape[-1]))
     if pool_out:
         y._dh_pooled = pool_out[0]
         y._dh_pool_arg = pool_out[1]                     # 2-bit arg-max codes of the fused pool (None when nothing is tracked)
@@ -999,9 +1035,7 @@ class _MaxPool(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         N, H, W, C = ctx.dims
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dy is not None:
-            g = dy.contiguous() if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy)
         if g is None:
             return None, None, None, None, None
 
@@ -1011,11 +1045,11 @@ class _MaxPool(torch.autograd.Function):
             else:
                 call("danhip_maxpool2x2_bwd", ptr(x), ptr(g), ptr(dst), N, H, W, C, acc, stream())
 
-        if ctx.xslot is not None:
-            # the pooled maximum is > 0 exactly where its source is, so a gradient masked at the pooled level scatters to
-            # an already ReLU-masked gradient; an unmasked one (autograd path) is masked by the producer's own backward
-            xs = ctx.xslot
-            if ctx.arg is not None and _pool_deliver_ok(ctx, dy) and _junction_ok(xs, dy, C):
+        # the pooled maximum is > 0 exactly where its source is, so a gradient masked at the pooled level scatters to an already
+        # ReLU-masked gradient; an unmasked one (autograd path) is masked by the producer's own backward, so it goes there by autograd
+        xs = ctx.xslot if (ctx.xslot is not None and _pool_deliver_ok(ctx, dy)) else None
+        if xs is not None:
+            if ctx.arg is not None and _junction_ok(xs, dy, C):
                 first = xs.pop_pending(TAP_L2NORM)
                 if first is not None:                    # the L2-norm branch is waiting: both gradients in one pass, dx written once
                     buf, _ = xs.target()
@@ -1025,13 +1059,7 @@ class _MaxPool(torch.autograd.Function):
                 else:
                     scatter(*xs.target())
                 return None, None, None, None, None
-            buf, acc = xs.target() if _pool_deliver_ok(ctx, dy) else (None, 0)
-            if buf is not None:
-                scatter(buf, acc)
-                return None, None, None, None, None
-        dx = torch.empty((N, H, W, C), dtype=g.dtype, device=g.device)
-        scatter(dx, 0)
-        return dx, None, None, None, None
+        return _deliver(xs, (N, H, W, C), g, scatter), None, None, None, None
 
 
 def _junction(l2, pool, buf, acc, is_relu, pool_first):
@@ -1071,11 +1099,7 @@ def max_pool_2x2(x):
     pbits = getattr(x, "_dh_pooled_bits", None)
     if pbits is not None and getattr(x, "_dh_pooled", None) is not None:
         y._dh_bits = [pbits]                             # the fused conv + pool kernel also wrote the pooled map's ReLU bit mask
-    if yslot is not None:
-        # consumers may mask by (pooled > 0) when the source is a ReLU output
-        yslot.__init__(y, xs.is_relu if xs is not None else False)
-        y._dh_slot = yslot
-    return y
+    return _publish(y, yslot, xs.is_relu if xs is not None else False)       # consumers may mask by (pooled > 0) when the source is a ReLU output
 
 
 class _MaxPool3x3S2(torch.autograd.Function):
@@ -1122,32 +1146,27 @@ class _L2Norm(torch.autograd.Function):
     def backward(ctx, dy):
         x, gamma = ctx.saved_tensors
         M = x.numel() // x.shape[-1]
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dy is not None:
-            g = dy.contiguous() if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy)
         if g is None:
             return None, None, None, None, None
-        sink = _grad_sink(ctx.g_param) if ctx.g_param is not None else None
-        dg = sink if sink is not None else torch.zeros_like(gamma)
+        dg, dg_ret = _grad_target(ctx.g_param, gamma.shape, gamma.device)
         xs = ctx.xslot
-        if xs is not None:
-            def alone(buf, acc):
-                call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc, 1 if xs.is_relu else 0, stream())
 
-            first = xs.pop_pending(TAP_POOL) if _junction_ok(xs, dy, x.shape[-1]) else None
+        def alone(buf, acc):
+            call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc, 1 if (xs is not None and xs.is_relu) else 0,
+                 stream())
+
+        if xs is not None and _junction_ok(xs, dy, x.shape[-1]):
+            first = xs.pop_pending(TAP_POOL)
             if first is not None:                        # the pool's scatter is waiting: both gradients in one pass, dx written once
                 buf, _ = xs.target()
                 _junction((x, gamma, g, dg), first[1], buf, first[0], xs.is_relu, 1)
-            elif sink is not None and _junction_ok(xs, dy, x.shape[-1]) and xs.pending is None:
+                return None, dg_ret, None, None, None
+            if dg_ret is None and xs.pending is None:
                 # first of the two to arrive.  (Only with a gradient sink: a dgamma handed back to autograd must be complete on return.)
                 xs.defer(TAP_L2NORM, alone, (x, gamma, g, dg))
-            else:
-                alone(*xs.target())
-            dx = None
-        else:
-            dx = torch.empty_like(x)
-            call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(dx), ptr(dg), M, x.shape[-1], 0, 0, stream())
-        return dx, (None if sink is not None else dg), None, None, None
+                return None, dg_ret, None, None, None
+        return _deliver(xs, x.shape, x, alone), dg_ret, None, None, None
 
 
 def l2_normalize(x, gamma):
@@ -1165,10 +1184,7 @@ def l2_normalize(x, gamma):
     track = torch.is_grad_enabled() and (x.requires_grad or gamma.requires_grad)
     yslot = _new_slot(track)
     y = _L2Norm.apply(x, gamma, gamma if isinstance(gamma, torch.nn.Parameter) else None, _slot_of(x) if track else None, yslot)
-    if yslot is not None:
-        yslot.__init__(y, False)
-        y._dh_slot = yslot
-    return y
+    return _publish(y, yslot, False)
 
 
 class _HeadSplit(torch.autograd.Function):
@@ -1264,10 +1280,6 @@ def heads_split(hs, cfg):
     return loc, cls
 
 
-# 1-element device tensor holding the current dynamic loss scale (set by the trainer around its backward pass), or None
-# (LOSS_SCALE_DEV: a field of OpsContext, see the top of the module)
-
-
 class _DetectionLoss(torch.autograd.Function):
     """Hard-negative mining + CE*(ratio+1) + smooth-L1 (train_sfd.py:350-417 / train_dan.py:286-324,470-478).
     Returns a 4-vector acc = [ce_sum, n_selected, loc_sum, n_pos] (device, no sync); the loss is
@@ -1356,9 +1368,7 @@ class _ResizeAdd(torch.autograd.Function):
         N, Hi, Wi, Ho, Wo, C = ctx.dims
         # the merged map feeds two convolutions in the LFPN (this level's fused 3x3 and the next level's upsample 1x1): both deliver into its
         # slot (write, then accumulate in the kernel epilogue) instead of returning two tensors for the autograd engine to add
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dout is not None:
-            g = dout.contiguous() if g is None else g.add_(dout)
+        g = _incoming(ctx.yslot, dout)
         if g is None:
             return None, None, None, None
         dup = None
@@ -1379,11 +1389,7 @@ def resize_bilinear_add(up, lateral=None, size=None):
         return out
     track = torch.is_grad_enabled() and (up.requires_grad or (lateral is not None and lateral.requires_grad))
     yslot = _new_slot(track)
-    out = _ResizeAdd.apply(up, lateral, size, yslot)
-    if yslot is not None:
-        yslot.__init__(out, False)
-        out._dh_slot = yslot
-    return out
+    return _publish(_ResizeAdd.apply(up, lateral, size, yslot), yslot, False)
 
 
 class _AvgPool2x2S1(torch.autograd.Function):
@@ -1403,20 +1409,15 @@ class _AvgPool2x2S1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         N, H, W, C = ctx.dims
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dy is not None:
-            g = dy.contiguous() if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy)
         if g is None:
             return None, None, None
-        xs = ctx.xslot
-        if xs is not None:                               # deliver into the producer's slot (+ its ReLU backward)
-            (x,) = ctx.saved_tensors
-            buf, acc = xs.target()
+        (x,) = ctx.saved_tensors                         # (kept only where the producer's slot wants its ReLU backward folded in)
+
+        def launch(buf, acc):
             call("danhip_avgpool2x2s1_same_bwd", ptr(g), ptr(x), ptr(buf), N, H, W, C, acc, stream())
-            return None, None, None
-        dx = torch.empty((N, H, W, C), dtype=ACT, device=g.device)
-        call("danhip_avgpool2x2s1_same_bwd", ptr(g), None, ptr(dx), N, H, W, C, 0, stream())
-        return dx, None, None
+
+        return _deliver(ctx.xslot, (N, H, W, C), g, launch), None, None
 
 
 def avg_pool_2x2_s1(x):
@@ -1429,11 +1430,7 @@ def avg_pool_2x2_s1(x):
     assert x.dtype == ACT and x.is_contiguous() and x.shape[-1] % 8 == 0
     track = torch.is_grad_enabled() and x.requires_grad
     yslot = _new_slot(track)
-    y = _AvgPool2x2S1.apply(x, _slot_of(x) if track else None, yslot)
-    if yslot is not None:
-        yslot.__init__(y, False)
-        y._dh_slot = yslot
-    return y
+    return _publish(_AvgPool2x2S1.apply(x, _slot_of(x) if track else None, yslot), yslot, False)
 
 
 class _Concat(torch.autograd.Function):
@@ -1451,14 +1448,8 @@ class _Concat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        g = ctx.yslot.take() if ctx.yslot is not None else None
         premasked = ctx.all_relu and dy is None          # slot deliveries arrive multiplied by (y > 0) = every input's own mask
-        if dy is not None:
-            dy = dy.contiguous()
-            if g is not None and g.shape[-1] != dy.shape[-1]:             # ragged output width: the slot carries the channel-padded layout
-                g[..., :dy.shape[-1]].add_(dy)
-            else:
-                g = dy if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy, torch.Tensor.contiguous, ragged=True)       # (ragged output width: the slot carries the channel-padded layout)
         if g is None:
             return (None,) * (3 + len(ctx.widths))
         grads, c0 = [], 0
@@ -1486,13 +1477,7 @@ def concat(tensors):
     all_relu = all(s is not None and s.is_relu for s in slots)
     yslot = _new_slot(True)
     y = _Concat.apply(slots, yslot, all_relu, *tensors)
-    if y.shape[-1] % 8 == 0:
-        yslot.__init__(y, all_relu)
-        y._dh_slot = yslot
-    else:                                                # ragged width: consumers deliver into the channel-padded layout (Cpad % 8 == 0)
-        yslot.__init__(y, all_relu, (y.shape[-1] + 7) // 8 * 8)
-        y._dh_pslot = yslot
-    return y
+    return _publish(y, yslot, all_relu, _ragged(y.shape[-1]))       # ragged width: consumers deliver into the channel-padded layout
 
 
 class _Add(torch.autograd.Function):
@@ -1513,9 +1498,7 @@ class _Add(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dy is not None:
-            g = dy.contiguous() if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy)
         if g is None:
             return (None,) * 5
         sa, sb = ctx.slots
@@ -1546,10 +1529,7 @@ def add(a, b):
     if a.dtype != ACT or not track or not _CTX.USE_SLOTS or a.shape != b.shape or a.shape[-1] % 8:
         return a + b
     yslot = _new_slot(True)
-    y = _Add.apply(a, b, _slot_of(a) if a.requires_grad else None, _slot_of(b) if b.requires_grad else None, yslot)
-    yslot.__init__(y, False)
-    y._dh_slot = yslot
-    return y
+    return _publish(_Add.apply(a, b, _slot_of(a) if a.requires_grad else None, _slot_of(b) if b.requires_grad else None, yslot), yslot, False)
 
 
 def _vptr(t):
@@ -1563,24 +1543,15 @@ def _vptr(t):
 
 
 def _wgrad_launch(d, xv, dyv, dw, db, cin_real, keep):
-    """Weight (+ bias) gradient of descriptor d with x / dy given as (possibly channel-slice) views, on the weight-gradient stream when the
-    trainer has it on (same ordering rules as _Conv2d.backward)."""
+    """Weight (+ bias) gradient of descriptor d with x / dy given as (possibly channel-slice) views, on the weight-gradient stream
+    whenever the trainer has it on (these callers' gradients back to autograd, if any, are complete at the join like the sinks)."""
     pitch = _lib.ConvPitch(xv.stride(2), dyv.stride(2), 0)
     ws, nws = _wgrad_scratch(d, dyv.device)
-    if _CTX.wgrad["on"]:
-        side = _CTX.wgrad["side"]
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        side.wait_event(ev)
-        e0 = _prof_begin(side)
-        call("danhip_conv2d_bwd_weight_strided", ctypes.byref(d), _vptr(xv), _vptr(dyv), ptr(dw), ptr(db), cin_real, ctypes.byref(pitch), ptr(ws), nws,
-             ctypes.c_void_p(side.cuda_stream))
-        _prof_end(e0, d, 2, side)
-        _CTX.wgrad["keep"].append((xv, dyv, ws) + tuple(keep))
-    else:
-        e0 = _prof_begin()
-        call("danhip_conv2d_bwd_weight_strided", ctypes.byref(d), _vptr(xv), _vptr(dyv), ptr(dw), ptr(db), cin_real, ctypes.byref(pitch), ptr(ws), nws, stream())
-        _prof_end(e0, d, 2)
+
+    def issue(st):
+        call("danhip_conv2d_bwd_weight_strided", ctypes.byref(d), _vptr(xv), _vptr(dyv), ptr(dw), ptr(db), cin_real, ctypes.byref(pitch), ptr(ws), nws, st)
+
+    _launch_wgrad(d, True, issue, (xv, dyv, ws) + tuple(keep))
 
 
 class _ContextBlock(torch.autograd.Function):
@@ -1658,22 +1629,21 @@ class _ContextBlock(torch.autograd.Function):
         wbs = ctx.saved_tensors[5:]
         N, H, W, C = x.shape
         dev = x.device
-        g = ctx.yslot.take() if ctx.yslot is not None else None
-        if dy is not None:
-            g = dy.contiguous() if g is None else g.add_(dy)
+        g = _incoming(ctx.yslot, dy)
         if g is None:
             return (None,) * (5 + ctx.nw)
         xs = ctx.xslot
         need_dx = ctx.needs_input_grad[0]
-        dx_ret, xbuf, xacc, xmask = None, None, 0, None
-        if need_dx:
-            if xs is not None:
-                xbuf, xacc = xs.target()
-                xmask = x if xs.is_relu else None
-            else:
-                xbuf = dx_ret = torch.empty_like(x)
+        xmask = x if (need_dx and xs is not None and xs.is_relu) else None
+        xbuf = None
         gr = torch.empty_like(g)
-        call("danhip_residual_bwd", ptr(g), ptr(r), ptr(xmask), ptr(gr), ptr(xbuf), xacc, g.numel(), stream())
+
+        def skip_path(buf, acc):                         # the first of x's three deliveries; the two 1 x 1 data gradients accumulate onto it
+            nonlocal xbuf
+            xbuf = buf
+            call("danhip_residual_bwd", ptr(g), ptr(r), ptr(xmask), ptr(gr), ptr(buf), acc, g.numel(), stream())
+
+        dx_ret = _deliver(xs, x.shape, x, skip_path) if need_dx else skip_path(None, 0)
         dhyper = torch.empty_like(hyper)
         dT = torch.empty_like(T)
         dU = torch.empty_like(U)
@@ -1681,19 +1651,11 @@ class _ContextBlock(torch.autograd.Function):
 
         def sinks(i):
             wp, bp = ctx.handles[i]
-            need_dw = ctx.needs_input_grad[5 + 2 * i] or ctx.blocks[i][0]
-            need_db = ctx.needs_input_grad[6 + 2 * i] or ctx.blocks[i][1]
             dw = db = None
-            if need_dw:
-                sk = _grad_sink(wp) if wp is not None else None
-                dw = sk if sk is not None else torch.zeros(ctx.khw[i] + (ctx.cin_real[i], ctx.couts[i]), dtype=torch.float32, device=dev)
-                if sk is None:
-                    grads[2 * i] = dw
-            if need_db:
-                sk = _grad_sink(bp) if bp is not None else None
-                db = sk if sk is not None else torch.zeros(ctx.couts[i], dtype=torch.float32, device=dev)
-                if sk is None:
-                    grads[2 * i + 1] = db
+            if ctx.needs_input_grad[5 + 2 * i] or ctx.blocks[i][0]:
+                dw, grads[2 * i] = _grad_target(wp, ctx.khw[i] + (ctx.cin_real[i], ctx.couts[i]), dev)
+            if ctx.needs_input_grad[6 + 2 * i] or ctx.blocks[i][1]:
+                db, grads[2 * i + 1] = _grad_target(bp, (ctx.couts[i],), dev)
             return dw, db
 
         def dgrad(i, dyv, mask, dxv, acc):
@@ -1748,9 +1710,7 @@ def context_block(x, params, hook_order, trace_params=None):
     track = torch.is_grad_enabled()
     handles, flat = [], []
     for w, b in params:
-        wp = w if (isinstance(w, torch.nn.Parameter) or hasattr(w, "_danhip_grad")) else None
-        bp = b if (isinstance(b, torch.nn.Parameter) or hasattr(b, "_danhip_grad")) else None
-        handles.append((wp, bp))
+        handles.append((_param_handle(w), _param_handle(b)))
         flat += [w, b]
     yslot = _new_slot(track)
     out = _ContextBlock.apply(x, _slot_of(x) if (track and x.requires_grad) else None, yslot, handles, hook_order, *flat)
@@ -1758,10 +1718,7 @@ def context_block(x, params, hook_order, trace_params=None):
         for k, prm in trace_params.items():
             _CTX.TRACE[id(prm)] = _CB_LAST[k].detach().contiguous()
         _CB_LAST.clear()
-    if yslot is not None:
-        yslot.__init__(out, False)
-        out._dh_slot = yslot
-    return out
+    return _publish(out, yslot, False)
 
 
 class _ConcatMix(torch.autograd.Function):
@@ -1812,11 +1769,12 @@ class _ConcatMix(torch.autograd.Function):
         N, H, W, C1, C2, Co = ctx.dims
         dev = a.device
         M = N * H * W
-        g = ctx.yslot.take() if ctx.yslot is not None else None          # slot deliveries are already multiplied by (out > 0)
-        if dy is not None:
+        def prepare(dy):                                 # (slot deliveries are already multiplied by (out > 0); the autograd tensor is not)
             dy = dy.contiguous().clone()
             call("danhip_relu_bwd_bias_grad", ptr(dy), ptr(out), None, M, Co, stream())
-            g = dy if g is None else g.add_(dy)
+            return dy
+
+        g = _incoming(ctx.yslot, dy, prepare)
         if g is None:
             return (None,) * 8
         wvp, bvp, lowp = ctx.handles
@@ -1830,25 +1788,19 @@ class _ConcatMix(torch.autograd.Function):
             ws, nws = _conv_scratch(d2, 1, dev)
             e0 = _prof_begin()
             xs = ctx.fslot
-            if xs is not None:
-                buf, acc = xs.target()
-                call("danhip_conv2d_bwd_data_ws", ctypes.byref(d2), ptr(g), ptr(wb_low), ptr(f) if xs.is_relu else None, ptr(buf), acc, ptr(ws), nws, stream())
-            else:
-                df = torch.empty_like(f)
-                call("danhip_conv2d_bwd_data_ws", ctypes.byref(d2), ptr(g), ptr(wb_low), None, ptr(df), 0, ptr(ws), nws, stream())
-            _prof_end(e0, d2, 5 if (xs is not None and xs.is_relu) else 1)
+            relu_f = xs is not None and xs.is_relu
+
+            def data_grad(buf, acc):
+                call("danhip_conv2d_bwd_data_ws", ctypes.byref(d2), ptr(g), ptr(wb_low), ptr(f) if relu_f else None, ptr(buf), acc, ptr(ws), nws, stream())
+
+            df = _deliver(xs, f.shape, f, data_grad)
+            _prof_end(e0, d2, 5 if relu_f else 1)
         dwv = dbv = None
         if need_dw:
-            sink = _grad_sink(wvp) if wvp is not None else None
-            dw = sink if sink is not None else torch.zeros((1, 1, C1 + C2, Co), dtype=torch.float32, device=dev)
+            dw, dwv = _grad_target(wvp, (1, 1, C1 + C2, Co), dev)
             db = None
             if need_db:
-                bs = _grad_sink(bvp) if bvp is not None else None
-                db = bs if bs is not None else torch.zeros(Co, dtype=torch.float32, device=dev)
-                if bs is None:
-                    dbv = db
-            if sink is None:
-                dwv = dw
+                db, dbv = _grad_target(bvp, (Co,), dev)
             # row block of a (+ the bias gradient: column sums of g), row block of f; then the columns of the OTHER part go back to zero
             _wgrad_launch(_desc(N, H, W, C1, Co, 1, 1, 1), a, g, dw[:, :, :C1, :], db, C1, (g,))
             _wgrad_launch(_desc(N, H, W, C2, Co, 1, 1, 1), f, g, dw[:, :, C1:, :], None, C2, (g,))
@@ -1870,8 +1822,7 @@ def concat_conv1x1_relu(a, f, wv, bv, split=None, trace_params=None):
     off-diagonal blocks of its gradient are then cleared.  trace_params: (w1, w2) kernel Parameters of the two parts (ops.TRACE: tests)."""
     assert not (_is_limbs(a) or _is_limbs(f)), "concat_conv1x1_relu is a 16-bit op (the nets take the unfused mix on the fp32 / split paths)"
     track = torch.is_grad_enabled() and (f.requires_grad or wv.requires_grad or _sink_trainable(wv))
-    wvp = wv if (isinstance(wv, torch.nn.Parameter) or hasattr(wv, "_danhip_grad")) else None
-    bvp = bv if (isinstance(bv, torch.nn.Parameter) or hasattr(bv, "_danhip_grad")) else None
+    wvp, bvp = _param_handle(wv), _param_handle(bv)
     lowp = getattr(wv, "_danhip_lower", None)
     yslot = _new_slot(track)
     out = _ConcatMix.apply(a.detach(), f, _slot_of(f) if (track and f.requires_grad) else None, yslot, (wvp, bvp, lowp),
@@ -1879,10 +1830,7 @@ def concat_conv1x1_relu(a, f, wv, bv, split=None, trace_params=None):
     if _CTX.TRACE is not None and trace_params is not None and split is not None:
         _CTX.TRACE[id(trace_params[0])] = out.detach()[..., :split[1]].contiguous()
         _CTX.TRACE[id(trace_params[1])] = out.detach()[..., split[1]:].contiguous()
-    if yslot is not None:
-        yslot.__init__(out, True)
-        out._dh_slot = yslot
-    return out
+    return _publish(out, yslot, True)
 
 
 class _BatchNorm(torch.autograd.Function):
@@ -1961,9 +1909,6 @@ class _DeformSample(torch.autograd.Function):
         return dx, doff, None, None, None, None, None
 
 
-# (KEEP_DEFORM_COL: a field of OpsContext, see the top of the module)
-
-
 class _DeformConv(torch.autograd.Function):
     """DeformConvOp / DeformConvBackpropOp (cpp/Deform/deform_conv.cc:392-535, :635-771) through the single-call entry
     points.  KEEP_DEFORM_COL (default on): the forward's im2col buffer (9x the activation, 1.9 GB at 160x160x256 batch 16) is kept for
@@ -2006,42 +1951,37 @@ class _DeformConv(torch.autograd.Function):
         kh, kw, stride, dilation, dg, cout, relu = ctx.cfg
         N, H, W, C = x.shape
         col, ctx.col = ctx.col, None
-        g = ctx.yslot.take() if ctx.yslot is not None else None          # slot deliveries arrive ReLU-masked
-        if dy is not None:
+        def prepare(dy):                                 # (slot deliveries arrive ReLU-masked; the autograd tensor does not)
             assert dy.dtype == ACT and dy.shape[-1] == cout
             dy = dy.contiguous()
             if relu:
                 dy = dy.clone()
                 call("danhip_relu_bwd_bias_grad", ptr(dy), ptr(y), None, dy.numel() // cout, cout, stream())
-            g = dy if g is None else g.add_(dy)
+            return dy
+
+        g = _incoming(ctx.yslot, dy, prepare)
         if g is None:
             return (None,) * 14
         bp = ctx.b_param
-        db_sink = _grad_sink(bp) if bp is not None else None
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = db_sink if db_sink is not None else torch.zeros(cout, dtype=torch.float32, device=x.device)
+        db, db_ret = _grad_target(bp, (cout,), x.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else (None, None)
+        dw, dw_ret = _grad_target(ctx.w_param, (1, 1, kh * kw * C, cout), x.device)       # (a sink: the flat gradient buffer's block)
+        doff = torch.empty_like(offsets)
+        nws = _lib.lib().danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1)
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
         # x's gradient goes straight into its producer's slot - times (x > 0) when x is a ReLU output, added to what other consumers (the
         # offset convolution) delivered - instead of through an autograd tensor the producer would clone, mask and add (three map-sized passes)
         xs = ctx.xslot if ctx.needs_input_grad[0] else None
-        if xs is not None:
-            dx, acc = xs.target()
-            relu_x = 1 if xs.is_relu else 0
-        else:
-            dx, acc, relu_x = torch.empty_like(x), 0, 0
-        doff = torch.empty_like(offsets)
-        dw_sink = _grad_sink(ctx.w_param) if ctx.w_param is not None else None       # the flat gradient buffer's block: accumulated in place
-        dw = dw_sink if dw_sink is not None else torch.zeros((1, 1, kh * kw * C, cout), dtype=torch.float32, device=x.device)
-        nws = _lib.lib().danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1)
-        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-        call("danhip_deform_conv_bwd_deliver", ptr(x), ptr(wb), ptr(offsets), ptr(g), ptr(col), ptr(dx), ptr(doff), ptr(dw), ptr(db), N, H, W, C, cout,
-             kh, kw, stride, dilation, dg, acc, relu_x, ptr(ws), nws, stream())
+
+        def launch(dx, acc):
+            call("danhip_deform_conv_bwd_deliver", ptr(x), ptr(wb), ptr(offsets), ptr(g), ptr(col), ptr(dx), ptr(doff), ptr(dw), ptr(db), N, H, W, C, cout,
+                 kh, kw, stride, dilation, dg, acc, 1 if (xs is not None and xs.is_relu) else 0, ptr(ws), nws, stream())
+
+        dx = _deliver(xs, x.shape, x, launch)
         if _CTX.GRAD_READY_HOOK is not None and bp is not None:
             _CTX.GRAD_READY_HOOK(bp)
-        if _CTX.GRAD_READY_HOOK is not None and dw_sink is not None:
+        if _CTX.GRAD_READY_HOOK is not None and dw_ret is None:
             _CTX.GRAD_READY_HOOK(ctx.w_param)
-        return ((None if xs is not None else dx), (None if dw_sink is not None else dw), (None if db_sink is not None else db), doff, None, None, None, None,
-                None, None, None, None, None, None)
+        return (dx, dw_ret, db_ret, doff) + (None,) * 10
 
 
 def deform_conv(x, w1x1, b, offsets, kh, kw, stride=1, dilation=1, deformable_group=1, relu=False):
@@ -2060,10 +2000,7 @@ def deform_conv(x, w1x1, b, offsets, kh, kw, stride=1, dilation=1, deformable_gr
     yslot = _new_slot(track)
     y = _DeformConv.apply(x, w1x1, b, offsets, kh, kw, stride, dilation, deformable_group, relu, bp, yslot,
                           _slot_of(x) if (track and x.requires_grad) else None, wp)
-    if yslot is not None:
-        yslot.__init__(y, relu)
-        y._dh_slot = yslot
-    return y
+    return _publish(y, yslot, relu)
 
 
 def preprocess_f32(img_rgb_u8):
