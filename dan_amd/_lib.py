@@ -103,6 +103,12 @@ SIGNATURES = {
     "danhip_conv2d_fwd_concat2": [DESC, P, P, I32, I32, P, P, P, ctypes.c_int, P],
     "danhip_conv2d_bwd_weight_strided": [DESC, P, P, P, P, I32, ctypes.POINTER(ConvPitch), P, ctypes.c_size_t, P],
     "danhip_relu_bwd_bias_grad": [P, P, P, I64, I32, P],
+    "danhip_relu_bwd_bias_grad_ws": [P, P, P, I64, I32, P, ctypes.c_size_t, P],
+    "danhip_l2norm_bwd_ws": [P, P, P, P, P, I64, I32, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P],
+    "danhip_l2norm_bwd_pool_scatter_ws": [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P],
+    "danhip_detection_loss_fwd_ws": [P, P, P, P, P, P, P, P, I32, I32, P, ctypes.c_size_t, P],
+    "danhip_sgd_momentum_flat_ws": [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P, ctypes.c_size_t, P],
+    "danhip_ordered_reduce_f32": [P, I32, I64, P, ctypes.c_int, P],
     "danhip_maxpool2x2_fwd": [P, P, I32, I32, I32, I32, P],
     "danhip_maxpool2x2_fwd_arg": [P, P, P, I32, I32, I32, I32, P],
     "danhip_maxpool2x2_bwd_arg": [P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
@@ -254,6 +260,10 @@ def _load(so_path, act_name):
         L.danhip_conv2d_workspace_bytes.argtypes = [DESC, ctypes.c_int]
         L.danhip_conv2d_bwd_weight_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_conv2d_bwd_weight_workspace_bytes.argtypes = [DESC]
+        for fn in (L.danhip_loss_workspace_bytes, L.danhip_sgd_workspace_bytes):
+            fn.restype, fn.argtypes = ctypes.c_size_t, []
+        L.danhip_reduce_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_reduce_workspace_bytes.argtypes = [I64, I32]
         L.danhip_deform_conv_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_deform_conv_workspace_bytes.argtypes = [I32, I32, I32, I32, I32, I32, I32, ctypes.c_int]
         L.danhip_deform_sample_bwd_workspace_bytes.restype = ctypes.c_size_t

@@ -20,7 +20,7 @@ void danhip_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* danhip_last_error(void) { return g_err; }
-extern "C" int danhip_version(void) { return 9; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch)
+extern "C" int danhip_version(void) { return 10; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch); 10: option "deterministic", danhip_ordered_reduce_f32, danhip_reduce_workspace_bytes and the _ws forms of the L2-norm / bias-gradient / loss / optimizer entry points
 extern "C" int danhip_act_dtype(void) {
 #ifdef DANHIP_FP16
   return DANHIP_F16;
@@ -39,6 +39,9 @@ extern "C" int danhip_act_dtype(void) {
 //   "deform_dx_untiled" DANHIP_DEFORM_DX_UNTILED  0 (default) / 1: the deformable backward's +-1 px gather as the wave-per-pixel kernel (A/B, tests)
 //   "pw_dgrad_ld_bn" DANHIP_PW_DGRAD_LD_BN  128 (default) / 256: widest tile of conv_pointwise.hip's data gradient WITH epilogue inputs (A/B:
 //                the 256-wide form reads dY once but measured no faster - S3FD 1198.6 vs 1197.6 img/s, DAN 433.9 vs 436.2)
+//   "deterministic" DANHIP_DETERMINISTIC  0 (default) / 1: every cross-workgroup fp32 sum of the S3FD training step in a fixed order (partials
+//                as plain stores into the caller's workspace + ordered_reduce.hip) instead of float atomics: bit-reproducible per (library build,
+//                CU count).  Entry points that would need atomics return DANHIP_EINVAL (danhip.h "Deterministic mode")
 namespace {
 // Thread safety ("no mutable globals" on the data path): the table is filled from the environment exactly once
 // (std::call_once, before the first read or write), every value is a relaxed atomic, and the kernels' host launchers read an option
@@ -48,7 +51,8 @@ struct Opt { const char* name; const char* env; int def; std::atomic<int> value;
 Opt g_opts[] = {{"splitk", "DANHIP_SPLITK", 1, {0}}, {"wgrad_slab", "DANHIP_WGRAD_SLAB", 1, {0}}, {"halo_b2", "DANHIP_HALO_B2", 0, {0}},
                 {"wgrad_b2", "DANHIP_WGRAD_B2", 0, {0}}, {"halo_general_epilogue", "DANHIP_HALO_GENERAL_EPILOGUE", 0, {0}},
                 {"deform_bwd_form", "DANHIP_DEFORM_BWD_FORM", 0, {0}}, {"pw_dgrad_ld_bn", "DANHIP_PW_DGRAD_LD_BN", 128, {0}},
-                {"wgrad_c8", "DANHIP_WGRAD_C8", 1, {0}}, {"deform_dx_untiled", "DANHIP_DEFORM_DX_UNTILED", 0, {0}}};
+                {"wgrad_c8", "DANHIP_WGRAD_C8", 1, {0}}, {"deform_dx_untiled", "DANHIP_DEFORM_DX_UNTILED", 0, {0}},
+                {"deterministic", "DANHIP_DETERMINISTIC", 0, {0}}};
 std::once_flag g_opts_once;
 Opt* find_opt(const char* name) {
   std::call_once(g_opts_once, [] {

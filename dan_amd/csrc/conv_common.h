@@ -205,6 +205,10 @@ WgradInstance wgrad_c8_select(const WgradCall& c);
 size_t wgrad_rows_workspace_bytes(const danhip_conv_desc* d);      // slab scratch the family's launch would use; 0 = none / not its shape
 size_t wgrad_pw_workspace_bytes(const danhip_conv_desc* d);
 
+size_t wgrad_c8_workspace_bytes(const WgradCall& c);                // deterministic mode only (0 otherwise / not its shape)
+// The ordered cross-workgroup sum of deterministic mode (ordered_reduce.hip; the order: danhip.h): out[c] (+)= sum_p part[p * pitch + c].
+int dh_ordered_reduce(const float* part, long pitch, int P, long C, float* out, int accumulate, hipStream_t s);
+
 // label of the instance most recently launched on this thread (danhip_conv_last_launch_label); "" before the first launch
 inline const char*& dh_last_launch_label() {
   static thread_local const char* label = "";

@@ -1009,6 +1009,7 @@ extern "C" int danhip_conv2d_bwd_data_takes_bits(const danhip_conv_desc* d) {
 // conv1_2's data gradient with conv1_1's weight / bias gradient folded in (conv_halo_c64.hip FUSE8): dX is never written.
 extern "C" int danhip_conv2d_bwd_data_first_supported(const danhip_conv_desc* d) {
   if (!d || check_desc(d) != DANHIP_OK || d->stride != 1) return 0;
+  if (danhip_option("deterministic") != 0) return 0;      // the folded kernel ends in float atomics: the caller takes the unfused pair (danhip.h)
   ConvArgs a = bwd_args(d);
   a.mask_bits = &g_rep_bits;
   a.fuse_x8 = &g_rep_act; a.fuse_dw = &g_rep_f32; a.fuse_cin_real = 3;

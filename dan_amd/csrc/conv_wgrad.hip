@@ -24,6 +24,9 @@ struct WgradArgs {
   int linear;
   int ci_tiles;        // number of input-channel tiles (blockIdx.x = co_tile * ci_tiles + ci_tile)
   int tapcols;         // 1: tile columns are the taps (C == 8 first layer): column chunk t = tap t, channels 0..7
+  float* slab;         // deterministic mode: split z stores its partial gradient plainly into row z of [splits][slab_row] floats - a row is the HWIO
+  long slab_row;       // gradient followed (at slab_db) by the bias gradient - and dh_ordered_reduce adds the rows onto dw / db in split order
+  long slab_db;
   FastDiv div_wo, div_howo;
 };
 
@@ -179,9 +182,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
       const int co = co0 + wco * TCO + o * 16 + (lane & 15);
-      if (co < a.Cout) atomicAdd(a.db + co, accb[o][0]);
+      if (co < a.Cout) {
+        if (a.slab) a.slab[(size_t)blockIdx.z * a.slab_row + a.slab_db + co] = accb[o][0];
+        else atomicAdd(a.db + co, accb[o][0]);
+      }
     }
   }
+  float* const part = a.slab ? a.slab + (size_t)blockIdx.z * a.slab_row : nullptr;      // (uniform)
 
   // epilogue: lane holds C[ci = i*16 + (lane>>4)*4 + r][co = o*16 + (lane&15)]
 #pragma unroll
@@ -195,7 +202,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
       for (int o = 0; o < NO; ++o) {
         const int co = co0 + wco * TCO + o * 16 + (lane & 15);
-        if (co < a.Cout) atomicAdd(a.dw + ((size_t)(t * a.cin_real + ci) * a.Cout + co), acc[i][o][r]);
+        if (co < a.Cout) {
+          const size_t e = (size_t)(t * a.cin_real + ci) * a.Cout + co;
+          if (part) part[e] = acc[i][o][r];           // every element of the row has exactly one writer: (ci tile, co tile, tap) of this split
+          else atomicAdd(a.dw + e, acc[i][o][r]);
+        }
       }
     }
   }
@@ -204,6 +215,39 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
 // first layer (8-channel image, dense tensors): the taps ride in the tile columns
 bool wgrad_tapcols(const WgradCall& c) {
   return c.d->Cin == 8 && c.d->kh * c.d->kw <= 16 && c.ldx == c.d->Cin && c.ldy == (c.d->Cout + 7) / 8 * 8;
+}
+
+// Split count of the generic kernel's pixel reduction for BCI x BCO tiles, and the deterministic mode's scratch: the launch and the workspace
+// query both read it.  A slab row is sized for cin_real = Cin (the query does not know cin_real).
+struct WgradPlan {
+  int splits, kt_per_split;
+  long slab_row, slab_db;
+  size_t slab_bytes;
+};
+WgradPlan plan_wgrad(const WgradCall& c, int BCI, int BCO) {
+  const danhip_conv_desc* d = c.d;
+  WgradPlan p{};
+  const bool tapcols = wgrad_tapcols(c);
+  const int co8 = (d->Cout + 7) / 8 * 8;
+  const int ktiles = (d->N * d->Ho * d->Wo + 63) / 64;
+  const int base_blocks = cdiv(co8, BCO) * (tapcols ? 1 : cdiv(d->Cin, BCI)) * (tapcols ? 1 : d->kh * d->kw);
+  // split the pixel reduction so that every CU holds as many workgroups as fit (LDS: two stages of the X and dY tiles; at most 4) in ONE
+  // wave of the grid — 1024 blocks of the 48 KB <128, 64> instance were 1.33 waves of 768 slots: the first layer's gradient ran its last
+  // third alone on a third of the chip — but keep >= 8 K tiles per split
+  const int lds_block = 2 * 64 * (BCI + BCO) * 2;
+  int per_cu = (160 * 1024) / lds_block;
+  if (per_cu > 4) per_cu = 4;
+  const int slots = per_cu * dh_cu_count();
+  int splits = slots / base_blocks;
+  const int max_splits = (ktiles + 7) / 8;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  p.kt_per_split = (ktiles + splits - 1) / splits;
+  p.splits = (ktiles + p.kt_per_split - 1) / p.kt_per_split;
+  p.slab_db = ((long)d->kh * d->kw * d->Cin * d->Cout + 3) / 4 * 4;
+  p.slab_row = p.slab_db + (d->Cout + 3) / 4 * 4;
+  p.slab_bytes = (size_t)p.splits * p.slab_row * sizeof(float);
+  return p;
 }
 
 template <int BCI, int BCO, int WCI_WAVES>
@@ -228,23 +272,24 @@ int launch_wgrad(const WgradCall& c, hipStream_t s) {
   const int co_tiles = cdiv(a.Co8, BCO);
   a.ci_tiles = a.tapcols ? 1 : cdiv(a.C, BCI);
   const int taps = a.tapcols ? 1 : a.kh * a.kw;
-  const int base_blocks = co_tiles * a.ci_tiles * taps;
-  // split the pixel reduction so that every CU holds as many workgroups as fit (LDS: two stages of the X and dY tiles; at most 4) in ONE
-  // wave of the grid — 1024 blocks of the 48 KB <128, 64> instance were 1.33 waves of 768 slots: the first layer's gradient ran its last
-  // third alone on a third of the chip — but keep >= 8 K tiles per split
-  const int lds_block = 2 * 64 * (BCI + BCO) * 2;
-  int per_cu = (160 * 1024) / lds_block;
-  if (per_cu > 4) per_cu = 4;
-  const int slots = per_cu * dh_cu_count();
-  int splits = slots / base_blocks;
-  const int max_splits = (a.ktiles + 7) / 8;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  a.kt_per_split = (a.ktiles + splits - 1) / splits;
-  splits = (a.ktiles + a.kt_per_split - 1) / a.kt_per_split;
+  const WgradPlan p = plan_wgrad(c, BCI, BCO);
+  a.kt_per_split = p.kt_per_split;
+  const int splits = p.splits;
+  const bool det = danhip_option("deterministic") != 0;
+  if (det) {
+    DH_REQUIRE(c.ws && ((uintptr_t)c.ws & 15) == 0 && c.ws_bytes >= p.slab_bytes, DANHIP_EINVAL,
+               "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
+    a.slab = reinterpret_cast<float*>(c.ws);
+    a.slab_row = p.slab_row;
+    a.slab_db = p.slab_db;
+  }
   dim3 grid((unsigned)(co_tiles * a.ci_tiles), (unsigned)taps, (unsigned)splits);
   hipLaunchKernelGGL((conv_wgrad_kernel<BCI, BCO, WCI_WAVES>), grid, dim3(256), 2 * 64 * (BCI + BCO) * 2, s, a);
   DH_LAUNCH_CHECK();
+  if (det) {
+    if (int rc = dh_ordered_reduce(a.slab, a.slab_row, splits, (long)a.kh * a.kw * a.cin_real * a.Cout, a.dw, 1, s)) return rc;
+    if (a.db) return dh_ordered_reduce(a.slab + a.slab_db, a.slab_row, splits, a.Cout, a.db, 1, s);
+  }
   return DANHIP_OK;
 }
 
@@ -256,13 +301,20 @@ WgradInstance wgrad_instance(const char* label) {
   return i;
 }
 
+// tile of the generic kernel for this call
+void wgrad_generic_tile(const WgradCall& c, bool& ci_wide, bool& co_wide) {
+  const int co8 = (c.d->Cout + 7) / 8 * 8;
+  ci_wide = c.d->Cin > 64 || wgrad_tapcols(c);      // (tap columns: 9 taps x 8 channels in the 128 rows)
+  co_wide = co8 > 64;
+}
+
 // THE kernel selection of a weight-gradient call: the order of precedence between the families, once.
 WgradInstance select_wgrad(const WgradCall& c) {
   if (WgradInstance i = wgrad_rows_select(c)) return i;
   if (WgradInstance i = wgrad_pw_select(c)) return i;
   if (WgradInstance i = wgrad_c8_select(c)) return i;
-  const int co8 = (c.d->Cout + 7) / 8 * 8;
-  const bool ci_wide = c.d->Cin > 64 || wgrad_tapcols(c), co_wide = co8 > 64;      // (tap columns: 9 taps x 8 channels in the 128 rows)
+  bool ci_wide, co_wide;
+  wgrad_generic_tile(c, ci_wide, co_wide);
   if (ci_wide && co_wide) return wgrad_instance<128, 128, 2>("conv_wgrad_kernel<128, 128, 2>");
   if (ci_wide) return wgrad_instance<128, 64, 2>("conv_wgrad_kernel<128, 64, 2>");
   if (!co_wide) return wgrad_instance<64, 64, 2>("conv_wgrad_kernel<64, 64, 2>");
@@ -280,6 +332,15 @@ extern "C" const char* danhip_conv_wgrad_kernel_label(const danhip_conv_desc* d)
 
 extern "C" size_t danhip_conv2d_bwd_weight_workspace_bytes(const danhip_conv_desc* d) {
   if (!d) return 0;
+  if (danhip_option("deterministic") != 0) {      // every descriptor has a size: the family select_wgrad picks, its partial rows + bias-gradient rows
+    if (const size_t r = wgrad_rows_workspace_bytes(d)) return r;
+    if (const size_t r = wgrad_pw_workspace_bytes(d)) return r;
+    const WgradCall c{d, nullptr, nullptr, nullptr, nullptr, 3, d->Cin, (d->Cout + 7) / 8 * 8, nullptr, 0};      // (the label's convention)
+    if (const size_t r = wgrad_c8_workspace_bytes(c)) return r;
+    bool ci_wide, co_wide;
+    wgrad_generic_tile(c, ci_wide, co_wide);
+    return plan_wgrad(c, ci_wide ? 128 : 64, co_wide ? 128 : 64).slab_bytes;
+  }
   if (!danhip_option("wgrad_slab")) return 0;
   const size_t r = wgrad_rows_workspace_bytes(d);
   return r ? r : wgrad_pw_workspace_bytes(d);

@@ -25,7 +25,10 @@ struct WgC8Args {
   int N, H, W, cin_real;
   int tiles_x, tiles_y, items;
   FastDiv div_tx, div_txy;
+  float* slab;         // deterministic mode: the workgroup's gradient goes to row blockIdx.x of [gridDim.x][C8_SLAB_ROW] floats (HWIO gradient,
+                       // then db at C8_SLAB_DB) as plain stores, and dh_ordered_reduce adds the rows onto dw / db
 };
+constexpr int C8_SLAB_DB = 9 * 4 * 64, C8_SLAB_ROW = C8_SLAB_DB + 64;
 
 constexpr int C8_TH = 8, C8_TW = 64, C8_PW = C8_TW + 2;
 constexpr int C8_PROWS = (C8_TH + 2) * C8_PW;                 // 660 patch pixels
@@ -144,6 +147,31 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_c8_kernel(const WgC8Args a)
 
   // ---- eight waves -> one gradient in LDS -> global atomics.  Lane holds acc[mt][nt][r] = dW[tap slot mt*4 + g][channel r][co = nt*16 + (lane & 15)]
   float* red = reinterpret_cast<float*>(smem);                 // [12 slots][4 channels][64 co]
+  if (a.slab) {
+    // No LDS float atomics: wave w stores its fragments into its own copy red[w][48 rows][64 co] (96 KiB of the 150 KiB the tiles held), the
+    // eight copies are added in wave order and the sum goes to the workgroup's slab row.  Row (mt*4 + g)*4 + r is rotated by 16 g columns:
+    // a ds_write_b32 is served in two halves of 32 lanes on 32 banks, and lanes l / l + 16 (g, g + 1: rows 4 x 64 floats apart) would share
+    // a bank unrotated; the reader (64 consecutive co of one row per wave) is conflict-free either way.
+    float* mine = red + wave * (12 * 4 * 64);
+#pragma unroll
+    for (int mt = 0; mt < 3; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mine[((mt * 4 + g) * 4 + r) * 64 + ((nt * 16 + (lane & 15) + 16 * g) & 63)] = acc[mt][nt][r];
+    __syncthreads();
+    float* row = a.slab + (size_t)blockIdx.x * C8_SLAB_ROW;
+    for (int i = tid; i < 10 * 4 * 64; i += 512) {              // slots 0..8: the taps; slot 9, channel 0: the column sums of dY (db)
+      const int co = i & 63, c = (i >> 6) & 3, slot = i >> 8;
+      const int src = (i & ~63) + ((co + 16 * (slot & 3)) & 63);
+      float s = red[src];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) s += red[w * (12 * 4 * 64) + src];
+      if (slot < 9) { if (c < a.cin_real) row[(slot * a.cin_real + c) * 64 + co] = s; }
+      else if (c == 0) row[C8_SLAB_DB + co] = s;
+    }
+    return;
+  }
   for (int i = tid; i < 12 * 4 * 64; i += 512) red[i] = 0.f;
   __syncthreads();
 #pragma unroll
@@ -175,12 +203,29 @@ int launch_wg_c8(const WgradCall& c, hipStream_t s) {
   a.div_txy = make_fastdiv(a.tiles_x * a.tiles_y);
   int G = dh_cu_count();
   if (a.items < G) G = a.items;
+  const bool det = danhip_option("deterministic") != 0;
+  if (det) {
+    DH_REQUIRE(c.ws && ((uintptr_t)c.ws & 15) == 0 && c.ws_bytes >= (size_t)G * C8_SLAB_ROW * sizeof(float), DANHIP_EINVAL,
+               "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
+    a.slab = reinterpret_cast<float*>(c.ws);
+  }
   hipLaunchKernelGGL(conv_wgrad_c8_kernel, dim3(G), dim3(512), C8_LDS, s, a);
   DH_LAUNCH_CHECK();
+  if (det) {
+    if (int rc = dh_ordered_reduce(a.slab, C8_SLAB_ROW, G, 9 * a.cin_real * 64, a.dw, 1, s)) return rc;
+    if (a.db) return dh_ordered_reduce(a.slab + C8_SLAB_DB, C8_SLAB_ROW, G, 64, a.db, 1, s);
+  }
   return DANHIP_OK;
 }
 
 }  // namespace
+
+size_t wgrad_c8_workspace_bytes(const WgradCall& c) {
+  if (danhip_option("deterministic") == 0 || !wgrad_c8_select(c)) return 0;
+  const danhip_conv_desc* d = c.d;
+  const int items = d->N * ((d->W + C8_TW - 1) / C8_TW) * ((d->H + C8_TH - 1) / C8_TH);
+  return (size_t)(items < dh_cu_count() ? items : dh_cu_count()) * C8_SLAB_ROW * sizeof(float);
+}
 
 // conv1_1: both operands staged once, taps as address offsets
 WgradInstance wgrad_c8_select(const WgradCall& c) {

@@ -32,6 +32,8 @@ struct WgPwArgs {
   float* slab;         // optional: partial tiles as plain stores + wg_pw_reduce_kernel (short launches; see conv_wgrad_rows.hip)
   int splits;
   int b2;              // 1: second barrier per K-step (option "wgrad_b2")
+  float* db_slab;      // deterministic mode: bias-gradient sums to row `split` of [splits][db_pitch] instead of atomics on db (conv_wgrad_rows.hip)
+  int db_pitch;
   FastDiv div_ci, div_pairs;
 };
 
@@ -274,7 +276,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int co = co0 + wco * 64 + (wci * 2 + e) * 16 + (lane & 15);
-      if (lane < 16 && co < a.Cout) atomicAdd(a.db + co, accb[e][0]);
+      if (lane < 16 && co < a.Cout) {
+        if (a.db_slab) a.db_slab[(size_t)split * a.db_pitch + co] = accb[e][0];
+        else atomicAdd(a.db + co, accb[e][0]);
+      }
     }
   }
 }
@@ -337,6 +342,9 @@ struct WgPwPlan {
   int co8, ksteps, ci_tiles, co_tiles, pairs, splits, steps_per_split;
   bool slab;              // slab form for short launches only (see conv_wgrad_rows.hip: on long ones the atomic tail hides under the other blocks' MFMAs)
   size_t slab_bytes;
+  bool det;               // deterministic mode (conv_wgrad_rows.hip): always the slab form, the bias-gradient rows behind the tiles
+  size_t db_off;
+  int db_pitch;
 };
 WgPwPlan plan_wg_pw(const danhip_conv_desc* d) {
   WgPwPlan p{};
@@ -352,6 +360,13 @@ WgPwPlan plan_wg_pw(const danhip_conv_desc* d) {
   p.splits = (p.ksteps + p.steps_per_split - 1) / p.steps_per_split;
   p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.steps_per_split <= 192);
   p.slab_bytes = (size_t)dh_cu_count() * 32 * 512 * 16;
+  p.det = danhip_option("deterministic") != 0;
+  if (p.det) {
+    p.slab = true;
+    p.db_pitch = (d->Cout + 3) / 4 * 4;
+    p.db_off = (size_t)p.pairs * p.splits * 32 * 512 * 16;
+    p.slab_bytes = p.db_off + (size_t)p.splits * p.db_pitch * sizeof(float);
+  }
   return p;
 }
 
@@ -374,13 +389,16 @@ int launch_wg_pw(const WgradCall& c, hipStream_t s) {
   a.xcd_grouped = (p.splits % 8 == 0 && p.pairs > 1) ? 1 : 0;
   a.splits = p.splits;
   a.b2 = danhip_option("wgrad_b2");
-  a.slab = (danhip_option("wgrad_slab") && c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
+  a.slab = ((p.det || danhip_option("wgrad_slab")) && c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
+  DH_REQUIRE(!p.det || a.slab, DANHIP_EINVAL, "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
+  if (p.det && c.db) { a.db_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + p.db_off); a.db_pitch = p.db_pitch; }
   hipLaunchKernelGGL(conv_wgrad_pw_kernel, dim3(p.pairs * p.splits), dim3(512), LDS, s, a);
   DH_LAUNCH_CHECK();
   if (a.slab) {
     hipLaunchKernelGGL(wg_pw_reduce_kernel, dim3(p.pairs * (32 * 512 / 64)), dim3(256), 0, s, a);
     DH_LAUNCH_CHECK();
   }
+  if (a.db_slab) return dh_ordered_reduce(a.db_slab, a.db_pitch, p.splits, d->Cout, c.db, 1, s);
   return DANHIP_OK;
 }
 

@@ -45,6 +45,8 @@ struct WgRowsArgs {
   int b2;              // 1: second barrier per K-step (option "wgrad_b2")
   float* slab;         // optional workspace: every block stores its partial tile here (plain 16-byte stores) and wg_rows_reduce_kernel combines
   int splits;
+  float* db_slab;      // deterministic mode: the block's bias-gradient sums go to row `split` of [splits][db_pitch] (plain stores) instead of atomics on db
+  int db_pitch;
   FastDiv div_tx, div_h, div_ci, div_pairs;
 #ifdef WR_TRACE
   unsigned* trace;     // tools/halo2_trace.hip -DTRACE_WGRAD: [2 groups][128 K-steps][4 stamps] shader clocks of workgroup 0, waves 0 and 4
@@ -415,7 +417,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       for (int o = 0; o < NO; ++o) __builtin_nontemporal_store(acc[t][o], dst + (t * NO + o) * 512);
     if (do_bias) {
       const int co = co0 + wco * NO * 16 + wci * 16 + (lane & 15);
-      if (lane < 16 && co < a.Cout) atomicAdd(a.db + co, accb[0]);
+      if (lane < 16 && co < a.Cout) {
+        if (a.db_slab) a.db_slab[(size_t)split * a.db_pitch + co] = accb[0];
+        else atomicAdd(a.db + co, accb[0]);
+      }
     }
     WR_CLK(3);
     return;
@@ -517,6 +522,9 @@ struct WgRowsPlan {
   int co8, ci_tiles, co_tiles, pairs, tiles_x, total_rows, splits, rows_per_split;
   bool slab;              // the slab form (partial tiles as plain stores + a combine pass) is worth taking ...
   size_t slab_bytes;      // ... and needs this much scratch (one register tile per workgroup, at most one workgroup per CU)
+  bool det;               // deterministic mode: always the slab form (any number of splits), the bias-gradient rows behind the tiles
+  size_t db_off;          // byte offset of the [splits][db_pitch] bias-gradient rows in the scratch
+  int db_pitch;
 };
 WgRowsPlan plan_wg_rows(const danhip_conv_desc* d) {
   WgRowsPlan p{};
@@ -537,6 +545,13 @@ WgRowsPlan plan_wg_rows(const danhip_conv_desc* d) {
   // extra pass costs more than it saves (batch 16: conv3_2 0.426 against 0.428 ms, conv2_2 0.479 against 0.455; profiles/r3).
   p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.rows_per_split <= 192);
   p.slab_bytes = (size_t)dh_cu_count() * 9 * (cot / 32) * 512 * 16;
+  p.det = danhip_option("deterministic") != 0;
+  if (p.det) {            // every launch through the slab (wg_rows_reduce_kernel's order is fixed by `splits`), db as rows for the ordered reduction
+    p.slab = true;
+    p.db_pitch = (d->Cout + 3) / 4 * 4;
+    p.db_off = (size_t)p.pairs * p.splits * 9 * (cot / 32) * 512 * 16;
+    p.slab_bytes = p.db_off + (size_t)p.splits * p.db_pitch * sizeof(float);
+  }
   return p;
 }
 
@@ -553,6 +568,8 @@ int launch_wg_rows(const WgradCall& c, hipStream_t s) {
   a.div_tx = make_fastdiv(a.tiles_x);
   a.div_h = make_fastdiv(d->H);
   a.slab = (c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
+  DH_REQUIRE(!p.det || a.slab, DANHIP_EINVAL, "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
+  if (p.det && c.db) { a.db_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + p.db_off); a.db_pitch = p.db_pitch; }
 #ifdef WR_TRACE
   constexpr int LDS = 6 * (32 * COT * 2) + 6 * 40 * 128 + 4096;
   a.trace = wr_trace_buffer();
@@ -585,6 +602,7 @@ int launch_wg_rows(const WgradCall& c, hipStream_t s) {
     hipLaunchKernelGGL((wg_rows_reduce_kernel<COT>), dim3(chunks), dim3(256), 0, s, a);
     DH_LAUNCH_CHECK();
   }
+  if (a.db_slab) return dh_ordered_reduce(a.db_slab, a.db_pitch, splits, d->Cout, c.db, 1, s);
   return DANHIP_OK;
 }
 

@@ -901,6 +901,7 @@ extern "C" size_t danhip_deform_sample_bwd_workspace_bytes(int32_t N, int32_t H,
 static int deform_sample_bwd_impl(const uint16_t* x, const uint16_t* offsets, const uint16_t* dS, uint16_t* dx, uint16_t* d_offsets,
                                   int32_t N, int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t stride, int32_t dilation,
                                   int32_t deformable_group, int accumulate, int relu_x, float* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "deform_sample_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   const bf16_t* rx = relu_x ? x : nullptr;              // dx *= (x > 0): x is a ReLU output whose producer takes dx as delivered
   DH_REQUIRE(x && offsets && dS && dx && d_offsets && workspace, DANHIP_EINVAL, "deform_sample_bwd: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && workspace_bytes >= danhip_deform_sample_bwd_workspace_bytes(N, H, W, C), DANHIP_EWORKSPACE,
@@ -1039,6 +1040,7 @@ static int deform_conv_bwd_impl(const uint16_t* x, const uint16_t* wb_packed, co
                                 int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t kh, int32_t kw, int32_t stride,
                                 int32_t dilation, int32_t deformable_group, int accumulate_dx, int relu_x, void* workspace,
                                 size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "deform_conv_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   DH_REQUIRE(x && wb_packed && offsets && dy && dx && d_offsets && dw && workspace, DANHIP_EINVAL, "deform_conv_bwd: null pointer");
   const size_t need = danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1);
   DH_REQUIRE(workspace_bytes >= need && need > 0, DANHIP_EWORKSPACE, "deform_conv_bwd: workspace too small");

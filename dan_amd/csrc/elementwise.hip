@@ -24,7 +24,9 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 
 // ------------------------------------------------------------------ ReLU backward + bias gradient (one pass over dy)
 // grid: (column groups of 8 channels) x (row chunks).  Each thread owns 8 channels and strides over rows.
-__global__ void relu_bwd_bias_kernel(bf16_t* __restrict__ dy, const bf16_t* __restrict__ y, float* __restrict__ db, long M, int C) {
+// `part` (deterministic mode): the block's C sums go to row blockIdx.x of part [gridDim.x][C] as plain stores instead of atomics onto db.
+__global__ void relu_bwd_bias_kernel(bf16_t* __restrict__ dy, const bf16_t* __restrict__ y, float* __restrict__ db, long M, int C,
+                                     float* __restrict__ part) {
   const int cg = C / 8;                                   // channel groups per row
   const int tpr = blockDim.x / cg > 0 ? blockDim.x / cg : 1;  // rows handled in parallel by one block
   const int g = threadIdx.x % cg, rsub = threadIdx.x / cg;
@@ -57,6 +59,12 @@ __global__ void relu_bwd_bias_kernel(bf16_t* __restrict__ dy, const bf16_t* __re
     for (int r = 0; r < tpr; ++r)
 #pragma unroll
       for (int i = 0; i < 8; ++i) t[i] += red[(r * cg + threadIdx.x) * 8 + i];
+    if (part) {
+      float4* row = reinterpret_cast<float4*>(part + (size_t)blockIdx.x * C + threadIdx.x * 8);
+      row[0] = make_float4(t[0], t[1], t[2], t[3]);
+      row[1] = make_float4(t[4], t[5], t[6], t[7]);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) atomicAdd(db + threadIdx.x * 8 + i, t[i]);
   }
@@ -197,6 +205,33 @@ __global__ void l2norm_fwd_kernel(const bf16_t* __restrict__ x, const float* __r
   }
 }
 
+// Deterministic mode's end of the two L2-norm backward kernels (no LDS float atomics): the wave's 64 / LPP pixel groups are summed by xor
+// shuffles (a fixed tree), lane group 0 stores the wave's C sums into the wave's own LDS slot (slots [waves][C], rows of C >= 64 floats
+// written as 16-byte vectors), the slots are added in wave order and the block's sums go to row blockIdx.x of part [gridDim.x][C].
+template <int LPP, int VPL>
+__device__ __forceinline__ void l2_bwd_dgamma_ordered(float (*dg)[8], float* slots, float* __restrict__ part, int C) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int sub = lane / LPP, l = lane % LPP;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int o = LPP; o < 64; o <<= 1) dg[v][i] += __shfl_xor(dg[v][i], o, 64);
+    if (sub == 0) {
+      float4* dst = reinterpret_cast<float4*>(slots + (size_t)wave * C + (v * LPP + l) * 8);
+      dst[0] = make_float4(dg[v][0], dg[v][1], dg[v][2], dg[v][3]);
+      dst[1] = make_float4(dg[v][4], dg[v][5], dg[v][6], dg[v][7]);
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float s = slots[c];
+    for (int w = 1; w < nw; ++w) s += slots[(size_t)w * C + c];
+    part[(size_t)blockIdx.x * C + c] = s;
+  }
+}
+
 // The arithmetic of the L2-norm backward, shared by l2norm_bwd_kernel and the gradient-junction kernel below.  Which products fuse with the
 // following add is WRITTEN OUT (contraction off, explicit fmaf) - as the compiler had chosen for l2norm_bwd_kernel - because left to the
 // compiler the choice depends on the surrounding code, and the junction kernel must reproduce l2norm_bwd_kernel bit for bit.
@@ -221,13 +256,18 @@ __device__ __forceinline__ float l2_bwd_dgamma(float dg, float f, float g, float
 
 // dx = gamma*inv*dy - x*inv^3 * sum_c(dy*gamma*x)   (second term dropped where sum x^2 <= 1e-10: clamp inactive grad)
 // dgamma[c] += sum_pix dy*x*inv.  dx is ACCUMULATED into when `accumulate` (the tapped map also feeds the next conv block).
-template <int LPP, int VPL>
+// DET: the deterministic mode's instance (ends in l2_bwd_dgamma_ordered, `part` set); the default instance carries none of that code - the
+// junction kernel below sits at its register bound (128 per lane: two 512-thread workgroups per CU).
+template <int LPP, int VPL, bool DET>
 __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma, const bf16_t* __restrict__ dy,
-                                  bf16_t* __restrict__ dx, float* __restrict__ dgamma, long M, int C, int accumulate, int relu_mask) {
+                                  bf16_t* __restrict__ dx, float* __restrict__ dgamma, long M, int C, int accumulate, int relu_mask,
+                                  float* __restrict__ part) {
   constexpr int PPW = 64 / LPP;
-  extern __shared__ float sg[];                    // [C] block-level dgamma accumulator
-  for (int c = threadIdx.x; c < C; c += blockDim.x) sg[c] = 0.f;
-  __syncthreads();
+  extern __shared__ float sg[];                    // [C] block-level dgamma accumulator ([waves][C] slots when `part`: deterministic mode)
+  if constexpr (!DET) {                            // (the ordered form writes every slot before it reads one)
+    for (int c = threadIdx.x; c < C; c += blockDim.x) sg[c] = 0.f;
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63;
   const int sub = lane / LPP, l = lane % LPP;
   const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -275,6 +315,7 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
       }
     }
   }
+  if constexpr (DET) { l2_bwd_dgamma_ordered<LPP, VPL>(dg, sg, part, C); return; }
 #pragma unroll
   for (int v = 0; v < VPL; ++v)
 #pragma unroll
@@ -291,16 +332,18 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
 // held when `accumulate`) is rounded to 16 bits before the second is added - so dx is bit-identical to it; `pool_first` is the other
 // arrival order (scatter, then L2 norm).  dgamma: as l2norm_bwd_kernel (per-lane partial sums over other pixel sets, so equal up to fp32
 // summation order only).
-template <int LPP>
+template <int LPP, bool DET>
 __global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
                                                                       const bf16_t* __restrict__ dy, const unsigned char* __restrict__ arg,
                                                                       const bf16_t* __restrict__ pdy, bf16_t* __restrict__ dx,
                                                                       float* __restrict__ dgamma, int N, int H, int W, int C, int Ho, int Wo,
-                                                                      int accumulate, int relu_mask, int pool_first) {
+                                                                      int accumulate, int relu_mask, int pool_first, float* __restrict__ part) {
   constexpr int PPW = 64 / LPP;                    // windows per wave
-  extern __shared__ float sg[];                    // [C] block-level dgamma accumulator
-  for (int c = threadIdx.x; c < C; c += blockDim.x) sg[c] = 0.f;
-  __syncthreads();
+  extern __shared__ float sg[];                    // [C] block-level dgamma accumulator ([waves][C] slots when `part`: deterministic mode)
+  if constexpr (!DET) {                            // (the ordered form writes every slot before it reads one)
+    for (int c = threadIdx.x; c < C; c += blockDim.x) sg[c] = 0.f;
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63;
   const int sub = lane / LPP, l = lane % LPP;
   const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -371,6 +414,7 @@ __global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16
       }
     }
   }
+  if constexpr (DET) { l2_bwd_dgamma_ordered<LPP, 1>(reinterpret_cast<float (*)[8]>(dg), sg, part, C); return; }
 #pragma unroll
   for (int i = 0; i < 8; ++i) atomicAdd(sg + l * 8 + i, dg[i]);
   __syncthreads();
@@ -408,7 +452,14 @@ inline int grid_for(long total, int block, int cap = 8192) {
 
 }  // namespace
 
-extern "C" int danhip_relu_bwd_bias_grad(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* stream) {
+// Deterministic mode (option "deterministic", read once per call): the partial rows of a sum over workgroups go to the caller's workspace and
+// through dh_ordered_reduce (ordered_reduce.hip); a call without workspace is refused, never served with atomics.
+int dh_ordered_reduce(const float* part, long pitch, int P, long C, float* out, int accumulate, hipStream_t s);
+#define DH_REQUIRE_DET_WS(who, rows, C)                                                                                                         \
+  DH_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= (size_t)(rows) * (size_t)(C) * sizeof(float), DANHIP_EINVAL,                            \
+             who ": deterministic mode needs a 16-byte aligned workspace of danhip_reduce_workspace_bytes(M, C) bytes (call " who "_ws)")
+
+static int relu_bwd_bias_grad_impl(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* ws, size_t ws_bytes, void* stream) {
   DH_REQUIRE(dy && M > 0 && C > 0, DANHIP_EINVAL, "relu_bwd_bias_grad: bad arguments");
   DH_REQUIRE(C % 8 == 0 && C / 8 <= 256, DANHIP_EINVAL, "relu_bwd_bias_grad: C=%d must be a multiple of 8 and <= 2048", C);
   if (!y && !db) return DANHIP_OK;
@@ -417,10 +468,19 @@ extern "C" int danhip_relu_bwd_bias_grad(uint16_t* dy, const uint16_t* y, float*
   const int tpr = block / cg > 0 ? block / cg : 1;
   long blocks = (M + tpr - 1) / tpr;
   if (blocks > 2048) blocks = 2048;
+  const bool det = db && danhip_option("deterministic") != 0;
+  if (det) DH_REQUIRE_DET_WS("danhip_relu_bwd_bias_grad", blocks, C);
   hipLaunchKernelGGL(relu_bwd_bias_kernel, dim3((unsigned)blocks), dim3(block), block * 8 * sizeof(float), (hipStream_t)stream, dy, y, db,
-                     (long)M, C);
+                     (long)M, C, det ? reinterpret_cast<float*>(ws) : nullptr);
   DH_LAUNCH_CHECK();
+  if (det) return dh_ordered_reduce(reinterpret_cast<const float*>(ws), C, (int)blocks, C, db, 1, (hipStream_t)stream);
   return DANHIP_OK;
+}
+extern "C" int danhip_relu_bwd_bias_grad(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* stream) {
+  return relu_bwd_bias_grad_impl(dy, y, db, M, C, nullptr, 0, stream);
+}
+extern "C" int danhip_relu_bwd_bias_grad_ws(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* ws, size_t ws_bytes, void* stream) {
+  return relu_bwd_bias_grad_impl(dy, y, db, M, C, ws, ws_bytes, stream);
 }
 
 namespace {
@@ -639,8 +699,8 @@ extern "C" int danhip_l2norm_fwd(const uint16_t* x, const float* gamma, uint16_t
   return DANHIP_OK;
 }
 
-extern "C" int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
-                                 int32_t C, int accumulate, int relu_mask, void* stream) {
+static int l2norm_bwd_impl(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
+                           int32_t C, int accumulate, int relu_mask, void* ws, size_t ws_bytes, void* stream) {
   DH_REQUIRE(x && gamma && dy && dx && dgamma && M > 0, DANHIP_EINVAL, "l2norm_bwd: bad arguments");
   DH_REQUIRE(C == 256 || C == 512 || C == 1024 || C == 128 || C == 64, DANHIP_EINVAL, "l2norm_bwd: C=%d unsupported", C);
   hipStream_t s = (hipStream_t)stream;
@@ -651,21 +711,39 @@ extern "C" int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const ui
   long blocks = (M + 16 * ppw - 1) / (16 * ppw);
   if (blocks > 512) blocks = 512;
   const dim3 g((unsigned)blocks), b(1024);
-  const size_t lds = (size_t)C * sizeof(float);
+  const bool det = danhip_option("deterministic") != 0;
+  if (det) DH_REQUIRE_DET_WS("danhip_l2norm_bwd", blocks, C);
+  float* part = det ? reinterpret_cast<float*>(ws) : nullptr;
+  const size_t lds = (size_t)C * sizeof(float) * (det ? 16 : 1);      // (16 wave slots of C = 1024 floats: the 64 KiB a launch may ask for)
+#define DH_L2BWD(LPP, VPL)                                                                                                                    \
+  do {                                                                                                                                        \
+    if (det) hipLaunchKernelGGL((l2norm_bwd_kernel<LPP, VPL, true>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask, part); \
+    else hipLaunchKernelGGL((l2norm_bwd_kernel<LPP, VPL, false>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask, part);    \
+  } while (0)
   switch (C) {
-    case 64: hipLaunchKernelGGL((l2norm_bwd_kernel<8, 1>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
-    case 128: hipLaunchKernelGGL((l2norm_bwd_kernel<16, 1>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
-    case 256: hipLaunchKernelGGL((l2norm_bwd_kernel<32, 1>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
-    case 512: hipLaunchKernelGGL((l2norm_bwd_kernel<64, 1>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
-    default: hipLaunchKernelGGL((l2norm_bwd_kernel<64, 2>), g, b, lds, s, x, gamma, dy, dx, dgamma, (long)M, C, accumulate, relu_mask); break;
+    case 64: DH_L2BWD(8, 1); break;
+    case 128: DH_L2BWD(16, 1); break;
+    case 256: DH_L2BWD(32, 1); break;
+    case 512: DH_L2BWD(64, 1); break;
+    default: DH_L2BWD(64, 2); break;
   }
+#undef DH_L2BWD
   DH_LAUNCH_CHECK();
+  if (det) return dh_ordered_reduce(part, C, (int)blocks, C, dgamma, 1, s);
   return DANHIP_OK;
 }
+extern "C" int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
+                                 int32_t C, int accumulate, int relu_mask, void* stream) {
+  return l2norm_bwd_impl(x, gamma, dy, dx, dgamma, M, C, accumulate, relu_mask, nullptr, 0, stream);
+}
+extern "C" int danhip_l2norm_bwd_ws(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
+                                    int32_t C, int accumulate, int relu_mask, void* ws, size_t ws_bytes, void* stream) {
+  return l2norm_bwd_impl(x, gamma, dy, dx, dgamma, M, C, accumulate, relu_mask, ws, ws_bytes, stream);
+}
 
-extern "C" int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
-                                              uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate,
-                                              int relu_mask, int pool_first, void* stream) {
+static int l2norm_bwd_pool_scatter_impl(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
+                                        uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate,
+                                        int relu_mask, int pool_first, void* ws, size_t ws_bytes, void* stream) {
   DH_REQUIRE(x && gamma && dy && arg && pooled_dy && dx && dgamma && N > 0 && H > 0 && W > 0, DANHIP_EINVAL, "l2norm_bwd_pool_scatter: bad arguments");
   DH_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, DANHIP_EINVAL, "l2norm_bwd_pool_scatter: C=%d unsupported", C);
   hipStream_t s = (hipStream_t)stream;
@@ -680,10 +758,19 @@ extern "C" int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* ga
     blocks = (blocks + sweeps - 1) / sweeps;
   }
   const dim3 g((unsigned)blocks), b(512);
-  const size_t lds = (size_t)C * sizeof(float);
-#define DH_JUNCTION(LPP) \
-  hipLaunchKernelGGL((l2norm_bwd_pool_scatter_kernel<LPP>), g, b, lds, s, x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, Ho, Wo, accumulate, \
-                     relu_mask, pool_first)
+  const bool det = danhip_option("deterministic") != 0;
+  if (det) DH_REQUIRE_DET_WS("danhip_l2norm_bwd_pool_scatter", blocks, C);
+  float* part = det ? reinterpret_cast<float*>(ws) : nullptr;
+  const size_t lds = (size_t)C * sizeof(float) * (det ? 8 : 1);
+#define DH_JUNCTION(LPP)                                                                                                                      \
+  do {                                                                                                                                        \
+    if (det)                                                                                                                                  \
+      hipLaunchKernelGGL((l2norm_bwd_pool_scatter_kernel<LPP, true>), g, b, lds, s, x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, Ho, Wo, \
+                         accumulate, relu_mask, pool_first, part);                                                                            \
+    else                                                                                                                                      \
+      hipLaunchKernelGGL((l2norm_bwd_pool_scatter_kernel<LPP, false>), g, b, lds, s, x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, Ho, Wo, \
+                         accumulate, relu_mask, pool_first, part);                                                                            \
+  } while (0)
   switch (C) {
     case 64: DH_JUNCTION(8); break;
     case 128: DH_JUNCTION(16); break;
@@ -692,7 +779,18 @@ extern "C" int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* ga
   }
 #undef DH_JUNCTION
   DH_LAUNCH_CHECK();
+  if (det) return dh_ordered_reduce(part, C, (int)blocks, C, dgamma, 1, s);
   return DANHIP_OK;
+}
+extern "C" int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
+                                              uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate,
+                                              int relu_mask, int pool_first, void* stream) {
+  return l2norm_bwd_pool_scatter_impl(x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, accumulate, relu_mask, pool_first, nullptr, 0, stream);
+}
+extern "C" int danhip_l2norm_bwd_pool_scatter_ws(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg,
+                                                 const uint16_t* pooled_dy, uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C,
+                                                 int accumulate, int relu_mask, int pool_first, void* ws, size_t ws_bytes, void* stream) {
+  return l2norm_bwd_pool_scatter_impl(x, gamma, dy, arg, pooled_dy, dx, dgamma, N, H, W, C, accumulate, relu_mask, pool_first, ws, ws_bytes, stream);
 }
 
 extern "C" int danhip_preprocess_u8(const uint8_t* img_rgb, uint16_t* out, int64_t npix, void* stream) {

@@ -461,6 +461,7 @@ extern "C" int danhip_batchnorm_fwd_train(const uint16_t* x, const float* gamma,
                                           float momentum, int relu, float* workspace, void* stream) {
   int rc = bn_check(x, M, C, "batchnorm_fwd_train");
   if (rc) return rc;
+  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "batchnorm_fwd_train: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   DH_REQUIRE(gamma && beta && y && save_mean && save_rstd && workspace, DANHIP_EINVAL, "batchnorm_fwd_train: null pointer");
   DH_REQUIRE(((uintptr_t)workspace & 7) == 0, DANHIP_EINVAL, "batchnorm_fwd_train: the workspace (2*C doubles) must be 8-byte aligned");
   double* sums = reinterpret_cast<double*>(workspace);
@@ -497,6 +498,7 @@ extern "C" int danhip_batchnorm_bwd(const uint16_t* x, const uint16_t* dy, const
                                     uint16_t* dx, float* dgamma, float* dbeta, int64_t M, int32_t C, void* stream) {
   int rc = bn_check(x, M, C, "batchnorm_bwd");
   if (rc) return rc;
+  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "batchnorm_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   DH_REQUIRE(dy && gamma && save_mean && save_rstd && dx && dgamma && dbeta, DANHIP_EINVAL, "batchnorm_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(dgamma, 0, sizeof(float) * C, s) != hipSuccess || hipMemsetAsync(dbeta, 0, sizeof(float) * C, s) != hipSuccess) {

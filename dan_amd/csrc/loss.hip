@@ -287,7 +287,8 @@ __global__ __launch_bounds__(1024) void kth_largest_rows_kernel(const float* __r
 // acc[0]=ce_sum acc[1]=n_selected acc[2]=loc_sum acc[3]=n_pos
 __global__ void detection_loss_fwd_kernel(const float* __restrict__ cls, const float* __restrict__ loc, const int* __restrict__ labels,
                                           const float* __restrict__ loc_t, const float* __restrict__ score, const float* __restrict__ thr,
-                                          unsigned char* __restrict__ sel, float* __restrict__ acc, int A, long total) {
+                                          unsigned char* __restrict__ sel, float* __restrict__ acc, int A, long total,
+                                          float* __restrict__ part) {      // part (deterministic mode): [gridDim.x][4] block sums instead of atomics
   __shared__ float sh[16];
   float ce = 0.f, ns = 0.f, ll = 0.f, np = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -313,7 +314,10 @@ __global__ void detection_loss_fwd_kernel(const float* __restrict__ cls, const f
     }
   }
   ce = block_sum(ce, sh); ns = block_sum(ns, sh); ll = block_sum(ll, sh); np = block_sum(np, sh);
-  if (threadIdx.x == 0) { atomicAdd(acc, ce); atomicAdd(acc + 1, ns); atomicAdd(acc + 2, ll); atomicAdd(acc + 3, np); }
+  if (threadIdx.x == 0) {
+    if (part) { *reinterpret_cast<float4*>(part + (size_t)blockIdx.x * 4) = make_float4(ce, ns, ll, np); return; }
+    atomicAdd(acc, ce); atomicAdd(acc + 1, ns); atomicAdd(acc + 2, ll); atomicAdd(acc + 3, np);
+  }
 }
 
 // dcls = sel ? (softmax - onehot) * ce_scale / n_sel : 0 ;  dloc = pos ? d smoothL1 / n_pos : 0   (both x gscale)
@@ -356,7 +360,8 @@ __global__ void detection_loss_bwd_kernel(const float* __restrict__ cls, const f
 // divided by dyn[0] and a step whose gradients hold an inf / NaN (dyn[3] != 0, set by grad_nonfinite_kernel) leaves w and v untouched.
 __global__ void sgd_momentum_flat_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v, const long* __restrict__ seg,
                                          const float* __restrict__ gmult, const float* __restrict__ wdc, int nseg, long total, float lr,
-                                         float momentum, float gscale, float* __restrict__ l2_out, const float* __restrict__ dyn) {
+                                         float momentum, float gscale, float* __restrict__ l2_out, const float* __restrict__ dyn,
+                                         float* __restrict__ l2_part) {    // l2_part (deterministic mode): [gridDim.x] block sums instead of atomics
   __shared__ float sh[8];
   float l2 = 0.f;
   bool skip = false;
@@ -402,7 +407,10 @@ __global__ void sgd_momentum_flat_kernel(float* __restrict__ w, const float* __r
   }
   if (l2_out) {
     l2 = block_sum(l2, sh);
-    if (threadIdx.x == 0) atomicAdd(l2_out, l2);
+    if (threadIdx.x == 0) {
+      if (l2_part) l2_part[blockIdx.x] = l2;
+      else atomicAdd(l2_out, l2);
+    }
   }
 }
 
@@ -538,17 +546,37 @@ extern "C" int danhip_hard_neg_select(const float* cls, const int32_t* labels, f
   return DANHIP_OK;
 }
 
-extern "C" int danhip_detection_loss_fwd(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets, const float* score,
-                                         const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A, void* stream) {
+int dh_ordered_reduce(const float* part, long pitch, int P, long C, float* out, int accumulate, hipStream_t s);      // ordered_reduce.hip
+
+static int detection_loss_fwd_impl(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets, const float* score,
+                                   const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A, void* ws, size_t ws_bytes, void* stream) {
   DH_REQUIRE(cls && loc && labels && loc_targets && score && thr && sel && acc4 && B > 0 && A > 0, DANHIP_EINVAL, "detection_loss_fwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(acc4, 0, sizeof(float) * 4, s) != hipSuccess) { danhip_set_error("detection_loss_fwd: memset failed"); return DANHIP_ELAUNCH; }
   const long total = (long)B * A;
   // (the four sums end in atomics on ONE 16-byte word: 1024 blocks spent ~40 of the kernel's 57 us queueing there; 128 fat blocks do not)
-  hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(grid_for(total, 1024, 128)), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel,
-                     acc4, A, total);
+  const int blocks = grid_for(total, 1024, 128);      // (the grid of the default launch below)
+  const bool det = danhip_option("deterministic") != 0;      // the block sums as rows of ws, finished in block order (danhip.h "Deterministic mode")
+  if (det)
+    DH_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= DANHIP_LOSS_WS_BYTES && ((uintptr_t)acc4 & 15) == 0, DANHIP_EINVAL,
+               "danhip_detection_loss_fwd: deterministic mode needs a 16-byte aligned workspace of DANHIP_LOSS_WS_BYTES (call danhip_detection_loss_fwd_ws)");
+  if (det)
+    hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(blocks), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel, acc4, A, total,
+                       reinterpret_cast<float*>(ws));
+  else
+    hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(grid_for(total, 1024, 128)), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel,
+                       acc4, A, total, (float*)nullptr);
   DH_LAUNCH_CHECK();
+  if (det) return dh_ordered_reduce(reinterpret_cast<const float*>(ws), 4, blocks, 4, acc4, 0, s);
   return DANHIP_OK;
+}
+extern "C" int danhip_detection_loss_fwd(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets, const float* score,
+                                         const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A, void* stream) {
+  return detection_loss_fwd_impl(cls, loc, labels, loc_targets, score, thr, sel, acc4, B, A, nullptr, 0, stream);
+}
+extern "C" int danhip_detection_loss_fwd_ws(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets, const float* score,
+                                            const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A, void* ws, size_t ws_bytes, void* stream) {
+  return detection_loss_fwd_impl(cls, loc, labels, loc_targets, score, thr, sel, acc4, B, A, ws, ws_bytes, stream);
 }
 
 extern "C" int danhip_detection_loss_bwd(const float* cls, const float* loc, const float* loc_targets, const uint8_t* sel, const float* acc4,
@@ -561,16 +589,47 @@ extern "C" int danhip_detection_loss_bwd(const float* cls, const float* loc, con
   return DANHIP_OK;
 }
 
-extern "C" int danhip_sgd_momentum_flat(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult, const float* wd_coef,
-                                        int32_t nseg, int64_t total, float lr, float momentum, float grad_scale, float* l2_out, void* stream) {
+static int sgd_momentum_flat_impl(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult, const float* wd_coef,
+                                  int32_t nseg, int64_t total, float lr, float momentum, float grad_scale, float* l2_out, void* ws, size_t ws_bytes,
+                                  void* stream) {
   DH_REQUIRE(w && g && v && seg_starts && gmult && wd_coef && nseg > 0 && total > 0, DANHIP_EINVAL, "sgd_momentum_flat: bad arguments");
   DH_REQUIRE(total % 4 == 0 && (((uintptr_t)w | (uintptr_t)g | (uintptr_t)v) & 15) == 0, DANHIP_EINVAL,
              "sgd_momentum_flat: buffers must be 16-byte aligned, total a multiple of 4 (segments start on 64-element boundaries)");
-  hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, v,
-                     reinterpret_cast<const long*>(seg_starts), gmult, wd_coef, nseg, (long)total, lr, momentum, grad_scale, l2_out,
-                     (const float*)nullptr);
+  int blocks = (int)((total / 4 + 255) / 256 < 4096 ? (total / 4 + 255) / 256 : 4096);      // (the default launch's grid, below)
+  const bool det = l2_out && danhip_option("deterministic") != 0;
+  float* part = nullptr;
+  if (det) {
+    // the L2 term in a fixed order: the grid is rounded up to a multiple of 64 (a workgroup without elements stores 0; w and v are
+    // elementwise, so the grid does not touch them), the workgroup sums are read as [rows][64], summed over the rows into 64 column sums
+    // behind them in ws, and those 64 are summed onto l2_out - two ordered reductions of at most 64 terms each
+    DH_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= DANHIP_SGD_WS_BYTES, DANHIP_EINVAL,
+               "danhip_sgd_momentum_flat: deterministic mode needs a 16-byte aligned workspace of DANHIP_SGD_WS_BYTES (call danhip_sgd_momentum_flat_ws)");
+    blocks = (blocks + 63) / 64 * 64;
+    part = reinterpret_cast<float*>(ws);
+  }
+  if (det)
+    hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, v,
+                       reinterpret_cast<const long*>(seg_starts), gmult, wd_coef, nseg, (long)total, lr, momentum, grad_scale, l2_out,
+                       (const float*)nullptr, part);
+  else
+    hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, v,
+                       reinterpret_cast<const long*>(seg_starts), gmult, wd_coef, nseg, (long)total, lr, momentum, grad_scale, l2_out,
+                       (const float*)nullptr, (float*)nullptr);
   DH_LAUNCH_CHECK();
+  if (det) {
+    if (int rc = dh_ordered_reduce(part, 64, blocks / 64, 64, part + 4096, 0, (hipStream_t)stream)) return rc;
+    return dh_ordered_reduce(part + 4096, 1, 64, 1, l2_out, 1, (hipStream_t)stream);
+  }
   return DANHIP_OK;
+}
+extern "C" int danhip_sgd_momentum_flat(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult, const float* wd_coef,
+                                        int32_t nseg, int64_t total, float lr, float momentum, float grad_scale, float* l2_out, void* stream) {
+  return sgd_momentum_flat_impl(w, g, v, seg_starts, gmult, wd_coef, nseg, total, lr, momentum, grad_scale, l2_out, nullptr, 0, stream);
+}
+extern "C" int danhip_sgd_momentum_flat_ws(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult, const float* wd_coef,
+                                           int32_t nseg, int64_t total, float lr, float momentum, float grad_scale, float* l2_out, void* ws,
+                                           size_t ws_bytes, void* stream) {
+  return sgd_momentum_flat_impl(w, g, v, seg_starts, gmult, wd_coef, nseg, total, lr, momentum, grad_scale, l2_out, ws, ws_bytes, stream);
 }
 
 // The same update under a dynamic loss scale kept on the device (no host round trip, capturable in the step's hipGraph):
@@ -583,10 +642,12 @@ extern "C" int danhip_sgd_momentum_flat_dynamic(float* w, const float* g, float*
              "sgd_momentum_flat_dynamic: bad arguments");
   DH_REQUIRE(total % 4 == 0 && (((uintptr_t)w | (uintptr_t)g | (uintptr_t)v) & 15) == 0, DANHIP_EINVAL,
              "sgd_momentum_flat_dynamic: buffers must be 16-byte aligned, total a multiple of 4");
+  DH_REQUIRE(!(l2_out && danhip_option("deterministic") != 0), DANHIP_EINVAL,
+             "sgd_momentum_flat_dynamic: l2_out has no deterministic form (pass NULL, or use danhip_sgd_momentum_flat_ws)");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(grad_nonfinite_kernel, dim3(grid_for(total / 4, 256, 2048)), dim3(256), 0, s, g, (long)total, loss_scale_state);
   hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, 4096)), dim3(256), 0, s, w, g, v, reinterpret_cast<const long*>(seg_starts),
-                     gmult, wd_coef, nseg, (long)total, lr, momentum, 1.f, l2_out, (const float*)loss_scale_state);
+                     gmult, wd_coef, nseg, (long)total, lr, momentum, 1.f, l2_out, (const float*)loss_scale_state, (float*)nullptr);
   hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, s, loss_scale_state);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;

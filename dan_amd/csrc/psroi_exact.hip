@@ -214,6 +214,7 @@ extern "C" int danhip_deform_psroi_pool_bwd(const float* top_diff, const float* 
                                             int32_t W, int32_t output_dim, int32_t group_size, int32_t pooled_size, int32_t part_size,
                                             int32_t sample_per_part, float spatial_scale, float trans_std, int32_t no_trans, int32_t num_classes,
                                             void* stream) {
+  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "deform_psroi_pool_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   DH_REQUIRE(top_diff && mapping_channel && data && rois && data_diff && (no_trans || (trans && trans_diff)) && B > 0, DANHIP_EINVAL,
              "deform_psroi_pool_bwd: null pointer");
   PsroiArgs a;

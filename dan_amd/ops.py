@@ -59,6 +59,12 @@ class OpsContext(object):
                        (backward) level by level: one head_split launch per level each way plus a cast_pad launch per level, through an
                        fp32 dY, into zero-filled prediction buffers (rounds 1-11); 1: one danhip_heads_split_fwd and one
                        danhip_heads_grad_pad for all levels (heads_split; values bit-identical)
+      deterministic    [DANHIP_DETERMINISTIC, 0]  True: bit-reproducible training step (the one switch that DOES change the sums' order on
+                       purpose: a fixed one).  use_context sets libdanhip's option "deterministic" while this context is active; every
+                       gradient / loss sum over workgroups then goes through a workspace this module allocates and the library's ordered
+                       reduction (include/danhip.h "Deterministic mode") instead of float atomics, and conv1_1's weight gradient is a launch
+                       of its own.  Ops without an ordered form (deformable conv, batch norm, PS-ROI pooling backward) raise.  One rank only.
+                       A trainer passes the flag on to FlatParams.sgd_step (the optimizer's L2 term).
       SPLIT_EVAL       True: convolutions of the fp32 inference path run as split-operand products on the fp16 MFMA (csrc/split_infer.hip;
                        models set it for precision "split"): fp32-accurate boxes at a third of the 16-bit rate instead of a tenth
     Diagnostic sinks (None = off): TRACE (tests: a dict in which every ReLU layer files its output under id(weight variable) and every
@@ -70,7 +76,7 @@ class OpsContext(object):
     device tensor of the dynamic loss scale, set around the backward pass), wgrad (the second backward stream: {"on", "side", "main",
     "keep"}; switched on around the backward pass and joined before the gradients are consumed; "keep" holds the tensors the side
     stream still reads until that join: no allocator reuse while in flight, also valid inside a hipGraph capture)."""
-    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "HEADS_BATCHED", "SPLIT_EVAL", "TRACE",
+    __slots__ = ("USE_SPLITK", "USE_SLOTS", "USE_RELU_BITS", "USE_POOL_ARG", "USE_JUNCTION", "POOL_ONLY_TRAIN", "KEEP_DEFORM_COL", "WGRAD_STREAM", "WGRAD_FIRST", "FUSE_FIRST_WGRAD", "HEADS_BATCHED", "SPLIT_EVAL", "deterministic", "TRACE",
                  "PROFILE", "PROFILE_BYTES", "GRAD_READY_HOOK", "LOSS_SCALE_DEV", "wgrad")
 
     def __init__(self, **overrides):
@@ -87,6 +93,7 @@ class OpsContext(object):
         self.FUSE_FIRST_WGRAD = env("DANHIP_FUSE_FIRST_WGRAD", "1") == "1"
         self.HEADS_BATCHED = env("DANHIP_HEADS_BATCHED", "1") == "1"
         self.SPLIT_EVAL = False
+        self.deterministic = env("DANHIP_DETERMINISTIC", "0") == "1"
         self.TRACE = self.PROFILE = self.PROFILE_BYTES = None
         self.GRAD_READY_HOOK = self.LOSS_SCALE_DEV = None
         self.wgrad = {"on": False, "side": None, "main": None, "keep": []}
@@ -108,10 +115,25 @@ def use_context(ctx):
     """Make `ctx` the active context for the duration of the block (process-wide: see OpsContext)."""
     global _CTX
     prev, _CTX = _CTX, ctx
+    _sync_deterministic(prev, ctx)
     try:
         yield ctx
     finally:
         _CTX = prev
+        _sync_deterministic(ctx, prev)
+
+
+def _sync_deterministic(old, new):
+    """libdanhip's launchers read the process-wide option "deterministic" once per call: it follows the active context.  (No library call,
+    and no library load, while no context asks for the mode.)"""
+    if bool(old.deterministic) != bool(new.deterministic):
+        call("danhip_set_option", b"deterministic", 1 if new.deterministic else 0)
+
+
+def _reduce_ws(M, C, dev):
+    """Workspace of the _ws forms of the memory-bound kernels in deterministic mode: -> (tensor, bytes)."""
+    n = int(_lib.lib().danhip_reduce_workspace_bytes(M, C))
+    return torch.empty(n, dtype=torch.uint8, device=dev), n
 
 
 
@@ -509,7 +531,7 @@ _SCRATCH_BYTES = {}          # (which, descriptor) -> bytes: one library query p
 
 
 def _wgrad_scratch(d, dev):
-    key = (2, d.N, d.H, d.W, d.Cin, d.Cout, d.kh, d.kw, d.stride, d.Ho)
+    key = (3 if _CTX.deterministic else 2, d.N, d.H, d.W, d.Cin, d.Cout, d.kh, d.kw, d.stride, d.Ho)      # (the mode changes the answer)
     n = _SCRATCH_BYTES.get(key)
     if n is None:
         n = _SCRATCH_BYTES[key] = _lib.lib().danhip_conv2d_bwd_weight_workspace_bytes(ctypes.byref(d))
@@ -640,7 +662,10 @@ class _Conv2d(torch.autograd.Function):
             _CTX.TRACE.setdefault("head_dy", []).append(g)
         db_in_wgrad = need_db and need_dw                        # the weight-gradient kernel also emits the bias gradient
         if need_db and not db_in_wgrad:
-            if co8 == d.Cout:
+            if co8 == d.Cout and _CTX.deterministic:
+                rws, nrws = _reduce_ws(M, co8, g.device)
+                call("danhip_relu_bwd_bias_grad_ws", ptr(g), None, ptr(db), M, co8, ptr(rws), nrws, stream())
+            elif co8 == d.Cout:
                 call("danhip_relu_bwd_bias_grad", ptr(g), None, ptr(db), M, co8, stream())
             else:
                 db.add_(g.view(M, co8)[:, :d.Cout].to(torch.float32).sum(0))
@@ -1066,6 +1091,11 @@ def _junction(l2, pool, buf, acc, is_relu, pool_first):
     """One launch for the two gradients of a tapped map (csrc/elementwise.hip, l2norm_bwd_pool_scatter_kernel)."""
     x, gamma, g, dg = l2
     arg, pg, (N, H, W, C) = pool
+    if _CTX.deterministic:
+        ws, nws = _reduce_ws(N * H * W, C, x.device)
+        call("danhip_l2norm_bwd_pool_scatter_ws", ptr(x), ptr(gamma), ptr(g), ptr(arg), ptr(pg), ptr(buf), ptr(dg), N, H, W, C, acc,
+             1 if is_relu else 0, pool_first, ptr(ws), nws, stream())
+        return
     call("danhip_l2norm_bwd_pool_scatter", ptr(x), ptr(gamma), ptr(g), ptr(arg), ptr(pg), ptr(buf), ptr(dg), N, H, W, C, acc, 1 if is_relu else 0,
          pool_first, stream())
 
@@ -1153,6 +1183,11 @@ class _L2Norm(torch.autograd.Function):
         xs = ctx.xslot
 
         def alone(buf, acc):
+            if _CTX.deterministic:
+                ws, nws = _reduce_ws(M, x.shape[-1], x.device)
+                call("danhip_l2norm_bwd_ws", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc,
+                     1 if (xs is not None and xs.is_relu) else 0, ptr(ws), nws, stream())
+                return
             call("danhip_l2norm_bwd", ptr(x), ptr(gamma), ptr(g), ptr(buf), ptr(dg), M, x.shape[-1], acc, 1 if (xs is not None and xs.is_relu) else 0,
                  stream())
 
@@ -1301,7 +1336,13 @@ class _DetectionLoss(torch.autograd.Function):
         sel = torch.empty((B, A), dtype=torch.uint8, device=dev)
         acc = torch.empty((4,), dtype=torch.float32, device=dev)
         call("danhip_hard_neg_select", ptr(cls), ptr(labels), ptr(score), ptr(counts), ptr(thr), ptr(k), B, A, float(ratio), int(at_least_one), stream())
-        call("danhip_detection_loss_fwd", ptr(cls), ptr(loc), ptr(labels), ptr(loc_t), ptr(score), ptr(thr), ptr(sel), ptr(acc), B, A, stream())
+        if _CTX.deterministic:
+            nlws = int(_lib.lib().danhip_loss_workspace_bytes())
+            lws = torch.empty((nlws,), dtype=torch.uint8, device=dev)
+            call("danhip_detection_loss_fwd_ws", ptr(cls), ptr(loc), ptr(labels), ptr(loc_t), ptr(score), ptr(thr), ptr(sel), ptr(acc), B, A,
+                 ptr(lws), nlws, stream())
+        else:
+            call("danhip_detection_loss_fwd", ptr(cls), ptr(loc), ptr(labels), ptr(loc_t), ptr(score), ptr(thr), ptr(sel), ptr(acc), B, A, stream())
         if _CTX.TRACE is not None:                           # tests: the hard-negative selection of this term (call order), imposed on the oracle's loss
             _CTX.TRACE.setdefault("loss_sel", []).append(sel)
         ctx.save_for_backward(cls, loc, loc_t, sel, acc)

@@ -67,6 +67,7 @@ class PBTrainer(DetectorTrainer):
     """pb_model_fn (train_pb.py:350-520): total = face + 0.66 * head + 0.33 * body (+ L2), each term
     CE*(ratio+1) over mined rows + smooth-L1 over positives (:440-504)."""
     WEIGHTS = {"face": 1.0, "head": 0.66, "body": 0.33}
+    DETERMINISTIC = True          # (tests/test_deterministic_gpu.py holds the two-trainer check)
 
     def loss_terms(self, images_u8, targets):
         out = self.model.forward(images_u8)

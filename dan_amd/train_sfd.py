@@ -99,12 +99,28 @@ class DetectorTrainer(object):
     train_dan.py:386-532): forward -> loss terms (hard-negative mining + CE*(ratio+1) + smooth-L1, each with its weight)
     -> backward into the flat gradient buffer (+ bucketed all-reduce) -> fused momentum SGD (L2 term, bias gradient x2).
     `world` ranks each see batch/world images; every term's gradient carries the 1/world of tf_replicate_model_fn.py:297-302.
-    Subclasses implement loss_terms(images_u8, *targets) -> list of (name, acc4 tensor)."""
+    Subclasses implement loss_terms(images_u8, *targets) -> list of (name, acc4 tensor).
+
+    deterministic=True: the step is bit-reproducible - two trainers built from one seed hold the same bits in weights, momenta and loss terms
+    after any number of steps (per library build and CU count; one rank).  The trainer then owns a copy of its ops context with
+    OpsContext.deterministic set and runs every step inside it.  Only trainers whose every reduction has an ordered form accept the flag
+    (DETERMINISTIC below); the others raise NotImplementedError("deterministic")."""
+
+    DETERMINISTIC = False
 
     def __init__(self, model, world=1, weight_decay=5e-4, negative_ratio=3.0, momentum=0.9, base_lr=1e-3, init_hw=(64, 64),
                  lr_boundaries=(1000, 80000, 100000), lr_factors=(0.1, 1.0, 0.1, 0.01), loss_scale=None, dynamic_loss_scale=None,
-                 loss_scale_growth_interval=1000, ops_ctx=None):
+                 loss_scale_growth_interval=1000, ops_ctx=None, deterministic=False):
         self.model = model
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            if not self.DETERMINISTIC or getattr(model, "deform", False):
+                raise NotImplementedError("deterministic")
+            if world != 1:
+                raise NotImplementedError("deterministic: one rank only (the all-reduce order is not covered)")
+            src = ops_ctx if ops_ctx is not None else ops.context()
+            ops_ctx = ops.OpsContext(**{k: getattr(src, k) for k in ops.OpsContext.__slots__ if k != "wgrad"})
+            ops_ctx.deterministic = True
         # the ops' steering state this trainer runs under (kernel-form switches, diagnostic sinks, the per-step hooks armed below): the
         # context active at construction unless one is handed in - every step runs inside it (ops.OpsContext)
         self.ops_ctx = ops_ctx if ops_ctx is not None else ops.context()
@@ -125,6 +141,8 @@ class DetectorTrainer(object):
         if dynamic_loss_scale:
             self.ls_state = torch.tensor([self.loss_scale, 0.0, float(loss_scale_growth_interval), 0.0], dtype=torch.float32, device=model.vs.device)
             self.loss_scale = 1.0                             # host-side factor of the loss terms; the device scalar carries the scale
+            if self.deterministic:
+                raise NotImplementedError("deterministic: the dynamic loss scale's optimizer entry has no ordered L2 sum (pass loss_scale=...)")
         self.world = world
         self.towers = 1                                       # towers of THIS rank inside one step (train_step_towers)
         self.negative_ratio = negative_ratio
@@ -145,7 +163,7 @@ class DetectorTrainer(object):
         # the persistent convolution kernels leave no CU for the update to hide on, so it only adds launches and HBM traffic mid-backward.
         # With more than one rank the end of the step is exposed to the last all-reduce anyway and the form may pay; nobody has measured it
         # (one-GPU boxes), so the default stays the single pass.
-        self.opt_overlap = (os.environ.get("DANHIP_OPT_OVERLAP", "0") == "1" and self.ls_state is None and self.flat.g.is_cuda
+        self.opt_overlap = (os.environ.get("DANHIP_OPT_OVERLAP", "0") == "1" and not self.deterministic and self.ls_state is None and self.flat.g.is_cuda
                             and (not self.buckets.enabled or self.buckets.device_collectives))
         if self.opt_overlap:
             self.buckets.enable_local()
@@ -252,7 +270,8 @@ class DetectorTrainer(object):
         ops.wgrad_overlap_join()
         # the L2 term is rank-independent: its gradient wd*w is added inside the fused optimizer kernel
         if not self.opt_overlap:                              # (else every bucket has been updated and re-packed behind its reduction)
-            self.flat.sgd_step(self._step_lr, self.momentum, grad_scale=1.0 / self.loss_scale, dynamic_state=self.ls_state)
+            self.flat.sgd_step(self._step_lr, self.momentum, grad_scale=1.0 / self.loss_scale, dynamic_state=self.ls_state,
+                               deterministic=bool(octx.deterministic))
         self.step_no += 1
         self.last = terms
         self.last_towers = tower_terms                        # every tower's terms: loss_values() reports their mean
@@ -346,6 +365,8 @@ class DetectorTrainer(object):
 
 class SFDTrainer(DetectorTrainer):
     """sfd_model_fn (train_sfd.py:261-467) + Momentum optimizer."""
+
+    DETERMINISTIC = True
 
     def loss_terms(self, images_u8, loc_targets, cls_targets):
         loc, cls = self.model.forward(images_u8)

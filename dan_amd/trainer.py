@@ -487,13 +487,20 @@ class FlatParams(object):
         call("danhip_sgd_momentum_flat", base(self.w, s), base(self.g, s), base(self.v, s), ptr(rel), base(self.gmult, k0), base(self.wdc, k0), nseg,
              e - s, float(lr), float(momentum), float(grad_scale), ptr(self.l2), stream())
 
-    def sgd_step(self, lr, momentum=0.9, grad_scale=1.0, dynamic_state=None):
-        """dynamic_state: fp32[4] device tensor {loss scale, clean steps, growth interval, flag} (danhip_sgd_momentum_flat_dynamic)."""
+    def sgd_step(self, lr, momentum=0.9, grad_scale=1.0, dynamic_state=None, deterministic=False):
+        """dynamic_state: fp32[4] device tensor {loss scale, clean steps, growth interval, flag} (danhip_sgd_momentum_flat_dynamic).
+        deterministic: the step runs under OpsContext.deterministic - the L2 term goes through a workspace and the ordered reduction."""
         self.mask_structured()
         self.l2.zero_()
         if dynamic_state is not None:
             call("danhip_sgd_momentum_flat_dynamic", ptr(self.w), ptr(self.g), ptr(self.v), ptr(self.seg), ptr(self.gmult), ptr(self.wdc),
                  len(self.names), self.total, float(lr), float(momentum), ptr(dynamic_state), ptr(self.l2), stream())
+        elif deterministic:
+            if getattr(self, "_sgd_ws", None) is None:
+                from . import _lib
+                self._sgd_ws = torch.empty(int(_lib.lib().danhip_sgd_workspace_bytes()), dtype=torch.uint8, device=self.w.device)
+            call("danhip_sgd_momentum_flat_ws", ptr(self.w), ptr(self.g), ptr(self.v), ptr(self.seg), ptr(self.gmult), ptr(self.wdc), len(self.names),
+                 self.total, float(lr), float(momentum), float(grad_scale), ptr(self.l2), ptr(self._sgd_ws), self._sgd_ws.numel(), stream())
         else:
             call("danhip_sgd_momentum_flat", ptr(self.w), ptr(self.g), ptr(self.v), ptr(self.seg), ptr(self.gmult), ptr(self.wdc), len(self.names),
                  self.total, float(lr), float(momentum), float(grad_scale), ptr(self.l2), stream())

@@ -60,10 +60,48 @@ int danhip_version(void);
  *   "wgrad_c8"   [DANHIP_WGRAD_C8, 1]    0: the first layer's weight gradient (3x3, 8-channel image, 64 outputs) on the general kernel instead of
  *                                           csrc/conv_wgrad_c8.hip
  *   "pw_dgrad_ld_bn" [DANHIP_PW_DGRAD_LD_BN, 128]  256: csrc/conv_pointwise.hip's data gradient with a ReLU mask / accumulation may take 256-wide tiles
+ *   "deterministic" [DANHIP_DETERMINISTIC, 0]  1: deterministic mode, see below
  * Results agree up to fp32 summation order whatever the setting.  danhip_set_option returns DANHIP_EINVAL for an unknown name. */
 int danhip_set_option(const char* name, int value);
 int danhip_get_option(const char* name);
 int danhip_act_dtype(void);   /* DANHIP_BF16 or DANHIP_F16 */
+
+/* ------------------------------------------------------------------------------------------------
+ * Deterministic mode (option "deterministic" = 1; default 0 changes nothing: same launches, same bytes, no workspace asked for).
+ * Every fp32 sum of the S3FD training step that crosses workgroups - weight / bias / gamma gradients, the loss sums, the optimizer's L2 term -
+ * leaves its workgroup as a plain store into a caller-provided workspace (one row of partial sums per workgroup) and is finished in a FIXED
+ * order, so two runs of the same call on the same inputs return the same bits.  Float atomics are not used (global or LDS).
+ *
+ * THE ORDER CONTRACT - danhip_ordered_reduce_f32(part [P][C], P, C, out [C], accumulate), the kernel every site hands its rows to:
+ *   P <= DANHIP_ORDERED_REDUCE_SEQ_MAX (64):  S[c] = (((part[0][c] + part[1][c]) + part[2][c]) + ...) + part[P-1][c]       (fp32, ascending p)
+ *   P >  DANHIP_ORDERED_REDUCE_SEQ_MAX:       G = ceil(P / 4);  S_k[c] = that sequential sum over the rows k G <= p < min(P, (k+1) G), k = 0..3;
+ *                                             S[c] = ((S_0[c] + S_1[c]) + S_2[c]) + S_3[c]
+ *   out[c] = S[c], or with accumulate != 0 out[c] = out[c] + S[c]: ONE add onto the old value.
+ * The grouping is a function of P alone - never of the grid size or the CU count.  (The combine kernels of the weight-gradient slab form,
+ * csrc/conv_wgrad_rows.hip / conv_wgrad_pw.hip, keep their own fixed order: wave w sums the splits w, w + 4, ... in rounds of eight, the
+ * four wave sums are added as (0 + 1) + (2 + 3), then one add onto dw.)
+ *
+ * Scope of "same bits": the NUMBER of partial rows of the weight-gradient kernels derives from the device's CU count, so results are
+ * reproducible per (library build, CU count) - not across devices with different CU counts, library versions, or more than one rank.
+ *
+ * In deterministic mode:
+ *   - danhip_conv2d_bwd_weight_workspace_bytes(d) > 0 for EVERY descriptor (the size includes the bias-gradient rows), and
+ *     danhip_conv2d_bwd_weight, or _ws / _strided with ws == NULL or too small, return DANHIP_EINVAL (no silent fall-back to atomics);
+ *   - danhip_conv2d_bwd_data_first_supported answers 0 (callers take danhip_conv2d_bwd_data_bits + danhip_conv2d_bwd_weight_ws);
+ *   - danhip_relu_bwd_bias_grad (db != NULL), danhip_l2norm_bwd, danhip_l2norm_bwd_pool_scatter, danhip_detection_loss_fwd and
+ *     danhip_sgd_momentum_flat[_dynamic] (l2_out != NULL) return DANHIP_EINVAL: call their _ws forms (declared next to them);
+ *   - out of scope, DANHIP_EINVAL: danhip_conv2d_bwd_data_bits_first, danhip_batchnorm_fwd_train, danhip_batchnorm_bwd, danhip_deform_sample_bwd,
+ *     danhip_deform_conv_bwd*, danhip_deform_psroi_pool_bwd (their float atomics have no ordered form).
+ * With the option at 0 the _ws forms behave exactly as the plain calls (the workspace is ignored). */
+#define DANHIP_ORDERED_REDUCE_SEQ_MAX 64
+int danhip_ordered_reduce_f32(const float* part, int32_t P, int64_t C, float* out, int accumulate, void* stream);
+/* Workspace of the _ws forms of danhip_relu_bwd_bias_grad / danhip_l2norm_bwd / danhip_l2norm_bwd_pool_scatter over M pixels (N*H*W) of C channels:
+ * one row of C partial sums per workgroup of the largest grid any of them launches (a function of M and C alone). */
+size_t danhip_reduce_workspace_bytes(int64_t M, int32_t C);
+#define DANHIP_LOSS_WS_BYTES 2048      /* danhip_detection_loss_fwd_ws: 128 workgroups x 4 sums */
+#define DANHIP_SGD_WS_BYTES 16640      /* danhip_sgd_momentum_flat_ws: 4096 workgroup sums + 64 column sums */
+size_t danhip_loss_workspace_bytes(void);   /* the two sizes above, for callers that bind the library without this header */
+size_t danhip_sgd_workspace_bytes(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense convolution (tf.layers.conv2d, padding='same'; net/sfd_net.py:81-89 conv_relu and every
@@ -201,7 +239,13 @@ int danhip_conv2d_bwd_weight(const danhip_conv_desc* d, const uint16_t* x, const
                              int32_t cin_real, void* stream);
 /* The same with a caller-provided scratch buffer: where danhip_conv2d_bwd_weight_workspace_bytes(d) > 0 and `ws` holds at least that many
  * bytes, the split partial sums leave the kernel as plain coalesced stores and a second small kernel combines them into dw_hwio (+=),
- * instead of fp32 atomics (4-5x the bytes per second; the atomic tail dominated the launch at <= 4 images per GPU).  ws == NULL: atomics. */
+ * instead of fp32 atomics (4-5x the bytes per second; the atomic tail dominated the launch at <= 4 images per GPU).  ws == NULL: atomics
+ * (deterministic mode: every descriptor has a workspace size, and a call without that workspace is DANHIP_EINVAL).
+ * Limitation: the query sees the descriptor alone and answers for DENSE pitches (x_pitch = Cin, y_pitch = Cout rounded up to 8).  In
+ * deterministic mode a danhip_conv2d_bwd_weight_strided call whose pitches make the selection fall to another kernel family (a pitch above
+ * 65535 elements declines the row-streaming kernel, a first-layer image that is not dense declines its kernel and changes the generic
+ * kernel's split count) may need a different size, which cannot be asked for: such a call returns DANHIP_EINVAL (every launcher checks
+ * ws_bytes against its own need; nothing is overrun).  Pitches of channel-slice views of tensors up to 65535 channels wide are unaffected. */
 size_t danhip_conv2d_bwd_weight_workspace_bytes(const danhip_conv_desc* d);
 int danhip_conv2d_bwd_weight_ws(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* dy, float* dw_hwio, float* db,
                                 int32_t cin_real, void* ws, size_t ws_bytes, void* stream);
@@ -209,6 +253,8 @@ int danhip_conv2d_bwd_weight_ws(const danhip_conv_desc* d, const uint16_t* x, co
 /* In place: dy *= (y > 0) (ReLU backward) when y != NULL; db[c] += sum over pixels of the masked dy.
  * dy bf16 [M, C]; y bf16 [M, C] or NULL; db fp32 [C] or NULL. */
 int danhip_relu_bwd_bias_grad(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* stream);
+/* Deterministic mode: db through ws (>= danhip_reduce_workspace_bytes(M, C) bytes; may be NULL when db is). */
+int danhip_relu_bwd_bias_grad_ws(uint16_t* dy, const uint16_t* y, float* db, int64_t M, int32_t C, void* ws, size_t ws_bytes, void* stream);
 
 /* Kernel-instance label a forward (which=0) / data-gradient (which=1; which=5 when relu_mask is passed) / forward-with-fused-pool
  * (which=4, danhip_conv2d_fwd_pool) call of this descriptor launches (the demangled name rocprofv3 reports) — lets bench.py attribute
@@ -238,6 +284,9 @@ int danhip_maxpool2x2_bwd_arg(const uint8_t* arg, const uint16_t* dy, uint16_t* 
 int danhip_l2norm_fwd(const uint16_t* x, const float* gamma, uint16_t* y, int64_t M, int32_t C, void* stream);
 int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
                       int32_t C, int accumulate, int relu_mask, void* stream);
+/* Deterministic mode: dgamma through ws (>= danhip_reduce_workspace_bytes(M, C) bytes); dx is bit-identical to the plain call in both modes. */
+int danhip_l2norm_bwd_ws(const uint16_t* x, const float* gamma, const uint16_t* dy, uint16_t* dx, float* dgamma, int64_t M,
+                         int32_t C, int accumulate, int relu_mask, void* ws, size_t ws_bytes, void* stream);
 /* Gradient junction of a tapped map x [N,H,W,C] (C in {64,128,256,512}) that feeds an L2 norm AND a 2 x 2 max-pool: one pass that equals
  * danhip_l2norm_bwd(x, gamma, dy, dx, dgamma, N*H*W, C, accumulate, relu_mask) followed by danhip_maxpool2x2_bwd_arg(arg, pooled_dy, dx, ...,
  * accumulate = 1) - or, with pool_first, the scatter (accumulate) followed by the L2 norm (accumulate = 1) - with dx written once.  dx is
@@ -245,6 +294,10 @@ int danhip_l2norm_bwd(const uint16_t* x, const float* gamma, const uint16_t* dy,
 int danhip_l2norm_bwd_pool_scatter(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
                                    uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate, int relu_mask,
                                    int pool_first, void* stream);
+/* Deterministic mode: dgamma through ws (>= danhip_reduce_workspace_bytes(N*H*W, C) bytes). */
+int danhip_l2norm_bwd_pool_scatter_ws(const uint16_t* x, const float* gamma, const uint16_t* dy, const uint8_t* arg, const uint16_t* pooled_dy,
+                                      uint16_t* dx, float* dgamma, int32_t N, int32_t H, int32_t W, int32_t C, int accumulate, int relu_mask,
+                                      int pool_first, void* ws, size_t ws_bytes, void* stream);
 /* tf.image.resize_bilinear(up, size(lateral)) (TF1 legacy mapping src = dst*(in/out), align_corners=False) fused with the
  * LFPN lateral add: out = lateral + resize(up) (lateral may be NULL) — net/pb_net.py:209-217, net/danet.py:363-371.
  * up bf16 [N,Hi,Wi,C], lateral/out bf16 [N,Ho,Wo,C], C % 8 == 0.  bwd: d_up (=|+= if accumulate) from d_out (the lateral's
@@ -335,6 +388,10 @@ int danhip_hard_neg_select(const float* cls, const int32_t* labels, float* score
 int danhip_detection_loss_fwd(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets,
                               const float* score, const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A,
                               void* stream);
+/* Deterministic mode: the four sums through ws (>= DANHIP_LOSS_WS_BYTES). */
+int danhip_detection_loss_fwd_ws(const float* cls, const float* loc, const int32_t* labels, const float* loc_targets,
+                                 const float* score, const float* thr, uint8_t* sel, float* acc4, int32_t B, int32_t A,
+                                 void* ws, size_t ws_bytes, void* stream);
 int danhip_detection_loss_bwd(const float* cls, const float* loc, const float* loc_targets, const uint8_t* sel,
                               const float* acc4, float* dcls, float* dloc, float ce_scale, float loc_scale, int32_t B,
                               int32_t A, void* stream);
@@ -346,6 +403,11 @@ int danhip_detection_loss_bwd(const float* cls, const float* loc, const float* l
 int danhip_sgd_momentum_flat(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult,
                              const float* wd_coef, int32_t nseg, int64_t total, float lr, float momentum, float grad_scale,
                              float* l2_out, void* stream);
+/* Deterministic mode: l2_out through ws (>= DANHIP_SGD_WS_BYTES): the workgroup sums (grid rounded up to a multiple of 64, idle workgroups
+ * store 0) are reduced as [rows][64] -> 64 column sums -> one sum, both by the ordered reduction.  w and v are elementwise: same bits in both modes. */
+int danhip_sgd_momentum_flat_ws(float* w, const float* g, float* v, const int64_t* seg_starts, const float* gmult,
+                                const float* wd_coef, int32_t nseg, int64_t total, float lr, float momentum, float grad_scale,
+                                float* l2_out, void* ws, size_t ws_bytes, void* stream);
 /* The same update under a DYNAMIC loss scale kept on the device (fp16 build; no host round trip, capturable in a hipGraph).
  * loss_scale_state: 4 floats {scale, clean steps so far, growth interval, scratch flag}.  One call = non-finite check of g; the
  * update with g / scale, skipped entirely (w, v untouched) when the check fired; then torch.cuda.amp.GradScaler's rule: scale x0.5
