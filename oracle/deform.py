@@ -124,15 +124,15 @@ def _coord_weight_parts(g, H, W):
     return oob, ih, iw, h_low, w_low, h_high, w_high
 
 
-def deform_conv_backward(x, w_oihw, offset, dy, stride=1, dilation=1, dg=1, padding="SAME"):
-    """DeformConvBackpropOp (deform_conv.cc:635-771): returns (dx, dw, doffset), explicit formulas (num_groups = 1)."""
-    co, ci, kh, kw = w_oihw.shape
+def deform_sample_backward(x, offset, col_grad, kh, kw, stride=1, dilation=1, dg=1, padding="SAME"):
+    """The two sampling gradients of DeformConvBackpropOp from a given column gradient col_grad [B, C, kh*kw, Ho, Wo] (the layout
+    deform_im2col returns): (dx [B,C,H,W], doffset [B, dg*2*kh*kw, Ho, Wo]), in x.dtype throughout."""
     T = kh * kw
     g = _sample_setup(x, offset, kh, kw, stride, dilation, dg, padding)
     B, C, H, W, Ho, Wo = g["B"], g["C"], g["H"], g["W"], g["Ho"], g["Wo"]
     cpg = C // dg
-    # col_grad = W^T . dY   [B, C, T, Ho, Wo]   (deform_conv.cc:736)
-    colg = torch.einsum("ok,bon->bkn", w_oihw.reshape(co, ci * T), dy.reshape(B, co, Ho * Wo)).reshape(B, dg, cpg, T, Ho, Wo)
+    assert col_grad.shape == (B, C, T, Ho, Wo), (col_grad.shape, (B, C, T, Ho, Wo))
+    colg = col_grad.reshape(B, dg, cpg, T, Ho, Wo)
     # ---- dOffset (deformable_col2im_coord_gpu_kernel)
     oob, ih, iw, h_low, w_low, h_high, w_high = _coord_weight_parts(g, H, W)
     xg = x.reshape(B, dg, cpg, H * W)
@@ -186,7 +186,18 @@ def deform_conv_backward(x, w_oihw, offset, dy, stride=1, dilation=1, dg=1, padd
         contrib = torch.where(ok.unsqueeze(2), wgt.unsqueeze(2) * colg, torch.zeros_like(colg))
         idx = (rh.long().clamp(0, H - 1) * W + rw.long().clamp(0, W - 1)).reshape(B, dg, 1, -1).expand(B, dg, cpg, -1)
         dx.scatter_add_(3, idx, contrib.reshape(B, dg, cpg, -1))
-    dx = dx.reshape(B, C, H, W)
+    return dx.reshape(B, C, H, W), doffset
+
+
+def deform_conv_backward(x, w_oihw, offset, dy, stride=1, dilation=1, dg=1, padding="SAME"):
+    """DeformConvBackpropOp (deform_conv.cc:635-771): returns (dx, dw, doffset), explicit formulas (num_groups = 1)."""
+    co, ci, kh, kw = w_oihw.shape
+    T = kh * kw
+    B, C = x.shape[0], x.shape[1]
+    Ho, Wo = dy.shape[2], dy.shape[3]
+    # col_grad = W^T . dY   [B, C, T, Ho, Wo]   (deform_conv.cc:736)
+    colg = torch.einsum("ok,bon->bkn", w_oihw.reshape(co, ci * T), dy.reshape(B, co, Ho * Wo)).reshape(B, C, T, Ho, Wo)
+    dx, doffset = deform_sample_backward(x, offset, colg, kh, kw, stride, dilation, dg, padding)
     # ---- dW = sum_b dY_b . col_b^T  (deform_conv.cc:757-768)
     col = deform_im2col(x, offset, kh, kw, stride, dilation, dg, padding).reshape(B, C * T, Ho * Wo)
     dw = torch.einsum("bon,bkn->ok", dy.reshape(B, co, Ho * Wo), col).reshape(co, ci, kh, kw)
