@@ -134,6 +134,9 @@ SIGNATURES = {
     "danhip_argsort_desc_f32": [P, I64, I32, P, P, ctypes.c_size_t, P],
     "danhip_augment_preprocess": [P, I32, I32, I32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), I32, I32, I32, I32, I32, P, I32, I32,
                                   P, ctypes.c_size_t, P],
+    "danhip_augment_item_init": [P, P, I32, I32, I32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), I32, I32, I32, I32, I32, I32,
+                                 ctypes.POINTER(ctypes.c_int32)],
+    "danhip_augment_preprocess_batch": [P, I32, I32, P, I32, I32, P, ctypes.c_size_t, P],
     "danhip_deform_psroi_pool_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P],
     "danhip_deform_psroi_pool_bwd": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P],
     "danhip_maxpool3x3s2_same_fwd": [P, P, I32, I32, I32, I32, P],
@@ -252,6 +255,10 @@ def _load(so_path, act_name):
         L.danhip_argsort_workspace_bytes.argtypes = [I64]
         L.danhip_argsort_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_augment_workspace_bytes.argtypes = []
+        L.danhip_augment_item_bytes.restype = ctypes.c_size_t
+        L.danhip_augment_item_bytes.argtypes = []
+        L.danhip_augment_batch_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_augment_batch_workspace_bytes.argtypes = [I32]
         L.danhip_set_option.restype = ctypes.c_int
         L.danhip_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
         L.danhip_get_option.restype = ctypes.c_int

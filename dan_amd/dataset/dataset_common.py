@@ -248,7 +248,7 @@ def decode_record(payload, decode=True):
 # ---------------------------------------------------------------------------------------------------------- the batch generator
 def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_readers, num_preprocessing_threads, image_preprocessing_fn,
                    anchor_encoder, num_epochs=None, is_training=True, seed=None, decode_device=None, decode_entropy="host",
-                   decode_progressive=False):
+                   decode_progressive=False, batch_preprocessing_fn=None):
     """dataset_common.py:33-193 as a generator of batches (lists of per-image entries; stacking is the caller's, the anchor encoder's
     outputs have fixed shapes).
 
@@ -263,7 +263,11 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
     dataset.jpeg.JpegDecoder and image_preprocessing_fn gets uint8 [H,W,3] tensors on that device (what preprocess_for_train takes).
     decode_entropy: "host" | "device", JpegDecoder's entropy argument (where the Huffman stage of that decoder runs).
     decode_progressive: JpegDecoder's progressive argument (True: complete progressive records are decoded on the device as well, not by
-    the Pillow fallback)."""
+    the Pillow fallback).
+    batch_preprocessing_fn: None = image_preprocessing_fn is called per image (above).  With decode_device and is_training, a function
+    (images, bboxes_list) -> (tensor [K, ...], list of K box arrays, list of the K kept indices) - preprocess_batch_for_train of the
+    preprocessing modules - gets every decoded group ONCE; the entries are the same, in the same order, as the per-image path's with the
+    same draws, each image a view out[k] of the batch tensor, the images whose boxes are all gone left out.  Ignored otherwise."""
     if split_name not in data_splits_num:
         raise ValueError('split name %s was not recognized.' % split_name)
     files = sorted(glob.glob(file_pattern.format(split_name)))
@@ -326,6 +330,15 @@ def slim_get_batch(num_classes, batch_size, split_name, file_pattern, num_reader
 
         def flush():
             images = decoder.decode_batch([it['image'] for it in group])
+            if batch_preprocessing_fn is not None and is_training:
+                out, boxes, kept = batch_preprocessing_fn(images, [it['object/bbox'] for it in group])
+                for k, (i, gbboxes) in enumerate(zip(kept, boxes)):
+                    e = [out[k], group[i]['filename'], group[i]['shape']]
+                    for grp in anchor_encoder(gbboxes):
+                        e += list(grp) if isinstance(grp, (list, tuple)) else [grp]
+                    yield e
+                del group[:]
+                return
             for it, image in zip(group, images):
                 it['image'] = image
                 yield entry(None, it)

@@ -6,7 +6,18 @@ re-cut for the device: the geometric functions decide a crop WINDOW and transfor
 boxes, float32 like the reference's tf ops), the colour function decides the op chain, and one libdanhip launch
 (danhip_augment_preprocess) produces the network input from the decoded uint8 image — nothing is materialised in between.
 Random numbers come from a `draws` object with uniform(lo, hi) / randint(lo, hi) / choice(n) (default: numpy RandomState; the
-reference's TF stream is not reproducible), so a fixed seed gives a fixed augmentation."""
+reference's TF stream is not reproducible), so a fixed seed gives a fixed augmentation.
+
+Order of the draws, per image, from one `Draws` (the order the reference's code reaches its random ops; this project's contract):
+  1. randint(0, 4): the colour ordering; 2. the four colour draws in the order that ordering applies its ops;
+  3. uniform(0, 1) < 0.5 chooses dan_random_sample, else data_anchor_sampling (:702);
+  4a. dan_random_sample: uniform(0.3, 1) x 4, choice(5), per attempt randint x, randint y (at most 25), then - only when all were rejected -
+      randint(0, number of boxes);
+  4b. data_anchor_sampling: randint(0, number of boxes) (the face), randint(0, anchor_ind) (the target scale), uniform (the final scale),
+      randint x, randint y (the patch position);
+  5. uniform(0, 1) < 0.5: the flip, of the resized image.
+preprocess_batch_for_train takes these for image 0, then image 1, ... from the one `Draws` it is given; augment_batch is the device pass
+for the whole group (danhip_augment_preprocess_batch: a number of launches that does not depend on the batch size)."""
 import ctypes
 
 import numpy as np
@@ -170,3 +181,97 @@ def preprocess_for_train(image, bboxes, out_shape, anchor_scales, data_format="c
     flip, boxes = random_flip_left_right(boxes, out_shape[1], draws)
     keep = ((boxes[:, 2] - boxes[:, 0]) > F(6.)) & ((boxes[:, 3] - boxes[:, 1]) > F(3.))
     return augment_image(image, ops, window, flip, out_shape), boxes[keep]
+
+
+# ---------------------------------------------------------------------------------------------------- the whole batch in one device pass
+FLIP_NONE, FLIP_RESIZED, FLIP_WINDOW = 0, 1, 2     # danhip_augment_item.flip: none / the resized image (this module) / the window, before the resize
+_BATCH_BUFFERS = {}                                # (device, stream) -> [capacity, pinned table staging ring, device table, workspace, upload events, calls]
+_STAGING_SLOTS = 4                                 # the host refills a staging slot only after the upload four calls back has left it
+
+
+def _batch_buffers(device, B):
+    """Table staging (pinned), device table and workspace of augment_batch, kept per device and stream and grown by doubling."""
+    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
+    buf = _BATCH_BUFFERS.get(key)
+    if buf is None or buf[0] < B:
+        cap = max(16, 2 * buf[0] if buf else 0, B)
+        nitem, nws = lib().danhip_augment_item_bytes(), lib().danhip_augment_batch_workspace_bytes(cap)
+        buf = [cap, torch.empty(_STAGING_SLOTS * cap * nitem, dtype=torch.uint8).pin_memory(), torch.empty(cap * nitem, dtype=torch.uint8, device=device),
+               torch.empty(nws, dtype=torch.uint8, device=device), [None] * _STAGING_SLOTS, 0]
+        _BATCH_BUFFERS[key] = buf
+    return buf
+
+
+def augment_batch(images, params, out_shape):
+    """The device pass for a whole batch: images = list of uint8 [H,W,3] device tensors of any sizes (separate tensors or contiguous views
+    into one decoder buffer), params = list of (ops, window, flip) as augment_image takes them (flip may also be FLIP_WINDOW)
+    -> [B, out_h, out_w, 8] network input.  One table upload and one library call (danhip_augment_preprocess_batch: 1 kernel launch, 3 when
+    an item has a contrast op), whatever B is; slice k equals augment_image(images[k], *params[k], out_shape)."""
+    B = len(images)
+    assert B > 0 and len(params) == B
+    device = images[0].device
+    oh, ow = int(out_shape[0]), int(out_shape[1])
+    buf = _batch_buffers(device, B)
+    cap, ring, table, ws, uploaded = buf[:5]
+    nitem = lib().danhip_augment_item_bytes()
+    slot = buf[5] % _STAGING_SLOTS
+    buf[5] += 1
+    if uploaded[slot] is not None:
+        uploaded[slot].synchronize()                                               # that slot's last table has left the staging buffer
+    staging = ring[slot * cap * nitem:(slot + 1) * cap * nitem]
+    first, nb = 0, ctypes.c_int32(0)
+    for k, (img, (ops, window, flip)) in enumerate(zip(images, params)):
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous() and img.device == device
+        codes = (ctypes.c_int32 * 4)(*([OP_CODES[n] for n, _ in ops][:4] + [0] * (4 - len(ops))))
+        vals = (ctypes.c_float * 4)(*([float(v) for _, v in ops][:4] + [0.0] * (4 - len(ops))))
+        call("danhip_augment_item_init", ctypes.c_void_p(staging.data_ptr() + k * nitem), ptr(img), int(img.shape[0]), int(img.shape[1]), len(ops),
+             codes, vals, int(window[0]), int(window[1]), int(window[2]), int(window[3]), int(flip), first, ctypes.byref(nb))
+        first += nb.value
+    table[:B * nitem].copy_(staging[:B * nitem], non_blocking=True)
+    uploaded[slot] = torch.cuda.Event()
+    uploaded[slot].record(torch.cuda.current_stream(device))
+    out = torch.empty((B, oh, ow, 8), dtype=ACT_DTYPE, device=device)
+    call("danhip_augment_preprocess_batch", ptr(table), B, first, ptr(out), oh, ow, ptr(ws), ws.numel(), stream())
+    out._real_channels = 3
+    return out
+
+
+def _host_half(image, bboxes, out_shape, anchor_scales, draws):
+    """The draws and box arithmetic of preprocess_for_train, in its order -> (ops, window, flip, boxes after the small-box filter)."""
+    bboxes = np.asarray(bboxes.detach().cpu().numpy() if torch.is_tensor(bboxes) else bboxes, F)
+    H, W = int(image.shape[0]), int(image.shape[1])
+    ops = distort_color(draws.randint(0, 4), draws, fast_mode=False)
+    if draws.uniform(0., 1.) < 0.5:
+        window, boxes = dan_random_sample(H, W, bboxes, out_shape, draws)
+    else:
+        window, boxes = data_anchor_sampling(H, W, bboxes, anchor_scales, out_shape, draws)
+    flip, boxes = random_flip_left_right(boxes, out_shape[1], draws)
+    keep = ((boxes[:, 2] - boxes[:, 0]) > F(6.)) & ((boxes[:, 3] - boxes[:, 1]) > F(3.))
+    return ops, window, flip, boxes[keep]
+
+
+def batch_for_train(images, bboxes_list, out_shape, host_half, draws):
+    """Shared by the three modules' preprocess_batch_for_train: host_half(image, bboxes, draws) -> (ops, window, flip, boxes) is drawn for image
+    0, then image 1, ... from one Draws; the images whose boxes are all gone are dropped on the host; one augment_batch call for the rest."""
+    assert len(images) == len(bboxes_list)
+    draws = draws or Draws()
+    kept, params, boxes_out = [], [], []
+    for k, (image, bboxes) in enumerate(zip(images, bboxes_list)):
+        if len(bboxes) == 0:                                                       # nothing to sample around: no draws, left out
+            continue
+        ops, window, flip, boxes = host_half(image, bboxes, draws)
+        if len(boxes):
+            kept.append(k); params.append((ops, window, flip)); boxes_out.append(boxes)
+    if not kept:
+        dev = images[0].device if images else None
+        return torch.empty((0, int(out_shape[0]), int(out_shape[1]), 8), dtype=ACT_DTYPE, device=dev), [], []
+    return augment_batch([images[k] for k in kept], params, out_shape), boxes_out, kept
+
+
+def preprocess_batch_for_train(images, bboxes_list, out_shape, anchor_scales, data_format="channels_last", scope=None, output_rgb=False, draws=None):
+    """preprocess_for_train for a decoded group: -> (network input [K,out_h,out_w,8], list of K box arrays, list of the K kept indices).
+    The draws of image 0, then image 1, ... are taken from one `draws`, so windows, flips and boxes equal len(images) successive
+    preprocess_for_train calls with the same seed; an image whose boxes are all gone is left out (known on the host, before the device pass)."""
+    if data_format != "channels_last" or output_rgb:
+        raise ValueError("the MI355X build feeds NHWC BGR (the reference's training scripts pass output_rgb=False)")
+    return batch_for_train(images, bboxes_list, out_shape, lambda im, b, d: _host_half(im, b, out_shape, anchor_scales, d), draws)

@@ -659,6 +659,40 @@ int danhip_augment_preprocess(const uint8_t* src, int32_t H, int32_t W, int32_t 
                               int32_t win_y, int32_t win_x, int32_t win_h, int32_t win_w, int32_t flip, uint16_t* dst, int32_t out_h,
                               int32_t out_w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The batched form (ABI version 11): B decoded images of DIFFERENT sizes -> one network input [B, out_h, out_w, 8] (same 16-bit layout), every
+ * image with exactly the arithmetic of danhip_augment_preprocess (the kernels share its device functions).  As with danhip_pack_entry_init /
+ * danhip_pack_conv_weights_batched, the caller fills a host array of fixed-size items with danhip_augment_item_init, copies it to the device
+ * with one copy and passes the device table here; the call itself touches no host memory, so it is stream-ordered and can be captured.
+ *   danhip_augment_item_init validates what it is given (DANHIP_EINVAL: null pointer, H / W <= 0, more than 4 ops, more than one contrast op,
+ *   an unknown op code, a non-positive window size, flip outside 0..2) and returns in *mean_blocks how many workgroups of the contrast-mean
+ *   launch the item owns (0 without a contrast op); first_mean_block is the running sum of those counts over the items before it and
+ *   total_mean_blocks of the call the sum over all items.  The window may leave the image.
+ *   flip: 0 none; 1 the resized image is flipped (dan / pb_preprocessing.py:707-714); 2 the window is flipped BEFORE the resize
+ *   (sfd_preprocessing.py:522-531, where the flip precedes tf.image.resize_images).  danhip_augment_preprocess keeps its 0 / non-zero meaning.
+ * KERNEL LAUNCHES PER CALL, whatever B is: 1 when total_mean_blocks == 0 (no item has a contrast op), otherwise 3 - the workspace zero-fill,
+ * one segmented fp64 reduction for the contrast means of all items that have the op (a workgroup's pixels belong to one image; the other items
+ * take no part), and the image pass (one workgroup = a 32 x 8 tile of one output image, grid z = image; the mean's final division is folded in).
+ * Items without a contrast op equal danhip_augment_preprocess bit for bit; with one, up to the fp64 summation order of the mean.
+ * workspace: danhip_augment_batch_workspace_bytes(B) bytes, 16-byte aligned, zeroed inside the call when it is used.  DANHIP_EINVAL for a null
+ * table / dst, B <= 0 (or > 65535), a non-positive output size; the CONTENTS of the table are on the device and are not validated by the call. */
+typedef struct {
+  const uint8_t* src;                      /* uint8 [H, W, 3] RGB, any byte alignment (views into a decoder's buffer) */
+  int32_t H, W;
+  int32_t nops, contrast_at;               /* contrast_at: index of the contrast op in the chain, -1 = none */
+  int32_t op[4];
+  float val[4];
+  int32_t win_y, win_x, win_h, win_w;
+  int32_t flip;
+  int32_t first_mean_block, mean_blocks, pad_;
+} danhip_augment_item;
+size_t danhip_augment_item_bytes(void);    /* sizeof(danhip_augment_item), for callers that bind the library without this header */
+int danhip_augment_item_init(danhip_augment_item* item, const uint8_t* src, int32_t H, int32_t W, int32_t nops, const int32_t* op_codes,
+                             const float* op_values, int32_t win_y, int32_t win_x, int32_t win_h, int32_t win_w, int32_t flip,
+                             int32_t first_mean_block, int32_t* mean_blocks);
+size_t danhip_augment_batch_workspace_bytes(int32_t B);
+int danhip_augment_preprocess_batch(const danhip_augment_item* table_dev, int32_t B, int32_t total_mean_blocks, uint16_t* dst, int32_t out_h,
+                                    int32_t out_w, void* workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------------------
  * Baseline JPEG decode in front of the input pipeline (ABI version 6): a record's 'image/encoded' bytes -> the uint8 [H,W,3] RGB device
  * image danhip_augment_preprocess reads, equal bit for bit to what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy upsampling) decodes.
