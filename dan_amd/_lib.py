@@ -57,6 +57,15 @@ class JpegDesc(ctypes.Structure):
                 ("out_offset", ctypes.c_int64), ("quant", (ctypes.c_uint16 * 64) * 4)]
 
 
+class ResizeItem(ctypes.Structure):
+    """danhip_resize_item: one resized / mirrored copy of danhip_resize_u8_linear_batch (filled by danhip_resize_item_init)."""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("H", "W", "pitch", "Ho", "Wo", "mirror", "first_tile", "tiles")] + \
+               [(n, ctypes.c_double) for n in ("fx", "fy", "scale_x", "scale_y")]
+
+
+DETECT_SELECT_LAUNCHES = 7     # DANHIP_DETECT_SELECT_LAUNCHES
+
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
 I64 = ctypes.c_int64
@@ -143,6 +152,9 @@ SIGNATURES = {
     "danhip_maxpool3x3s2_same_bwd": [P, P, P, I32, I32, I32, I32, P],
     "danhip_resize_u8_linear": [P, I32, I32, P, I32, I32, I32, ctypes.c_double, ctypes.c_double, P],
     "danhip_bbox_vote": [P, P, I32, I32, ctypes.c_double, I32, P, P, P, ctypes.c_size_t, P],
+    "danhip_resize_item_init": [P, I64, I32, I32, I32, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, I32, ctypes.POINTER(ctypes.c_int32)],
+    "danhip_resize_u8_linear_batch": [P, P, I32, P, I64, P, I64, P],
+    "danhip_detect_select": [P, P, I32, I32, FL, I32, FL, P, P, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), P],
     "danhip_wider_quantize": [P, ctypes.c_int, P, P, I32, I32, I32, P, P, I32, I32, P, P],
     "danhip_wider_score_range": [P, I64, P, P, ctypes.c_size_t, P],
     "danhip_wider_eval": [P, P, I64, P, P, P, I64, P, I32, I32, I32, I32, ctypes.c_double, P, ctypes.c_size_t, P, P],
@@ -288,6 +300,10 @@ def _load(so_path, act_name):
         L.danhip_deform_conv_fused.restype = ctypes.c_int
         L.danhip_deform_conv_fused.argtypes = [I32] * 9
         L.danhip_bbox_vote_workspace_bytes.argtypes = [I32, I32]
+        L.danhip_resize_item_bytes.restype = ctypes.c_size_t
+        L.danhip_resize_item_bytes.argtypes = []
+        L.danhip_detect_select_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_detect_select_workspace_bytes.argtypes = [I64]
         L.danhip_wider_score_range_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_wider_score_range_workspace_bytes.argtypes = []
         L.danhip_wider_eval_workspace_bytes.restype = ctypes.c_size_t

@@ -5,6 +5,7 @@
 //   * bbox_vote        : the score-weighted box voting of eval_dan.py:201-241 (IoU with the +1 convention, merge >= threshold,
 //                        singleton clusters dropped, float64 arithmetic as numpy does it, float32 results).
 #include "common.h"
+#include "resize_u8.h"
 
 namespace {
 
@@ -13,40 +14,13 @@ inline int grid_for(long total, int block, int cap = 4096) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-__device__ __forceinline__ int cv_round_to_short(float v) {      // saturate_cast<short>(float) = cvRound (half to even) + clamp
-  int r = __float2int_rn(v);
-  return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-}
-
-// one thread per (dy, dx, c): both passes recomputed from the four source bytes (the integer formulas make that exact)
+// one thread per (dy, dx): the pixel arithmetic is resize_u8.h's, shared with the batched form (evalpipe_ragged_exact.hip)
 __global__ void resize_u8_linear_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, int Ho, int Wo, int C,
                                         double scale_x, double scale_y) {
   const long total = (long)Ho * Wo;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int dx = (int)(idx % Wo), dy = (int)(idx / Wo);
-    float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= (float)sx;
-    bool xedge = false;                                          // dx >= xmax: horizontal pass copies S[sx] * ONE
-    if (sx < 0) { fx = 0.f; sx = 0; }
-    if (sx >= W - 1) { fx = 0.f; sx = W - 1; xedge = true; }
-    float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
-    int sy = (int)floorf(fy);
-    fy -= (float)sy;
-    const int a0 = cv_round_to_short((1.f - fx) * 2048.f), a1 = cv_round_to_short(fx * 2048.f);
-    const int b0 = cv_round_to_short((1.f - fy) * 2048.f), b1 = cv_round_to_short(fy * 2048.f);
-    int sy0 = sy, sy1 = sy + 1;                                  // rows are clamped (BORDER_REPLICATE), coefficients kept
-    sy0 = sy0 < 0 ? 0 : (sy0 > H - 1 ? H - 1 : sy0);
-    sy1 = sy1 < 0 ? 0 : (sy1 > H - 1 ? H - 1 : sy1);
-    const int sx1 = xedge ? sx : sx + 1;
-    for (int c = 0; c < C; ++c) {
-      const int p00 = src[((long)sy0 * W + sx) * C + c], p01 = src[((long)sy0 * W + sx1) * C + c];
-      const int p10 = src[((long)sy1 * W + sx) * C + c], p11 = src[((long)sy1 * W + sx1) * C + c];
-      const int r0 = xedge ? p00 * 2048 : p00 * a0 + p01 * a1;
-      const int r1 = xedge ? p10 * 2048 : p10 * a0 + p11 * a1;
-      const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-      dst[idx * C + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-    }
+    resize_u8_linear_pixel(src, (long)W * C, H, W, C, false, scale_x, scale_y, dy, dx, dst + idx * C);
   }
 }
 

@@ -3,11 +3,13 @@ flip test, multi-scale tests and box voting, with the same function names, argum
 (eval_dan.py:95-297).  Images are uint8 HWC device tensors; detections are device tensors whose rows are
 (xmin, ymin, xmax, ymax, score).  The image resize (cv2.resize in the reference) and the voting loop (numpy in the
 reference) are libdanhip kernels; everything stays on the device until write_to_txt."""
+import ctypes
+
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import call, lib, ptr, stream
+from ._lib import ResizeItem, call, lib, ptr, stream
 
 NMS_THRESHOLD = 0.3          # eval_dan.py:69-70
 MEMORY_LIMIT = 577.0         # :71-72
@@ -300,3 +302,125 @@ def detect_image(net, image, pyramid=True):
     if pyramid:
         dets.append(multi_scale_test_pyramid(net, image, max_shrink))
     return bbox_vote(torch.cat([d.to(torch.float64) for d in dets], dim=0))
+
+
+# ---- the same pipeline for B images of DIFFERENT sizes, without a host round trip.  The forward passes stay per (image, scale); everything
+# around them is size-agnostic: ONE launch makes every resized / mirrored copy of every image (danhip_resize_u8_linear_batch), one library
+# call per pass does detect_face's cut and order, the size filter and flip_test's mirror map into the image's rows of the packed voting
+# buffer (danhip_detect_select: a radix select instead of the arg-sort of all A anchors, no boolean compaction), and ONE voting launch takes
+# the per-image counts from the device.
+FILTER_NONE, FILTER_BIG, FILTER_SMALL = 0, 1, 2          # danhip_detect_select's filter: none / max(w, h) > 30 / min(w, h) < 100
+
+
+def scale_passes(height, width, pyramid=True):
+    """The passes detect_image walks for an image of this size, in its order: [(scale, mirrored, filter)] (host arithmetic on the size)."""
+    shrink, max_shrink = get_shrink(height, width)
+    passes = [(shrink, 0, FILTER_NONE), (shrink, 1, FILTER_NONE)]              # detect_face, flip_test
+    st = 0.5 if max_shrink >= 0.75 else 0.5 * max_shrink                      # multi_scale_test
+    passes.append((st, 0, FILTER_BIG))
+    bt = min(2, max_shrink) if max_shrink > 1 else (st + max_shrink) / 2
+    bs = [bt]
+    if max_shrink > 2:
+        bt *= 2
+        while bt < max_shrink:
+            bs.append(bt)
+            bt *= 2
+        bs.append(max_shrink)
+    passes += [(b, 0, FILTER_SMALL if bt > 1 else FILTER_BIG) for b in bs]
+    if pyramid:                                                               # multi_scale_test_pyramid
+        passes.append((0.25, 0, FILTER_BIG))
+        passes += [(sc, 0, FILTER_SMALL if sc > 1 else FILTER_BIG) for sc in (0.75, 1.25, 1.5, 1.75) if sc <= max_shrink]
+    return passes
+
+
+def resize_image_batch(images, requests):
+    """Every resized / mirrored copy in ONE launch: images = list of contiguous uint8 [H,W,3] device tensors (separate tensors or views into
+    one buffer, at any byte offset), requests = [(image index, fx, fy, mirror)] -> list of uint8 [Ho,Wo,3] tensors (views into one buffer),
+    request for request equal to resize_image(image.flip(1).contiguous() if mirror else image, fx, fy).  One pinned table, one upload."""
+    n = len(requests)
+    assert n > 0
+    device = images[0].device
+    for im in images:
+        assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous() and im.device == device
+    base = min(im.data_ptr() for im in images)                # "one source buffer": the span of the sources' addresses
+    src_bytes = max(im.data_ptr() + im.numel() for im in images) - base
+    nitem = ctypes.sizeof(ResizeItem)
+    staging = torch.empty(n * nitem, dtype=torch.uint8, pin_memory=True)
+    first, at, nt, shapes = 0, 0, ctypes.c_int32(0), []
+    for k, (i, fx, fy, mirror) in enumerate(requests):
+        H, W = int(images[i].shape[0]), int(images[i].shape[1])
+        Wo, Ho = int(np.rint(W * fx)), int(np.rint(H * fy))
+        call("danhip_resize_item_init", ctypes.c_void_p(staging.data_ptr() + k * nitem), images[i].data_ptr() - base, H, W, 3 * W, at, Ho, Wo,
+             float(fx), float(fy), int(mirror), first, ctypes.byref(nt))
+        first += nt.value
+        shapes.append((at, Ho, Wo))
+        at += (3 * Ho * Wo + 255) // 256 * 256
+    table = staging.to(device, non_blocking=True)
+    out = torch.empty(at, dtype=torch.uint8, device=device)
+    call("danhip_resize_u8_linear_batch", ctypes.c_void_p(staging.data_ptr()), ptr(table), n, ctypes.c_void_p(base), src_bytes, ptr(out), at, stream())
+    return [out[o:o + 3 * ho * wo].view(ho, wo, 3) for o, ho, wo in shapes]
+
+
+def detect_select(bboxes, scores, shrink, top, rows, valid, filter=FILTER_NONE, mirror_width=None):
+    """The tail of one pass on the device (danhip_detect_select): rows float64 [top,5] and valid uint8 [top] are written in place.
+    -> the number of kernel launches the call issued (a constant: _lib.DETECT_SELECT_LAUNCHES)."""
+    A = int(scores.shape[0])
+    bboxes, scores = bboxes.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous()
+    assert tuple(bboxes.shape) == (A, 4) and tuple(rows.shape) == (top, 5) and rows.dtype == torch.float64 and rows.is_contiguous()
+    assert tuple(valid.shape) == (top,) and valid.dtype == torch.uint8 and valid.is_contiguous()
+    nbytes = int(lib().danhip_detect_select_workspace_bytes(A))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device)
+    launches = ctypes.c_int32(0)
+    call("danhip_detect_select", ptr(bboxes), ptr(scores), A, int(top), float(shrink), int(filter), -1.0 if mirror_width is None else float(mirror_width),
+         ptr(rows), ptr(valid), ptr(ws), nbytes, ctypes.byref(launches), stream())
+    return launches.value
+
+
+def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
+    """detect_image for a list of uint8 [H_i,W_i,3] device tensors of ANY sizes (they may be views into one buffer, the JPEG decoder's)
+    -> (dets fp32 [B, max_per_image, 5], num int32 [B]) on the device, the layout WiderEvaluator.add takes; rows beyond num[b] are
+    unspecified.  Per image the result equals detect_image(net, images[b], pyramid): the forwards are the same batch-1 calls.  No device
+    value is read on the host between the first launch and the return."""
+    B = len(images)
+    assert B > 0
+    device = images[0].device
+    images = [im.contiguous() for im in images]
+    cap = int(max_per_image * 1.5)
+    plans = [scale_passes(int(im.shape[0]), int(im.shape[1]), pyramid) for im in images]
+    requests, where = [], {}                                                   # one copy per distinct (image, scale, mirrored)
+    for i, plan in enumerate(plans):
+        for scale, mirror, _ in plan:
+            if (scale != 1 or mirror) and (i, scale, mirror) not in where:
+                where[(i, scale, mirror)] = len(requests)
+                requests.append((i, scale, scale, mirror))
+    copies = resize_image_batch(images, requests)
+    n = max(len(plan) for plan in plans) * cap
+    det = torch.empty((B, n, 5), dtype=torch.float64, device=device)
+    valid = torch.zeros((B, n), dtype=torch.uint8, device=device)
+    for i, plan in enumerate(plans):
+        at = 0
+        for scale, mirror, filt in plan:
+            image = copies[where[(i, scale, mirror)]] if (scale != 1 or mirror) else images[i]
+            bboxes, scores = net(image)
+            top = min(int(scores.shape[0]) - 1, cap)
+            if top > 0:
+                detect_select(bboxes, scores, scale, top, det[i, at:at + top], valid[i, at:at + top], filt,
+                              float(images[i].shape[1]) if mirror else None)
+            at += max(top, 0)
+    valid = valid.bool()
+    # the voting input as detect_images builds it: valid rows by descending score, ties higher index first; invalid rows carry -inf
+    key = torch.where(valid, det[..., 4].to(torch.float32), torch.full((), float("-inf"), dtype=torch.float32, device=device))
+    order = torch.stack([ops.argsort_desc(key[b].contiguous(), ties_high_index_first=True) for b in range(B)])
+    packed = torch.gather(det, 1, order.unsqueeze(2).expand(-1, -1, 5)).contiguous()
+    counts = valid.sum(dim=1).to(torch.int32)
+    out = torch.empty((B, max_per_image, 5), dtype=torch.float32, device=device)
+    num = torch.empty((B,), dtype=torch.int32, device=device)
+    ws = torch.empty((lib().danhip_bbox_vote_workspace_bytes(B, n),), dtype=torch.uint8, device=device)
+    call("danhip_bbox_vote", ptr(packed), ptr(counts), B, n, float(nms_threshold), int(max_per_image), ptr(out), ptr(num), ptr(ws), ws.numel(), stream())
+    return out, num
+
+
+def detect_encoded(net, datas, decoder, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
+    """JPEG byte strings -> detections: dataset.jpeg.JpegDecoder.decode_batch (device decode; a stream the decoder refuses, a progressive one
+    by default, takes its Pillow fallback) -> detect_image_list on the decoder's views."""
+    return detect_image_list(net, decoder.decode_batch(list(datas)), pyramid, nms_threshold, max_per_image)

@@ -13,3 +13,15 @@ def detect_images(net, images):
     """The same passes for B images of one size, batched (eval_dan.detect_images): (dets [B, 750, 5], num [B]) on the device."""
     from .eval_dan import detect_images as _detect_images
     return _detect_images(net, images, pyramid=False)
+
+
+def detect_image_list(net, images):
+    """The same passes for images of different sizes (eval_dan.detect_image_list): (dets [B, 750, 5], num [B]) on the device."""
+    from .eval_dan import detect_image_list as _detect_image_list
+    return _detect_image_list(net, images, pyramid=False)
+
+
+def detect_encoded(net, datas, decoder):
+    """JPEG byte strings -> detections (eval_dan.detect_encoded) without the pyramid pass."""
+    from .eval_dan import detect_encoded as _detect_encoded
+    return _detect_encoded(net, datas, decoder, pyramid=False)

@@ -694,6 +694,57 @@ int danhip_augment_preprocess_batch(const danhip_augment_item* table_dev, int32_
                                     int32_t out_w, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------------------
+ * Test-time pipeline for images of DIFFERENT sizes (ABI version 12; dan_amd/eval_dan.py:detect_image_list; csrc/evalpipe_ragged_exact.hip).
+ *
+ * danhip_resize_u8_linear_batch: every resized and / or mirrored copy of every image in ONE launch.  All sources lie in one source buffer
+ * and all results in one destination buffer; an item names a source view uint8 [H, W, 3] (src + src_offset, any byte alignment, rows `pitch`
+ * bytes apart) and its result uint8 [Ho, Wo, 3] (dst + dst_offset, dense).  The arithmetic is danhip_resize_u8_linear's, pixel for pixel
+ * (the kernels share one device function); mirror = 1 reads source column W-1-x, i.e. the item is the resize of image.flip(1); fx = fy = 1
+ * with mirror = 1 is the plain mirrored copy.  As with danhip_augment_item_init, the caller fills a host array of items with
+ * danhip_resize_item_init (first_tile = the running sum of the *tiles it returned for the items before), uploads it with one copy and passes
+ * BOTH tables: the host table is validated before anything is launched, the kernel reads the device table.  A workgroup's pixels belong to
+ * one item; the grid is the flat list of all items' tiles, so items of very different sizes leave no workgroup idle.
+ * DANHIP_EINVAL with a message, before any launch - from danhip_resize_item_init: a non-positive size, Ho / Wo that are not rint(H * fy) /
+ * rint(W * fx) in double, pitch < 3 * W, fx / fy not positive and finite, mirror outside 0 / 1, a negative offset or first_tile; from the
+ * batch call in addition: an item init did not fill, a tile prefix that does not add up, a source range that leaves [0, src_bytes), a
+ * destination range that leaves [0, dst_bytes) or overlaps another item's.
+ *
+ * danhip_detect_select: the tail of one detection pass - detect_face's order and cut (eval_dan.py:107-116), the size filter of
+ * multi_scale_test / multi_scale_test_pyramid and flip_test's mirror map - written straight into the voting buffer.
+ *   boxes fp32 [A,4] rows (ymin, xmin, ymax, xmax), scores fp32 [A]; K <= min(A, 2048) (the pipeline's K = min(A - 1, int(max_per_image * 1.5)));
+ *   rows double [K,5] = (xmin, ymin, xmax, ymax, score), valid uint8 [K].
+ *   Row r is element r of the descending arg-sort of the scores with equal scores taken HIGHER index first (danhip_argsort_desc_f32 with
+ *   ties_high_index_first: numpy's argsort()[::-1]; -0 = +0).  Coordinates are box / shrink in fp32, correctly rounded (a true division:
+ *   __fdiv_rn; the build passes no flag that relaxes fp32 division and compiles the file with -ffp-contract=off), then widened to double.
+ *   mirror_width >= 0 (the width w of the image flip_test mirrored): xmin' = (w - xmax) - 1, xmax' = (w - xmin) - 1 in fp32; < 0: none.
+ *   filter 0: valid = 1; 1 "big": max(w, h) > 30; 2 "small": min(w, h) < 100, with w = (xmax - xmin) + 1, h = (ymax - ymin) + 1 in fp32 on
+ *   the row BEFORE the mirror map.
+ *   Precondition: the scores are finite.  With NaNs nothing is read or written out of bounds, but which rows come out is not promised.
+ *   No sort of the A scores: a radix select (11 + 11 + 10 bits of the order-preserving key) finds the K-th key, the keys above it and the
+ *   highest-index ties of it are collected, and those K are ordered in LDS.  KERNEL LAUNCHES PER CALL: DANHIP_DETECT_SELECT_LAUNCHES = 7,
+ *   whatever A is (zero-fill, three histograms, tie count, collect, emit); *launches (may be NULL) receives the number the call issued.
+ *   workspace: danhip_detect_select_workspace_bytes(A) bytes, 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  int64_t src_offset, dst_offset;          /* bytes from the call's src / dst */
+  int32_t H, W, pitch;                     /* source rows are `pitch` bytes apart (>= 3 * W) */
+  int32_t Ho, Wo;
+  int32_t mirror;
+  int32_t first_tile, tiles;               /* the item's workgroups: [first_tile, first_tile + tiles) of the grid */
+  double fx, fy;
+  double scale_x, scale_y;                 /* 1 / fx, 1 / fy, what the kernel computes with */
+} danhip_resize_item;
+size_t danhip_resize_item_bytes(void);     /* sizeof(danhip_resize_item), for callers that bind the library without this header */
+int danhip_resize_item_init(danhip_resize_item* item, int64_t src_offset, int32_t H, int32_t W, int32_t pitch, int64_t dst_offset, int32_t Ho,
+                            int32_t Wo, double fx, double fy, int32_t mirror, int32_t first_tile, int32_t* tiles);
+int danhip_resize_u8_linear_batch(const danhip_resize_item* table_host, const danhip_resize_item* table_dev, int32_t n, const uint8_t* src,
+                                  int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, void* stream);
+#define DANHIP_DETECT_SELECT_LAUNCHES 7
+size_t danhip_detect_select_workspace_bytes(int64_t A);
+int danhip_detect_select(const float* boxes, const float* scores, int32_t A, int32_t K, float shrink, int32_t filter, float mirror_width,
+                         double* rows, uint8_t* valid, void* workspace, size_t workspace_bytes, int32_t* launches, void* stream);
+
+/* --------------------------------------------------------------------------------------------------
  * Baseline JPEG decode in front of the input pipeline (ABI version 6): a record's 'image/encoded' bytes -> the uint8 [H,W,3] RGB device
  * image danhip_augment_preprocess reads, equal bit for bit to what Pillow (libjpeg-turbo, JDCT_ISLOW, fancy upsampling) decodes.
  * The serial half - marker parsing, Huffman decoding - runs on host threads (csrc/jpeg_entropy.cpp, no HIP call: these entry points work in
