@@ -7,7 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("n", [1, 2, 5, 1000, 8191, 8192, 8193, 34125, 65536, 87360])
+@pytest.mark.parametrize("n", [1, 2, 5, 1000, 8191, 8192, 8193, 34125, 65536, 65537, 87360, 200000])
 @pytest.mark.parametrize("levels", [0, 17])          # 0: distinct random floats; 17: quantised to 17 values (long runs of ties)
 def test_argsort_desc_matches_torch_stable_sort(n, levels, dev):
     from dan_amd import ops
