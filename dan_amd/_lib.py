@@ -173,6 +173,7 @@ SIGNATURES = {
     "danhip_hard_neg_select": [P, P, P, P, P, P, I32, I32, FL, ctypes.c_int, P],
     "danhip_detection_loss_fwd": [P, P, P, P, P, P, P, P, I32, I32, P],
     "danhip_detection_loss_bwd": [P, P, P, P, P, P, P, FL, FL, I32, I32, P],
+    "danhip_cls_accuracy": [P, P, P, P, I32, I32, P],
     "danhip_sgd_momentum_flat": [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P],
     "danhip_sgd_momentum_flat_dynamic": [P, P, P, P, P, P, I32, I64, FL, FL, P, P, P],
     "danhip_anchors_generate": [P, P, P, P, P, P, I32, I32, I32, FL, FL, FL, I32, P],

@@ -351,6 +351,41 @@ __global__ void detection_loss_bwd_kernel(const float* __restrict__ cls, const f
   }
 }
 
+// ---------------------------------------------------------------- streaming classification accuracy (tf.metrics.accuracy over final_mask)
+// counts[0] += #(sel != 0 and argmax(cls) == clip(label, 0, 2)), counts[1] += #(sel != 0): train_sfd.py:383-390.  argmax of two logits with
+// tf.argmax's tie rule (first index): class 1 only when cls[1] > cls[0].  One pass, <= 13 bytes per anchor (sel, then logits and label of the
+// selected ones only).  A thread carries both counters in ONE 64-bit word (correct << 32 | counted): a workgroup sees fewer than 2^32 anchors
+// (the launcher's index check), so the halves never carry into each other through the wave and workgroup sums.  Per workgroup one 64-bit
+// integer atomic instruction (lane 0 -> counts[0], lane 1 -> counts[1]); integer sums: the same bits in any order, so there is no
+// deterministic form.
+constexpr int kAccThreads = DANHIP_CLS_ACCURACY_THREADS, kAccMaxBlocks = DANHIP_CLS_ACCURACY_MAX_BLOCKS;
+__global__ __launch_bounds__(kAccThreads) void cls_accuracy_kernel(const float* __restrict__ cls, const int* __restrict__ labels,
+                                                                   const unsigned char* __restrict__ sel, unsigned long long* __restrict__ counts,
+                                                                   unsigned total) {
+  __shared__ unsigned long long sh[kAccThreads / 64];
+  unsigned long long v = 0;
+  // (i < total < 2^31 and the stride is at most kAccMaxBlocks * kAccThreads = 2^18: the unsigned index cannot wrap)
+  for (unsigned i = blockIdx.x * kAccThreads + threadIdx.x; i < total; i += gridDim.x * kAccThreads) {
+    if (sel[i]) {
+      const float2 l = *reinterpret_cast<const float2*>(cls + (size_t)i * 2);
+      const int target = min(max(labels[i], 0), 2);
+      const int pred = l.y > l.x ? 1 : 0;
+      v += 1ull + ((unsigned long long)(pred == target) << 32);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int w = 0; w < kAccThreads / 64; ++w) t += sh[w];
+    const unsigned long long add = threadIdx.x == 0 ? t >> 32 : (t & 0xffffffffull);
+    if (add) atomicAdd(counts + threadIdx.x, add);
+  }
+}
+
 // ---------------------------------------------------------------- optimizer
 // flat fp32 buffers; segment s covers [seg[s], seg[s+1]); gmult = gradient multiplier, wdc = weight_decay * coefficient
 // Vector form: every segment starts on a 64-element boundary and total is padded to one (danhip_sgd_momentum_flat checks), so a
@@ -585,6 +620,19 @@ extern "C" int danhip_detection_loss_bwd(const float* cls, const float* loc, con
   const long total = (long)B * A;
   hipLaunchKernelGGL(detection_loss_bwd_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, (hipStream_t)stream, cls, loc, loc_targets, sel,
                      acc4, dcls, dloc, ce_scale, loc_scale, total);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_cls_accuracy(const float* cls, const int32_t* labels, const uint8_t* sel, int64_t* counts, int32_t B, int32_t A, void* stream) {
+  DH_REQUIRE(cls && labels && sel && counts && B > 0 && A > 0, DANHIP_EINVAL, "cls_accuracy: bad arguments (null pointer or empty batch)");
+  DH_REQUIRE(((uintptr_t)cls & 7) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)counts & 7) == 0, DANHIP_EINVAL,
+             "cls_accuracy: cls and counts must be 8-byte aligned, labels 4-byte aligned");
+  const int64_t total = (int64_t)B * A;
+  DH_REQUIRE(total <= INT32_MAX, DANHIP_EINVAL, "cls_accuracy: B * A = %lld anchors exceeds the kernel's 32-bit index range (2^31 - 1)",
+             (long long)total);
+  hipLaunchKernelGGL(cls_accuracy_kernel, dim3(grid_for(total, kAccThreads, kAccMaxBlocks)), dim3(kAccThreads), 0, (hipStream_t)stream, cls, labels,
+                     sel, reinterpret_cast<unsigned long long*>(counts), (unsigned)total);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

@@ -175,7 +175,12 @@ def precision_scope(precision):
 def prepare_input(img_u8_rgb, precision="act"):
     """uint8 RGB [B,H,W,3] (device) -> network input.  precision "act": the build's 16-bit activation type (training and fast inference);
     "fp32": the fp32 inference path (ops._f32_infer: every layer then runs the fp32 kernels); "split": fp32 maps between the ops as in
-    "fp32", convolutions as three-limb-product half convolutions (inside precision_scope)."""
+    "fp32", convolutions as three-limb-product half convolutions (inside precision_scope).
+    A [B,H,W,8] tensor of the activation type IS a network input already (preprocess_batch_for_train's output: augmented, mean-subtracted,
+    BGR, zero padded - what the training driver feeds) and passes through under "act"."""
+    if precision == "act" and img_u8_rgb.dtype == ops.ACT and img_u8_rgb.shape[-1] == 8:
+        img_u8_rgb._real_channels = 3
+        return img_u8_rgb
     if precision in ("fp32", "split"):
         return ops.preprocess_f32(img_u8_rgb)
     x = ops.preprocess_u8(img_u8_rgb)

@@ -1322,7 +1322,7 @@ class _DetectionLoss(torch.autograd.Function):
     ignored: it uses ctx.scale (= d total_loss / d this loss term) instead."""
 
     @staticmethod
-    def forward(ctx, cls, loc, labels, loc_t, ratio, at_least_one, scale):
+    def forward(ctx, cls, loc, labels, loc_t, ratio, at_least_one, scale, metric_counts=None):
         B, A, _ = cls.shape
         # the kernels read raw pointers: a wrong dtype would be misread silently
         assert cls.dtype == torch.float32 and loc.dtype == torch.float32 and loc_t.dtype == torch.float32, "detection_loss: fp32 logits / targets"
@@ -1345,6 +1345,8 @@ class _DetectionLoss(torch.autograd.Function):
             call("danhip_detection_loss_fwd", ptr(cls), ptr(loc), ptr(labels), ptr(loc_t), ptr(score), ptr(thr), ptr(sel), ptr(acc), B, A, stream())
         if _CTX.TRACE is not None:                           # tests: the hard-negative selection of this term (call order), imposed on the oracle's loss
             _CTX.TRACE.setdefault("loss_sel", []).append(sel)
+        if metric_counts is not None:                        # the reference's cls_accuracy over this term's final_mask (one more launch; opt-in)
+            cls_accuracy(cls, labels, sel, metric_counts)
         ctx.save_for_backward(cls, loc, loc_t, sel, acc)
         ctx.cfg = (ratio, scale)
         ctx.aux = (score, thr, k, counts)
@@ -1362,11 +1364,25 @@ class _DetectionLoss(torch.autograd.Function):
         if _CTX.LOSS_SCALE_DEV is not None:                  # dynamic loss scale (fp16 build): a device scalar, so the step stays capturable
             dcls.mul_(_CTX.LOSS_SCALE_DEV)
             dloc.mul_(_CTX.LOSS_SCALE_DEV)
-        return dcls, dloc, None, None, None, None, None
+        return dcls, dloc, None, None, None, None, None, None
 
 
-def detection_loss(cls, loc, labels, loc_t, ratio=3.0, at_least_one=False, scale=1.0):
-    return _DetectionLoss.apply(cls, loc, labels, loc_t, ratio, at_least_one, scale)
+def detection_loss(cls, loc, labels, loc_t, ratio=3.0, at_least_one=False, scale=1.0, metric_counts=None):
+    """metric_counts: None, or an int64 [2] device tensor {correct, total} that cls_accuracy adds this term's mined anchors to."""
+    return _DetectionLoss.apply(cls, loc, labels, loc_t, ratio, at_least_one, scale, metric_counts)
+
+
+def cls_accuracy(cls, labels, sel, counts):
+    """The reference's streaming tf.metrics.accuracy (train_sfd.py:383-395) on the device: over the anchors with sel != 0 (final_mask, as
+    detection_loss's forward wrote it), counts[0] += #(argmax(cls, -1) == clip(labels, 0, 2)) and counts[1] += their number.  cls fp32
+    [B,A,2], labels int32 [B,A], sel uint8 [B,A], counts int64 [2] (added to: a running total the caller zeroes once).  One launch, no sync;
+    integer sums, so the same bits with and without OpsContext.deterministic."""
+    B, A, _ = cls.shape
+    assert cls.dtype == torch.float32 and cls.shape[2] == 2 and labels.dtype == torch.int32 and labels.shape == (B, A), "cls_accuracy: fp32 [B,A,2] logits, int32 [B,A] labels"
+    assert sel.dtype == torch.uint8 and sel.shape == (B, A) and counts.dtype == torch.int64 and counts.numel() == 2, "cls_accuracy: uint8 [B,A] sel, int64 [2] counts"
+    assert cls.device == labels.device == sel.device == counts.device
+    call("danhip_cls_accuracy", ptr(cls), ptr(labels), ptr(sel), ptr(counts), B, A, stream())
+    return counts
 
 
 def preprocess_u8(img_rgb_u8):

@@ -124,7 +124,8 @@ class DANTrainer(DetectorTrainer):
                                                    self.routing_seed, 0, counter_dev=self._routing_ctr)
             self._routing_ctr.add_(B * A)
             final_loc = final_loc * self._loc_scale2                                                   # :452
-        acc1 = ops.detection_loss(cls1, loc1, cls_targets, loc_targets, ratio=self.negative_ratio, at_least_one=True, scale=self.loss_scale / self.num_towers)
+        acc1 = ops.detection_loss(cls1, loc1, cls_targets, loc_targets, ratio=self.negative_ratio, at_least_one=True, scale=self.loss_scale / self.num_towers,
+                                  metric_counts=self.metric_counts)                                      # cls_accuracy is stage 1's (mining_0): train_dan.py:447, :454-457
         acc2 = ops.detection_loss(cls2, loc2, final_mask, final_loc, ratio=self.negative_ratio, at_least_one=True, scale=self.loss_scale / self.num_towers)
         self.last_routing = (final_mask, final_loc)
         return [("stage1", 1.0, acc1), ("stage2", 1.0, acc2)]
@@ -135,3 +136,13 @@ def encode_batch_dan(anchors, gt_boxes_list):
     ymin, xmin, ymax, xmax, inside = anchors.anchors
     t, l, _, m = anchors.enc.encode_anchors_batch(gt_boxes_list, ymin, xmin, ymax, xmax, inside, match_mining=False)
     return t, l, m
+
+
+def main(argv=None):
+    """`python -m dan_amd.train_dan --data_dir D --model_dir M`: the reference's `python train_dan.py ...` (dan_amd/train_cli.py)."""
+    from .train_cli import main as run
+    return run(argv, model="dan")
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

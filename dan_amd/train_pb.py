@@ -75,6 +75,17 @@ class PBTrainer(DetectorTrainer):
         for k in ("face", "head", "body"):
             loc, cls = out[k]
             loc_t, cls_t, _ = targets[k]
-            acc = ops.detection_loss(cls, loc, cls_t, loc_t, ratio=self.negative_ratio, at_least_one=False, scale=self.loss_scale * self.WEIGHTS[k] / self.num_towers)
+            acc = ops.detection_loss(cls, loc, cls_t, loc_t, ratio=self.negative_ratio, at_least_one=False, scale=self.loss_scale * self.WEIGHTS[k] / self.num_towers,
+                                     metric_counts=self.metric_counts if k == "face" else None)        # cls_accuracy is the face term's: train_pb.py:447, :466-470
             terms.append((k, self.WEIGHTS[k], acc))
         return terms
+
+
+def main(argv=None):
+    """`python -m dan_amd.train_pb --data_dir D --model_dir M`: the reference's `python train_pb.py ...` (dan_amd/train_cli.py)."""
+    from .train_cli import main as run
+    return run(argv, model="pb")
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -110,8 +110,12 @@ class DetectorTrainer(object):
 
     def __init__(self, model, world=1, weight_decay=5e-4, negative_ratio=3.0, momentum=0.9, base_lr=1e-3, init_hw=(64, 64),
                  lr_boundaries=(1000, 80000, 100000), lr_factors=(0.1, 1.0, 0.1, 0.01), loss_scale=None, dynamic_loss_scale=None,
-                 loss_scale_growth_interval=1000, ops_ctx=None, deterministic=False):
+                 loss_scale_growth_interval=1000, ops_ctx=None, deterministic=False, metrics=False, end_lr=1e-6):
         self.model = model
+        self.end_lr = end_lr                                  # the floor of the schedule (flag end_learning_rate, train_sfd.py:100-102, :433)
+        # metrics=True: the reference's streaming cls_accuracy (tf.metrics.accuracy over the mined anchors of the term its predictions['classes']
+        # comes from) is counted on the device - one more launch per step on that term; {correct, total} since construction, read by metric_values()
+        self.metric_counts = torch.zeros(2, dtype=torch.int64, device=model.vs.device) if metrics else None
         self.deterministic = bool(deterministic)
         if self.deterministic:
             if not self.DETERMINISTIC or getattr(model, "deform", False):
@@ -236,7 +240,7 @@ class DetectorTrainer(object):
     def _eager_towers_in_context(self, towers, octx):
         self.flat.zero_grad()
         self.buckets.begin_step()
-        self._step_lr = lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors)
+        self._step_lr = lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors, self.end_lr)
         self._epoch_bumped = False
         if self.opt_overlap:
             self.flat.l2.zero_()                              # (every bucket's update adds its share of the L2 term)
@@ -299,7 +303,7 @@ class DetectorTrainer(object):
         self._capture()
 
     def _capture(self):
-        self._graph_lr = lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors)
+        self._graph_lr = lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors, self.end_lr)
         g = torch.cuda.CUDAGraph()
         step_no = self.step_no
         # The collectives are the library's own RCCL calls on the buckets' stream (trainer.RcclComm): recorded like kernels, no framework
@@ -312,7 +316,7 @@ class DetectorTrainer(object):
         self._graph, self._graph_terms = g, terms
 
     def _graph_step(self, images_u8, *targets):
-        if lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors) != self._graph_lr:
+        if lr_schedule(self.step_no, self.base_lr, self.lr_boundaries, self.lr_factors, self.end_lr) != self._graph_lr:
             self._capture()
         _tree_copy(self._static, (images_u8,) + tuple(targets))
         self._graph.replay()
@@ -362,6 +366,14 @@ class DetectorTrainer(object):
         out["total"] = total + out["l2"]
         return out
 
+    def metric_values(self):
+        """{'cls_accuracy': correct / total} over every step since construction (tf.metrics.accuracy's running value; 0.0 before the first
+        counted anchor, as tf's safe division).  One device read (synchronises).  Needs metrics=True."""
+        if self.metric_counts is None:
+            raise RuntimeError("metric_values: build the trainer with metrics=True")
+        correct, total = self.metric_counts.tolist()
+        return {"cls_accuracy": correct / total if total else 0.0}
+
 
 class SFDTrainer(DetectorTrainer):
     """sfd_model_fn (train_sfd.py:261-467) + Momentum optimizer."""
@@ -370,10 +382,21 @@ class SFDTrainer(DetectorTrainer):
 
     def loss_terms(self, images_u8, loc_targets, cls_targets):
         loc, cls = self.model.forward(images_u8)
-        acc = ops.detection_loss(cls, loc, cls_targets, loc_targets, ratio=self.negative_ratio, at_least_one=False, scale=self.loss_scale / self.num_towers)
+        acc = ops.detection_loss(cls, loc, cls_targets, loc_targets, ratio=self.negative_ratio, at_least_one=False, scale=self.loss_scale / self.num_towers,
+                                 metric_counts=self.metric_counts)                                       # cls_accuracy: train_sfd.py:386-390
         return [("face", 1.0, acc)]
 
     def losses(self):
         """(cross_entropy, loc_loss, l2_loss, total) as python floats (synchronises)."""
         v = self.loss_values()
         return v["face"][0], v["face"][1], v["l2"], v["total"]
+
+
+def main(argv=None):
+    """`python -m dan_amd.train_sfd --data_dir D --model_dir M`: the reference's `python train_sfd.py ...` (dan_amd/train_cli.py)."""
+    from .train_cli import main as run
+    return run(argv, model="sfd")
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -395,6 +395,16 @@ int danhip_detection_loss_fwd_ws(const float* cls, const float* loc, const int32
 int danhip_detection_loss_bwd(const float* cls, const float* loc, const float* loc_targets, const uint8_t* sel,
                               const float* acc4, float* dcls, float* dloc, float ce_scale, float loc_scale, int32_t B,
                               int32_t A, void* stream);
+/* Streaming classification accuracy, the reference's tf.metrics.accuracy over final_mask (train_sfd.py:383-395, train_dan.py:454-462):
+ * over the anchors with sel != 0 (as danhip_detection_loss_fwd wrote them), counts[0] += #(argmax(cls, -1) == clip(label, 0, 2)) and
+ * counts[1] += their number.  argmax takes the first index on equal logits (tf.argmax).  counts int64 [2] is ADDED to, never cleared: the
+ * metric is a running total over all steps; the caller zeroes it once.  Integer sums, so the result has the same bits in deterministic
+ * mode and out of it; no host read-back, no synchronisation.  B * A must not exceed 2^31 - 1 (32-bit indices): DANHIP_EINVAL.
+ * Launch shape: workgroups of DANHIP_CLS_ACCURACY_THREADS, at most DANHIP_CLS_ACCURACY_MAX_BLOCKS of them (beyond their product a
+ * workgroup loops). */
+#define DANHIP_CLS_ACCURACY_THREADS 256
+#define DANHIP_CLS_ACCURACY_MAX_BLOCKS 1024
+int danhip_cls_accuracy(const float* cls, const int32_t* labels, const uint8_t* sel, int64_t* counts, int32_t B, int32_t A, void* stream);
 /* Fused multi-tensor momentum SGD over flat fp32 buffers (train_sfd.py:419-447): for element i of segment s
  * (seg_starts[s] <= i < seg_starts[s+1]): g' = (g*grad_scale + wd_coef[s]*w) * gmult[s]; v = m*v + g'; w -= lr*v.
  * l2_out (optional) += sum 0.5*wd_coef[s]*w^2 (the L2 loss term at the pre-update weights).
