@@ -16,11 +16,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-// bit r = packed 16-bit ReLU output r > 0 (conv_common.h)
-__device__ __forceinline__ unsigned c8_pos_bits8(const u32x4& t) { return dh_pos_bits8_acc<0>(t, 0u); }
-
 struct C8Geom {
   int units_x;            // ceil(W / 16)
   long units;             // N * H * units_x
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256) void conv3x3_c8_kernel(const ConvArgs a, const
 #pragma unroll
     for (int m = 0; m < 4; ++m) acc[m] = DH_MFMA_16x16x32(wr[m][2], f2, acc[m]);
     unsigned pbyte[2] = {0u, 0u};
-    u32x4 o2[2];
+    dh_u32x4 o2[2];
 #pragma unroll
     for (int P = 0; P < 2; ++P) {                   // this lane: output channels [P*32 + q*8, +8) of pixel x0 + px
       f32x4 lo = acc[2 * P], hi = acc[2 * P + 1];
@@ -103,8 +98,8 @@ __global__ __launch_bounds__(256) void conv3x3_c8_kernel(const ConvArgs a, const
         lo[0] = dh_relu(lo[0]); lo[1] = dh_relu(lo[1]); lo[2] = dh_relu(lo[2]); lo[3] = dh_relu(lo[3]);
         hi[0] = dh_relu(hi[0]); hi[1] = dh_relu(hi[1]); hi[2] = dh_relu(hi[2]); hi[3] = dh_relu(hi[3]);
       }
-      o2[P] = u32x4{pack2bf(lo[0], lo[1]), pack2bf(lo[2], lo[3]), pack2bf(hi[0], hi[1]), pack2bf(hi[2], hi[3])};
-      pbyte[P] = c8_pos_bits8(o2[P]);
+      o2[P] = dh_u32x4{pack2bf(lo[0], lo[1]), pack2bf(lo[2], lo[3]), pack2bf(hi[0], hi[1]), pack2bf(hi[2], hi[3])};
+      pbyte[P] = dh_pos_bits8_acc<0>(o2[P], 0u);
     }
     // WHOLE 128-byte lines per store instruction (round 5): a lane's two pieces are the [0, 64) and [64, 128) halves of its pixel's line, so
     // storing piece P from every lane wrote 16 half lines per instruction and the layer's 839 MB went out as 1062 MB of write traffic
@@ -113,22 +108,22 @@ __global__ __launch_bounds__(256) void conv3x3_c8_kernel(const ConvArgs a, const
     // half from the odd one), instruction 2 the odd pixels'.
     {
       const bool odd = px & 1;
-      u32x4 give, got;
+      dh_u32x4 give, got;
 #pragma unroll
       for (int e = 0; e < 4; ++e) give[e] = odd ? o2[0][e] : o2[1][e];
 #pragma unroll
       for (int e = 0; e < 4; ++e) got[e] = dh_lane_xor1(give[e]);
       // even lane: own low half (pixel px) + the odd neighbour's low half (pixel px + 1); odd lane: the even neighbour's high half (px - 1) + own high half
-      const u32x4 first = odd ? got : o2[0], second = odd ? o2[1] : got;
+      const dh_u32x4 first = odd ? got : o2[0], second = odd ? o2[1] : got;
       const int pe = px & ~1;                       // the even pixel of the pair
       bf16_t* line = reinterpret_cast<bf16_t*>(a.y) + ((size_t)(unsigned)(t.base + pe)) * 64 + (odd ? 32 : 0) + q * 8;
       if (t.x0 + pe < a.W) {
-        if (NT) __builtin_nontemporal_store(first, reinterpret_cast<u32x4*>(line));
-        else *reinterpret_cast<u32x4*>(line) = first;
+        if (NT) __builtin_nontemporal_store(first, reinterpret_cast<dh_u32x4*>(line));
+        else *reinterpret_cast<dh_u32x4*>(line) = first;
       }
       if (t.x0 + pe + 1 < a.W) {
-        if (NT) __builtin_nontemporal_store(second, reinterpret_cast<u32x4*>(line + 64));
-        else *reinterpret_cast<u32x4*>(line + 64) = second;
+        if (NT) __builtin_nontemporal_store(second, reinterpret_cast<dh_u32x4*>(line + 64));
+        else *reinterpret_cast<dh_u32x4*>(line + 64) = second;
       }
     }
     // ReLU bit mask of the output for the next layer's data gradient (danhip_relu_bits layout: 8 bytes per pixel): this lane's two bytes

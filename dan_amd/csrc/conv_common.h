@@ -1,6 +1,6 @@
 // Shared between the convolution kernels: their argument block, the epilogue helpers and the kernel selection (ConvInstance below).
 #pragma once
-#include "common.h"
+#include "lds_dma.h"
 
 struct ConvArgs {
   const bf16_t* x;
@@ -101,7 +101,6 @@ __device__ __forceinline__ float dh_relu(float v) {
 // (clang lowers the generic vector min to compares and selects, hence the asm).
 typedef __attribute__((ext_vector_type(2))) unsigned short dh_u16x2;
 typedef __attribute__((ext_vector_type(2))) unsigned dh_u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned dh_u32x4;
 __device__ __forceinline__ dh_u16x2 dh_pos2(unsigned packed) {
   unsigned r;
   asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(packed), "s"(0x00010001u));

@@ -62,11 +62,6 @@ struct HaloGeom {
 #define H_STEP_DONE() do { } while (0)
 #endif
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Epilogue of one lane's 4 consecutive channels (Co % 64 == 0: always a full, aligned quad).
 //   forward : v = acc + bias; relu?; (+ residual, bf16) -> bf16 or fp32
 //   dgrad   : v = acc; * (mask > 0)?; (+= old)?          -> bf16
@@ -109,9 +104,8 @@ __device__ __forceinline__ void halo_finish4(const ConvArgs& a, const f32x4& acc
 
 // 8 consecutive channels of one pixel (two interleaved channel tiles): 16-byte mask / residual / old-value reads, one
 // 16-byte store (fp32 output: two float4 stores).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 template <bool DGRAD>
-__device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo, const f32x4& hi, const float (&b)[8], const uint4& in0,
+__device__ __forceinline__ dh_u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo, const f32x4& hi, const float (&b)[8], const uint4& in0,
                                               const uint4& in1, size_t o) {
   float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   if (!DGRAD) {
@@ -126,7 +120,7 @@ __device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo
       float* y = reinterpret_cast<float*>(a.y) + o;
       *reinterpret_cast<float4*>(y) = make_float4(v[0], v[1], v[2], v[3]);
       *reinterpret_cast<float4*>(y + 4) = make_float4(v[4], v[5], v[6], v[7]);
-      return u32x4{0u, 0u, 0u, 0u};
+      return dh_u32x4{0u, 0u, 0u, 0u};
     }
     if (a.split_out) {                  // limb layout of the next convolution (split_infer.hip): o = pixel * 3 Co + co, set by the caller
       dh_range_check<8>(v, a.range_flag);
@@ -134,10 +128,10 @@ __device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo
       dh_split4(v, h0, l0);
       dh_split4(v + 4, h1, l1);
       bf16_t* y = reinterpret_cast<bf16_t*>(a.y) + o;
-      const u32x4 hi = {h0.x, h0.y, h1.x, h1.y}, lo = {l0.x, l0.y, l1.x, l1.y};
-      *reinterpret_cast<u32x4*>(y) = hi;
-      *reinterpret_cast<u32x4*>(y + a.Co) = lo;
-      *reinterpret_cast<u32x4*>(y + 2 * a.Co) = hi;
+      const dh_u32x4 hi = {h0.x, h0.y, h1.x, h1.y}, lo = {l0.x, l0.y, l1.x, l1.y};
+      *reinterpret_cast<dh_u32x4*>(y) = hi;
+      *reinterpret_cast<dh_u32x4*>(y + a.Co) = lo;
+      *reinterpret_cast<dh_u32x4*>(y + 2 * a.Co) = hi;
       return hi;
     }
     if (a.resid) {
@@ -157,22 +151,14 @@ __device__ __forceinline__ u32x4 halo_finish8(const ConvArgs& a, const f32x4& lo
       for (int r = 0; r < 8; ++r) v[r] += bf2f(op[r]);
     }
   }
-  const u32x4 t = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
-  *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(a.y) + o) = t;      // (non-temporal stores measured neutral here)
+  const dh_u32x4 t = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+  *reinterpret_cast<dh_u32x4*>(reinterpret_cast<bf16_t*>(a.y) + o) = t;      // (non-temporal stores measured neutral here)
   return t;
 }
 
-// ReLU bit mask of 8 packed 16-bit ReLU OUTPUTS (bit r = value r > 0; conv_common.h: dh_pos_bits8_acc)
-__device__ __forceinline__ unsigned pos_bits8(const u32x4& t) { return dh_pos_bits8_acc<0>(t, 0u); }
 // OR over the four lanes that share frow (the wave's 64 channels of one pixel): lane fq contributes bytes fq (pair 0) and 4 + fq (pair 1)
 __device__ __forceinline__ uint2 gather_bits64(unsigned b0, unsigned b1, int fq) {
   return uint2{dh_or_rows(b0 << (8 * fq)), dh_or_rows(b1 << (8 * fq))};
-}
-
-// 16-byte LDS-DMA through a buffer descriptor: address = base + voff (per lane) + soff (uniform); a lane whose voff is out
-// of range (0xFFFFFFFF) writes ZEROS to its LDS slot.
-__device__ __forceinline__ void bufdma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, void* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (LDS_AS void*)lds_wave_base, 16, voff, soff, 0, 0);
 }
 
 // TPS: taps per step (1 or 3); NSW: weight ring depth (prefetch distance D = NSW-1 steps);
@@ -277,7 +263,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       if (piece > PPIECES - 1) piece = PPIECES - 1;
       unsigned voff = psrc[k];
       if (ragged_chunk && ((lane & 7) ^ (pgeo[k] & 7)) >= g.crem) voff = 0xFFFFFFFFu;
-      bufdma16(rsrc_x, voff, (unsigned)(p_cc * 128), dst + piece * 1024);
+      bufdma16_lds(rsrc_x, voff, (unsigned)(p_cc * 128), dst + piece * 1024);
     }
     ++p_idx;
     if (++p_cc == g.cch) {
@@ -300,7 +286,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (piece > PPIECES - 1) piece = PPIECES - 1;
     unsigned voff = psrc[K];
     if (ragged_chunk && ((lane & 7) ^ (pgeo[K] & 7)) >= g.crem) voff = 0xFFFFFFFFu;
-    bufdma16(rsrc_x, voff, (unsigned)(p_cc * 128), dst + piece * 1024);
+    bufdma16_lds(rsrc_x, voff, (unsigned)(p_cc * 128), dst + piece * 1024);
     if (K == PL - 1) {
       ++p_idx;
       if (++p_cc == g.cch) {
@@ -338,7 +324,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     char* dst = smem + WRING + (w_idx % NSW) * WBYTES;
     const unsigned soff = (unsigned)((w_nb * BN) * a.Kpad + (w_step * TPS) * a.C + w_cc * 64) * 2u;   // uniform
 #pragma unroll
-    for (int k = 0; k < WL; ++k) bufdma16(rsrc_w, wlane[k], soff, dst + (wave * WL + k) * 1024);
+    for (int k = 0; k < WL; ++k) bufdma16_lds(rsrc_w, wlane[k], soff, dst + (wave * WL + k) * 1024);
     ++w_idx;
     if (++w_step == SPC) {
       w_step = 0;
@@ -365,7 +351,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int t = wave * 64 + lane;                                     // (waves 0-3 only)
     const int y = y0 + t / TW, x = x0 + t % TW;
     const unsigned off = (y < a.H && x < a.W) ? (unsigned)((n * a.H + y) * a.W + x) * (unsigned)(a.Co / 8) + (unsigned)(nb * (BN / 8)) : 0xFFFFFFFFu;
-    bufdma16(rsrc_b, off, 0u, smem + SBIAS + wave * 1024);
+    bufdma16_lds(rsrc_b, off, 0u, smem + SBIAS + wave * 1024);
   };
 
   // ---- compute-side per-lane constants --------------------------------------------------------------------------
@@ -455,7 +441,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (int i = tid; i < a.Co; i += 512) sb[i] = a.bias ? a.bias[i] : 0.f;
     __builtin_amdgcn_s_waitcnt(0xC07F);
   }
-  wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   auto epilogue = [&]() __attribute__((always_inline)) {
@@ -511,7 +497,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
         for (int r = 0; r < 8; ++r) bv[q][r] = (!DGRAD && cok[q]) ? reinterpret_cast<const float*>(smem + SBIAS)[cb + q * 32 + r] : 0.f;
       }
-      [[maybe_unused]] u32x4 pk[POOL ? NPAIR : 1][POOL ? NPT : 1];      // POOL: packed outputs (zero where the pixel is outside)
+      [[maybe_unused]] dh_u32x4 pk[POOL ? NPAIR : 1][POOL ? NPT : 1];      // POOL: packed outputs (zero where the pixel is outside)
       if constexpr (BITS_OK) {
         if (a.mask_bits) {                           // the staged bit mask: 8 bytes = this wave's 64 channels of one pixel
           // The staging area was filled by LDS-DMA in step 1 of this item (retired by the counted waits many steps ago: tests/
@@ -577,7 +563,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // residual take the general epilogue: with a second array live, or this one in the forward instances, the allocator spilled
         // 60-75 registers.)
         const bf16_t* extra = (DGRAD && a.accumulate) ? reinterpret_cast<const bf16_t*>(a.y) : nullptr;      // (uniform)
-        [[maybe_unused]] u32x4 inx[NPT][NPAIR];
+        [[maybe_unused]] dh_u32x4 inx[NPT][NPAIR];
         if (extra) {
           const __amdgpu_buffer_rsrc_t rsrc_e =
               __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(extra), 0, (int)((unsigned)(a.N * a.H * a.W) * (unsigned)a.Co * 2u), 0x00020000);
@@ -592,7 +578,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         for (int p = 0; p < NPT; ++p) {
           const unsigned yo = okp[p] ? (pix[p] * (unsigned)a.Co + (unsigned)cb) * 2u : OOB;
           [[maybe_unused]] unsigned pb[2] = {0u, 0u};
-          [[maybe_unused]] u32x4 ttq[2];
+          [[maybe_unused]] dh_u32x4 ttq[2];
 #pragma unroll
           for (int q = 0; q < NPAIR; ++q) {
             float v[8] = {acc[2 * q][p][0], acc[2 * q][p][1], acc[2 * q][p][2], acc[2 * q][p][3],
@@ -612,7 +598,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
               for (int r = 0; r < 8; ++r) v[r] += bf2f(xp[r]);
             }
-            u32x4 tt = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+            dh_u32x4 tt = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
 #ifdef H_ABLATE_STORE_PATTERN
             // timing-only build (WRONG layout): the same bytes per item, but every store instruction covers ONE contiguous KiB
             // (lane * 16 bytes inside the item's own 64 KiB of the output) instead of 16 half cache lines 512 bytes apart
@@ -622,11 +608,11 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             else __builtin_amdgcn_raw_buffer_store_b128(tt, rsrc_y, (int)((cok[q] ? yo : OOB) + q * 64), 0, 0);
 #endif
             if constexpr (POOL) {
-              if (!(okp[p] && cok[q])) tt = u32x4{0u, 0u, 0u, 0u};
+              if (!(okp[p] && cok[q])) tt = dh_u32x4{0u, 0u, 0u, 0u};
               pk[q][p] = tt;
             }
             if constexpr (EMIT_OK) {
-              if (a.bits_out) pb[q & 1] = pos_bits8(tt);
+              if (a.bits_out) pb[q & 1] = dh_pos_bits8_acc<0>(tt, 0u);
             }
           }
 #ifndef H_ABLATE_STORE_PATTERN
@@ -637,13 +623,13 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             // one with both high halves; instruction 1 writes the even pixels' lines whole, instruction 2 the odd pixels'.  Same number of
             // store instructions; a pixel outside the map or channels beyond Cout stay out-of-range offsets.
             const bool odd = frow & 1;
-            u32x4 give, got;
+            dh_u32x4 give, got;
 #pragma unroll
             for (int e = 0; e < 4; ++e) give[e] = odd ? ttq[0][e] : ttq[1][e];
 #pragma unroll
             for (int e = 0; e < 4; ++e) got[e] = dh_lane_xor1(give[e]);
             const unsigned yo_n = dh_lane_xor1(yo);              // the neighbour's pixel (OOB when it is outside the map)
-            const u32x4 first = odd ? got : ttq[0], second = odd ? ttq[1] : got;
+            const dh_u32x4 first = odd ? got : ttq[0], second = odd ? ttq[1] : got;
             const unsigned off1 = odd ? (cok[1] ? yo_n : OOB) + 64u : (cok[0] ? yo : OOB);
             const unsigned off2 = odd ? (cok[1] ? yo : OOB) + 64u : (cok[0] ? yo_n : OOB);
             __builtin_amdgcn_raw_buffer_store_b128(first, rsrc_y, (int)off1, 0, 0);
@@ -679,7 +665,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             [[maybe_unused]] unsigned pb2[2] = {0u, 0u};
 #pragma unroll
             for (int q = 0; q < NPAIR; ++q) {
-              u32x4 m;
+              dh_u32x4 m;
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 const unsigned v = pkmax_relu(pk[q][p][e], pk[q][p + PV][e]);
@@ -687,10 +673,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
               }
               __builtin_amdgcn_raw_buffer_store_b128(m, rsrc_p, (int)((cok[q] ? po : OOB) + q * 64), 0, 0);
               if constexpr (EMIT_OK) {
-                if (a.pool_bits_out) pb2[q & 1] = pos_bits8(m);
+                if (a.pool_bits_out) pb2[q & 1] = dh_pos_bits8_acc<0>(m, 0u);
               }
               if (a.pool_arg_out) {                  // (uniform) arg-max codes of the window for danhip_maxpool2x2_bwd_arg: 2 bytes per lane and channel pair
-                u32x4 tr;
+                dh_u32x4 tr;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) tr[e] = dh_lane_xor1(pk[q][p][e]);
                 const unsigned codes = dh_argmax2x2_codes16(pk[q][p], tr, pk[q][p + PV], m);
@@ -756,10 +742,10 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         [[maybe_unused]] unsigned pb[2] = {0u, 0u};
 #pragma unroll
         for (int q = 0; q < NPAIR; ++q) {
-          u32x4 r = {0u, 0u, 0u, 0u};
+          dh_u32x4 r = {0u, 0u, 0u, 0u};
           if (ok && cok[q]) r = halo_finish8<DGRAD>(a, acc[2 * q][p], acc[2 * q + 1][p], bv[q], in0[q], in1[q], o0 + q * 32);
           if constexpr (POOL) pk[q][p] = r;
-          if constexpr (EMIT_OK) pb[q & 1] = pos_bits8(r);
+          if constexpr (EMIT_OK) pb[q & 1] = dh_pos_bits8_acc<0>(r, 0u);
           acc[2 * q][p] = f32x4{0.f, 0.f, 0.f, 0.f};
           acc[2 * q + 1][p] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -790,16 +776,16 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           [[maybe_unused]] unsigned pb2[2] = {0u, 0u};
 #pragma unroll
           for (int q = 0; q < NPAIR; ++q) {
-            u32x4 m;
+            dh_u32x4 m;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const unsigned v = pkmax_relu(pk[q][p][e], pk[q][p + PV][e]);
               m[e] = pkmax_relu(v, dh_lane_xor1(v));
             }
-            if (okp) *reinterpret_cast<u32x4*>(a.pool_y + op + q * 32) = m;
-            if constexpr (EMIT_OK) pb2[q & 1] = pos_bits8(m);
+            if (okp) *reinterpret_cast<dh_u32x4*>(a.pool_y + op + q * 32) = m;
+            if constexpr (EMIT_OK) pb2[q & 1] = dh_pos_bits8_acc<0>(m, 0u);
             if (a.pool_arg_out) {
-              u32x4 tr;
+              dh_u32x4 tr;
 #pragma unroll
               for (int e = 0; e < 4; ++e) tr[e] = dh_lane_xor1(pk[q][p][e]);
               const unsigned codes = dh_argmax2x2_codes16(pk[q][p], tr, pk[q][p + PV], m);
@@ -890,13 +876,13 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         if constexpr (BITS_OK) {
           if (STEP == 1 && cc == 0 && a.mask_bits) issue_bits(c_sp, c_nb);
         }
-        if (!more_w) wait_vmcnt<0>();              // tail of this block's work
+        if (!more_w) dh_wait_vmcnt<0>();              // tail of this block's work
         else if constexpr (SPC == 9) {
-          if (p_live) wait_vmcnt<(D - 1) * WL + np_a(STEP)>();
-          else wait_vmcnt<(D - 1) * WL>();
+          if (p_live) dh_wait_vmcnt<(D - 1) * WL + np_a(STEP)>();
+          else dh_wait_vmcnt<(D - 1) * WL>();
         } else {
-          if (patch_age <= D - 1) wait_vmcnt<(D - 1) * WL + PL>();
-          else wait_vmcnt<(D - 1) * WL>();
+          if (patch_age <= D - 1) dh_wait_vmcnt<(D - 1) * WL + PL>();
+          else dh_wait_vmcnt<(D - 1) * WL>();
         }
         ++patch_age;
         __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0): fragments are in registers before the MFMA phase starts
@@ -946,13 +932,13 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         mma(offW + stage_of(STEP) * WBYTES, pofs, stepc);
         __builtin_amdgcn_sched_barrier(0);
         H_STAMP(1);
-        if (!w_prev) wait_vmcnt<0>();
+        if (!w_prev) dh_wait_vmcnt<0>();
         else if constexpr (SPC == 9) {
-          if (p_live) wait_vmcnt<(D - 2) * WL + np_b(STEP)>();
-          else wait_vmcnt<(D - 2) * WL>();
+          if (p_live) dh_wait_vmcnt<(D - 2) * WL + np_b(STEP)>();
+          else dh_wait_vmcnt<(D - 2) * WL>();
         } else {
-          if (patch_age <= D - 2) wait_vmcnt<(D - 2) * WL + PL>();
-          else wait_vmcnt<(D - 2) * WL>();
+          if (patch_age <= D - 2) dh_wait_vmcnt<(D - 2) * WL + PL>();
+          else dh_wait_vmcnt<(D - 2) * WL>();
         }
         __builtin_amdgcn_s_barrier();              // b1
         H_STAMP(2);
@@ -1008,7 +994,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
   }
 #ifdef H_TRACE
-  wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
   __syncthreads();
   if (blockIdx.x == 0)
     for (int i = tid; i < 1024; i += 512) g.trace[i] = reinterpret_cast<const unsigned*>(smem + SBIAS + 4096)[i];

@@ -19,11 +19,6 @@ struct C64Geom {
   FastDiv div_tx, div_txy;
 };
 
-template <int N>
-__device__ __forceinline__ void c64_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // FUSE8 (round 6, data gradient only): the call is conv1_2's data gradient and its output dX is conv1_1's dY, which nothing reads but conv1_1's
 // WEIGHT gradient (the first layer has no data gradient).  Instead of storing dX (839 MB per batch-16 step at 640 x 640) for conv_wgrad_c8.hip to
 // read back (188 us, the LAST kernel of backward, with the other queue empty), every tile's masked dX goes to LDS in 16 bits — the values the store
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (tid < 64) reinterpret_cast<float*>(smem + RWBASE)[tid] = a.bias ? a.bias[tid] : 0.f;
     __builtin_amdgcn_s_waitcnt(0xC07F);
   }
-  c64_wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   int buf = 0;
   for (;;) {
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     C64_H(12, xa); C64_H(13, xb); C64_H(14, xc); C64_H(15, xa); C64_H(16, xb); C64_H(17, xc);
 #undef C64_H
     // ---- hand-off: the next patch has landed (own pieces) and everybody is done reading this one
-    c64_wait_vmcnt<0>();
+    dh_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     // ---- epilogue (its stores drain under the next tile's MFMAs)
     {
@@ -258,10 +253,9 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       float bv[8];
 #pragma unroll
       for (int r = 0; r < 8; ++r) bv[r] = DGRAD ? 0.f : reinterpret_cast<const float*>(smem + RWBASE)[cbase + r];
-      typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-      u32x4 pk[NPT];                                         // packed outputs of this lane (zero outside the image), for the fused pool
+      dh_u32x4 pk[NPT];                                         // packed outputs of this lane (zero outside the image), for the fused pool
 #pragma unroll
-      for (int p = 0; p < NPT; ++p) pk[p] = u32x4{0u, 0u, 0u, 0u};
+      for (int p = 0; p < NPT; ++p) pk[p] = dh_u32x4{0u, 0u, 0u, 0u};
       // Data gradient: the staged mask, then the staged old value, are folded into the accumulators for ALL fragments before the first
       // store — the compiler orders an LDS read behind everything vmcnt counts (it cannot tell a DMA from a store), so a read issued
       // after a store would wait out a full write latency.  Two passes keep the live set at one 16-byte vector per fragment.
@@ -328,16 +322,16 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           } else {
             // (mask and old value were folded into acc above)
           }
-          const u32x4 tt = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+          const dh_u32x4 tt = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
           if (a.y)            // (uniform; NULL = the pool-only inference call / the folded first-layer gradient: the map is never written)
-            __builtin_nontemporal_store(tt, reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(a.y) + o0));   // streamed: re-read only after it left the L2
+            __builtin_nontemporal_store(tt, reinterpret_cast<dh_u32x4*>(reinterpret_cast<bf16_t*>(a.y) + o0));   // streamed: re-read only after it left the L2
           pk[p] = tt;
         }
         if constexpr (FUSE8) {                       // the tile of dX the store would have written (zeros outside the image), [pixel][64 channels];
           // 16-byte chunk c of pixel t sits at position c ^ ((t & 7) ^ ((t >> 3) & 1) << 2): with the plain layout every pixel starts on bank 0
           // (128-byte pitch) - the eight lanes of a ds_write_b128 group conflicted 8 ways and the transposing reads 4 ways; swizzled, neither does
           const int fz = (t & 7) ^ (((t >> 3) & 1) << 2);
-          *reinterpret_cast<u32x4*>(smem + DXBASE + t * 128 + (((cbase >> 3) ^ fz) << 4)) = pk[p];
+          *reinterpret_cast<dh_u32x4*>(smem + DXBASE + t * 128 + (((cbase >> 3) ^ fz) << 4)) = pk[p];
         }
 #pragma unroll
         for (int c = 0; c < NCT; ++c) acc[c][p] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -397,16 +391,16 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         for (int p = 0; p < 2; ++p) {
           const int t = wm * 64 + p * 16 + frow;
           const int y = y0 + t / TW, x = x0 + t % TW;
-          u32x4 m;
+          dh_u32x4 m;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned v = pkmax_relu(pk[p][e], pk[p + 2][e]);
             m[e] = pkmax_relu(v, dh_lane_xor1(v));
           }
           if (y < a.H && x < a.W && (frow & 1) == 0)
-            *reinterpret_cast<u32x4*>(a.pool_y + ((size_t)((n * Hp + (y >> 1)) * Wp + (x >> 1))) * 64 + cbase) = m;
+            *reinterpret_cast<dh_u32x4*>(a.pool_y + ((size_t)((n * Hp + (y >> 1)) * Wp + (x >> 1))) * 64 + cbase) = m;
           if (a.pool_arg_out) {                      // (uniform) 2-bit arg-max codes of the window for the pool's backward: 2 bytes per lane
-            u32x4 tr;
+            dh_u32x4 tr;
 #pragma unroll
             for (int e = 0; e < 4; ++e) tr[e] = dh_lane_xor1(pk[p][e]);
             const unsigned codes = dh_argmax2x2_codes16(pk[p], tr, pk[p + 2], m);

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
 
   stage(kt_lo, kt_lo & 1);
   for (int kt = kt_lo; kt < kt_hi; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dh_wait_vmcnt<0>();
     __syncthreads();                                    // tile kt landed; everyone is done reading the other stage
     if (kt + 1 < kt_hi) stage(kt + 1, (kt + 1) & 1);
     const char* sA = smem + (kt & 1) * STAGE;

@@ -30,39 +30,24 @@ struct PwGeom {
   FastDiv div_nb;
 };
 
-typedef __attribute__((ext_vector_type(4))) unsigned pw_u32x4;
-
-template <int N>
-__device__ __forceinline__ void pw_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void pw_dma16(pw_u32x4 rsrc, unsigned voff, unsigned lds_addr) {      // voff out of range: zeros land in LDS
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ pw_u32x4 pw_make_rsrc(const void* p, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)p;
-  return pw_u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
-}
-__device__ __forceinline__ pw_u32x4 pw_load16(const void* p) {        // asm load: counted by hand (pw_wait_vmcnt + pw_land)
-  pw_u32x4 v;
+__device__ __forceinline__ dh_u32x4 pw_load16(const void* p) {        // asm load: counted by hand (dh_wait_vmcnt + pw_land)
+  dh_u32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
-__device__ __forceinline__ void pw_land(pw_u32x4& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void pw_land(dh_u32x4& v) { asm volatile("" : "+v"(v)); }
 
 // Dynamic wait: at most `n` vector-memory operations of this wave may stay outstanding (n wave-uniform, clamped to the hardware's 63)
 __device__ __forceinline__ void pw_wait_vmcnt_dyn(int n) {
-  if (n <= 0) pw_wait_vmcnt<0>();
-  else if (n <= 2) pw_wait_vmcnt<2>();
-  else if (n <= 4) pw_wait_vmcnt<4>();
-  else if (n <= 6) pw_wait_vmcnt<6>();
-  else if (n <= 8) pw_wait_vmcnt<8>();
-  else if (n <= 12) pw_wait_vmcnt<12>();
-  else if (n <= 16) pw_wait_vmcnt<16>();
-  else if (n <= 24) pw_wait_vmcnt<24>();
-  else pw_wait_vmcnt<32>();
+  if (n <= 0) dh_wait_vmcnt<0>();
+  else if (n <= 2) dh_wait_vmcnt<2>();
+  else if (n <= 4) dh_wait_vmcnt<4>();
+  else if (n <= 6) dh_wait_vmcnt<6>();
+  else if (n <= 8) dh_wait_vmcnt<8>();
+  else if (n <= 12) dh_wait_vmcnt<12>();
+  else if (n <= 16) dh_wait_vmcnt<16>();
+  else if (n <= 24) dh_wait_vmcnt<24>();
+  else dh_wait_vmcnt<32>();
 }
 // ... rounded DOWN to the nearest encodable step (waiting for more than necessary is always safe)
 __device__ __forceinline__ int pw_floor_count(int n) {
@@ -121,10 +106,10 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
   auto wkey = [](int r) __attribute__((always_inline)) -> int { return (r & 3) | (((r >> 3) & 1) << 2); };
   // (pitched view: the last pixel's row ends C elements after its start, whatever the pitch)
   const unsigned c_first = TWO ? (unsigned)a.ksplit * 64u : (unsigned)a.C;         // channels the first source carries
-  const pw_u32x4 rsrc_x = pw_make_rsrc(a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + c_first) * 2u);      // rows >= M are out of range: zero fill
-  [[maybe_unused]] const pw_u32x4 rsrc_x2 =
-      pw_make_rsrc(TWO ? a.x2 : a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + ((unsigned)a.C - c_first)) * 2u);
-  const pw_u32x4 rsrc_w = pw_make_rsrc(a.w, (unsigned)(g.NB * BN) * (unsigned)a.Kpad * 2u);
+  const dh_u32x4 rsrc_x = dh_make_rsrc(a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + c_first) * 2u);      // rows >= M are out of range: zero fill
+  [[maybe_unused]] const dh_u32x4 rsrc_x2 =
+      dh_make_rsrc(TWO ? a.x2 : a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + ((unsigned)a.C - c_first)) * 2u);
+  const dh_u32x4 rsrc_w = dh_make_rsrc(a.w, (unsigned)(g.NB * BN) * (unsigned)a.Kpad * 2u);
   unsigned avoff[APW], wvoff[WPW];
 #pragma unroll
   for (int k = 0; k < APW; ++k) {
@@ -178,20 +163,20 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
 #pragma unroll
       for (int k = 0; k < APW; ++k) {
         const unsigned voff = ((tmask[k] >> d_tap) & 1u) ? pbase[k] + toff : 0xFFFFFFFFu;
-        pw_dma16(rsrc_x, voff | inv, base + (wave * APW + k) * 1024);
+        dh_dma16(rsrc_x, voff | inv, base + (wave * APW + k) * 1024);
       }
     } else {
       unsigned kk = (unsigned)d_k;
-      pw_u32x4 rs = rsrc_x;
+      dh_u32x4 rs = rsrc_x;
       if constexpr (TWO) {
         if (d_k >= a.ksplit) { kk = (unsigned)(d_k - a.ksplit); rs = rsrc_x2; }      // wave-uniform: four s_cselect
       }
       const unsigned sa = (unsigned)(d_mt * BM) * (unsigned)(a.ldx * 2) + kk * 128u;
 #pragma unroll
-      for (int k = 0; k < APW; ++k) pw_dma16(rs, (avoff[k] + sa) | inv, base + (wave * APW + k) * 1024);
+      for (int k = 0; k < APW; ++k) dh_dma16(rs, (avoff[k] + sa) | inv, base + (wave * APW + k) * 1024);
     }
 #pragma unroll
-    for (int k = 0; k < WPW; ++k) pw_dma16(rsrc_w, (wvoff[k] + sw) | inv, base + ABYTES + (wave * WPW + k) * 1024);
+    for (int k = 0; k < WPW; ++k) dh_dma16(rsrc_w, (wvoff[k] + sw) | inv, base + ABYTES + (wave * WPW + k) * 1024);
     ++d_idx;
     if constexpr (TAPS) {
       if (++d_cc == a.cpt) { d_cc = 0; ++d_tap; if (++d_tj == a.kw) { d_tj = 0; ++d_ti; } }
@@ -245,7 +230,7 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
     const int pend = st_age <= NST - 2 - (LATE ? 1 : 0) ? st_cnt : 0;
     pw_wait_vmcnt_dyn(pw_floor_count((NST - 2) * DPW + pend));
     __builtin_amdgcn_s_barrier();                      // ... for every wave; and every wave is done reading slot (c_idx - 1) % NST
-    [[maybe_unused]] pw_u32x4 ld_m[NPT][NPAIR], ld_o[NPT][NPAIR], ld_b[NPAIR][2];
+    [[maybe_unused]] dh_u32x4 ld_m[NPT][NPAIR], ld_o[NPT][NPAIR], ld_b[NPAIR][2];
     const int cb = c_nb * BN + wn * 64 + fq * 8;       // this lane's 8 consecutive channels of pair 0 (+32 per pair)
     if constexpr (LAST && LD) {
       if constexpr (DGRAD) {
@@ -325,7 +310,7 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
 #pragma unroll
       for (int p = 0; p < NPT; ++p) {
         const long m = (long)c_mt * BM + wm * TP + p * 16 + frow;
-        [[maybe_unused]] pw_u32x4 tq[2];
+        [[maybe_unused]] dh_u32x4 tq[2];
 #pragma unroll
         for (int q = 0; q < NPAIR; ++q) {
           float v[8];
@@ -358,11 +343,11 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
               }
             }
           }
-          const pw_u32x4 t = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+          const dh_u32x4 t = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
           if constexpr (NPAIR == 2) {
             tq[q] = t;
           } else {
-            if (m < a.M) *reinterpret_cast<pw_u32x4*>(reinterpret_cast<bf16_t*>(a.y) + (size_t)m * a.ldy + cb + q * 32) = t;
+            if (m < a.M) *reinterpret_cast<dh_u32x4*>(reinterpret_cast<bf16_t*>(a.y) + (size_t)m * a.ldy + cb + q * 32) = t;
           }
           ++ns;
           acc[2 * q][p] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -375,16 +360,16 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
           // trade pieces: the even pixel's lane ends up with both low halves, the odd one with both high halves; instruction 1 writes the
           // even pixels' lines whole, instruction 2 the odd pixels'.  Same number of store instructions (the counted waits rely on it).
           const bool odd = frow & 1;
-          pw_u32x4 give, got;
+          dh_u32x4 give, got;
 #pragma unroll
           for (int e = 0; e < 4; ++e) give[e] = odd ? tq[0][e] : tq[1][e];
 #pragma unroll
           for (int e = 0; e < 4; ++e) got[e] = dh_lane_xor1(give[e]);
-          const pw_u32x4 first = odd ? got : tq[0], second = odd ? tq[1] : got;
+          const dh_u32x4 first = odd ? got : tq[0], second = odd ? tq[1] : got;
           const long me = m & ~1l;
           bf16_t* line = reinterpret_cast<bf16_t*>(a.y) + (size_t)me * a.ldy + cb + (odd ? 32 : 0);
-          if (me < a.M) *reinterpret_cast<pw_u32x4*>(line) = first;
-          if (me + 1 < a.M) *reinterpret_cast<pw_u32x4*>(line + a.ldy) = second;
+          if (me < a.M) *reinterpret_cast<dh_u32x4*>(line) = first;
+          if (me + 1 < a.M) *reinterpret_cast<dh_u32x4*>(line + a.ldy) = second;
         }
       }
       st_age = 0;
@@ -407,7 +392,7 @@ __device__ __forceinline__ void pw_body(const ConvArgs a, const PwGeom g) {
       if (!decode(c_v, c_mt, c_nb)) break;
     }
   }
-  pw_wait_vmcnt<0>();                                  // zero-fill pieces of the steps beyond the stream may still be landing
+  dh_wait_vmcnt<0>();                                  // zero-fill pieces of the steps beyond the stream may still be landing
 }
 
 template <int BN, int NST, bool DGRAD, bool LD, bool TAPS>

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
   stage(kt_begin, 0);
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int buf = (kt - kt_begin) & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dh_wait_vmcnt<0>();
     __syncthreads();
     if (kt + 1 < kt_end) stage(kt + 1, buf ^ 1);
     const char* sX = smem + buf * STAGE;

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_c8_kernel(const WgC8Args a)
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  dh_wait_vmcnt<0>();
   __syncthreads();
   int buf = 0;
   for (;;) {
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_c8_kernel(const WgC8Args a)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = DH_MFMA_16x16x32(xf[mt], yf[nt], acc[mt][nt]);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the next tile has landed (own pieces) ...
+    dh_wait_vmcnt<0>();          // the next tile has landed (own pieces) ...
     __syncthreads();                                           // ... and everybody is done reading this one
     if (!has_next) break;
     it = nxt;

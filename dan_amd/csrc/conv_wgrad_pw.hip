@@ -17,7 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wgrad_split.h"
 
 namespace {
 
@@ -37,23 +37,6 @@ struct WgPwArgs {
   FastDiv div_ci, div_pairs;
 };
 
-typedef __attribute__((ext_vector_type(4))) unsigned wp_u32x4;
-template <int N>
-__device__ __forceinline__ void wp_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wp_dma16(wp_u32x4 rsrc, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ wp_u32x4 wp_make_rsrc(const void* p, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)p;
-  return wp_u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
-}
-__device__ __forceinline__ int wp_f128(int pc) { return ((pc >> 1) & 1) | (((pc >> 3) & 1) << 1); }
-__device__ __forceinline__ int wp_f256(int px) { return (px & 3) | (((px >> 3) & 1) << 2); }
-
 __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wgrad_pw_kernel(const WgPwArgs a) {
   constexpr int XSUB = 32 * 128;                      // one [32 px][64 ci] sub-tile
   constexpr int YSUB = 32 * 256;                      // one [32 px][128 co] sub-tile
@@ -72,15 +55,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   const int pairs = a.ci_tiles * a.co_tiles;
   int split, pair;
-  if (a.xcd_grouped) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int sq = (int)fdiv((unsigned)slot, a.div_pairs);
-    pair = slot - sq * pairs;
-    split = sq * 8 + xcd;
-  } else {
-    split = (int)fdiv(blockIdx.x, a.div_pairs);
-    pair = (int)blockIdx.x - split * pairs;
-  }
+  wg_block_to_split_pair(a, pairs, split, pair);
   const int co_tile = (int)fdiv((unsigned)pair, a.div_ci);
   const int ci_tile = pair - co_tile * a.ci_tiles;
   const int ci0 = ci_tile * 256, co0 = co_tile * 256;
@@ -89,8 +64,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   if (k_begin >= k_end) return;
   const int V = (k_end - k_begin + DEPTH - 1) / DEPTH * DEPTH;
 
-  const wp_u32x4 rsrc_x = wp_make_rsrc(a.x, ((unsigned)(a.M - 1) * (unsigned)a.ldx + (unsigned)a.C) * 2u);          // pixels >= M: out of range, zero fill
-  const wp_u32x4 rsrc_y = wp_make_rsrc(a.dy, ((unsigned)(a.M - 1) * (unsigned)a.ldy + (unsigned)a.Co8) * 2u);
+  const dh_u32x4 rsrc_x = dh_make_rsrc(a.x, ((unsigned)(a.M - 1) * (unsigned)a.ldx + (unsigned)a.C) * 2u);          // pixels >= M: out of range, zero fill
+  const dh_u32x4 rsrc_y = dh_make_rsrc(a.dy, ((unsigned)(a.M - 1) * (unsigned)a.ldy + (unsigned)a.Co8) * 2u);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(LDS_AS char*)smem);
 
   // ---- DMA lane constants: wave w moves X pieces 2w, 2w+1 (sub-tile p >> 2, pixels 8 (p & 3) ..) and dY pieces 2w, 2w+1 (sub-tile
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     {
       const int pz = wave * 2 + k, sub = pz >> 2, pp = pz & 3;
       const int l8 = lane >> 3, pcol = pp * 8 + l8;
-      const int chunk = (lane & 7) ^ (wp_f128(pcol) << 1);
+      const int chunk = (lane & 7) ^ (dh_swz128(pcol) << 1);
       const int ci = ci0 + sub * 64;
       vx[k] = ci < a.C ? (unsigned)pcol * (unsigned)(a.ldx * 2) + (unsigned)(ci * 2 + (chunk << 4)) : 0xFFFFFFFFu;
       xdst[k] = XBASE + sub * XSUB + pp * 1024;
@@ -110,7 +85,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     {
       const int pz = wave * 2 + k, sub = pz >> 3, pp = pz & 7;
       const int lp = lane >> 4, cpos = lane & 15, px = pp * 4 + lp;
-      const int chunk = cpos ^ (wp_f256(px) << 1);
+      const int chunk = cpos ^ (dh_swz256(px) << 1);
       const int co = co0 + sub * 128 + chunk * 8;
       vy[k] = co < a.Co8 ? (unsigned)px * (unsigned)(a.ldy * 2) + (unsigned)(co * 2) : 0xFFFFFFFFu;
       ydst[k] = YBASE + sub * YSUB + pp * 1024;
@@ -121,9 +96,9 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const unsigned inv = kstep < k_end ? 0u : 0xFFFFFFFFu;                       // beyond this block's share: zero fill
     const unsigned sx = (unsigned)(kstep * 32) * (unsigned)(a.ldx * 2), sy = (unsigned)(kstep * 32) * (unsigned)(a.ldy * 2);
 #pragma unroll
-    for (int k = 0; k < 2; ++k) wp_dma16(rsrc_x, (vx[k] + sx) | (vx[k] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u) | inv, lds0 + SL * XS + xdst[k]);
+    for (int k = 0; k < 2; ++k) dh_dma16(rsrc_x, (vx[k] + sx) | (vx[k] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u) | inv, lds0 + SL * XS + xdst[k]);
 #pragma unroll
-    for (int k = 0; k < 2; ++k) wp_dma16(rsrc_y, (vy[k] + sy) | (vy[k] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u) | inv, lds0 + SL * YS + ydst[k]);
+    for (int k = 0; k < 2; ++k) dh_dma16(rsrc_y, (vy[k] + sy) | (vy[k] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u) | inv, lds0 + SL * YS + ydst[k]);
   };
 
   // ---- fragment addresses of ring slot 0
@@ -135,13 +110,13 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   for (int h = 0; h < 2; ++h) {
     const int pcol = 8 * g + 4 * h + q;
     xbase[h] = XBASE + pcol * 128 + (p & 1) * 8;
-    xkey[h] = wp_f128(pcol) << 1;                     // swizzle key of this lane's pixel row (chunk units)
+    xkey[h] = dh_swz128(pcol) << 1;                     // swizzle key of this lane's pixel row (chunk units)
   }
   int yaddr[4];
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
     const int px = 8 * g + q;
-    const int ch = (((wco & 1) * 4 + o) * 2 + (p >> 1)) ^ (wp_f256(px) << 1);
+    const int ch = (((wco & 1) * 4 + o) * 2 + (p >> 1)) ^ (dh_swz256(px) << 1);
     yaddr[o] = YBASE + (wco >> 1) * YSUB + px * 256 + (ch << 4) + (p & 1) * 8;
   }
   int xoff[8][2];                                     // [ci fragment i][pixel half]
@@ -199,7 +174,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   dma_step(std::integral_constant<int, 0>{}, k_begin);
   dma_step(std::integral_constant<int, 1>{}, k_begin + 1);
   static_assert(P == 2, "prologue issues P steps");
-  wp_wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // K-step v (slot U = v % 4):   A:  DMA(v+P) + mem(v) | b1 | MFMA(v) | b2        B:  MFMA(v) | b1 | DMA(v+1+P) + mem(v+1) | b2
@@ -213,7 +188,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         __builtin_amdgcn_sched_barrier(0);
         mem(uc);
         __builtin_amdgcn_sched_barrier(0);
-        wp_wait_vmcnt<(P - 1) * DPW>();
+        dh_wait_vmcnt<(P - 1) * DPW>();
         __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
         __builtin_amdgcn_s_barrier();                // b1
         __builtin_amdgcn_sched_barrier(0);
@@ -234,7 +209,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         __builtin_amdgcn_sched_barrier(0);
         if (k_begin + v + U < k_end) mma();
         __builtin_amdgcn_sched_barrier(0);
-        wp_wait_vmcnt<(P - 1) * DPW>();
+        dh_wait_vmcnt<(P - 1) * DPW>();
         __builtin_amdgcn_s_barrier();                // b1
         dma_step(std::integral_constant<int, (U + 1 + P) % DEPTH>{}, k_begin + v + U + 1 + P);
         __builtin_amdgcn_sched_barrier(0);
@@ -247,7 +222,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 3>{});
     }
   }
-  wp_wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
 
   // ---- epilogue: lane holds dW[ci = ci0 + wci*128 + i*16 + g*4 + r][co = co0 + wco*64 + o*16 + (lane & 15)]
   if (a.slab) {                                        // slab form: register order, 1 KiB per wave-instruction, slots [i*4 + o][wave][lane]
@@ -285,8 +260,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 // Second pass of the slab form (the combine of conv_wgrad_rows.hip for the 256 x 256 tile): a workgroup owns 64 consecutive float4 slots,
-// wave w sums the splits w, w + 4, ..., wave 0 adds the total into dW[ci][co].  Slots of waves without real channels were never written
-// and are skipped (the same test as the kernel's `active`).
+// sums them over the splits (wg_sum_splits), wave 0 adds the total into dW[ci][co].  Slots of waves without real channels were never
+// written and are skipped (the same test as the kernel's `active`).
 __global__ __launch_bounds__(256) void wg_pw_reduce_kernel(const WgPwArgs a) {
   constexpr int TILE = 32 * 512;
   __shared__ f32x4 part[4][64];
@@ -299,24 +274,8 @@ __global__ __launch_bounds__(256) void wg_pw_reduce_kernel(const WgPwArgs a) {
   const int co_tile = pair / a.ci_tiles, ci_tile = pair - co_tile * a.ci_tiles;
   const int ci0 = ci_tile * 256, co0 = co_tile * 256;
   if (!(ci0 + wci * 128 < a.C && co0 + wco * 64 < a.Co8)) return;       // (uniform over the workgroup: `wave` is the same for its 64 slots)
-  const f32x4* src = reinterpret_cast<const f32x4*>(a.slab) + q;
-  auto blk = [&](int split) -> size_t {
-    return a.xcd_grouped ? (size_t)(((split >> 3) * pairs + pair) * 8 + (split & 7)) : (size_t)(split * pairs + pair);
-  };
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-  int sp = w;
-  for (; sp + 28 < a.splits; sp += 32) {
-    f32x4 v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = __builtin_nontemporal_load(src + blk(sp + 4 * e) * TILE);
-    s0 += (v[0] + v[1]) + (v[2] + v[3]);
-    s1 += (v[4] + v[5]) + (v[6] + v[7]);
-  }
-  for (; sp < a.splits; sp += 4) s0 += __builtin_nontemporal_load(src + blk(sp) * TILE);
-  part[w][lane] = s0 + s1;
-  __syncthreads();
-  if (w != 0) return;
-  const f32x4 sum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+  f32x4 sum;
+  if (!wg_sum_splits<TILE>(a, pairs, pair, q, lane, w, part, sum)) return;
   const int i = io >> 2, o = io & 3, g = lane >> 4;
   const int co = co0 + wco * 64 + o * 16 + (lane & 15);
   if (co >= a.Cout) return;
@@ -339,12 +298,8 @@ bool wg_pw_eligible(const danhip_conv_desc* d) {
 
 // The launch geometry of an eligible descriptor, computed once: the workspace query and the launch both read it.
 struct WgPwPlan {
-  int co8, ksteps, ci_tiles, co_tiles, pairs, splits, steps_per_split;
-  bool slab;              // slab form for short launches only (see conv_wgrad_rows.hip: on long ones the atomic tail hides under the other blocks' MFMAs)
-  size_t slab_bytes;
-  bool det;               // deterministic mode (conv_wgrad_rows.hip): always the slab form, the bias-gradient rows behind the tiles
-  size_t db_off;
-  int db_pitch;
+  int co8, ksteps, ci_tiles, co_tiles;
+  WgSplitPlan split;      // the K-steps over the chip
 };
 WgPwPlan plan_wg_pw(const danhip_conv_desc* d) {
   WgPwPlan p{};
@@ -352,21 +307,7 @@ WgPwPlan plan_wg_pw(const danhip_conv_desc* d) {
   p.ksteps = (d->N * d->H * d->W + 31) / 32;
   p.ci_tiles = (d->Cin + 255) / 256;
   p.co_tiles = (p.co8 + 255) / 256;
-  p.pairs = p.ci_tiles * p.co_tiles;
-  int splits = dh_cu_count() / p.pairs;
-  if (splits < 1) splits = 1;
-  if (splits > p.ksteps) splits = p.ksteps;
-  p.steps_per_split = (p.ksteps + splits - 1) / splits;
-  p.splits = (p.ksteps + p.steps_per_split - 1) / p.steps_per_split;
-  p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.steps_per_split <= 192);
-  p.slab_bytes = (size_t)dh_cu_count() * 32 * 512 * 16;
-  p.det = danhip_option("deterministic") != 0;
-  if (p.det) {
-    p.slab = true;
-    p.db_pitch = (d->Cout + 3) / 4 * 4;
-    p.db_off = (size_t)p.pairs * p.splits * 32 * 512 * 16;
-    p.slab_bytes = p.db_off + (size_t)p.splits * p.db_pitch * sizeof(float);
-  }
+  p.split = wg_split_plan(p.ksteps, p.ci_tiles, p.co_tiles, 32 * 512, d->Cout);
   return p;
 }
 
@@ -383,23 +324,9 @@ int launch_wg_pw(const WgradCall& c, hipStream_t s) {
   a.ksteps = p.ksteps;
   a.ci_tiles = p.ci_tiles;
   a.co_tiles = p.co_tiles;
-  a.steps_per_split = p.steps_per_split;
+  a.steps_per_split = p.split.per_split;
   a.div_ci = make_fastdiv(a.ci_tiles);
-  a.div_pairs = make_fastdiv(p.pairs);
-  a.xcd_grouped = (p.splits % 8 == 0 && p.pairs > 1) ? 1 : 0;
-  a.splits = p.splits;
-  a.b2 = danhip_option("wgrad_b2");
-  a.slab = ((p.det || danhip_option("wgrad_slab")) && c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
-  DH_REQUIRE(!p.det || a.slab, DANHIP_EINVAL, "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
-  if (p.det && c.db) { a.db_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + p.db_off); a.db_pitch = p.db_pitch; }
-  hipLaunchKernelGGL(conv_wgrad_pw_kernel, dim3(p.pairs * p.splits), dim3(512), LDS, s, a);
-  DH_LAUNCH_CHECK();
-  if (a.slab) {
-    hipLaunchKernelGGL(wg_pw_reduce_kernel, dim3(p.pairs * (32 * 512 / 64)), dim3(256), 0, s, a);
-    DH_LAUNCH_CHECK();
-  }
-  if (a.db_slab) return dh_ordered_reduce(a.db_slab, a.db_pitch, p.splits, d->Cout, c.db, 1, s);
-  return DANHIP_OK;
+  return wg_split_launch(a, p.split, c, &conv_wgrad_pw_kernel, LDS, &wg_pw_reduce_kernel, 32 * 512, s);
 }
 
 }  // namespace
@@ -407,7 +334,7 @@ int launch_wg_pw(const WgradCall& c, hipStream_t s) {
 size_t wgrad_pw_workspace_bytes(const danhip_conv_desc* d) {
   if (!wg_pw_eligible(d)) return 0;
   const WgPwPlan p = plan_wg_pw(d);
-  return p.slab ? p.slab_bytes : 0;
+  return p.split.slab ? p.split.slab_bytes : 0;
 }
 
 WgradInstance wgrad_pw_select(const WgradCall& c) {

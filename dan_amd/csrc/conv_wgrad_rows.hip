@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wgrad_split.h"
 
 namespace {
 
@@ -85,26 +85,6 @@ struct WgRowsArgs {
 #define WR_STEP_DONE() do { } while (0)
 #endif
 
-template <int N>
-__device__ __forceinline__ void wr_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// 16-byte-per-lane LDS-DMA as inline asm: hipcc counts a builtin LDS-DMA as a pending LDS write and drains it (vmcnt(0)) in front of
-// the next ds_read it cannot prove disjoint — every K-step here.  Hidden in asm the DMA is counted by hand (wr_wait_vmcnt) and stays
-// in flight across the barriers.  M0 (the LDS destination base) is written in the statement that uses it and restored after.
-typedef __attribute__((ext_vector_type(4))) unsigned wr_u32x4;
-__device__ __forceinline__ void wr_dma16(wr_u32x4 rsrc, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ wr_u32x4 wr_make_rsrc(const void* p, unsigned bytes) {   // raw buffer descriptor: base, stride 0, num_records, flags
-  const unsigned long long a = (unsigned long long)p;
-  return wr_u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
-}
-__device__ __forceinline__ int wr_f128(int pc) { return ((pc >> 1) & 1) | (((pc >> 3) & 1) << 1); }      // 32-byte-slot swizzles
-__device__ __forceinline__ int wr_f256(int px) { return (px & 3) | (((px >> 3) & 1) << 2); }
-
 // scalar generator of the block's K-step stream (one instance runs ahead for the DMA)
 struct RowGen {
   int strip, n, x0, y, warm, left;
@@ -139,15 +119,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   // ---- block -> (ci tile, co tile, split of the K-step stream); the (ci, co) pairs of one split read the same rows: same XCD
   const int pairs = a.ci_tiles * a.co_tiles;
   int split, pair;
-  if (a.xcd_grouped) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int sq = (int)fdiv((unsigned)slot, a.div_pairs);
-    pair = slot - sq * pairs;
-    split = sq * 8 + xcd;
-  } else {
-    split = (int)fdiv(blockIdx.x, a.div_pairs);
-    pair = (int)blockIdx.x - split * pairs;
-  }
+  wg_block_to_split_pair(a, pairs, split, pair);
   const int co_tile = (int)fdiv((unsigned)pair, a.div_ci);
   const int ci_tile = pair - co_tile * a.ci_tiles;
   const int ci0 = ci_tile * 64, co0 = co_tile * COT;
@@ -160,8 +132,8 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   const int V = (steps + DEPTH - 1) / DEPTH * DEPTH;
 
   // (the last pixel's row ends C / Co8 channels after its start whatever the pitch)
-  const wr_u32x4 rsrc_x = wr_make_rsrc(a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + (unsigned)a.C) * 2u);
-  const wr_u32x4 rsrc_y = wr_make_rsrc(a.dy, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldy + (unsigned)a.Co8) * 2u);
+  const dh_u32x4 rsrc_x = dh_make_rsrc(a.x, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldx + (unsigned)a.C) * 2u);
+  const dh_u32x4 rsrc_y = dh_make_rsrc(a.dy, ((unsigned)(a.N * a.H * a.W - 1) * (unsigned)a.ldy + (unsigned)a.Co8) * 2u);
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(LDS_AS char*)smem);
 
   // ---- the K-step generator (wave-uniform scalars)
@@ -226,14 +198,14 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       const unsigned bady = (s.xvalid && (unsigned)s.xrow < (unsigned)a.H) ? 0u : 0xFFFFFFFFu;
       const unsigned sbase = (unsigned)(((s.n * a.H + s.xrow) * a.W + xs) * a.ldx + ci0) * 2u;      // may wrap; exact for valid lanes
       const unsigned voff = (vx + sbase) | vxbad | bady;
-      wr_dma16(rsrc_x, voff, lds0 + XBASE + SL * XS + pc5 * 1024);
+      dh_dma16(rsrc_x, voff, lds0 + XBASE + SL * XS + pc5 * 1024);
     }
     {
       const int xs = s.x0 + ypiece * PXP;
       const unsigned bady = (s.yvalid && (unsigned)s.yrow < (unsigned)a.H) ? 0u : 0xFFFFFFFFu;
       const unsigned sbase = (unsigned)(((s.n * a.H + s.yrow) * a.W + xs) * a.ldy + co0) * 2u;
       const unsigned voff = (vy + sbase) | vybad | bady;
-      wr_dma16(rsrc_y, voff, lds0 + YBASE + SL * YS + ypiece * 1024);
+      dh_dma16(rsrc_y, voff, lds0 + YBASE + SL * YS + ypiece * 1024);
     }
   };
 
@@ -245,14 +217,14 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int pcol = j + 8 * g + 4 * h + q;
-      const int ch = (wci * 2 + (p >> 1)) ^ (wr_f128(pcol) << 1);
+      const int ch = (wci * 2 + (p >> 1)) ^ (dh_swz128(pcol) << 1);
       xaddr[j][h] = XBASE + pcol * 128 + (ch << 4) + (p & 1) * 8;
     }
   int yaddr[NO];                                      // half 1 (pixel + 4) is + 4*RBY: the swizzle does not see bit 2 of the pixel
 #pragma unroll
   for (int o = 0; o < NO; ++o) {
     const int px = 8 * g + q;
-    const int ch = ((wco * NO + o) * 2 + (p >> 1)) ^ ((COT == 128 ? wr_f256(px) : wr_f128(px)) << 1);
+    const int ch = ((wco * NO + o) * 2 + (p >> 1)) ^ ((COT == 128 ? dh_swz256(px) : dh_swz128(px)) << 1);
     yaddr[o] = YBASE + px * RBY + (ch << 4) + (p & 1) * 8;
   }
 
@@ -318,7 +290,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     static_assert(P == 4, "prologue issues P steps");
   }
   WR_CLK(1);
-  wr_wait_vmcnt<0>();
+  dh_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   // K-step v (ring slot U = v % 6):   A:  mem(v) + DMA(v+P) | b1 | MFMA(v) | b2        B:  MFMA(v) | b1 | mem(v+1) + DMA(v+1+P) | b2
@@ -338,7 +310,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         mem(uc);
         __builtin_amdgcn_sched_barrier(0);
         gen_next(nxt, P + 1);                        // the next K-step's DMA geometry (scalar work under the reads' latency)
-        wr_wait_vmcnt<2 * (P - 1)>();
+        dh_wait_vmcnt<2 * (P - 1)>();
         __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
         WR_STAMP(1);
         __builtin_amdgcn_s_barrier();                // b1
@@ -371,7 +343,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         flags >>= 1;
         __builtin_amdgcn_sched_barrier(0);
         WR_STAMP(1);
-        wr_wait_vmcnt<2 * (P - 1)>();
+        dh_wait_vmcnt<2 * (P - 1)>();
         __builtin_amdgcn_s_barrier();                // b1
         WR_STAMP(2);
         dma_step(std::integral_constant<int, (U + 1 + P) % DEPTH>{}, nxt);
@@ -388,7 +360,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
     }
   }
-  wr_wait_vmcnt<0>();                                 // zero-fill pieces of the steps beyond the stream are still landing
+  dh_wait_vmcnt<0>();                                 // zero-fill pieces of the steps beyond the stream are still landing
   WR_CLK(2);
 #ifdef WR_TRACE
   __syncthreads();
@@ -442,14 +414,14 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (lane < 16 && co < a.Cout) atomicAdd(a.db + co, accb[0]);
   }
 #ifdef WR_CLOCK
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the epilogue's atomics have been accepted by the memory system when the end stamp is taken
+  dh_wait_vmcnt<0>();                                 // the epilogue's atomics have been accepted by the memory system when the end stamp is taken
   WR_CLK(3);
 #endif
 }
 
-// Second pass of the slab form: a 256-thread workgroup owns 64 consecutive float4 slots of one (ci, co) tile; wave w sums the splits
-// w, w + 4, ... (eight independent 16-byte loads in flight per lane), the four partial sums meet in LDS and wave 0 adds the result (four
-// consecutive ci of one co) into the HWIO gradient.  Slot -> element as in the kernel above: q = (t * NO + o) * 512 + wave * 64 + lane.
+// Second pass of the slab form: a 256-thread workgroup owns 64 consecutive float4 slots of one (ci, co) tile, sums them over the splits
+// (wg_sum_splits) and wave 0 adds the result (four consecutive ci of one co) into the HWIO gradient.  Slot -> element as in the kernel
+// above: q = (t * NO + o) * 512 + wave * 64 + lane.
 template <int COT>
 __global__ __launch_bounds__(256) void wg_rows_reduce_kernel(const WgRowsArgs a) {
   constexpr int NO = COT / 32, TILE = 9 * NO * 512;
@@ -458,24 +430,8 @@ __global__ __launch_bounds__(256) void wg_rows_reduce_kernel(const WgRowsArgs a)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int chunk = blockIdx.x;                       // 64-slot chunk; TILE % 64 == 0, so a chunk never straddles two tiles
   const int pair = chunk / (TILE / 64), q = (chunk - pair * (TILE / 64)) * 64 + lane;
-  const f32x4* src = reinterpret_cast<const f32x4*>(a.slab) + q;
-  auto blk = [&](int split) -> size_t {             // the block that computed (split, pair): inverse of the kernel's mapping
-    return a.xcd_grouped ? (size_t)(((split >> 3) * pairs + pair) * 8 + (split & 7)) : (size_t)(split * pairs + pair);
-  };
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-  int sp = w;
-  for (; sp + 28 < a.splits; sp += 32) {              // eight splits of this wave per round
-    f32x4 v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = __builtin_nontemporal_load(src + blk(sp + 4 * e) * TILE);
-    s0 += (v[0] + v[1]) + (v[2] + v[3]);
-    s1 += (v[4] + v[5]) + (v[6] + v[7]);
-  }
-  for (; sp < a.splits; sp += 4) s0 += __builtin_nontemporal_load(src + blk(sp) * TILE);
-  part[w][lane] = s0 + s1;
-  __syncthreads();
-  if (w != 0) return;
-  const f32x4 sum = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+  f32x4 sum;
+  if (!wg_sum_splits<TILE>(a, pairs, pair, q, lane, w, part, sum)) return;
   const int to = q >> 9, wave = (q >> 6) & 7;
   const int t = to / NO, o = to - t * NO;
   const int wci = wave & 3, wco = wave >> 2, g = lane >> 4;
@@ -519,12 +475,8 @@ bool wg_rows_eligible(const danhip_conv_desc* d) {
 
 // The launch geometry of an eligible descriptor, computed once: the workspace query and the launch both read it.
 struct WgRowsPlan {
-  int co8, ci_tiles, co_tiles, pairs, tiles_x, total_rows, splits, rows_per_split;
-  bool slab;              // the slab form (partial tiles as plain stores + a combine pass) is worth taking ...
-  size_t slab_bytes;      // ... and needs this much scratch (one register tile per workgroup, at most one workgroup per CU)
-  bool det;               // deterministic mode: always the slab form (any number of splits), the bias-gradient rows behind the tiles
-  size_t db_off;          // byte offset of the [splits][db_pitch] bias-gradient rows in the scratch
-  int db_pitch;
+  int co8, ci_tiles, co_tiles, tiles_x, total_rows;
+  WgSplitPlan split;      // the rows (one K-step each) over the chip
 };
 WgRowsPlan plan_wg_rows(const danhip_conv_desc* d) {
   WgRowsPlan p{};
@@ -532,26 +484,9 @@ WgRowsPlan plan_wg_rows(const danhip_conv_desc* d) {
   p.co8 = (d->Cout + 7) / 8 * 8;
   p.ci_tiles = d->Cin / 64;
   p.co_tiles = (p.co8 + cot - 1) / cot;
-  p.pairs = p.ci_tiles * p.co_tiles;
   p.tiles_x = (d->W + 31) / 32;
   p.total_rows = d->N * p.tiles_x * d->H;
-  int splits = dh_cu_count() / p.pairs;
-  if (splits < 1) splits = 1;
-  if (splits > p.total_rows) splits = p.total_rows;
-  p.rows_per_split = (p.total_rows + splits - 1) / splits;
-  p.splits = (p.total_rows + p.rows_per_split - 1) / p.rows_per_split;
-  // The slab form pays when the launch is short (every block reaches its epilogue together and nothing hides the tail: 2-4 images per
-  // GPU, the 40x40 / 20x20 levels); on long launches the blocks drift apart, the atomic tail hides under other blocks' MFMAs and the
-  // extra pass costs more than it saves (batch 16: conv3_2 0.426 against 0.428 ms, conv2_2 0.479 against 0.455; profiles/r3).
-  p.slab = p.splits >= 2 && (danhip_option("wgrad_slab") == 2 || p.rows_per_split <= 192);
-  p.slab_bytes = (size_t)dh_cu_count() * 9 * (cot / 32) * 512 * 16;
-  p.det = danhip_option("deterministic") != 0;
-  if (p.det) {            // every launch through the slab (wg_rows_reduce_kernel's order is fixed by `splits`), db as rows for the ordered reduction
-    p.slab = true;
-    p.db_pitch = (d->Cout + 3) / 4 * 4;
-    p.db_off = (size_t)p.pairs * p.splits * 9 * (cot / 32) * 512 * 16;
-    p.slab_bytes = p.db_off + (size_t)p.splits * p.db_pitch * sizeof(float);
-  }
+  p.split = wg_split_plan(p.total_rows, p.ci_tiles, p.co_tiles, 9 * (cot / 32) * 512, d->Cout);
   return p;
 }
 
@@ -567,9 +502,6 @@ int launch_wg_rows(const WgradCall& c, hipStream_t s) {
   a.total_rows = p.total_rows;
   a.div_tx = make_fastdiv(a.tiles_x);
   a.div_h = make_fastdiv(d->H);
-  a.slab = (c.ws && p.slab && c.ws_bytes >= p.slab_bytes) ? reinterpret_cast<float*>(c.ws) : nullptr;
-  DH_REQUIRE(!p.det || a.slab, DANHIP_EINVAL, "conv2d_bwd_weight: deterministic mode needs a workspace of danhip_conv2d_bwd_weight_workspace_bytes(d) bytes (call danhip_conv2d_bwd_weight_ws)");
-  if (p.det && c.db) { a.db_slab = reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + p.db_off); a.db_pitch = p.db_pitch; }
 #ifdef WR_TRACE
   constexpr int LDS = 6 * (32 * COT * 2) + 6 * 40 * 128 + 4096;
   a.trace = wr_trace_buffer();
@@ -581,29 +513,16 @@ int launch_wg_rows(const WgradCall& c, hipStream_t s) {
   (void)attr_ok;
   a.ci_tiles = p.ci_tiles;
   a.co_tiles = p.co_tiles;
-  const int pairs = p.pairs, splits = p.splits;
-  a.rows_per_split = p.rows_per_split;
+  a.rows_per_split = p.split.per_split;
   a.div_ci = make_fastdiv(a.ci_tiles);
-  a.div_pairs = make_fastdiv(pairs);
-  a.xcd_grouped = (splits % 8 == 0 && pairs > 1) ? 1 : 0;
   static const int ablate = [] { const char* e = getenv("DANHIP_WGRAD_ABLATE"); return e ? atoi(e) : 0; }();
   a.ablate = ablate;
-  a.b2 = danhip_option("wgrad_b2");
-  a.splits = splits;
 #ifdef WR_CLOCK
   a.clk = wr_clock_buffer();
-  g_wr_clock_blocks = pairs * splits;
+  g_wr_clock_blocks = p.split.pairs * p.split.splits;
   g_wr_clock_steps = a.rows_per_split;
 #endif
-  hipLaunchKernelGGL((conv_wgrad_rows_kernel<COT>), dim3(pairs * splits), dim3(512), LDS, s, a);
-  DH_LAUNCH_CHECK();
-  if (a.slab) {
-    const int chunks = pairs * 9 * (COT / 32) * 512 / 64;
-    hipLaunchKernelGGL((wg_rows_reduce_kernel<COT>), dim3(chunks), dim3(256), 0, s, a);
-    DH_LAUNCH_CHECK();
-  }
-  if (a.db_slab) return dh_ordered_reduce(a.db_slab, a.db_pitch, splits, d->Cout, c.db, 1, s);
-  return DANHIP_OK;
+  return wg_split_launch(a, p.split, c, &conv_wgrad_rows_kernel<COT>, LDS, &wg_rows_reduce_kernel<COT>, 9 * (COT / 32) * 512, s);
 }
 
 }  // namespace
@@ -611,7 +530,7 @@ int launch_wg_rows(const WgradCall& c, hipStream_t s) {
 size_t wgrad_rows_workspace_bytes(const danhip_conv_desc* d) {
   if (!wg_rows_eligible(d)) return 0;
   const WgRowsPlan p = plan_wg_rows(d);
-  return p.slab ? p.slab_bytes : 0;
+  return p.split.slab ? p.split.slab_bytes : 0;
 }
 
 WgradInstance wgrad_rows_select(const WgradCall& c) {

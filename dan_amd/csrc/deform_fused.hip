@@ -13,7 +13,7 @@
 //     channels of one pixel), fp32 accumulators across the 9 * dg K-steps, bias / ReLU epilogue.
 // `col` (optional): the rounded samples are ALSO stored as the column buffer, for a caller that keeps it for the filter gradient
 // (dan_amd/ops.py KEEP_DEFORM_COL); inference passes NULL and the 9x activation-sized buffer never exists.
-#include "common.h"
+#include "lds_dma.h"
 
 // 64 pixels per workgroup (256 threads, 80 KB of LDS at Cout = 256): TWO workgroups per CU, so one gathers while the other multiplies --
 // 1.105 -> 1.045 ms at 160 x 160 x 256, offsets N(0, 2 px), against the 128-pixel / 512-thread form (one resident workgroup, 96 KB).
@@ -23,13 +23,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned df_u32x4;
-
-__device__ __forceinline__ void df_dma16(df_u32x4 rsrc, unsigned voff, unsigned lds_addr) {      // voff out of range: zeros land in LDS
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
 __device__ __forceinline__ void df_unpack8(const uint4& u, float* f) {
   const unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(BM * 4, 2) void deform_fused_fwd_kernel(const Fused
   }
 
   // ---- weight DMA: piece = 8 rows x 128 B; lane -> (row = piece*8 + lane/8, 16-byte chunk lane%8), chunk c of row r lands at c ^ (r & 7)
-  const df_u32x4 rsrc_w = {(unsigned)(unsigned long long)a.w, (unsigned)((unsigned long long)a.w >> 32) & 0xFFFFu,
+  const dh_u32x4 rsrc_w = {(unsigned)(unsigned long long)a.w, (unsigned)((unsigned long long)a.w >> 32) & 0xFFFFu,
                            (unsigned)((a.Cout + 63) / 64 * 64) * (unsigned)a.Kpad * 2u, 0x00020000u};
   unsigned wvoff[WPW];
 #pragma unroll
@@ -106,7 +99,7 @@ __global__ __launch_bounds__(BM * 4, 2) void deform_fused_fwd_kernel(const Fused
   auto issue_w = [&](int ks, int stage) __attribute__((always_inline)) {
     const unsigned lds = (unsigned)(2 * ABYTES + stage * WBYTES);
 #pragma unroll
-    for (int k = 0; k < WPW; ++k) df_dma16(rsrc_w, wvoff[k] + (unsigned)ks * 128u, lds + (unsigned)(wave * WPW + k) * 1024u);
+    for (int k = 0; k < WPW; ++k) dh_dma16(rsrc_w, wvoff[k] + (unsigned)ks * 128u, lds + (unsigned)(wave * WPW + k) * 1024u);
   };
 
   // ---- gather of K-step ks: loads now, blend + LDS write later

@@ -34,6 +34,8 @@ int danhip_option(const char* name) {
   if (!strcmp(name, "wgrad_slab")) { const char* e = getenv("DANHIP_WGRAD_SLAB"); return e ? atoi(e) : 1; }
   return 0;
 }
+// (deterministic mode is off in this program: the ordered bias-gradient sum of ordered_reduce.hip is never reached)
+int dh_ordered_reduce(const float*, long, int, long, float*, int, hipStream_t) { return DANHIP_EINVAL; }
 
 static unsigned short rnd_bf16(unsigned& st) {
   st = st * 1664525u + 1013904223u;

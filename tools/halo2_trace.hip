@@ -48,6 +48,8 @@ int danhip_option(const char* name) {
   if (!strcmp(name, "halo2_ablate")) { const char* e = getenv("DANHIP_HALO2_ABLATE"); return e ? atoi(e) : 0; }
   return 0;
 }
+// (deterministic mode is off in this program: the ordered bias-gradient sum of ordered_reduce.hip is never reached)
+int dh_ordered_reduce(const float*, long, int, long, float*, int, hipStream_t) { return DANHIP_EINVAL; }
 
 static unsigned short rnd_bf16(unsigned& st) {
   st = st * 1664525u + 1013904223u;
