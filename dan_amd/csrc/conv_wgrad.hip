@@ -362,7 +362,16 @@ static int bwd_weight_impl(const danhip_conv_desc* d, const uint16_t* x, const u
     DH_REQUIRE(same || valid, DANHIP_EINVAL, "conv: Ho/Wo (%d,%d) is neither the 'same' nor the 'valid' output size", d->Ho, d->Wo);
   }
   const WgradCall c{d, x, dy, dw_hwio, db, cin_real, ldx, ldy, ws, ws_bytes};
-  return dh_run_instance(select_wgrad(c), c, (hipStream_t)stream);
+  const WgradInstance inst = select_wgrad(c);
+  if (danhip_option("deterministic") != 0) {
+    // the workspace query answered for dense pitches: a call whose pitches move it to another family would run on a size (and an order of
+    // summation) nobody asked for, or pass the launcher's own check only because the other family's slab happens to be larger (danhip.h)
+    const WgradCall dense{d, x, dy, dw_hwio, db, cin_real, d->Cin, co8, ws, ws_bytes};
+    DH_REQUIRE(select_wgrad(dense).launch == inst.launch, DANHIP_EINVAL,
+               "conv2d_bwd_weight_strided: deterministic mode: pitches (%d, %d) move the call to %s, the workspace query answers for dense pitches", ldx, ldy,
+               inst.label);
+  }
+  return dh_run_instance(inst, c, (hipStream_t)stream);
 }
 
 extern "C" int danhip_conv2d_bwd_weight(const danhip_conv_desc* d, const uint16_t* x, const uint16_t* dy, float* dw_hwio, float* db,

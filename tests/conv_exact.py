@@ -7,6 +7,10 @@ not depend on summation order, split, slab or atomic form: the device result mus
 or twice shows as a whole-number difference.  A 16-bit output is exact as long as |value| <= 256 (every integer up to 256 is a bf16 value; IEEE
 half reaches 2048): LIMIT16 is asserted on the reference of every case whose output is stored in 16 bits, before anything is compared.
 
+The same argument covers the second set of entry points - the channel-slice view calls (danhip_conv2d_*_strided, kinds vfwd / vdgrad / vwgrad:
+operands inside wider buffers whose other channels hold a NaN pattern), danhip_conv2d_fwd_concat2, padding='valid' - and, with quarters instead
+of integers, the whole DAN context block against its unfused float64 composition (BLOCK_CASES, tests/test_conv_views_exact_gpu.py).
+
 Nothing in the first three sections needs a GPU or the library; the runners at the end import dan_amd lazily."""
 import ctypes
 import functools
@@ -27,28 +31,36 @@ def same_pad(n, k, s):
     return total // 2, total - total // 2, out
 
 
-def conv_ref(x, w, b=None, stride=1):
-    """x [N,H,W,Cin], w [kh,kw,Cin,Cout], b [Cout] or None, all float64 -> [N,Ho,Wo,Cout] float64 (cross-correlation, explicit 'same' padding)."""
+def out_size(n, k, s, valid=False):
+    """Output length of one axis: 'valid' floor((n - k) / s) + 1 (no padding), TF 'same' ceil(n / s)."""
+    return (n - k) // s + 1 if valid else same_pad(n, k, s)[2]
+
+
+def conv_ref(x, w, b=None, stride=1, valid=False):
+    """x [N,H,W,Cin], w [kh,kw,Cin,Cout], b [Cout] or None, all float64 -> [N,Ho,Wo,Cout] float64 (cross-correlation; explicit 'same' padding,
+    or none at all with valid: the windows that fit, rows / columns behind the last window are not read)."""
     assert x.dtype == F64 and w.dtype == F64
     kh, kw = w.shape[0], w.shape[1]
-    pt, pb, _ = same_pad(x.shape[1], kh, stride)
-    pl, pr, _ = same_pad(x.shape[2], kw, stride)
-    xp = F.pad(x.permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    xp = x.permute(0, 3, 1, 2)
+    if not valid:
+        pt, pb, _ = same_pad(x.shape[1], kh, stride)
+        pl, pr, _ = same_pad(x.shape[2], kw, stride)
+        xp = F.pad(xp, (pl, pr, pt, pb))
     return F.conv2d(xp, w.permute(3, 2, 0, 1), b, stride=stride).permute(0, 2, 3, 1).contiguous()
 
 
-def dgrad_ref(dy, w, H, W, stride=1):
+def dgrad_ref(dy, w, H, W, stride=1, valid=False):
     """Data gradient from autograd: d/dx of <conv_ref(x, w), dy>."""
     x = torch.zeros((dy.shape[0], H, W, w.shape[2]), dtype=F64, requires_grad=True)
-    conv_ref(x, w, None, stride).backward(dy)
+    conv_ref(x, w, None, stride, valid).backward(dy)
     return x.grad
 
 
-def wgrad_ref(x, dy, kh, kw, stride=1):
+def wgrad_ref(x, dy, kh, kw, stride=1, valid=False):
     """Weight and bias gradient from autograd."""
     w = torch.zeros((kh, kw, x.shape[3], dy.shape[3]), dtype=F64, requires_grad=True)
     b = torch.zeros((dy.shape[3],), dtype=F64, requires_grad=True)
-    conv_ref(x, w, b, stride).backward(dy)
+    conv_ref(x, w, b, stride, valid).backward(dy)
     return w.grad, b.grad
 
 
@@ -134,7 +146,7 @@ def cin_real_of(shape, cin_real=None):
 
 
 @functools.lru_cache(maxsize=2)
-def forward_inputs(shape, seed=1, cin_real=None):
+def forward_inputs(shape, seed=1, cin_real=None, valid=False):
     """x (ternary, density 1024 / K), w (+-1), bias and residual in [-8, 8]; pre = conv + bias in float64.  A first-layer shape (Cin = 8 -> 64)
     has 3 real channels: channels 3..7 of the image stay zero and the weight is [3,3,3,64]."""
     N, H, W, Cin, Cout, kh, kw, s = shape
@@ -144,39 +156,39 @@ def forward_inputs(shape, seed=1, cin_real=None):
     x[..., :cr] = ternary((N, H, W, cr), density(kh * kw * cr), g)
     w = signs((kh, kw, cr, Cout), g)
     b = small((Cout,), g)
-    pre = conv_ref(x[..., :cr].contiguous(), w, b, s)
+    pre = conv_ref(x[..., :cr].contiguous(), w, b, s, valid)
     res = small(tuple(pre.shape), g)
     return dict(x=x, w=w, b=b, res=res, pre=pre, cin_real=cr)
 
 
 @functools.lru_cache(maxsize=2)
-def dgrad_inputs(shape, seed=2):
+def dgrad_inputs(shape, seed=2, valid=False):
     """dy (ternary, density 1024 / (taps Cout), channels Cout .. Cout8 zero), w (+-1), mask in [-2, 2] (zeros and negatives), old dx in [-8, 8]."""
     N, H, W, Cin, Cout, kh, kw, s = shape
     g = gen(seed + sum(shape))
-    Ho, Wo = same_pad(H, kh, s)[2], same_pad(W, kw, s)[2]
+    Ho, Wo = out_size(H, kh, s, valid), out_size(W, kw, s, valid)
     dy = torch.zeros((N, Ho, Wo, co8_of(Cout)), dtype=F64)
     dy[..., :Cout] = ternary((N, Ho, Wo, Cout), density(kh * kw * Cout), g)
     w = signs((kh, kw, Cin, Cout), g)
     mask = small((N, H, W, Cin), g, -2, 2)
     old = small((N, H, W, Cin), g)
-    dx = dgrad_ref(dy[..., :Cout].contiguous(), w, H, W, s)
+    dx = dgrad_ref(dy[..., :Cout].contiguous(), w, H, W, s, valid)
     return dict(dy=dy, w=w, mask=mask, old=old, dx=dx)
 
 
 @functools.lru_cache(maxsize=2)
-def wgrad_inputs(shape, seed=3, cin_real=None):
+def wgrad_inputs(shape, seed=3, cin_real=None, valid=False):
     """x, dy dense ternary (p = 2/3), pre-filled dw / db in [-8, 8]; |dw| <= N H W + 8 < 2^24."""
     N, H, W, Cin, Cout, kh, kw, s = shape
     g = gen(seed + sum(shape) + (cin_real or 0))
     cr = cin_real_of(shape, cin_real)
-    Ho, Wo = same_pad(H, kh, s)[2], same_pad(W, kw, s)[2]
+    Ho, Wo = out_size(H, kh, s, valid), out_size(W, kw, s, valid)
     x = torch.zeros((N, H, W, Cin), dtype=F64)
     x[..., :cr] = ternary((N, H, W, cr), 2 / 3, g)
     dy = torch.zeros((N, Ho, Wo, co8_of(Cout)), dtype=F64)
     dy[..., :Cout] = ternary((N, Ho, Wo, Cout), 2 / 3, g)
     dw0, db0 = small((kh, kw, cr, Cout), g), small((Cout,), g)
-    dw, db = wgrad_ref(x[..., :cr].contiguous(), dy[..., :Cout].contiguous(), kh, kw, s)
+    dw, db = wgrad_ref(x[..., :cr].contiguous(), dy[..., :Cout].contiguous(), kh, kw, s, valid)
     return dict(x=x, dy=dy, dw0=dw0, db0=db0, dw=dw + dw0, db=db + db0, cin_real=cr)
 
 
@@ -322,10 +334,10 @@ def wgrad_workspace_bytes(shape, cus):
     return 0
 
 
-def plan_splitk(shape, which, cus):
+def plan_splitk(shape, which, cus, valid=False):
     """conv_igemm.hip plan_splitk for a forward (which = 0) / data-gradient (which = 1) call: (splits, K tiles per split, M, Co); splits = 1: none."""
     N, H, W, Cin, Cout, kh, kw, s = shape
-    Ho, Wo = same_pad(H, kh, s)[2], same_pad(W, kw, s)[2]
+    Ho, Wo = out_size(H, kh, s, valid), out_size(W, kw, s, valid)
     if which == 0:
         M, Co, C = N * Ho * Wo, Cout, Cin
     else:
@@ -346,8 +358,8 @@ def plan_splitk(shape, which, cus):
     return cdiv(ktiles, per), per, M, Co
 
 
-def conv_workspace_bytes(shape, which, cus):
-    splits, _, M, Co = plan_splitk(shape, which, cus)
+def conv_workspace_bytes(shape, which, cus, valid=False):
+    splits, _, M, Co = plan_splitk(shape, which, cus, valid)
     return splits * M * Co * 4 if splits >= 2 else 0
 
 
@@ -442,6 +454,322 @@ POOL_EDGES = [
 FOLD_SHAPES = [(1, 30, 62), (3, 40, 96)]
 
 
+# 'valid' padding (the ResNet stem and one 3x3): (id, kind, shape, family, cin_real, extra)
+VALID_CASES = [
+    ("fwd_valid_stem", "fwd", S(2, 29, 35, 8, 64, 7, 2), FLAT + "256, 64, 1, false>", 3, ""),
+    ("dgrad_valid_stem", "dgrad", S(2, 29, 35, 8, 64, 7, 2), FLAT + "64, 16, 1, true>", None, "splitk"),
+    ("wgrad_valid_stem", "wgrad", S(2, 29, 35, 8, 64, 7, 2), "conv_wgrad_kernel<64, 64, 2>", 3, ""),
+    ("fwd_valid_3x3", "fwd", S(1, 9, 11, 64, 64), FLAT + "256, 64, 1, true>", None, "splitk"),
+    ("dgrad_valid_3x3", "dgrad", S(1, 9, 11, 64, 64), FLAT + "256, 64, 1, true>", None, "splitk"),
+    ("wgrad_valid_3x3", "wgrad", S(1, 9, 11, 64, 64), "conv_wgrad_kernel<64, 64, 2>", None, ""),
+]
+
+# ---- channel-slice views (danhip_conv2d_{fwd,bwd_data,bwd_weight}_strided): every operand is channels c0 : c0 + C of a wider NHWC buffer whose
+# other channels hold NAN16, a bit pattern that is a NaN in bf16 and in IEEE half.  A read outside the slice poisons the result, a store
+# outside it changes the pattern (compared as int16: a stray store of 0 shows too).  The buffers are the context block's (ops._ContextBlock):
+# T 192 wide, hyper 256, the block input C or C + 128; slices at 0:64, 64:128, 128:192, 192:256.
+NAN16 = 0x7FFF
+C64F, C64D = "conv3x3_c64_kernel<false>", "conv3x3_c64_kernel<true>"
+# forward: (id, shape, label of the table's call, (x width, x c0, y width, y c0), relu_channels strictly inside, extra)
+#   the table's call: with the scratch the library asks for, ReLU on all channels - on `inside` channels where extra says "partial"
+#   extra: "plus" (the weight the block packs a 3x1 and a 1x3 convolution into), "splitk" (the call with scratch splits K: restated plan)
+VFWD_CASES = [
+    ("pw_cat192", S(1, 40, 56, 256, 192, 1), PW + "64, 4, false, true, false>", (384, 64, 256, 64), 128, "partial"),      # 17.5 items of 128 pixels
+    ("pw_b1", S(1, 40, 56, 256, 64, 1), PW + "64, 4, false, true, false>", (256, 0, 256, 0), 32, ""),
+    ("c64", S(1, 30, 62, 64, 64), C64F, (192, 64, 256, 192), 32, ""),
+    ("c64_plus", S(1, 30, 62, 64, 64), C64F, (192, 0, 256, 128), 32, "plus"),
+    ("splitk_2x6x6", S(2, 6, 6, 64, 64), FLAT + "256, 64, 1, true>", (192, 0, 256, 128), 32, "splitk"),
+    ("splitk_cat192", S(16, 3, 3, 1024, 192, 1), FLAT + "256, 64, 1, true>", (1024, 0, 256, 64), 128, "splitk partial"),
+]
+# data gradient: (id, shape, label of the masked accumulating call with scratch, (dy width, c0, dx width, c0, mask width, c0), extra)
+VDGRAD_CASES = [
+    ("c64", S(1, 30, 62, 64, 64), C64D, (256, 128, 192, 0, 192, 0), ""),
+    ("c64_plus", S(1, 30, 62, 64, 64), C64D, (256, 192, 192, 64, 192, 64), "plus"),
+    ("splitk_2x6x6", S(2, 6, 6, 64, 64), FLAT + "256, 64, 1, true>", (256, 128, 192, 0, 256, 64), "splitk"),
+    ("flat_cat192", S(16, 3, 3, 1024, 192, 1), FLAT + "128, 128, 2, true>", (256, 64, 1152, 64, 1088, 64), ""),      # K = 192: three K tiles, no split
+    ("splitk_res", S(16, 3, 3, 256, 1024, 1), FLAT + "128, 128, 2, true>", (1088, 64, 384, 64, 320, 64), "splitk"),   # the residual conv's: 4 splits
+    ("pw_cat192", S(1, 40, 56, 256, 192, 1), PW + "128, 4, true, true, false>", (256, 64, 384, 64, 320, 64), ""),
+]
+# weight gradient: (id, shape, label, (x width, c0, dy width, c0), extra); "det": also twice in deterministic mode, "pitch": declined by the
+# row-streaming kernel (its lane offsets hold pitches up to 65535)
+VWGRAD_CASES = [
+    ("rows", S(3, 37, 40, 64, 64), "conv_wgrad_rows_kernel<64>", (192, 0, 256, 128), "det"),
+    ("pw", S(2, 50, 50, 256, 192, 1), "conv_wgrad_pw_kernel", (384, 64, 256, 64), "det"),
+    ("generic", S(16, 3, 3, 1024, 192, 1), "conv_wgrad_kernel<128, 128, 2>", (1088, 64, 256, 64), ""),
+    ("pitch65600", S(1, 4, 40, 64, 64), "conv_wgrad_kernel<64, 64, 2>", (65600, 64, 256, 128), "pitch"),
+]
+# danhip_conv2d_fwd_concat2: (id, (N, H, W), c1, c2, Cout, src_pitch, label); 2240 pixels = 17.5 items
+CONCAT2_CASES = [
+    ("64_192_128", (1, 40, 56), 64, 192, 128, 256, "conv_pointwise_concat2_kernel<128, 4>"),
+    ("256_64_64", (1, 40, 56), 256, 64, 64, 320, "conv_pointwise_concat2_kernel<64, 4>"),
+    ("256_256_256", (1, 40, 56), 256, 256, 256, 256, "conv_pointwise_concat2_kernel<256, 3>"),
+]
+
+
+def plus_mask():
+    """[3,3,64,64] 0 / 1: the 3x1 taps in the middle column for outputs 0..31, the 1x3 taps in the middle row for outputs 32..63."""
+    m = torch.zeros((3, 3, 64, 64), dtype=F64)
+    m[:, 1, :, :32] = 1
+    m[1, :, :, 32:] = 1
+    return m
+
+
+def view_kernel(shape, which, cus, scratch=False, partial=False, ld=True):
+    """select_conv (conv_igemm.hip) restated for a stride-1 'same' view call: the label of a forward (which = 0; partial: ReLU on some columns
+    only) or data-gradient (which = 1; ld: with a mask or accumulating) call, with / without the scratch the library asks for."""
+    N, H, W, Cin, Cout, kh, kw, s = shape
+    assert s == 1
+    M = N * H * W
+    C, Co = (Cin, Cout) if which == 0 else (co8_of(Cout), Cin)
+    tf = lambda v: "true" if v else "false"
+    if kh == 3 and kw == 3 and C == 64 and Co == 64 and not partial and H * W / (cdiv(H, 8) * 8 * cdiv(W, 32) * 32) >= 0.78:
+        return C64F if which == 0 else C64D
+    prefer = scratch and plan_splitk(shape, which, cus)[0] >= 2 and cdiv(M, 128) * cdiv(Co, 128) * 2 <= cus
+    if not prefer and C % 64 == 0 and Co % 64 == 0 and M >= 2048 and kh * kw <= 32:
+        ld = ld or which == 0
+        bn = 256 if Co % 256 == 0 and not (which == 1 and ld) else 128 if Co % 128 == 0 else 64
+        return PW + "%d, %d, %s, %s, %s>" % (bn, 3 if bn == 256 else 4, tf(which == 1), tf(ld), tf(kh * kw > 1))
+    bn = 128 if Co % 128 == 0 else 64 if Co % 64 == 0 else 16 if Co <= 16 else 32 if Co <= 32 else 64
+    tile = {128: "128, 128, 2", 64: "256, 64, 1", 32: "256, 32, 1", 16: "64, 16, 1" if M <= 256 * 128 else "256, 16, 1"}[bn]
+    return FLAT + "%s, %s>" % (tile, tf(C % 64 == 0))
+
+
+def view_forward_inputs(shape, plus=False):
+    inp = dict(forward_inputs(shape))
+    if plus:
+        inp["w"] = inp["w"] * plus_mask()
+        inp["pre"] = conv_ref(inp["x"], inp["w"], inp["b"], 1)
+    return inp
+
+
+def view_forward_outputs(inp, relu_co):
+    y = inp["pre"].clone()
+    y[..., :relu_co] = torch.relu(y[..., :relu_co])
+    return y
+
+
+def view_dgrad_inputs(shape, plus=False):
+    inp = dict(dgrad_inputs(shape))
+    if plus:
+        N, H, W, Cin, Cout = shape[:5]
+        inp["w"] = inp["w"] * plus_mask()
+        inp["dx"] = dgrad_ref(inp["dy"][..., :Cout].contiguous(), inp["w"], H, W, 1)
+    return inp
+
+
+def concat2_shape(case):
+    cid, nhw, c1, c2, cout, pitch, label = case
+    return S(*nhw, c1 + c2, cout, 1)
+
+
+def check_vfwd(case, cus):
+    cid, kind, shp, family, extra = case
+    Cout, inside, edge = shp[4], extra["inside"], extra["edge"]
+    inp = view_forward_inputs(shp, "plus" in edge)
+    check_forward_inputs(inp, relu=True)
+    pre = inp["pre"]
+    assert 0 < inside < Cout and inside % 8 == 0
+    # partial ReLU: the linear columns hold a negative value (a ReLU there shows), the ReLU columns a negative pre-activation and an exact 0
+    assert int((pre[..., inside:] < 0).sum()) >= 1 and int((pre[..., :inside] < 0).sum()) >= 1
+    assert int((view_forward_outputs(inp, inside)[..., :inside] == 0).sum()) >= 1
+    nws = conv_workspace_bytes(shp, 0, cus)
+    if "splitk" in edge:
+        assert plan_splitk(shp, 0, cus)[0] >= 2, "the case is there for a split K"
+    assert view_kernel(shp, 0, cus, scratch=bool(nws), partial="partial" in edge) == family, "the table's family is not what the selection reads as"
+    if "plus" in edge:
+        assert int((inp["w"] == 0).sum()) == 6 * 64 * 64 and inp["w"][1, 1].abs().min().item() == 1
+    xw, xc, yw, yc = extra["geom"]
+    assert xc + shp[3] <= xw and yc + Cout <= yw and (xw | xc | yw | yc) % 8 == 0
+    return dict(max=pre.abs().max().item(), zeros=int((pre == 0).sum()), splits=plan_splitk(shp, 0, cus)[0])
+
+
+def check_vdgrad(case, cus):
+    cid, kind, shp, family, extra = case
+    inp = view_dgrad_inputs(shp, "plus" in extra["edge"])
+    check_dgrad_inputs(inp)
+    assert int((inp["dx"] != 0).sum()) >= 1
+    nws = conv_workspace_bytes(shp, 1, cus)
+    if "splitk" in extra["edge"]:
+        assert plan_splitk(shp, 1, cus)[0] >= 2, "the case is there for a split K"
+    assert view_kernel(shp, 1, cus, scratch=bool(nws), ld=True) == family, "the table's family is not what the selection reads as"
+    yw, yc, xw, xc, mw, mc = extra["geom"]
+    assert yc + co8_of(shp[4]) <= yw and xc + shp[3] <= xw and mc + shp[3] <= mw and (yw | yc | xw | xc | mw | mc) % 8 == 0
+    return dict(max=inp["dx"].abs().max().item(), splits=plan_splitk(shp, 1, cus)[0])
+
+
+def check_vwgrad(case, cus):
+    cid, kind, shp, family, extra = case
+    inp = wgrad_inputs(shp)
+    check_wgrad_inputs(inp)
+    xw, xc, yw, yc = extra["geom"]
+    assert xc + shp[3] <= xw and yc + co8_of(shp[4]) <= yw and (xw | xc | yw | yc) % 8 == 0 and shp[0] * shp[1] * shp[2] * max(xw, yw) < 2 ** 31
+    rows, pw = wg_rows_eligible(shp) and max(xw, yw) <= 0xFFFF, wg_pw_eligible(shp)
+    assert family.startswith("conv_wgrad_rows_kernel<") == rows and (family == "conv_wgrad_pw_kernel") == (pw and not rows)
+    if extra["edge"] == "pitch":
+        assert wg_rows_eligible(shp) and xw > 0xFFFF, "the case is there for a pitch the row-streaming kernel declines"
+    return dict(max=inp["dw"].abs().max().item())
+
+
+def check_concat2(case, cus):
+    cid, kind, shp, family, extra = case
+    inp = forward_inputs(shp)
+    check_forward_inputs(inp, relu=True)
+    M, c1, c2, pitch = shp[0] * shp[1] * shp[2], extra["c1"], shp[3] - extra["c1"], extra["pitch"]
+    assert M >= 2048 and M % 128 != 0 and c1 % 64 == 0 and c2 % 64 == 0 and pitch >= max(c1, c2) and pitch % 8 == 0
+    # both sources matter to every output column: a K-step taken from the wrong source, or skipped, changes the sums
+    assert int((inp["x"][..., :c1] != 0).sum()) >= 1 and int((inp["x"][..., c1:] != 0).sum()) >= 1
+    return dict(max=inp["pre"].abs().max().item(), zeros=int((inp["pre"] == 0).sum()))
+
+
+VIEW_CHECKS = dict(vfwd=check_vfwd, vdgrad=check_vdgrad, vwgrad=check_vwgrad, concat2=check_concat2)
+
+
+# ---- the DAN context block (net/danet.py se_inception_block), unfused, in float64: ten convolutions, TF 'same' 2x2 / stride-1 average pool,
+# concat, residual add - and its autograd.  ops.context_block computes the same function another way (three 1x1s as one, branch 2's 1x1 in
+# front of its pool, each 3x1 / 1x3 pair as one 3x3, slices instead of a concat); with the operands below every value either route stores in
+# 16 bits is a multiple of 1/4 that both 16-bit types hold exactly and every fp32 sum is exact, so the two agree to the last bit.
+BLOCK_LAYERS = [("branch1_conv_1x1", 1, 1, None, 64), ("branch2_conv_1x1", 1, 1, None, 64), ("branch3_conv_1x1", 1, 1, None, 64), ("branch3_conv_3x1", 3, 1, 64, 32),
+                ("branch3_conv_1x3", 1, 3, 64, 32), ("branch4_conv_1x1", 1, 1, None, 64), ("branch4_conv_3x3", 3, 3, 64, 64), ("branch4_conv_1x3", 3, 1, 64, 32),
+                ("branch4_conv_3x1", 1, 3, 64, 32), ("residual_conv", 1, 1, 256, None)]          # (kh, kw, Cin, Cout); None = the block's channel count
+# (id, (N, H, W, C), seed, non-zero products per output of the layers above, density of x and of the upstream gradient)
+#   streaming: 2079 pixels = 16.2 items of the streaming GEMM (its floor is 2048), 33 x 63 of 40 x 64 tile pixels = 0.81: the register-resident
+#   64 -> 64 kernel takes the 3x3s, the row-streaming kernel their weight gradients; splitk: 72 pixels, every convolution with >= 8 K tiles splits
+BLOCK_CASES = [
+    ("streaming_1x33x63", (1, 33, 63, 256), 1, (4, 4, 4, 4, 4, 4, 6, 4, 4, 4), 0.25, 0.05),
+    ("splitk_2x6x6", (2, 6, 6, 256), 2, (4, 4, 4, 4, 4, 4, 6, 4, 4, 4), 0.25, 0.05),
+]
+
+
+def conv_taps(x, w, b):
+    """conv_ref for stride 1 / 'same' as one float64 matrix product per tap over the shifted map (the block's reference: many times faster on
+    a CPU than the float64 convolution, and differentiable the same way)."""
+    kh, kw = w.shape[0], w.shape[1]
+    N, H, W, _ = x.shape
+    (pt, pb, _), (pl, pr, _) = same_pad(H, kh, 1), same_pad(W, kw, 1)
+    xp = F.pad(x, (0, 0, pl, pr, pt, pb))
+    y = b.reshape(1, 1, 1, -1)
+    for i in range(kh):
+        for j in range(kw):
+            y = y + xp[:, i:i + H, j:j + W] @ w[i, j]
+    return y
+
+
+def avg_pool_ref(x):
+    """tf.layers.average_pooling2d(x, (2, 2), 1, 'same'): window rows h, h + 1 and columns w, w + 1, divided by the number of them inside the map."""
+    N, H, W, C = x.shape
+    xp = F.pad(x, (0, 0, 0, 1, 0, 1))
+    s = xp[:, :H, :W] + xp[:, 1:, :W] + xp[:, :H, 1:] + xp[:, 1:, 1:]
+    cnt = torch.full((H, W), 4.0, dtype=F64)
+    cnt[H - 1, :], cnt[:, W - 1] = 2.0, 2.0
+    cnt[H - 1, W - 1] = 1.0
+    return s / cnt.reshape(1, H, W, 1)
+
+
+@functools.lru_cache(maxsize=2)
+def block_inputs(nhwc, seed, products, px, pdy):
+    """Sparse integer input and upstream gradient, sparse ternary kernels (about `products` non-zero taps per output), biases in [-1, 1]."""
+    N, H, W, C = nhwc
+    g = gen(seed)
+    P = {}
+    for (name, kh, kw, cin, cout), k in zip(BLOCK_LAYERS, products):
+        cin, cout = cin or C, cout or C
+        P[name + "/kernel"] = ternary((kh, kw, cin, cout), min(1.0, k / (kh * kw * cin)), g)
+        P[name + "/bias"] = small((cout,), g, -1, 1)
+    x = ternary((N, H, W, C), px, g) * small((N, H, W, C), g, 1, 2)
+    dy = ternary((N, H, W, C), pdy, g)
+    return dict(x=x, dy=dy, P=P)
+
+
+def block_ref(x, P, commuted=False):
+    """-> (out, dict of every intermediate).  commuted: branch 2 as conv-then-pool (the order ops.context_block takes; the same function)."""
+    t = {}
+
+    def cr(inp, name, key):
+        t[key + "_pre"] = conv_taps(inp, P[name + "/kernel"], P[name + "/bias"])
+        t[key + "_pre"].retain_grad() if t[key + "_pre"].requires_grad else None
+        t[key] = torch.relu(t[key + "_pre"])
+        return t[key]
+
+    b1 = cr(x, "branch1_conv_1x1", "b1")
+    if commuted:
+        t["p2"] = conv_taps(x, P["branch2_conv_1x1/kernel"], P["branch2_conv_1x1/bias"])
+        t["p2"].retain_grad() if t["p2"].requires_grad else None
+        t["b2_pre"] = avg_pool_ref(t["p2"])
+        t["b2_pre"].retain_grad() if t["b2_pre"].requires_grad else None
+        b2 = t["b2"] = torch.relu(t["b2_pre"])
+    else:
+        t["avg"] = avg_pool_ref(x)
+        b2 = cr(t["avg"], "branch2_conv_1x1", "b2")
+    b3 = cr(x, "branch3_conv_1x1", "b3")
+    b3a, b3b = cr(b3, "branch3_conv_3x1", "b3a"), cr(b3, "branch3_conv_1x3", "b3b")
+    b4 = cr(x, "branch4_conv_1x1", "b4")
+    b43 = cr(b4, "branch4_conv_3x3", "b43")
+    b4a, b4b = cr(b43, "branch4_conv_1x3", "b4a"), cr(b43, "branch4_conv_3x1", "b4b")
+    t["hyper"] = torch.cat([b1, b2, b3a, b3b, b4a, b4b], dim=-1)
+    r = cr(t["hyper"], "residual_conv", "res")
+    t["out"] = r + x
+    return t["out"], t
+
+
+RELUS = ("b1", "b2", "b3", "b3a", "b3b", "b4", "b43", "b4a", "b4b", "res")
+
+
+@functools.lru_cache(maxsize=4)
+def block_reference(case, commuted=False):
+    """The reference of one BLOCK_CASES entry: (inputs, dict of out, dx, the 20 variable gradients and every intermediate with its gradient)."""
+    cid, nhwc, seed, products, px, pdy = case
+    inp = block_inputs(nhwc, seed, products, px, pdy)
+    x = inp["x"].clone().requires_grad_(True)
+    P = {n: v.clone().requires_grad_(True) for n, v in inp["P"].items()}
+    out, t = block_ref(x, P, commuted)
+    out.backward(inp["dy"])
+    return inp, dict(out=out.detach(), dx=x.grad, grads={n: v.grad for n, v in P.items()}, t=t)
+
+
+def holds16(v):
+    """every element survives a round trip through bf16 and through IEEE half"""
+    v = v.detach()
+    return bool(torch.equal(v.to(torch.bfloat16).to(F64), v)) and bool(torch.equal(v.to(torch.float16).to(F64), v))
+
+
+def check_block_case(case):
+    """The conditions of an exact block case, on the reference alone; returns figures for the log."""
+    (inp, ref), (_, com) = block_reference(case, False), block_reference(case, True)
+    x, dy, t, tc = inp["x"], inp["dy"], ref["t"], com["t"]
+    # the two orders of branch 2 are the same function, exactly (every quarter and half is dyadic)
+    assert torch.equal(ref["out"], com["out"]) and torch.equal(ref["dx"], com["dx"]) and all(torch.equal(ref["grads"][n], com["grads"][n]) for n in ref["grads"])
+    # ---- every tensor either route stores in 16 bits: forward ...
+    stored = {"x": x, "avg(x)": t["avg"], "p2 = conv(x) before the pool": tc["p2"], "T[b3 | b4]": torch.cat([t["b3"], t["b4"]], -1), "hyper": t["hyper"], "U": t["b43"],
+              "r": t["res"], "out": t["out"], "dy": dy}
+    # ... and backward: gr = dy (r > 0); d hyper, dU, dT with their ReLU masks applied = the gradients of the pre-activations; dT[128:192] = the
+    # pool's backward; x's buffer after each of its three deliveries (skip path, the fused 1x1's data gradient, branch 1's)
+    g = {k: t[k + "_pre"].grad for k in RELUS}
+    stored.update({"gr": g["res"], "d hyper": torch.cat([g["b1"], g["b2"], g["b3a"], g["b3b"], g["b4a"], g["b4b"]], -1), "dU": g["b43"],
+                   "dT": torch.cat([g["b3"], g["b4"], tc["p2"].grad], -1)})
+    dx_b1 = dgrad_ref(g["b1"], inp["P"]["branch1_conv_1x1/kernel"], x.shape[1], x.shape[2])
+    stored.update({"xbuf after the skip path": dy, "xbuf after the fused 1x1": ref["dx"] - dx_b1, "xbuf = dx": ref["dx"]})
+    for name, v in stored.items():
+        assert holds16(v), (name, "does not survive 16 bits", v.abs().max().item())
+        assert torch.equal(v * 4, (v * 4).round()), name
+    # ---- every fp32 sum below 2^24 in units of its terms (quarters): the sum of the magnitudes of a convolution's terms, forward and weight gradient
+    worst = 0.0
+    for (name, kh, kw, _, _), key, src in zip(BLOCK_LAYERS, ("b1", "b2", "b3", "b3a", "b3b", "b4", "b43", "b4a", "b4b", "res"),
+                                              (x, t["avg"], x, t["b3"], t["b3"], x, t["b4"], t["b43"], t["b43"], t["hyper"])):
+        w, b = inp["P"][name + "/kernel"], inp["P"][name + "/bias"]
+        fwd = conv_ref(src.detach().abs(), w.abs(), b.abs()).max().item()
+        dw, db = wgrad_ref(src.detach().abs(), g[key].abs(), kh, kw)
+        dxs = dgrad_ref(g[key].abs(), w.abs(), x.shape[1], x.shape[2]).max().item()
+        worst = max(worst, fwd, dw.max().item(), db.max().item(), dxs)
+    assert worst * 4 < 2 ** 24, worst
+    # ---- the case cannot go trivial
+    for k in RELUS:
+        assert int((t[k] != 0).sum()) >= 1, (k, "is all zero")
+        assert int((t[k + "_pre"] <= 0).sum()) >= 1 and int((t[k + "_pre"] > 0).sum()) >= 1, (k, "ReLU without zeros or without positives")
+    assert all(int((v != 0).sum()) >= 1 for v in ref["grads"].values()) and len(ref["grads"]) == 20 and int((ref["dx"] != dy).sum()) >= 1
+    return dict(max16=max(v.abs().max().item() for v in stored.values()), worst_sum=worst, dx_nonzero=int((ref["dx"] != 0).sum()),
+                grad_nonzero={n: int((v != 0).sum()) for n, v in ref["grads"].items()})
+
+
 def dispatch_rows():
     """The 30 rows of tests/test_conv_dispatch_gpu.CASES as (id, shape8, call, family)."""
     import test_conv_dispatch_gpu as D
@@ -459,31 +787,38 @@ def all_cases():
     out += [("wgrad_" + n, "wgrad", s, f, dict(edge=e, cin_real=c)) for n, s, f, c, e in WGRAD_EDGES]
     out += [("pool_" + n, "pool", s, f, dict(edge="")) for n, s, f in POOL_EDGES]
     out += [("fold_%dx%dx%d" % nhw, "fold", S(*nhw, 64, 64), "conv3x3_c64_kernel<true, true>", dict(edge="")) for nhw in FOLD_SHAPES]
+    out += [(n, k, s, f, dict(edge=e, cin_real=c, valid=True)) for n, k, s, f, c, e in VALID_CASES]
+    out += [("vfwd_" + n, "vfwd", s, f, dict(edge=e, geom=g, inside=i)) for n, s, f, g, i, e in VFWD_CASES]
+    out += [("vdgrad_" + n, "vdgrad", s, f, dict(edge=e, geom=g)) for n, s, f, g, e in VDGRAD_CASES]
+    out += [("vwgrad_" + n, "vwgrad", s, f, dict(edge=e, geom=g)) for n, s, f, g, e in VWGRAD_CASES]
+    out += [("concat2_" + c[0], "concat2", concat2_shape(c), c[6], dict(edge="", c1=c[2], pitch=c[5])) for c in CONCAT2_CASES]
     return out
 
 
 def check_case_inputs(case, cus=256):
     """The conditions of one case on its reference and on the restated plans (no GPU); returns the figures for the log."""
     cid, kind, shp, family, extra = case
-    edge, row = extra.get("edge", ""), extra.get("row")
+    edge, row, valid = extra.get("edge", ""), extra.get("row"), bool(extra.get("valid"))
+    if kind in VIEW_CHECKS:
+        return VIEW_CHECKS[kind](case, cus)
     if kind == "fwd":
-        inp = forward_inputs(shp)
+        inp = forward_inputs(shp, cin_real=extra.get("cin_real"), valid=valid)
         check_forward_inputs(inp, relu=True)
         if edge == "splitk":
-            assert plan_splitk(shp, 0, cus)[0] >= 2, "the case is there for a split K"
+            assert plan_splitk(shp, 0, cus, valid)[0] >= 2, "the case is there for a split K"
         return dict(max=inp["pre"].abs().max().item(), zeros=int((inp["pre"] == 0).sum()))
     if kind == "pool":
         inp = forward_inputs(shp)
         check_forward_inputs(inp, relu=True, pool=True)
         return dict(max=inp["pre"].abs().max().item(), zeros=int((inp["pre"] == 0).sum()), late_ties=late_ties(torch.relu(inp["pre"])))
     if kind == "dgrad":
-        inp = dgrad_inputs(shp)
+        inp = dgrad_inputs(shp, valid=valid)
         check_dgrad_inputs(inp)
         if edge == "splitk":
-            assert plan_splitk(shp, 1, cus)[0] >= 2, "the case is there for a split K"
+            assert plan_splitk(shp, 1, cus, valid)[0] >= 2, "the case is there for a split K"
         return dict(max=inp["dx"].abs().max().item())
     if kind == "wgrad":
-        inp = wgrad_inputs(shp, cin_real=extra.get("cin_real"))
+        inp = wgrad_inputs(shp, cin_real=extra.get("cin_real"), valid=valid)
         check_wgrad_inputs(inp)
         check_wgrad_cuts(shp, edge, cus)
         return dict(max=inp["dw"].abs().max().item())
@@ -558,8 +893,8 @@ class _Api:
     def stream(self):
         return self.lib.stream()
 
-    def desc(self, shp):
-        return self.ops._desc(*shp)
+    def desc(self, shp, valid=False):
+        return self.ops._desc(*shp, valid=valid)
 
     def a16(self, t):
         return t.to(self.act).to(self.dev)
@@ -594,14 +929,15 @@ class _Api:
 
 def run_fwd(api, cid, shp, family, extra):
     N, H, W, Cin, Cout, kh, kw, s = shp
-    inp = forward_inputs(shp)
+    valid = bool(extra.get("valid"))
+    inp = forward_inputs(shp, cin_real=extra.get("cin_real"), valid=valid)
     check_forward_inputs(inp, relu=True)
-    d, L, ptr = api.desc(shp), api.L, api.ptr
+    d, L, ptr = api.desc(shp, valid), api.L, api.ptr
     dp = ctypes.byref(d)
     x, w, b, res = api.a16(inp["x"]), api.f32(inp["w"]), api.f32(inp["b"]), api.a16(inp["res"])
     wf, _ = api.ops.pack_conv_weight(d, w, need_bwd=False)
     nws = L.danhip_conv2d_workspace_bytes(dp, 0)
-    assert nws == conv_workspace_bytes(shp, 0, api.cus)
+    assert nws == conv_workspace_bytes(shp, 0, api.cus, valid)
     ws, nws = api.scratch(nws)
     row, edge = extra.get("row"), extra.get("edge", "")
 
@@ -627,7 +963,7 @@ def run_fwd(api, cid, shp, family, extra):
             bits_call()
         return
     if edge == "splitk":
-        assert nws and plan_splitk(shp, 0, api.cus)[0] >= 2
+        assert nws and plan_splitk(shp, 0, api.cus, valid)[0] >= 2
     outs = [False, True] if edge != "f32only" else [True]
     for use_ws in ([False, True] if nws else [False]):
         for f32out in outs:
@@ -646,14 +982,15 @@ def run_fwd(api, cid, shp, family, extra):
 
 def run_dgrad(api, cid, shp, family, extra):
     N, H, W, Cin, Cout, kh, kw, s = shp
-    inp = dgrad_inputs(shp)
+    valid = bool(extra.get("valid"))
+    inp = dgrad_inputs(shp, valid=valid)
     check_dgrad_inputs(inp)
-    d, L, ptr = api.desc(shp), api.L, api.ptr
+    d, L, ptr = api.desc(shp, valid), api.L, api.ptr
     dp = ctypes.byref(d)
     dy, mask, old = api.a16(inp["dy"]), api.a16(inp["mask"]), api.a16(inp["old"])
     _, wb = api.ops.pack_conv_weight(d, api.f32(inp["w"]), need_bwd=True)
     nws = L.danhip_conv2d_workspace_bytes(dp, 1)
-    assert nws == conv_workspace_bytes(shp, 1, api.cus)
+    assert nws == conv_workspace_bytes(shp, 1, api.cus, valid)
     ws, nws = api.scratch(nws)
     takes_bits = bool(L.danhip_conv2d_bwd_data_takes_bits(dp))
     bits = relu_bits(inp["mask"]).to(api.dev) if takes_bits else None
@@ -680,7 +1017,7 @@ def run_dgrad(api, cid, shp, family, extra):
             assert_equal(dx, dgrad_outputs(inp, form != "none", acc), "%s acc=%d" % (cid, acc))
         return
     if edge == "splitk":
-        assert nws and plan_splitk(shp, 1, api.cus)[0] >= 2
+        assert nws and plan_splitk(shp, 1, api.cus, valid)[0] >= 2
     if edge == "pw256":
         assert L.danhip_set_option(b"pw_dgrad_ld_bn", 256) == 0
     try:
@@ -706,10 +1043,11 @@ def run_dgrad(api, cid, shp, family, extra):
 
 def run_wgrad(api, cid, shp, family, extra):
     N, H, W, Cin, Cout, kh, kw, s = shp
-    inp = wgrad_inputs(shp, cin_real=extra.get("cin_real"))
+    valid = bool(extra.get("valid"))
+    inp = wgrad_inputs(shp, cin_real=extra.get("cin_real"), valid=valid)
     check_wgrad_inputs(inp)
     cr = inp["cin_real"]
-    d, L, ptr = api.desc(shp), api.L, api.ptr
+    d, L, ptr = api.desc(shp, valid), api.L, api.ptr
     dp = ctypes.byref(d)
     x, dy = api.a16(inp["x"]), api.a16(inp["dy"])
     nws = L.danhip_conv2d_bwd_weight_workspace_bytes(dp)
@@ -815,7 +1153,170 @@ def run_fold(api, cid, shp, family, extra):
     assert_equal(dx, inp["dx"], cid + " dx of the unfolded call")
 
 
-RUNNERS = dict(fwd=run_fwd, dgrad=run_dgrad, wgrad=run_wgrad, pool=run_pool, fold=run_fold)
+# ---- channel-slice views
+def view_buffer(api, dims, width, c0, t=None):
+    """[N,H,W,width] of NAN16 with t (float64 [N,H,W,C], or nothing) in channels c0 : c0 + C -> (buffer, the slice as a view)."""
+    N, H, W, C = dims
+    buf = torch.full((N, H, W, width), NAN16, dtype=torch.int16, device=api.dev).view(api.act)
+    if t is not None:
+        buf[..., c0:c0 + C] = api.a16(t)
+    return buf, buf[..., c0:c0 + C]
+
+
+def assert_background(buf, c0, C, what):
+    raw = buf.view(torch.int16)
+    changed = int((raw[..., :c0] != NAN16).sum()) + int((raw[..., c0 + C:] != NAN16).sum())
+    assert changed == 0, "%s: %d elements outside the written slice changed" % (what, changed)
+
+
+def run_vfwd(api, cid, shp, family, extra):
+    N, H, W, Cin, Cout, kh, kw, s = shp
+    edge, inside = extra["edge"], extra["inside"]
+    inp = view_forward_inputs(shp, "plus" in edge)
+    check_forward_inputs(inp, relu=True)
+    d, L, ptr, vptr = api.desc(shp), api.L, api.ptr, api.ops._vptr
+    dp = ctypes.byref(d)
+    xw, xc, yw, yc = extra["geom"]
+    xbuf, xv = view_buffer(api, (N, H, W, Cin), xw, xc, inp["x"])
+    wf, _ = api.ops.pack_conv_weight(d, api.f32(inp["w"]), need_bwd=False)
+    b = api.f32(inp["b"])
+    nws = L.danhip_conv2d_workspace_bytes(dp, 0)
+    assert nws == conv_workspace_bytes(shp, 0, api.cus)
+    if "splitk" in edge:
+        assert nws and plan_splitk(shp, 0, api.cus)[0] >= 2
+    ws, nws = api.scratch(nws)
+    pitch = api.lib.ConvPitch(xw, yw, 0)
+    for use_ws in ([False, True] if nws else [False]):
+        for relu, relu_ch in ((1, Cout), (1, inside), (1, 0), (0, Cout)):
+            ybuf, yv = view_buffer(api, (N, H, W, Cout), yw, yc)
+            api.ok(L.danhip_conv2d_fwd_strided(dp, vptr(xv), ptr(wf), ptr(b), vptr(yv), relu, relu_ch, ctypes.byref(pitch), ptr(ws) if use_ws else None,
+                                               nws if use_ws else 0, api.stream()))
+            relu_co = relu_ch if relu else 0
+            what = "%s ws=%d relu=%d relu_channels=%d" % (cid, use_ws, relu, relu_ch)
+            want = view_kernel(shp, 0, api.cus, scratch=use_ws, partial=0 < relu_co < Cout)
+            if use_ws == bool(nws) and (0 < relu_co < Cout) == ("partial" in edge):
+                assert want == family, (what, want, family)       # the call the table lists
+            api.launched(cid, what, want, want=want)
+            assert_equal(yv, view_forward_outputs(inp, relu_co), what)
+            assert_background(ybuf, yc, Cout, what)
+
+
+def run_vdgrad(api, cid, shp, family, extra):
+    N, H, W, Cin, Cout, kh, kw, s = shp
+    edge = extra["edge"]
+    inp = view_dgrad_inputs(shp, "plus" in edge)
+    check_dgrad_inputs(inp)
+    d, L, ptr, vptr = api.desc(shp), api.L, api.ptr, api.ops._vptr
+    dp = ctypes.byref(d)
+    co8 = co8_of(Cout)
+    yw, yc, xw, xc, mw, mc = extra["geom"]
+    dybuf, dyv = view_buffer(api, (N, H, W, co8), yw, yc, inp["dy"])
+    mbuf, mv = view_buffer(api, (N, H, W, Cin), mw, mc, inp["mask"])
+    mdense = api.a16(inp["mask"])
+    _, wb = api.ops.pack_conv_weight(d, api.f32(inp["w"]), need_bwd=True)
+    nws = L.danhip_conv2d_workspace_bytes(dp, 1)
+    assert nws == conv_workspace_bytes(shp, 1, api.cus)
+    if "splitk" in edge:
+        assert nws and plan_splitk(shp, 1, api.cus)[0] >= 2
+    ws, nws = api.scratch(nws)
+    for form in ("none", "view", "dense"):                   # no mask / the mask a slice of a third buffer (aux_pitch) / a dense mask (aux_pitch = 0)
+        pitch = api.lib.ConvPitch(yw, xw, mw if form == "view" else 0)
+        m = None if form == "none" else vptr(mv) if form == "view" else ptr(mdense)
+        for use_ws in ([False, True] if nws else [False]):
+            for acc in (0, 1):
+                dxbuf, dxv = view_buffer(api, (N, H, W, Cin), xw, xc, inp["old"])
+                api.ok(L.danhip_conv2d_bwd_data_strided(dp, vptr(dyv), ptr(wb), m, vptr(dxv), acc, ctypes.byref(pitch), ptr(ws) if use_ws else None,
+                                                        nws if use_ws else 0, api.stream()))
+                what = "%s mask=%s ws=%d acc=%d" % (cid, form, use_ws, acc)
+                want = view_kernel(shp, 1, api.cus, scratch=use_ws, ld=form != "none" or bool(acc))
+                if use_ws == bool(nws) and form != "none" and acc:
+                    assert want == family, (what, want, family)   # the call the table lists
+                api.launched(cid, what, want, want=want)
+                assert_equal(dxv, dgrad_outputs(inp, form != "none", acc), what)
+                assert_background(dxbuf, xc, Cin, what)
+
+
+def run_vwgrad(api, cid, shp, family, extra):
+    N, H, W, Cin, Cout, kh, kw, s = shp
+    edge = extra["edge"]
+    inp = wgrad_inputs(shp)
+    check_wgrad_inputs(inp)
+    d, L, ptr, vptr = api.desc(shp), api.L, api.ptr, api.ops._vptr
+    dp = ctypes.byref(d)
+    xw, xc, yw, yc = extra["geom"]
+    xbuf, xv = view_buffer(api, (N, H, W, Cin), xw, xc, inp["x"])
+    dybuf, dyv = view_buffer(api, (N, H, W, co8_of(Cout)), yw, yc, inp["dy"])
+    pitch = api.lib.ConvPitch(xw, yw, 0)
+
+    def call(ws, nws):
+        dw, db = api.f32(inp["dw0"]), api.f32(inp["db0"])
+        rc = L.danhip_conv2d_bwd_weight_strided(dp, vptr(xv), vptr(dyv), ptr(dw), ptr(db), Cin, ctypes.byref(pitch), ptr(ws) if nws else None, nws, api.stream())
+        return rc, dw, db
+
+    def exact(rc, dw, db, what):
+        api.ok(rc)
+        got = api.launched(cid, what, family)
+        assert_equal(dw, inp["dw"], "%s %s dw" % (cid, what))
+        assert_equal(db, inp["db"], "%s %s db" % (cid, what))
+        return got
+
+    assert L.danhip_get_option(b"deterministic") == 0
+    nws = L.danhip_conv2d_bwd_weight_workspace_bytes(dp)      # (the query answers for dense pitches)
+    assert nws == wgrad_workspace_bytes(shp, api.cus)
+    ws, nws = api.scratch(nws)
+    dense = L.danhip_conv_wgrad_kernel_label(dp).decode()
+    for form in ("atomic", "ws"):
+        got = exact(*call(ws, nws if form == "ws" else 0), form)
+        if edge == "pitch":                                  # the row-streaming kernel declines: the generic tiles take the call
+            assert dense.startswith("conv_wgrad_rows_kernel<") and got.startswith("conv_wgrad_kernel<"), (dense, got)
+        else:
+            assert got == dense, (got, dense)
+    if edge not in ("det", "pitch"):
+        return
+    assert L.danhip_set_option(b"deterministic", 1) == 0
+    try:
+        nws = L.danhip_conv2d_bwd_weight_workspace_bytes(dp)
+        assert nws > 0
+        ws, nws = api.scratch(nws)
+        if edge == "pitch":                                  # danhip.h: the query cannot answer for this call's family -> DANHIP_EINVAL, nothing launched
+            rc, dw, db = call(ws, nws)
+            assert rc == -1, rc
+            torch.cuda.synchronize()
+            assert_equal(dw, inp["dw0"], cid + " refused call: dw untouched")
+            return
+        runs = []
+        for i in range(2):
+            rc, dw, db = call(ws, nws)
+            exact(rc, dw, db, "deterministic run %d" % i)
+            runs.append((dw, db))
+        assert torch.equal(runs[0][0].view(torch.int32), runs[1][0].view(torch.int32)) and torch.equal(runs[0][1].view(torch.int32), runs[1][1].view(torch.int32))
+    finally:
+        L.danhip_set_option(b"deterministic", 0)
+
+
+def run_concat2(api, cid, shp, family, extra):
+    N, H, W, Cin, Cout, kh, kw, s = shp
+    c1, pitch = extra["c1"], extra["pitch"]
+    c2 = Cin - c1
+    inp = forward_inputs(shp)
+    check_forward_inputs(inp, relu=True)
+    d, L, ptr, vptr = api.desc(shp), api.L, api.ptr, api.ops._vptr
+    dp = ctypes.byref(d)
+    assert L.danhip_conv2d_fwd_concat2_supported(dp, c1, pitch) == 1
+    # two separate buffers `pitch` wide: the first source in channels 0 : c1, the second right-aligned in pitch - c2 : pitch
+    abuf, av = view_buffer(api, (N, H, W, c1), pitch, 0, inp["x"][..., :c1])
+    fbuf, fv = view_buffer(api, (N, H, W, c2), pitch, pitch - c2, inp["x"][..., c1:])
+    wf, _ = api.ops.pack_conv_weight(d, api.f32(inp["w"]), need_bwd=False)
+    b = api.f32(inp["b"])
+    for relu in (0, 1):
+        y = torch.full((N, H, W, Cout), float("nan"), dtype=api.act, device=api.dev)
+        api.ok(L.danhip_conv2d_fwd_concat2(dp, vptr(av), vptr(fv), c1, pitch, ptr(wf), ptr(b), ptr(y), relu, api.stream()))
+        api.launched(cid, "relu=%d" % relu, family)
+        assert_equal(y, forward_outputs(inp, relu, False), "%s relu=%d" % (cid, relu))
+
+
+RUNNERS = dict(fwd=run_fwd, dgrad=run_dgrad, wgrad=run_wgrad, pool=run_pool, fold=run_fold, vfwd=run_vfwd, vdgrad=run_vdgrad, vwgrad=run_vwgrad,
+               concat2=run_concat2)
 
 
 def run_case(case, dev):

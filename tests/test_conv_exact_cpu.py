@@ -49,6 +49,56 @@ def test_stride_two_puts_the_odd_pad_pixel_at_the_bottom_right():
     assert CE.conv_ref(x, w, None, 2).abs().sum().item() == 0
 
 
+@pytest.mark.parametrize("shape", [(2, 29, 35, 3, 8, 7, 7, 2), (1, 9, 11, 6, 5, 3, 3, 1), (1, 10, 12, 4, 3, 3, 3, 2), (2, 8, 7, 4, 3, 5, 2, 3)])
+def test_valid_reference_is_the_oracle_convolution_and_its_gradients(shape):
+    """padding='valid': floor((in - k) / s) + 1 windows, no padding; (10, 12) at stride 2 and (8, 7) at stride 3 leave rows / columns behind the
+    last window that no output reads (their data gradient is 0)."""
+    N, H, W, Cin, Cout, kh, kw, s = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    x, w, b = torch.randn((N, H, W, Cin), generator=g), torch.randn((kh, kw, Cin, Cout), generator=g), torch.randn((Cout,), generator=g)
+    xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    want = T.conv2d_valid(xr, wr, br, stride=s)
+    got = CE.conv_ref(x.double(), w.double(), b.double(), s, valid=True)
+    assert tuple(got.shape) == (N, CE.out_size(H, kh, s, True), CE.out_size(W, kw, s, True), Cout) == tuple(want.shape)
+    assert (got - want.detach().double()).abs().max().item() <= 1e-5 * max(1.0, want.abs().max().item())
+    dy = torch.randn(want.shape, generator=g)
+    want.backward(dy)
+    dx = CE.dgrad_ref(dy.double(), w.double(), H, W, s, valid=True)
+    dw, db = CE.wgrad_ref(x.double(), dy.double(), kh, kw, s, valid=True)
+    for a, r in ((dx, xr.grad), (dw, wr.grad), (db, br.grad)):
+        assert a.shape == r.shape and (a - r.double()).abs().max().item() <= 1e-5 * max(1.0, r.abs().max().item())
+    # by hand: output (i, j) reads the window whose top-left pixel is (i s, j s)
+    i, j = got.shape[1] - 1, got.shape[2] - 1
+    win = x[0, i * s:i * s + kh, j * s:j * s + kw].double()
+    assert abs((win.unsqueeze(-1) * w.double()).sum((0, 1, 2))[0].item() + b[0].item() - got[0, i, j, 0].item()) <= 1e-9
+    if (H - kh) % s:
+        assert dx[:, (got.shape[1] - 1) * s + kh:].abs().sum().item() == 0
+
+
+def test_view_selection_and_plus_kernel_restate_the_sources_by_hand():
+    # conv_halo_c64.hip c64_eligible: 3x3 64 -> 64 with 30 x 62 of 32 x 64 tile pixels = 0.91 >= 0.78, and no partial ReLU; 37 x 40 of 40 x 64 = 0.58:
+    # declined -> 4440 pixels >= 2048: the streaming GEMM's tap form, 64 wide
+    S = CE.S
+    assert CE.view_kernel(S(1, 30, 62, 64, 64), 0, 256, scratch=True) == "conv3x3_c64_kernel<false>"
+    assert CE.view_kernel(S(1, 30, 62, 64, 64), 1, 256, scratch=True) == "conv3x3_c64_kernel<true>"
+    assert CE.view_kernel(S(3, 37, 40, 64, 64), 0, 256) == "conv_pointwise_kernel<64, 4, false, true, true>"
+    # ... with a partial ReLU the 1860 pixels are below the streaming GEMM's floor: flat-M, and with scratch its 8 tiles split K in 2
+    assert CE.view_kernel(S(1, 30, 62, 64, 64), 0, 256, scratch=True, partial=True) == "conv_igemm_kernel<256, 64, 1, true>"
+    assert CE.plan_splitk(S(1, 30, 62, 64, 64), 0, 256)[0] == 2 and CE.plan_splitk(S(2, 6, 6, 64, 64), 0, 256) == (2, 5, 72, 64)
+    # 16 images of 3 x 3, 1024 -> 192: 144 pixels, 64-wide tiles: 1 x 3 tiles, 16 K tiles -> min(171, 16 / 4, 36) = 4 splits of 4
+    assert CE.plan_splitk(S(16, 3, 3, 1024, 192, 1), 0, 256) == (4, 4, 144, 192)
+    # its data gradient has K = 192: 3 K tiles < 8, no split; the residual conv's (K = 1024, 256 columns: 2 x 2 tiles of 128) splits in 4
+    assert CE.plan_splitk(S(16, 3, 3, 1024, 192, 1), 1, 256)[0] == 1 and CE.plan_splitk(S(16, 3, 3, 256, 1024, 1), 1, 256) == (4, 4, 144, 256)
+    # streaming GEMM: 256-wide tiles where Co % 256 == 0, except a data gradient with epilogue inputs (option pw_dgrad_ld_bn = 128)
+    assert CE.view_kernel(S(1, 40, 56, 256, 192, 1), 1, 256, ld=True) == "conv_pointwise_kernel<128, 4, true, true, false>"
+    assert CE.view_kernel(S(1, 40, 56, 256, 192, 1), 1, 256, ld=False) == "conv_pointwise_kernel<256, 3, true, false, false>"
+    assert CE.view_kernel(S(1, 40, 56, 192, 256, 1), 0, 256) == "conv_pointwise_kernel<256, 3, false, true, false>"
+    m = CE.plus_mask()
+    assert m[:, :, 5, 7].tolist() == [[0, 1, 0], [0, 1, 0], [0, 1, 0]] and m[:, :, 5, 40].tolist() == [[0, 0, 0], [1, 1, 1], [0, 0, 0]]
+    for dt in (torch.bfloat16, torch.float16):                     # the background pattern is a NaN in both 16-bit types
+        assert bool(torch.tensor([CE.NAN16], dtype=torch.int16).view(dt).isnan().all())
+
+
 def test_pool_codes_and_bit_masks_follow_their_rules():
     g = torch.Generator().manual_seed(2)
     x = torch.randn((2, 7, 9, 8), generator=g).double()
@@ -102,6 +152,52 @@ def test_case_meets_its_conditions_on_the_reference(case):
     weight-gradient / split-K case is there for (256 CUs: the MI355X, and what the library assumes without a device)."""
     figs = CE.check_case_inputs(case, cus=256)
     print(case[0], figs)
+
+
+def test_average_pool_reference_is_the_oracle_pool():
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn((2, 5, 7, 3), generator=g).double()
+    assert (CE.avg_pool_ref(x) - T.avg_pool_2x2_s1_same(x)).abs().max().item() <= 1e-12
+    for k in ((1, 1), (3, 3), (3, 1), (1, 3)):                     # the block's per-tap matrix products are the reference convolution
+        w, b = torch.randn(k + (3, 4), generator=g).double(), torch.randn((4,), generator=g).double()
+        assert (CE.conv_taps(x, w, b) - CE.conv_ref(x, w, b)).abs().max().item() <= 1e-12
+    one = torch.ones((1, 3, 3, 1), dtype=F64)                     # the divisor counts the pixels inside the map: a constant map stays constant
+    assert torch.equal(CE.avg_pool_ref(one), one)
+    v = torch.arange(9, dtype=F64).reshape(1, 3, 3, 1)
+    assert CE.avg_pool_ref(v)[0, :, :, 0].tolist() == [[2.0, 3.0, 3.5], [5.0, 6.0, 6.5], [6.5, 7.5, 8.0]]
+
+
+@pytest.mark.parametrize("case", CE.BLOCK_CASES, ids=[c[0] for c in CE.BLOCK_CASES])
+def test_block_case_meets_its_conditions_on_the_reference(case):
+    """tests/test_conv_views_exact_gpu.py compares ops.context_block with this reference by equality.  That needs: the two orders of branch 2
+    (pool-then-conv, conv-then-pool) equal in float64; every tensor either route stores in 16 bits - activations, the accumulated dT, dU and x's
+    gradient buffer after each delivery - a multiple of 1/4 that survives bf16 and IEEE half; every fp32 sum below 2^24 quarters; and, so that
+    the case cannot go trivial, every branch output non-zero, every ReLU with zeros and positives, every variable gradient non-zero."""
+    figs = CE.check_block_case(case)
+    print(case[0], figs)
+
+
+def test_block_reference_is_the_oracle_block():
+    """The float64 block against the oracle network's context block (fp32, its own convolutions and pool) on random weights: output, input
+    gradient and every variable's gradient."""
+    from oracle import nets as ON
+    g = torch.Generator().manual_seed(9)
+    C = 64
+    P32 = {}
+    for name, kh, kw, cin, cout in CE.BLOCK_LAYERS:
+        cin, cout = cin or C, cout or C
+        P32["blk/" + name + "/kernel"] = (torch.randn((kh, kw, cin, cout), generator=g) / (kh * kw * cin) ** 0.5).requires_grad_(True)
+        P32["blk/" + name + "/bias"] = (0.1 * torch.randn((cout,), generator=g)).requires_grad_(True)
+    x32 = torch.randn((2, 5, 7, C), generator=g).requires_grad_(True)
+    dy = torch.randn((2, 5, 7, C), generator=g)
+    ON.se_inception_block_v1(ON.Params(P32), x32, "blk").backward(dy)
+    for commuted in (False, True):
+        x = x32.detach().double().requires_grad_(True)
+        P = {n[4:]: v.detach().double().requires_grad_(True) for n, v in P32.items()}
+        out, _ = CE.block_ref(x, P, commuted)
+        out.backward(dy.double())
+        for got, want in [(x.grad, x32.grad)] + [(P[n[4:]].grad, v.grad) for n, v in P32.items()]:
+            assert got.shape == want.shape and (got - want.double()).abs().max().item() <= 1e-4 * max(1.0, want.abs().max().item())
 
 
 def test_tables_cover_every_dispatch_row_and_family():
