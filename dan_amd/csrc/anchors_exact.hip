@@ -439,13 +439,6 @@ __global__ void fill_int_kernel(int* p, int v, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
 }
 
-inline int grid_for(long total, int block, int cap = 2048) {
-  long b = (total + block - 1) / block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" int danhip_anchors_generate(float* ymin, float* xmin, float* ymax, float* xmax, const float* anchor_h, const float* anchor_w,
@@ -453,7 +446,7 @@ extern "C" int danhip_anchors_generate(float* ymin, float* xmin, float* ymax, fl
                                        int32_t out_offset, void* stream) {
   DH_REQUIRE(ymin && xmin && ymax && xmax && anchor_h && anchor_w && depth > 0 && layer_h > 0 && layer_w > 0 && out_offset >= 0, DANHIP_EINVAL,
              "anchors_generate: bad arguments");
-  hipLaunchKernelGGL(anchors_generate_kernel, dim3(grid_for((long)layer_h * layer_w * depth, 256)), dim3(256), 0, (hipStream_t)stream, ymin, xmin,
+  hipLaunchKernelGGL(anchors_generate_kernel, dim3(dh_grid_for((long)layer_h * layer_w * depth, 256, 2048)), dim3(256), 0, (hipStream_t)stream, ymin, xmin,
                      ymax, xmax, anchor_h, anchor_w, depth, layer_h, layer_w, stride, offset_h, offset_w, out_offset);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -462,7 +455,7 @@ extern "C" int danhip_anchors_generate(float* ymin, float* xmin, float* ymax, fl
 extern "C" int danhip_iou_matrix(const float* ymin, const float* xmin, const float* ymax, const float* xmax, const uint8_t* inside_mask,
                                  const float* gt_boxes, float* overlaps, int32_t A, int32_t G, void* stream) {
   DH_REQUIRE(ymin && xmin && ymax && xmax && gt_boxes && overlaps && A > 0 && G > 0, DANHIP_EINVAL, "iou_matrix: bad arguments");
-  hipLaunchKernelGGL(iou_matrix_kernel, dim3(grid_for((long)A * G, 256, 4096)), dim3(256), 0, (hipStream_t)stream, ymin, xmin, ymax, xmax,
+  hipLaunchKernelGGL(iou_matrix_kernel, dim3(dh_grid_for((long)A * G, 256, 4096)), dim3(256), 0, (hipStream_t)stream, ymin, xmin, ymax, xmax,
                      inside_mask, gt_boxes, overlaps, A, G);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -471,8 +464,8 @@ extern "C" int danhip_iou_matrix(const float* ymin, const float* xmin, const flo
 extern "C" size_t danhip_match_workspace_bytes(int32_t A, int32_t G) { return sizeof(int) * (size_t)(2 * G + 16) + sizeof(HeapItem) * (size_t)A; }
 
 static int prep_colmax(const float* ov, int* colkey, int A, int G, hipStream_t s) {
-  hipLaunchKernelGGL(fill_int_kernel, dim3(grid_for(G, 256)), dim3(256), 0, s, colkey, INT_MIN, G);
-  hipLaunchKernelGGL(colmax_kernel, dim3(grid_for((long)A * G, 256, 512)), dim3(256), sizeof(int) * G, s, ov, colkey, A, G);
+  hipLaunchKernelGGL(fill_int_kernel, dim3(dh_grid_for(G, 256, 2048)), dim3(256), 0, s, colkey, INT_MIN, G);
+  hipLaunchKernelGGL(colmax_kernel, dim3(dh_grid_for((long)A * G, 256, 512)), dim3(256), sizeof(int) * G, s, ov, colkey, A, G);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -486,7 +479,7 @@ extern "C" int danhip_dual_max_match(const float* overlaps, int32_t A, int32_t G
   int* colkey = reinterpret_cast<int*>(workspace);
   int rc = prep_colmax(overlaps, colkey, A, G, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(dual_max_match_kernel, dim3(grid_for(A, 128)), dim3(128), 0, s, overlaps, colkey, match_indices, match_scores, A, G, low_thres,
+  hipLaunchKernelGGL(dual_max_match_kernel, dim3(dh_grid_for(A, 128, 2048)), dim3(128), 0, s, overlaps, colkey, match_indices, match_scores, A, G, low_thres,
                      high_thres, ignore_between);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -511,8 +504,8 @@ extern "C" int danhip_small_mining_match(const float* overlaps, int32_t A, int32
   HeapItem* heap = reinterpret_cast<HeapItem*>(colkey + 2 * G + 16 - ((2 * G) % 2));
   int rc = prep_colmax(overlaps, colkey, A, G, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(fill_int_kernel, dim3(grid_for(G, 256)), dim3(256), 0, s, cnt, 0, G);
-  hipLaunchKernelGGL(smm_phase12_kernel, dim3(grid_for(A, 128)), dim3(128), 0, s, overlaps, colkey, match_indices, match_scores, cnt, A, G,
+  hipLaunchKernelGGL(fill_int_kernel, dim3(dh_grid_for(G, 256, 2048)), dim3(256), 0, s, cnt, 0, G);
+  hipLaunchKernelGGL(smm_phase12_kernel, dim3(dh_grid_for(A, 128, 2048)), dim3(128), 0, s, overlaps, colkey, match_indices, match_scores, cnt, A, G,
                      negative_low_thres, negative_high_thres, positive_thres);
   DH_LAUNCH_CHECK();
   hipLaunchKernelGGL(smm_phase3_kernel, dim3(1), dim3(1024), 0, s, overlaps, match_indices, match_scores, cnt, heap, A, G, min_match,
@@ -526,7 +519,7 @@ extern "C" int danhip_encode_anchors(const float* ymin, const float* xmin, const
                                      float ps0, float ps1, float ps2, float ps3, float scale, void* stream) {
   DH_REQUIRE(ymin && xmin && ymax && xmax && gt_boxes && match_indices && targets && labels && A > 0, DANHIP_EINVAL,
              "encode_anchors: bad arguments");
-  hipLaunchKernelGGL(encode_anchors_kernel, dim3(grid_for(A, 256)), dim3(256), 0, (hipStream_t)stream, ymin, xmin, ymax, xmax, gt_boxes,
+  hipLaunchKernelGGL(encode_anchors_kernel, dim3(dh_grid_for(A, 256, 2048)), dim3(256), 0, (hipStream_t)stream, ymin, xmin, ymax, xmax, gt_boxes,
                      match_indices, targets, labels, matched_gt, A, ps0, ps1, ps2, ps3, scale);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -570,20 +563,20 @@ extern "C" int danhip_encode_anchors_batched(const float* ymin, const float* xmi
   p.heap = w; w += al256(sizeof(HeapItem) * (size_t)B * A);
   p.midx = reinterpret_cast<int*>(w);
   p.targets = targets; p.scores = scores; p.matched = matched_gt; p.labels = labels; p.A = A;
-  hipLaunchKernelGGL(batch_init_kernel, dim3(grid_for(total_gt, 256)), dim3(256), 0, s, p.colkey, p.cnt, total_gt);
-  hipLaunchKernelGGL(batch_iou_kernel, dim3(grid_for((long)A * max_gt, 256, 1024), B), dim3(256), 0, s, p);
-  hipLaunchKernelGGL(batch_colmax_kernel, dim3(grid_for(A, 256 * 8), max_gt, B), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(batch_init_kernel, dim3(dh_grid_for(total_gt, 256, 2048)), dim3(256), 0, s, p.colkey, p.cnt, total_gt);
+  hipLaunchKernelGGL(batch_iou_kernel, dim3(dh_grid_for((long)A * max_gt, 256, 1024), B), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(batch_colmax_kernel, dim3(dh_grid_for(A, 256 * 8, 2048), max_gt, B), dim3(256), 0, s, p);
   if (match_mining)
-    hipLaunchKernelGGL(batch_phase12_kernel, dim3(grid_for(A, 128), B), dim3(128), 0, s, p, 1, negative_low_thres, ignore_thres, positive_thres);
+    hipLaunchKernelGGL(batch_phase12_kernel, dim3(dh_grid_for(A, 128, 2048), B), dim3(128), 0, s, p, 1, negative_low_thres, ignore_thres, positive_thres);
   else
-    hipLaunchKernelGGL(batch_phase12_kernel, dim3(grid_for(A, 128), B), dim3(128), 0, s, p, 0, ignore_thres, positive_thres, 0.f);
+    hipLaunchKernelGGL(batch_phase12_kernel, dim3(dh_grid_for(A, 128, 2048), B), dim3(128), 0, s, p, 0, ignore_thres, positive_thres, 0.f);
   if (match_mining) {
     const size_t lds = sizeof(unsigned long long) * 16 * (size_t)p3_chunks(A) + sizeof(int) * (size_t)max_gt;
     DH_REQUIRE(lds <= 120 * 1024, DANHIP_EINVAL, "encode_anchors_batched: A=%d / max_gt=%d exceed the phase-3 LDS plan", A, max_gt);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(batch_phase3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(batch_phase3_kernel, dim3(B), dim3(1024), lds, s, p, min_match, stop_positive_thres);
   }
-  hipLaunchKernelGGL(batch_encode_kernel, dim3(grid_for(A, 256), B), dim3(256), 0, s, p, ps0, ps1, ps2, ps3, scale);
+  hipLaunchKernelGGL(batch_encode_kernel, dim3(dh_grid_for(A, 256, 2048), B), dim3(256), 0, s, p, ps0, ps1, ps2, ps3, scale);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -591,7 +584,7 @@ extern "C" int danhip_encode_anchors_batched(const float* ymin, const float* xmi
 extern "C" int danhip_decode_anchors(const float* pred, const float* ymin, const float* xmin, const float* ymax, const float* xmax, float* boxes,
                                      int32_t B, int32_t A, float ps0, float ps1, float ps2, float ps3, void* stream) {
   DH_REQUIRE(pred && ymin && xmin && ymax && xmax && boxes && B > 0 && A > 0, DANHIP_EINVAL, "decode_anchors: bad arguments");
-  hipLaunchKernelGGL(decode_anchors_kernel, dim3(grid_for((long)B * A, 256)), dim3(256), 0, (hipStream_t)stream, pred, ymin, xmin, ymax, xmax, boxes,
+  hipLaunchKernelGGL(decode_anchors_kernel, dim3(dh_grid_for((long)B * A, 256, 2048)), dim3(256), 0, (hipStream_t)stream, pred, ymin, xmin, ymax, xmax, boxes,
                      B, A, ps0, ps1, ps2, ps3);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -599,7 +592,7 @@ extern "C" int danhip_decode_anchors(const float* pred, const float* ymin, const
 
 extern "C" int danhip_face_scores(const float* cls, float* score, int32_t* mask, float threshold, int64_t n, void* stream) {
   DH_REQUIRE(cls && (score || mask) && n > 0, DANHIP_EINVAL, "face_scores: bad arguments");
-  hipLaunchKernelGGL(face_scores_kernel, dim3(grid_for((long)n, 256)), dim3(256), 0, (hipStream_t)stream, cls, score, mask, threshold, (long)n);
+  hipLaunchKernelGGL(face_scores_kernel, dim3(dh_grid_for((long)n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, cls, score, mask, threshold, (long)n);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

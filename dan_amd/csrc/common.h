@@ -88,6 +88,17 @@ __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {  // one packed
   const f32x2 v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
+// eight activations (one 16-byte lane access) <-> fp32
+__device__ __forceinline__ void dh_unpack8(const uint4& u, float* f) {
+  const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) unpack2bf(w[i], f[2 * i], f[2 * i + 1]);
+}
+__device__ __forceinline__ uint4 dh_pack8(const float* f) {
+  uint4 u;
+  u.x = pack2bf(f[0], f[1]); u.y = pack2bf(f[2], f[3]); u.z = pack2bf(f[4], f[5]); u.w = pack2bf(f[6], f[7]);
+  return u;
+}
 
 // ---------------------------------------------------------------- fast division by a runtime constant
 struct FastDiv {
@@ -122,3 +133,17 @@ __device__ __forceinline__ void bufdma16_lds(__amdgpu_buffer_rsrc_t rsrc, unsign
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Blocks of a grid-stride launch: one thread per item, at most `cap` blocks, at least one.  No default cap: the cap is the launch's tuning.
+static inline int dh_grid_for(long total, int block, int cap) {
+  long b = (total + block - 1) / block;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+// TF 'same' padding in front of a dimension (the extra pixel of an odd total goes behind)
+static inline int dh_same_pad_before(int in, int out, int k, int s) {
+  int total = (out - 1) * s + k - in;
+  if (total < 0) total = 0;
+  return total / 2;
+}

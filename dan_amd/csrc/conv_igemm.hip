@@ -472,12 +472,6 @@ ConvInstance select_conv(const ConvArgs& a) {
 
 int launch_conv(const ConvArgs& a, hipStream_t s) { return dh_run_instance(select_conv(a), a, s); }
 
-inline int same_pad_before(int in, int out, int k, int s) {
-  int total = (out - 1) * s + k - in;
-  if (total < 0) total = 0;
-  return total / 2;
-}
-
 int check_desc(const danhip_conv_desc* d) {
   DH_REQUIRE(d != nullptr, DANHIP_EINVAL, "conv: null descriptor");
   DH_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, DANHIP_EINVAL, "conv: non-positive dims");
@@ -595,8 +589,8 @@ ConvArgs fwd_args(const danhip_conv_desc* d) {
   ConvArgs a{};
   a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Cout;
   a.kh = d->kh; a.kw = d->kw; a.stride = d->stride;
-  a.pad_t = same_pad_before(d->H, d->Ho, d->kh, d->stride);
-  a.pad_l = same_pad_before(d->W, d->Wo, d->kw, d->stride);
+  a.pad_t = dh_same_pad_before(d->H, d->Ho, d->kh, d->stride);
+  a.pad_l = dh_same_pad_before(d->W, d->Wo, d->kw, d->stride);
   a.M = d->N * d->Ho * d->Wo;
   a.taps = d->kh * d->kw;
   a.Kpad = round_up(a.taps * a.C, 64);
@@ -611,7 +605,7 @@ ConvArgs bwd_args(const danhip_conv_desc* d) {
   ConvArgs a{};
   const int co8 = round_up(d->Cout, 8);
   const int taps = d->kh * d->kw;
-  const int pad_t = same_pad_before(d->H, d->Ho, d->kh, d->stride), pad_l = same_pad_before(d->W, d->Wo, d->kw, d->stride);
+  const int pad_t = dh_same_pad_before(d->H, d->Ho, d->kh, d->stride), pad_l = dh_same_pad_before(d->W, d->Wo, d->kw, d->stride);
   // a forward convolution of dy with the tap-flipped, transposed weights; pad' = k-1-pad
   a.N = d->N; a.H = d->Ho; a.W = d->Wo; a.C = co8; a.Ho = d->H; a.Wo = d->W; a.Co = d->Cin;
   a.kh = d->kh; a.kw = d->kw; a.stride = 1;

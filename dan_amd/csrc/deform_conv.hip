@@ -10,24 +10,14 @@
 // reference does with CudaAtomicAdd :314-326).
 //
 // Offsets: NHWC [B,Ho,Wo, dg*2*kh*kw], channel (g*kh*kw + t)*2 + {0: dh, 1: dw}  (deform_conv.cu:251-259).
-#include "common.h"
+// The three sampling rules themselves live in deform_sample.h; the kernels here keep their addressing, load scheduling and reductions.
+#include "deform_sample.h"
 
 namespace {
 
 struct DeformGeom {
   int N, H, W, C, Ho, Wo, kh, kw, stride, dil, dg, pad_t, pad_l;
 };
-
-__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) unpack2bf(w[i], f[2 * i], f[2 * i + 1]);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 u;
-  u.x = pack2bf(f[0], f[1]); u.y = pack2bf(f[2], f[3]); u.z = pack2bf(f[4], f[5]); u.w = pack2bf(f[6], f[7]);
-  return u;
-}
 
 // A 256-thread block owns SAMPLE_PXB consecutive output pixels of ONE output row: (image, row, first column) are block-uniform
 // (scalar registers) and a thread's item q -> (pixel in the block, tap, 8-channel chunk) is 32-bit arithmetic — the earlier form (one
@@ -47,7 +37,6 @@ __global__ __launch_bounds__(256) void deform_sample_fwd_kernel(const bf16_t* __
   const int h_in = ho * g.stride - g.pad_t;
   const long m0 = (long)rowid * g.Wo + wo0;
   const bf16_t* xn = x + ((long)n * g.H * g.W) * g.C;
-  const int cur_h = g.H - h_in;
   // Three items per trip: the three offset words are fetched first, then all twelve corner rows are in flight together — a trip
   // costs two dependent memory latencies instead of six (the kernel is latency bound, not bandwidth bound: 16 bytes per lane and load).
   constexpr int U = 3;
@@ -67,39 +56,28 @@ __global__ __launch_bounds__(256) void deform_sample_fwd_kernel(const bf16_t* __
       oraw[u] = *reinterpret_cast<const unsigned*>(offs + (m0 + pxl[u]) * offc + (grp[u] * taps + t[u]) * 2);
     }
     uint4 c4[U][4];
-    float wq[U][4];
-    bool in[U];
+    DeformFwdTap tap[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = t[u] / g.kw, j = t[u] - i * g.kw;
       const int w_in = (wo0 + pxl[u]) * g.stride - g.pad_l;
-      const float off_h = bf2f((bf16_t)(oraw[u] & 0xffffu)), off_w = bf2f((bf16_t)(oraw[u] >> 16));
-      const float h_im = (float)(h_in + i * g.dil) + off_h;             // deform_conv.cu:261-262
-      const float w_im = (float)(w_in + j * g.dil) + off_w;
-      in[u] = h_im >= 0 && w_im >= 0 && h_im < g.H && w_im < g.W;       // :263
-      float mh = (float)(i * g.dil) + off_h, mw = (float)(j * g.dil) + off_w;     // :264-265 (relative to (h_in, w_in))
-      if (!in[u]) { mh = (float)(-h_in); mw = (float)(-w_in); }         // (any valid address: the result is discarded)
-      const int cur_w = g.W - w_in;                                     // :266-268
-      int h_low = (int)floorf(mh), w_low = (int)floorf(mw), h_high, w_high;       // deformable_im2col_bilinear :94-112
-      if (h_low >= cur_h - 1) { h_high = h_low = cur_h - 1; mh = (float)h_low; } else h_high = h_low + 1;
-      if (w_low >= cur_w - 1) { w_high = w_low = cur_w - 1; mw = (float)w_low; } else w_high = w_low + 1;
-      const float lh = mh - h_low, lw = mw - w_low, hh = 1 - lh, hw = 1 - lw;
-      wq[u][0] = hh * hw; wq[u][1] = hh * lw; wq[u][2] = lh * hw; wq[u][3] = lh * lw;         // :118-125
+      const DeformOffset off = deform_offset_pair(oraw[u]);
+      const DeformFwdTap s = deform_fwd_tap(h_in, w_in, i * g.dil, j * g.dil, off.h, off.w, g.H, g.W);
+      tap[u] = s;
       const bf16_t* base = xn + chunk[u] * 8;
-      const int rl = (h_in + h_low) * g.W + w_in, rh = (h_in + h_high) * g.W + w_in;      // pixel indices inside image n
-      c4[u][0] = *reinterpret_cast<const uint4*>(base + (long)(rl + w_low) * g.C);
-      c4[u][1] = *reinterpret_cast<const uint4*>(base + (long)(rl + w_high) * g.C);
-      c4[u][2] = *reinterpret_cast<const uint4*>(base + (long)(rh + w_low) * g.C);
-      c4[u][3] = *reinterpret_cast<const uint4*>(base + (long)(rh + w_high) * g.C);
+      const int rl = (h_in + s.h_low) * g.W + w_in, rh = (h_in + s.h_high) * g.W + w_in;  // pixel indices inside image n
+      c4[u][0] = *reinterpret_cast<const uint4*>(base + (long)(rl + s.w_low) * g.C);
+      c4[u][1] = *reinterpret_cast<const uint4*>(base + (long)(rl + s.w_high) * g.C);
+      c4[u][2] = *reinterpret_cast<const uint4*>(base + (long)(rh + s.w_low) * g.C);
+      c4[u][3] = *reinterpret_cast<const uint4*>(base + (long)(rh + s.w_high) * g.C);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float v1[8], v2[8], v3[8], v4[8], out[8];
-      unpack8(c4[u][0], v1); unpack8(c4[u][1], v2); unpack8(c4[u][2], v3); unpack8(c4[u][3], v4);
+      dh_unpack8(c4[u][0], v1); dh_unpack8(c4[u][1], v2); dh_unpack8(c4[u][2], v3); dh_unpack8(c4[u][3], v4);
 #pragma unroll
-      for (int e = 0; e < 8; ++e)       // (explicit fma chain: the fused kernel of deform_fused.hip must round the same way)
-        out[e] = in[u] ? fmaf(wq[u][3], v4[e], fmaf(wq[u][2], v3[e], fmaf(wq[u][1], v2[e], wq[u][0] * v1[e]))) : 0.f;
-      if (live[u]) *reinterpret_cast<uint4*>(S + ((m0 + pxl[u]) * taps + t[u]) * g.C + chunk[u] * 8) = pack8(out);
+      for (int e = 0; e < 8; ++e) out[e] = tap[u].in ? deform_blend(tap[u].wq, v1[e], v2[e], v3[e], v4[e]) : 0.f;
+      if (live[u]) *reinterpret_cast<uint4*>(S + ((m0 + pxl[u]) * taps + t[u]) * g.C + chunk[u] * 8) = dh_pack8(out);
     }
   }
 }
@@ -129,30 +107,18 @@ __global__ void deform_sample_bwd_kernel(const bf16_t* __restrict__ x, const bf1
     const float inv_h = (float)(h_in + i * g.dil) + bf2f(op[0]);      // absolute sample coordinate (:365-366, :304-305)
     const float inv_w = (float)(w_in + j * g.dil) + bf2f(op[1]);
     float cg[8];
-    unpack8(*reinterpret_cast<const uint4*>(dS + (m * taps + t) * g.C + chunk * 8), cg);
+    dh_unpack8(*reinterpret_cast<const uint4*>(dS + (m * taps + t) * g.C + chunk * 8), cg);
     const bf16_t* base = x + ((long)n * g.H * g.W) * g.C + chunk * 8;
-    const float Hf = (float)g.H, Wf = (float)g.W;
-    // ---- dOffset: get_coordinate_weight (:177-221); out-of-range samples give 0 (:371-373)
+    // ---- dOffset: get_coordinate_weight; out-of-range samples give 0
     float s_h = 0.f, s_w = 0.f;
-    if (!(inv_h < 0 || inv_w < 0 || inv_h >= Hf || inv_w >= Wf)) {
-      float ih = inv_h, iw = inv_w;
-      int h_low = (int)ih, w_low = (int)iw, h_high, w_high;           // (int) truncation as in the reference
-      if (h_low >= g.H - 1) { h_high = h_low = g.H - 1; ih = (float)h_low; } else h_high = h_low + 1;
-      if (w_low >= g.W - 1) { w_high = w_low = g.W - 1; iw = (float)w_low; } else w_high = w_low + 1;
+    const DeformCoordWeights cw = deform_coord_weights(inv_h, inv_w, g.H, g.W);
+    if (cw.in) {
       float vll[8], vlh[8], vhl[8], vhh[8];
-      unpack8(*reinterpret_cast<const uint4*>(base + ((long)h_low * g.W + w_low) * g.C), vll);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((long)h_low * g.W + w_high) * g.C), vlh);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((long)h_high * g.W + w_low) * g.C), vhl);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((long)h_high * g.W + w_high) * g.C), vhh);
-      const float a_w = (float)(w_low + 1) - iw, b_w = iw - (float)w_low;
-      const float a_h = (float)(h_low + 1) - ih, b_h = ih - (float)h_low;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float wgt_h = -1.f * a_w * vll[e] + -1.f * b_w * vlh[e] + a_w * vhl[e] + b_w * vhh[e];
-        const float wgt_w = -1.f * a_h * vll[e] + a_h * vlh[e] + -1.f * b_h * vhl[e] + b_h * vhh[e];
-        s_h += wgt_h * cg[e];
-        s_w += wgt_w * cg[e];
-      }
+      dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)cw.hl * g.W + cw.wl) * g.C), vll);
+      dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)cw.hl * g.W + cw.wh) * g.C), vlh);
+      dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)cw.hh * g.W + cw.wl) * g.C), vhl);
+      dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)cw.hh * g.W + cw.wh) * g.C), vhh);
+      deform_coord_sum8(cw, vll, vlh, vhl, vhh, cg, s_h, s_w);
     }
     if (!live) { s_h = 0.f; s_w = 0.f; }
     for (int o = 1; o < cpg8; o <<= 1) { s_h += __shfl_xor(s_h, o); s_w += __shfl_xor(s_w, o); }
@@ -161,26 +127,14 @@ __global__ void deform_sample_bwd_kernel(const bf16_t* __restrict__ x, const bf1
       dp[0] = f2bf(s_h);
       dp[1] = f2bf(s_w);
     }
-    // ---- dX: get_gradient_weight (:130-173) scattered to the <= 4 corners (:311-326)
-    if (live && !(inv_h < 0 || inv_h > Hf || inv_w < 0 || inv_w > Wf)) {
-      float ah = fmaxf(inv_h, 0.f), aw = fmaxf(inv_w, 0.f);
-      int hl = (int)ah, wl = (int)aw, hh, wh;
-      const bool ch = hl >= g.H - 1, cw = wl >= g.W - 1;
-      if (ch) { hh = hl = g.H - 1; ah = (float)hl; } else hh = hl + 1;
-      if (cw) { wh = wl = g.W - 1; aw = (float)wl; } else wh = wl + 1;
-      const int rh[4] = {hl, hl, hh, hh}, rw[4] = {wl, wh, wl, wh};
-      const float wg[4] = {((float)(hl + 1) - ah) * ((float)(wl + 1) - aw), ((float)(hl + 1) - ah) * (aw + 1.f - (float)wh),
-                           (ah + 1.f - (float)hh) * ((float)(wl + 1) - aw), (ah + 1.f - (float)hh) * (aw + 1.f - (float)wh)};
-      const bool dup[4] = {false, cw, ch, ch || cw};
+    // ---- dX: get_gradient_weight scattered to the <= 4 corners
+    const CornerSet cs = corner_set(inv_h, inv_w, g.H, g.W);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const bool ok = !dup[k] && fabsf(inv_h - (float)rh[k]) < 1.f && fabsf(inv_w - (float)rw[k]) < 1.f && rh[k] >= 0 && rh[k] < g.H &&
-                        rw[k] >= 0 && rw[k] < g.W;
-        if (ok) {
-          float* dst = dx + (((long)n * g.H + rh[k]) * g.W + rw[k]) * g.C + chunk * 8;
+    for (int k = 0; k < 4; ++k) {
+      if (live && cs.ok[k]) {
+        float* dst = dx + (((long)n * g.H + cs.rh[k]) * g.W + cs.rw[k]) * g.C + chunk * 8;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) atomicAdd(dst + e, wg[k] * cg[e]);
-        }
+        for (int e = 0; e < 8; ++e) atomicAdd(dst + e, cs.wg[k] * cg[e]);
       }
     }
   }
@@ -218,7 +172,6 @@ __global__ void deform_sample_bwd_c64_kernel(const bf16_t* __restrict__ x, const
   const long nwork = (long)g.N * g.Ho * g.Wo * taps * g.dg;              // (m, t, grp) triples, grp fastest
   const long wave0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long nwaves = (long)gridDim.x * (blockDim.x >> 6);
-  const float Hf = (float)g.H, Wf = (float)g.W;
   for (long wk = wave0; wk < nwork; wk += nwaves) {
     const int grp = (int)(wk % g.dg);
     long r = wk / g.dg;
@@ -237,17 +190,12 @@ __global__ void deform_sample_bwd_c64_kernel(const bf16_t* __restrict__ x, const
     const bf16_t* base = x + ((long)n * g.H * g.W) * g.C + c;
     // ---- dOffset (get_coordinate_weight)
     float s_h = 0.f, s_w = 0.f;
-    if (!(inv_h < 0 || inv_w < 0 || inv_h >= Hf || inv_w >= Wf)) {
-      float ih = inv_h, iw = inv_w;
-      int h_low = (int)ih, w_low = (int)iw, h_high, w_high;
-      if (h_low >= g.H - 1) { h_high = h_low = g.H - 1; ih = (float)h_low; } else h_high = h_low + 1;
-      if (w_low >= g.W - 1) { w_high = w_low = g.W - 1; iw = (float)w_low; } else w_high = w_low + 1;
-      const float vll = bf2f(base[((long)h_low * g.W + w_low) * g.C]), vlh = bf2f(base[((long)h_low * g.W + w_high) * g.C]);
-      const float vhl = bf2f(base[((long)h_high * g.W + w_low) * g.C]), vhh = bf2f(base[((long)h_high * g.W + w_high) * g.C]);
-      const float a_w = (float)(w_low + 1) - iw, b_w = iw - (float)w_low;
-      const float a_h = (float)(h_low + 1) - ih, b_h = ih - (float)h_low;
-      s_h = (-1.f * a_w * vll + -1.f * b_w * vlh + a_w * vhl + b_w * vhh) * cg;
-      s_w = (-1.f * a_h * vll + a_h * vlh + -1.f * b_h * vhl + b_h * vhh) * cg;
+    const DeformCoordWeights cw = deform_coord_weights(inv_h, inv_w, g.H, g.W);
+    if (cw.in) {
+      const float vll = bf2f(base[((long)cw.hl * g.W + cw.wl) * g.C]), vlh = bf2f(base[((long)cw.hl * g.W + cw.wh) * g.C]);
+      const float vhl = bf2f(base[((long)cw.hh * g.W + cw.wl) * g.C]), vhh = bf2f(base[((long)cw.hh * g.W + cw.wh) * g.C]);
+      s_h = (-1.f * cw.a_w * vll + -1.f * cw.b_w * vlh + cw.a_w * vhl + cw.b_w * vhh) * cg;
+      s_w = (-1.f * cw.a_h * vll + cw.a_h * vlh + -1.f * cw.b_h * vhl + cw.b_h * vhh) * cg;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { s_h += __shfl_xor(s_h, o, 64); s_w += __shfl_xor(s_w, o, 64); }
@@ -257,23 +205,10 @@ __global__ void deform_sample_bwd_c64_kernel(const bf16_t* __restrict__ x, const
       dp[1] = f2bf(s_w);
     }
     // ---- dX (get_gradient_weight), wave-uniform corner geometry
-    if (!(inv_h < 0 || inv_h > Hf || inv_w < 0 || inv_w > Wf)) {
-      float ah = fmaxf(inv_h, 0.f), aw = fmaxf(inv_w, 0.f);
-      int hl = (int)ah, wl = (int)aw, hh, wh;
-      const bool ch = hl >= g.H - 1, cw = wl >= g.W - 1;
-      if (ch) { hh = hl = g.H - 1; ah = (float)hl; } else hh = hl + 1;
-      if (cw) { wh = wl = g.W - 1; aw = (float)wl; } else wh = wl + 1;
-      const int rh[4] = {hl, hl, hh, hh}, rw[4] = {wl, wh, wl, wh};
-      const float wg[4] = {((float)(hl + 1) - ah) * ((float)(wl + 1) - aw), ((float)(hl + 1) - ah) * (aw + 1.f - (float)wh),
-                           (ah + 1.f - (float)hh) * ((float)(wl + 1) - aw), (ah + 1.f - (float)hh) * (aw + 1.f - (float)wh)};
-      const bool dup[4] = {false, cw, ch, ch || cw};
+    const CornerSet cs = corner_set(inv_h, inv_w, g.H, g.W);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const bool ok = !dup[k] && fabsf(inv_h - (float)rh[k]) < 1.f && fabsf(inv_w - (float)rw[k]) < 1.f && rh[k] >= 0 && rh[k] < g.H &&
-                        rw[k] >= 0 && rw[k] < g.W;
-        if (ok) atomicAdd(dx + (((long)n * g.H + rh[k]) * g.W + rw[k]) * g.C + c, wg[k] * cg);
-      }
-    }
+    for (int k = 0; k < 4; ++k)
+      if (cs.ok[k]) atomicAdd(dx + (((long)n * g.H + cs.rh[k]) * g.W + cs.rw[k]) * g.C + c, cs.wg[k] * cg);
   }
 }
 
@@ -287,53 +222,6 @@ __global__ void deform_sample_bwd_c64_kernel(const bf16_t* __restrict__ x, const
 // has all nine taps' loads in flight and reduces the 18 sums with a transposing butterfly (29 shuffles instead of 108).
 
 __device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
-struct CornerSet {
-  int rh[4], rw[4];
-  float wg[4];
-  bool ok[4];
-};
-// get_gradient_weight (deform_conv.cu:130-173) + the guards of deformable_col2im_gpu_kernel (:311-326) for one sampling position
-__device__ __forceinline__ CornerSet corner_set(float inv_h, float inv_w, int H, int W) {
-  CornerSet cs;
-  const bool in = !(inv_h < 0 || inv_h > (float)H || inv_w < 0 || inv_w > (float)W);
-  float ah = fmaxf(inv_h, 0.f), aw = fmaxf(inv_w, 0.f);
-  if (!in) { ah = 0.f; aw = 0.f; }
-  int hl = (int)ah, wl = (int)aw, hh, wh;
-  const bool ch = hl >= H - 1, cw = wl >= W - 1;
-  if (ch) { hh = hl = H - 1; ah = (float)hl; } else hh = hl + 1;
-  if (cw) { wh = wl = W - 1; aw = (float)wl; } else wh = wl + 1;
-  cs.rh[0] = hl; cs.rh[1] = hl; cs.rh[2] = hh; cs.rh[3] = hh;
-  cs.rw[0] = wl; cs.rw[1] = wh; cs.rw[2] = wl; cs.rw[3] = wh;
-  cs.wg[0] = ((float)(hl + 1) - ah) * ((float)(wl + 1) - aw);
-  cs.wg[1] = ((float)(hl + 1) - ah) * (aw + 1.f - (float)wh);
-  cs.wg[2] = (ah + 1.f - (float)hh) * ((float)(wl + 1) - aw);
-  cs.wg[3] = (ah + 1.f - (float)hh) * (aw + 1.f - (float)wh);
-  const bool dup[4] = {false, cw, ch, ch || cw};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    cs.ok[k] = in && !dup[k] && fabsf(inv_h - (float)cs.rh[k]) < 1.f && fabsf(inv_w - (float)cs.rw[k]) < 1.f && cs.rh[k] >= 0 && cs.rh[k] < H &&
-               cs.rw[k] >= 0 && cs.rw[k] < W;
-  return cs;
-}
-
-// The weight corner_set() gives the corner that IS pixel (h, w), or 0: wg[k] and ok[k] factor into a row part and a column part
-// (dup[1] = cw, dup[2] = ch, dup[3] = ch || cw), so the gather evaluates the two 1-D factors directly.
-__device__ __forceinline__ float axis_factor(float inv, int target, int L) {
-  float a = fmaxf(inv, 0.f);
-  int lo = (int)a, hi;
-  const bool clamp = lo >= L - 1;
-  if (clamp) { hi = lo = L - 1; a = (float)lo; } else hi = lo + 1;
-  const bool near = fabsf(inv - (float)target) < 1.f;
-  float f = 0.f;
-  if (target == lo) f = (float)(lo + 1) - a;                 // corners 0/1 (rows) or 0/2 (columns)
-  else if (target == hi && !clamp) f = a + 1.f - (float)hi;  // the high corner, unless it duplicates the low one
-  return near ? f : 0.f;
-}
-__device__ __forceinline__ float corner_weight_at(float inv_h, float inv_w, int h, int w, int H, int W) {
-  if (inv_h < 0 || inv_h > (float)H || inv_w < 0 || inv_w > (float)W) return 0.f;
-  return axis_factor(inv_h, h, H) * axis_factor(inv_w, w, W);
-}
 
 // The 18 sums of an item, spread over its 8 lanes -> lane l8 holds the (dh, dw) pair of tap (4*b0 + 2*b1 + b2) and stores it as one 32-bit
 // word: a transposing butterfly (14 + 6 shuffles).  `dp` = the item's 18 bf16 of dOffset (an even element index: 32-bit aligned pairs).
@@ -368,15 +256,15 @@ __device__ __forceinline__ void doff_far_corners(unsigned farm, bool live, const
   while (farm) {                                                        // (uniform inside an 8-lane item; rare)
     const int t = __builtin_ctz(farm);
     farm &= farm - 1;
-    const unsigned oraw = *reinterpret_cast<const unsigned*>(uo + 2 * t);
+    const DeformOffset off = deform_offset_pair(*reinterpret_cast<const unsigned*>(uo + 2 * t));
     const int nh = h_in + (t / 3) * g.dil, nw = w_in + (t % 3) * g.dil;
-    const CornerSet cs = corner_set((float)nh + bf2f((bf16_t)(oraw & 0xffffu)), (float)nw + bf2f((bf16_t)(oraw >> 16)), g.H, g.W);
+    const CornerSet cs = corner_set((float)nh + off.h, (float)nw + off.w, g.H, g.W);
     bool any_far = false;
 #pragma unroll
     for (int k = 0; k < 4; ++k) any_far = any_far || (cs.ok[k] && (abs(cs.rh[k] - nh) > R || abs(cs.rw[k] - nw) > R));
     if (!any_far) continue;
     float cg[8];
-    unpack8(*reinterpret_cast<const uint4*>(ud + t * g.C), cg);
+    dh_unpack8(*reinterpret_cast<const uint4*>(ud + t * g.C), cg);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const bool far = abs(cs.rh[k] - nh) > R || abs(cs.rw[k] - nw) > R;
@@ -401,7 +289,6 @@ __device__ __forceinline__ void deform_bwd_doff9_c64_body(const bf16_t* __restri
   const int offc = g.dg * 18;
   const int lane = threadIdx.x & 63, l8 = lane & 7;
   const unsigned nwork = (unsigned)g.N * g.Ho * g.Wo * g.dg;            // (< 2^31: checked by the launcher)
-  const float Hf = (float)g.H, Wf = (float)g.W;
   const float lim = (float)R;
   for (unsigned wbase = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 8u; wbase < nwork; wbase += gridDim.x * (blockDim.x >> 6) * 8u) {
     const unsigned item = wbase + (lane >> 3);
@@ -421,38 +308,28 @@ __device__ __forceinline__ void deform_bwd_doff9_c64_body(const bf16_t* __restri
 #pragma unroll
     for (int tb = 0; tb < 3; ++tb) {
       uint4 v[3][4], cgr[3];
-      float ca_w[3], cb_w[3], ca_h[3], cb_h[3];
+      DeformCoordWeights cw[3];
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const int t = tb * 3 + u;
+        // (decoded in place: through deform_offset_pair hipcc turns the range test below into compares that cost the fp16 build 8 bytes of scratch)
         const unsigned oraw = *reinterpret_cast<const unsigned*>(uo + 2 * t);
         const float off_h = bf2f((bf16_t)(oraw & 0xffffu)), off_w = bf2f((bf16_t)(oraw >> 16));
         if (off_h < -lim || off_h >= lim || off_w < -lim || off_w >= lim) farm |= 1u << t;
-        const float inv_h = (float)(h_in + tb * g.dil) + off_h, inv_w = (float)(w_in + u * g.dil) + off_w;
-        const bool in = !(inv_h < 0 || inv_w < 0 || inv_h >= Hf || inv_w >= Wf);
-        float ih = in ? inv_h : 0.f, iw = in ? inv_w : 0.f;
-        int hl = (int)ih, wl = (int)iw, hh, wh;
-        if (hl >= g.H - 1) { hh = hl = g.H - 1; ih = (float)hl; } else hh = hl + 1;
-        if (wl >= g.W - 1) { wh = wl = g.W - 1; iw = (float)wl; } else wh = wl + 1;
-        ca_w[u] = in ? (float)(wl + 1) - iw : 0.f; cb_w[u] = in ? iw - (float)wl : 0.f;      // get_coordinate_weight (:177-221)
-        ca_h[u] = in ? (float)(hl + 1) - ih : 0.f; cb_h[u] = in ? ih - (float)hl : 0.f;
-        v[u][0] = *reinterpret_cast<const uint4*>(ub + (long)(hl * g.W + wl) * g.C);
-        v[u][1] = *reinterpret_cast<const uint4*>(ub + (long)(hl * g.W + wh) * g.C);
-        v[u][2] = *reinterpret_cast<const uint4*>(ub + (long)(hh * g.W + wl) * g.C);
-        v[u][3] = *reinterpret_cast<const uint4*>(ub + (long)(hh * g.W + wh) * g.C);
+        cw[u] = deform_coord_weights((float)(h_in + tb * g.dil) + off_h, (float)(w_in + u * g.dil) + off_w, g.H, g.W);
+        const DeformCoordWeights& c = cw[u];
+        v[u][0] = *reinterpret_cast<const uint4*>(ub + (long)(c.hl * g.W + c.wl) * g.C);
+        v[u][1] = *reinterpret_cast<const uint4*>(ub + (long)(c.hl * g.W + c.wh) * g.C);
+        v[u][2] = *reinterpret_cast<const uint4*>(ub + (long)(c.hh * g.W + c.wl) * g.C);
+        v[u][3] = *reinterpret_cast<const uint4*>(ub + (long)(c.hh * g.W + c.wh) * g.C);
         cgr[u] = *reinterpret_cast<const uint4*>(ud + t * g.C);
       }
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         float vll[8], vlh[8], vhl[8], vhh[8], cg[8];
-        unpack8(v[u][0], vll); unpack8(v[u][1], vlh); unpack8(v[u][2], vhl); unpack8(v[u][3], vhh); unpack8(cgr[u], cg);
-        const float a_w = ca_w[u], b_w = cb_w[u], a_h = ca_h[u], b_h = cb_h[u];
+        dh_unpack8(v[u][0], vll); dh_unpack8(v[u][1], vlh); dh_unpack8(v[u][2], vhl); dh_unpack8(v[u][3], vhh); dh_unpack8(cgr[u], cg);
         float s_h = 0.f, s_w = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          s_h += (-1.f * a_w * vll[e] + -1.f * b_w * vlh[e] + a_w * vhl[e] + b_w * vhh[e]) * cg[e];
-          s_w += (-1.f * a_h * vll[e] + a_h * vlh[e] + -1.f * b_h * vhl[e] + b_h * vhh[e]) * cg[e];
-        }
+        deform_coord_sum8(cw[u], vll, vlh, vhl, vhh, cg, s_h, s_w);
         sv[2 * (tb * 3 + u)] = s_h;
         sv[2 * (tb * 3 + u) + 1] = s_w;
       }
@@ -508,8 +385,8 @@ __device__ __forceinline__ void deform_bwd_dx_gather9_c64_body(const bf16_t* __r
     float wgt[ROUNDS];
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
-      const float inv_h = (float)nhv[r] + bf2f((bf16_t)(oraw[r] & 0xffffu)), inv_w = (float)nwv[r] + bf2f((bf16_t)(oraw[r] >> 16));
-      const float wv = corner_weight_at(inv_h, inv_w, h, w, g.H, g.W);
+      const DeformOffset off = deform_offset_pair(oraw[r]);
+      const float wv = corner_weight_at((float)nhv[r] + off.h, (float)nwv[r] + off.w, h, w, g.H, g.W);
       wgt[r] = valid[r] ? wv : 0.f;
     }
     float acc = 0.f;
@@ -589,7 +466,6 @@ __device__ __forceinline__ void deform_bwd_doff_tile_c64_body(const bf16_t* __re
   const int lane = threadIdx.x & 63, l8 = lane & 7;
   const int slot = threadIdx.x >> 3;
   const int pw = slot % DT_W, ph0 = slot / DT_W;
-  const float Hf = (float)g.H, Wf = (float)g.W;
 #pragma unroll 1
   for (int bt = 0; bt < 4; ++bt) {
     const int ho_raw = th0 + 2 * bt + ph0, wo_raw = tw0 + pw;
@@ -615,27 +491,20 @@ __device__ __forceinline__ void deform_bwd_doff_tile_c64_body(const bf16_t* __re
       sv[6] = 0.f; sv[7] = 0.f;
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
-        const float off_h = bf2f((bf16_t)(orw[u] & 0xffffu)), off_w = bf2f((bf16_t)(orw[u] >> 16));
-        if (off_h < -(float)R || off_h >= (float)R || off_w < -(float)R || off_w >= (float)R) farm |= 1u << (tb * 3 + u);
-        const float inv_h = (float)(h_in + tb) + off_h, inv_w = (float)(w_in + u) + off_w;
-        const bool in = !(inv_h < 0 || inv_w < 0 || inv_h >= Hf || inv_w >= Wf);
-        float ih = in ? inv_h : 0.f, iw = in ? inv_w : 0.f;
-        int hl = (int)ih, wl = (int)iw, hh, wh;
-        if (hl >= g.H - 1) { hh = hl = g.H - 1; ih = (float)hl; } else hh = hl + 1;
-        if (wl >= g.W - 1) { wh = wl = g.W - 1; iw = (float)wl; } else wh = wl + 1;
-        const float a_w = in ? (float)(wl + 1) - iw : 0.f, b_w = in ? iw - (float)wl : 0.f;      // get_coordinate_weight (:177-221)
-        const float a_h = in ? (float)(hl + 1) - ih : 0.f, b_h = in ? ih - (float)hl : 0.f;
-        const int rl = hl - (th0 - (R + 1)), rh = hh - (th0 - (R + 1)), cl = wl - (tw0 - (R + 1)), ch = wh - (tw0 - (R + 1));
+        const DeformOffset off = deform_offset_pair(orw[u]);
+        if (off.h < -(float)R || off.h >= (float)R || off.w < -(float)R || off.w >= (float)R) farm |= 1u << (tb * 3 + u);
+        const DeformCoordWeights c = deform_coord_weights((float)(h_in + tb) + off.h, (float)(w_in + u) + off.w, g.H, g.W);
+        const int rl = c.hl - (th0 - (R + 1)), rh = c.hh - (th0 - (R + 1)), cl = c.wl - (tw0 - (R + 1)), ch = c.wh - (tw0 - (R + 1));
         const bool staged = rl >= 0 && rh < DT_RH && cl >= 0 && ch < DT_RW;
         uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0;
-        if (in && staged) {
+        if (c.in && staged) {
           v0 = sx[(rl * DT_RW + cl) * 8 + l8]; v1 = sx[(rl * DT_RW + ch) * 8 + l8];
           v2 = sx[(rh * DT_RW + cl) * 8 + l8]; v3 = sx[(rh * DT_RW + ch) * 8 + l8];
         }
-        if (__any(in && !staged)) {                                     // (an offset outside [-R, R): rare in this form)
-          if (in && !staged) {
-            v0 = *reinterpret_cast<const uint4*>(ub + (long)(hl * g.W + wl) * g.C); v1 = *reinterpret_cast<const uint4*>(ub + (long)(hl * g.W + wh) * g.C);
-            v2 = *reinterpret_cast<const uint4*>(ub + (long)(hh * g.W + wl) * g.C); v3 = *reinterpret_cast<const uint4*>(ub + (long)(hh * g.W + wh) * g.C);
+        if (__any(c.in && !staged)) {                                   // (an offset outside [-R, R): rare in this form)
+          if (c.in && !staged) {
+            v0 = *reinterpret_cast<const uint4*>(ub + (long)(c.hl * g.W + c.wl) * g.C); v1 = *reinterpret_cast<const uint4*>(ub + (long)(c.hl * g.W + c.wh) * g.C);
+            v2 = *reinterpret_cast<const uint4*>(ub + (long)(c.hh * g.W + c.wl) * g.C); v3 = *reinterpret_cast<const uint4*>(ub + (long)(c.hh * g.W + c.wh) * g.C);
           }
         }
         // get_coordinate_weight's two sums, with the corner weights (the same for every channel) taken out of the channel sum: four dot
@@ -649,8 +518,8 @@ __device__ __forceinline__ void deform_bwd_doff_tile_c64_body(const bf16_t* __re
           d_ll = dh_dot2(cgw[e], w0[e], d_ll); d_lh = dh_dot2(cgw[e], w1[e], d_lh);
           d_hl = dh_dot2(cgw[e], w2[e], d_hl); d_hh = dh_dot2(cgw[e], w3[e], d_hh);
         }
-        sv[2 * u] = a_w * (d_hl - d_ll) + b_w * (d_hh - d_lh);
-        sv[2 * u + 1] = a_h * (d_lh - d_ll) + b_h * (d_hh - d_hl);
+        sv[2 * u] = c.a_w * (d_hl - d_ll) + c.b_w * (d_hh - d_lh);
+        sv[2 * u + 1] = c.a_h * (d_lh - d_ll) + c.b_h * (d_hh - d_hl);
       }
       const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
       float r4[4], r2[2];
@@ -737,8 +606,8 @@ __device__ __forceinline__ void deform_bwd_dx_tile_c64_body(const bf16_t* __rest
       // output pixel of the candidate: (nominal position) + pad - tap, pad = 1: row h + dh + 1 - ti, staged at row index (that) - (th0 - R - 1)
       const int nh = h + dh, nw = w + dw;
       const unsigned oraw = soff[((ph + dh + R + 2 - ti) * DT_RW + (pw + dw + R + 2 - tj)) * 9 + t];
-      const float inv_h = (float)nh + bf2f((bf16_t)(oraw & 0xffffu)), inv_w = (float)nw + bf2f((bf16_t)(oraw >> 16));
-      float wv = corner_weight_at(inv_h, inv_w, h, w, g.H, g.W);
+      const DeformOffset off = deform_offset_pair(oraw);
+      float wv = corner_weight_at((float)nh + off.h, (float)nw + off.w, h, w, g.H, g.W);
       if (!live) wv = 0.f;
       const int row = (((n * g.Ho + (nh + 1 - ti)) * g.Wo) + (nw + 1 - tj)) * 9 + t;       // (used only where wv != 0: a valid output pixel)
       unsigned m8 = (unsigned)(__ballot(wv != 0.f) >> gbase) & 0xffu;
@@ -761,7 +630,7 @@ __device__ __forceinline__ void deform_bwd_dx_tile_c64_body(const bf16_t* __rest
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float f[8];
-          unpack8(d4[q], f);
+          dh_unpack8(d4[q], f);
 #pragma unroll
           for (int e = 0; e < 8; ++e) acc[e] += w4[q] * f[e];
         }
@@ -775,17 +644,17 @@ __device__ __forceinline__ void deform_bwd_dx_tile_c64_body(const bf16_t* __rest
     }
     if (relu_x) {                                                            // x is a ReLU output: its producer's ReLU backward, folded in here
       float m[8];
-      unpack8(*reinterpret_cast<const uint4*>(relu_x + o), m);
+      dh_unpack8(*reinterpret_cast<const uint4*>(relu_x + o), m);
 #pragma unroll
       for (int e = 0; e < 8; ++e) if (!(m[e] > 0.f)) acc[e] = 0.f;
     }
     if (accumulate) {
       float old[8];
-      unpack8(*reinterpret_cast<const uint4*>(dx + o), old);
+      dh_unpack8(*reinterpret_cast<const uint4*>(dx + o), old);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += old[e];
     }
-    *reinterpret_cast<uint4*>(dx + o) = pack8(acc);
+    *reinterpret_cast<uint4*>(dx + o) = dh_pack8(acc);
   }
 }
 
@@ -815,17 +684,17 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __rest
     float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     if (relu_x) {
       float m[8];
-      unpack8(*reinterpret_cast<const uint4*>(relu_x + i * 8), m);
+      dh_unpack8(*reinterpret_cast<const uint4*>(relu_x + i * 8), m);
 #pragma unroll
       for (int e = 0; e < 8; ++e) if (!(m[e] > 0.f)) f[e] = 0.f;
     }
     if (accumulate) {
       float o[8];
-      unpack8(*reinterpret_cast<const uint4*>(dst + i * 8), o);
+      dh_unpack8(*reinterpret_cast<const uint4*>(dst + i * 8), o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] += o[e];
     }
-    *reinterpret_cast<uint4*>(dst + i * 8) = pack8(f);
+    *reinterpret_cast<uint4*>(dst + i * 8) = dh_pack8(f);
   }
 }
 
@@ -833,10 +702,9 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __rest
 __global__ __launch_bounds__(256) void deform_far_stat_kernel(const bf16_t* __restrict__ offs, long pairs, unsigned* __restrict__ stat) {
   unsigned c2 = 0, c1 = 0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (long)gridDim.x * blockDim.x) {
-    const unsigned w = reinterpret_cast<const unsigned*>(offs)[i];
-    const float dh = bf2f((bf16_t)(w & 0xffffu)), dw = bf2f((bf16_t)(w >> 16));
-    c2 += (!(dh >= -2.f && dh < 2.f) || !(dw >= -2.f && dw < 2.f)) ? 1u : 0u;
-    c1 += (!(dh >= -1.f && dh < 1.f) || !(dw >= -1.f && dw < 1.f)) ? 1u : 0u;
+    const DeformOffset d = deform_offset_pair(reinterpret_cast<const unsigned*>(offs)[i]);
+    c2 += (!(d.h >= -2.f && d.h < 2.f) || !(d.w >= -2.f && d.w < 2.f)) ? 1u : 0u;
+    c1 += (!(d.h >= -1.f && d.h < 1.f) || !(d.w >= -1.f && d.w < 1.f)) ? 1u : 0u;
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) { c2 += __shfl_xor(c2, o, 64); c1 += __shfl_xor(c1, o, 64); }
@@ -858,18 +726,10 @@ int make_geom(DeformGeom* g, int N, int H, int W, int C, int kh, int kw, int str
   g->Ho = (H + stride - 1) / stride;
   g->Wo = (W + stride - 1) / stride;
   // SAME pad_before from the UNDILATED kernel (deform_conv.cc:473-479)
-  int th = (g->Ho - 1) * stride + kh - H; if (th < 0) th = 0;
-  int tw = (g->Wo - 1) * stride + kw - W; if (tw < 0) tw = 0;
-  g->pad_t = th / 2; g->pad_l = tw / 2;
+  g->pad_t = dh_same_pad_before(H, g->Ho, kh, stride);
+  g->pad_l = dh_same_pad_before(W, g->Wo, kw, stride);
   DH_REQUIRE((int64_t)N * g->Ho * g->Wo * kh * kw * C < (1ll << 40), DANHIP_EINVAL, "%s: tensor too large", what);
   return DANHIP_OK;
-}
-
-inline int grid_for(long total, int block = 256, int cap = 16384) {
-  long b = (total + block - 1) / block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace
@@ -930,9 +790,9 @@ static int deform_sample_bwd_impl(const uint16_t* x, const uint16_t* offsets, co
     // 3.4 / 7.7 ms in the +-2 gather form; s = 2.0 -> 53 % -> 43 ms; the scatter form: 12.0 ms whatever the offsets); the +-1 window
     // (81 candidates per input pixel and group instead of 225) while fewer than 1 / 128 of the taps lie outside [-1, 1).
     BwdGate gate{stat, (unsigned)(pairs / 20 * 3), (unsigned)(pairs / 128), danhip_option("deform_bwd_form")};
-    hipLaunchKernelGGL(deform_far_stat_kernel, dim3(grid_for(pairs, 256, 1024)), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(offsets), pairs, stat);
+    hipLaunchKernelGGL(deform_far_stat_kernel, dim3(dh_grid_for(pairs, 256, 1024)), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(offsets), pairs, stat);
     if (lazy_zero)
-      hipLaunchKernelGGL(zero_if_far_kernel, dim3(grid_for(nx / 4, 256, 2048)), dim3(256), 0, s, reinterpret_cast<uint4*>(workspace), nx / 4, stat, gate.force);
+      hipLaunchKernelGGL(zero_if_far_kernel, dim3(dh_grid_for(nx / 4, 256, 2048)), dim3(256), 0, s, reinterpret_cast<uint4*>(workspace), nx / 4, stat, gate.force);
     if (tiled) {
       const unsigned tgrid = (unsigned)((tile_blocks + 7) / 8 * 8);       // 8 XCDs x their share of the items (the kernels map blockIdx -> item)
       hipLaunchKernelGGL(deform_bwd_doff_tile_c64_kernel, dim3(tgrid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(x),
@@ -941,29 +801,29 @@ static int deform_sample_bwd_impl(const uint16_t* x, const uint16_t* offsets, co
       hipLaunchKernelGGL(deform_bwd_dx_tile_c64_kernel, dim3(tgrid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(offsets),
                          reinterpret_cast<const bf16_t*>(dS), workspace, reinterpret_cast<bf16_t*>(dx), g, accumulate, gate, rx, tiles_h, tiles_w);
     } else {
-      const dim3 gd(grid_for((nd + 31) / 32 * 256, 256, 65536)), gg(grid_for((ng + 3) / 4 * 256, 256, 65536));
+      const dim3 gd(dh_grid_for((nd + 31) / 32 * 256, 256, 65536)), gg(dh_grid_for((ng + 3) / 4 * 256, 256, 65536));
       hipLaunchKernelGGL(deform_bwd_doff9_c64_kernel, gd, dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g, gate);
       hipLaunchKernelGGL(deform_bwd_dx_gather9_c64_kernel, gg, dim3(256), 0, s, offsets, dS, workspace, dx, g, accumulate, gate, rx);
     }
     // the scatter form's two kernels on small grids (grid-stride loops): empty ~10 us each when a gather form runs
     const long nwork = (long)N * g.Ho * g.Wo * kh * kw * deformable_group;
-    hipLaunchKernelGGL(deform_sample_bwd_c64_kernel, dim3(grid_for((nwork + 3) / 4 * 256, 256, 2048)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g,
+    hipLaunchKernelGGL(deform_sample_bwd_c64_kernel, dim3(dh_grid_for((nwork + 3) / 4 * 256, 256, 2048)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g,
                        gate);
-    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(nx / 8, 256, 2048)), dim3(256), 0, s, workspace, dx, nx / 8, accumulate, gate, rx);
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(dh_grid_for(nx / 8, 256, 2048)), dim3(256), 0, s, workspace, dx, nx / 8, accumulate, gate, rx);
     DH_LAUNCH_CHECK();
     return DANHIP_OK;
   }
   const BwdGate none{nullptr, 0u, 0u, 0};
   if (C / deformable_group == 64) {
     const long nwork = (long)N * g.Ho * g.Wo * kh * kw * deformable_group;
-    hipLaunchKernelGGL(deform_sample_bwd_c64_kernel, dim3(grid_for((nwork + 3) / 4 * 256, 256, 65536)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g,
+    hipLaunchKernelGGL(deform_sample_bwd_c64_kernel, dim3(dh_grid_for((nwork + 3) / 4 * 256, 256, 65536)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g,
                        none);
   } else {
     const long total = (long)N * g.Ho * g.Wo * kh * kw * (C / 8);
-    hipLaunchKernelGGL(deform_sample_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g);
+    hipLaunchKernelGGL(deform_sample_bwd_kernel, dim3(dh_grid_for(total, 256, 16384)), dim3(256), 0, s, x, offsets, dS, workspace, d_offsets, g);
   }
   DH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(nx / 8)), dim3(256), 0, s, workspace, dx, nx / 8, accumulate, none, rx);
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(dh_grid_for(nx / 8, 256, 16384)), dim3(256), 0, s, workspace, dx, nx / 8, accumulate, none, rx);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

@@ -13,6 +13,7 @@
 //     channels of one pixel), fp32 accumulators across the 9 * dg K-steps, bias / ReLU epilogue.
 // `col` (optional): the rounded samples are ALSO stored as the column buffer, for a caller that keeps it for the filter gradient
 // (dan_amd/ops.py KEEP_DEFORM_COL); inference passes NULL and the 9x activation-sized buffer never exists.
+#include "deform_sample.h"
 #include "lds_dma.h"
 
 // 64 pixels per workgroup (256 threads, 80 KB of LDS at Cout = 256): TWO workgroups per CU, so one gathers while the other multiplies --
@@ -22,12 +23,6 @@
 #endif
 
 namespace {
-
-__device__ __forceinline__ void df_unpack8(const uint4& u, float* f) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) unpack2bf(w[i], f[2 * i], f[2 * i + 1]);
-}
 
 struct FusedArgs {
   const bf16_t* x;        // [N,H,W,C]
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(BM * 4, 2) void deform_fused_fwd_kernel(const Fused
   };
 
   // ---- gather of K-step ks: loads now, blend + LDS write later
-  struct Taps { uint4 cn[2][4]; float wq[2][4]; bool in[2]; };         // per pixel: the four corner pieces (8 channels each), their weights
+  struct Taps { uint4 cn[2][4]; DeformFwdTap tap[2]; };                // per pixel: the four corner pieces (8 channels each), their weights
   // the offset pairs of a K-step are fetched one step before its gather (a dependent load in front of the eight corner loads would put a
   // memory latency at the head of every K-step)
   unsigned oraw_next[2];
@@ -121,28 +116,18 @@ __global__ __launch_bounds__(BM * 4, 2) void deform_fused_fwd_kernel(const Fused
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int h_in = h_in2[u], w_in = w_in2[u];
-      const int cur_h = a.H - h_in, cur_w = a.W - w_in;
-      const float off_h = bf2f((bf16_t)(oraw[u] & 0xffffu)), off_w = bf2f((bf16_t)(oraw[u] >> 16));
-      const float h_im = (float)(h_in + i * a.dil) + off_h;             // deform_conv.cu:261-262
-      const float w_im = (float)(w_in + j * a.dil) + off_w;
-      const bool in = h_im >= 0 && w_im >= 0 && h_im < a.H && w_im < a.W;         // :263
-      g.in[u] = in;
-      float mh = (float)(i * a.dil) + off_h, mw = (float)(j * a.dil) + off_w;     // :264-265 (relative to (h_in, w_in))
-      if (!in) { mh = (float)(-h_in); mw = (float)(-w_in); }            // (any valid address: the result is discarded)
-      int h_low = (int)floorf(mh), w_low = (int)floorf(mw), h_high, w_high;       // deformable_im2col_bilinear :94-112
-      if (h_low >= cur_h - 1) { h_high = h_low = cur_h - 1; mh = (float)h_low; } else h_high = h_low + 1;
-      if (w_low >= cur_w - 1) { w_high = w_low = cur_w - 1; mw = (float)w_low; } else w_high = w_low + 1;
-      const float lh = mh - h_low, lw = mw - w_low, hh = 1 - lh, hw = 1 - lw;
-      g.wq[u][0] = hh * hw; g.wq[u][1] = hh * lw; g.wq[u][2] = lh * hw; g.wq[u][3] = lh * lw;          // :118-125
+      const DeformOffset off = deform_offset_pair(oraw[u]);
+      g.tap[u] = deform_fwd_tap(h_in, w_in, i * a.dil, j * a.dil, off.h, off.w, a.H, a.W);
+      const DeformFwdTap& s = g.tap[u];
       // (24-bit multiplies: rows, pixels of one image and C are all below 2^24 and an image below 2^32 elements — the launcher checks;
       // the 64-bit forms cost three quarter-rate v_mul_lo_u32 / v_mad_u64_u32 per corner in a loop that is VALU-bound)
       const bf16_t* base = xq2[u] + grp * 64;
-      const unsigned rl = __umul24((unsigned)(h_in + h_low), (unsigned)a.W) + (unsigned)w_in;
-      const unsigned rh = __umul24((unsigned)(h_in + h_high), (unsigned)a.W) + (unsigned)w_in;
-      g.cn[u][0] = *reinterpret_cast<const uint4*>(base + __umul24(rl + (unsigned)w_low, (unsigned)a.C));
-      g.cn[u][1] = *reinterpret_cast<const uint4*>(base + __umul24(rl + (unsigned)w_high, (unsigned)a.C));
-      g.cn[u][2] = *reinterpret_cast<const uint4*>(base + __umul24(rh + (unsigned)w_low, (unsigned)a.C));
-      g.cn[u][3] = *reinterpret_cast<const uint4*>(base + __umul24(rh + (unsigned)w_high, (unsigned)a.C));
+      const unsigned rl = __umul24((unsigned)(h_in + s.h_low), (unsigned)a.W) + (unsigned)w_in;
+      const unsigned rh = __umul24((unsigned)(h_in + s.h_high), (unsigned)a.W) + (unsigned)w_in;
+      g.cn[u][0] = *reinterpret_cast<const uint4*>(base + __umul24(rl + (unsigned)s.w_low, (unsigned)a.C));
+      g.cn[u][1] = *reinterpret_cast<const uint4*>(base + __umul24(rl + (unsigned)s.w_high, (unsigned)a.C));
+      g.cn[u][2] = *reinterpret_cast<const uint4*>(base + __umul24(rh + (unsigned)s.w_low, (unsigned)a.C));
+      g.cn[u][3] = *reinterpret_cast<const uint4*>(base + __umul24(rh + (unsigned)s.w_high, (unsigned)a.C));
     }
   };
   uint4 pend[2];
@@ -151,11 +136,10 @@ __global__ __launch_bounds__(BM * 4, 2) void deform_fused_fwd_kernel(const Fused
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       float v1[8], v2[8], v3[8], v4[8], o[8];
-      df_unpack8(g.cn[u][0], v1); df_unpack8(g.cn[u][1], v2); df_unpack8(g.cn[u][2], v3); df_unpack8(g.cn[u][3], v4);
+      dh_unpack8(g.cn[u][0], v1); dh_unpack8(g.cn[u][1], v2); dh_unpack8(g.cn[u][2], v3); dh_unpack8(g.cn[u][3], v4);
 #pragma unroll
-      for (int e = 0; e < 8; ++e)       // (the explicit fma chain of deform_sample_fwd_kernel: identical column values)
-        o[e] = fmaf(g.wq[u][3], v4[e], fmaf(g.wq[u][2], v3[e], fmaf(g.wq[u][1], v2[e], g.wq[u][0] * v1[e])));
-      const bool keep = g.in[u] && live2[u];        // a select on the packed words (a branch around the blend costs more than the blend)
+      for (int e = 0; e < 8; ++e) o[e] = deform_blend(g.tap[u].wq, v1[e], v2[e], v3[e], v4[e]);     // (as deform_sample_fwd_kernel: identical column values)
+      const bool keep = g.tap[u].in && live2[u];        // a select on the packed words (a branch around the blend costs more than the blend)
       uint4 outv;
       outv.x = keep ? pack2bf(o[0], o[1]) : 0u; outv.y = keep ? pack2bf(o[2], o[3]) : 0u;
       outv.z = keep ? pack2bf(o[4], o[5]) : 0u; outv.w = keep ? pack2bf(o[6], o[7]) : 0u;
@@ -296,9 +280,8 @@ int danhip_launch_deform_fused_fwd(const uint16_t* x, const uint16_t* wf_packed,
   a.N = N; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.Kpad = kpad; a.dg = dg; a.stride = stride; a.dil = dil; a.relu = relu;
   a.Ho = (H + stride - 1) / stride;
   a.Wo = (W + stride - 1) / stride;
-  int th = (a.Ho - 1) * stride + 3 - H; if (th < 0) th = 0;            // SAME pad_before from the undilated kernel (deform_conv.cc:473-479)
-  int tw = (a.Wo - 1) * stride + 3 - W; if (tw < 0) tw = 0;
-  a.pad_t = th / 2; a.pad_l = tw / 2;
+  a.pad_t = dh_same_pad_before(H, a.Ho, 3, stride);                    // SAME pad_before from the undilated kernel (deform_conv.cc:473-479)
+  a.pad_l = dh_same_pad_before(W, a.Wo, 3, stride);
   a.M = (long)N * a.Ho * a.Wo;
   if (Cout == 256) return launch_fused<256, FUSED_BM>(a, s);
   if (Cout == 128) return launch_fused<128, FUSED_BM>(a, s);

@@ -11,16 +11,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 struct bf8 { uint4 v; };
-__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) unpack2bf(w[i], f[2 * i], f[2 * i + 1]);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 u;
-  u.x = pack2bf(f[0], f[1]); u.y = pack2bf(f[2], f[3]); u.z = pack2bf(f[4], f[5]); u.w = pack2bf(f[6], f[7]);
-  return u;
-}
 
 // ------------------------------------------------------------------ ReLU backward + bias gradient (one pass over dy)
 // grid: (column groups of 8 channels) x (row chunks).  Each thread owns 8 channels and strides over rows.
@@ -36,14 +26,14 @@ __global__ void relu_bwd_bias_kernel(bf16_t* __restrict__ dy, const bf16_t* __re
       const long o = m * C + g * 8;
       uint4 d = *reinterpret_cast<const uint4*>(dy + o);
       float f[8];
-      unpack8(d, f);
+      dh_unpack8(d, f);
       if (y) {
         uint4 yy = *reinterpret_cast<const uint4*>(y + o);
         float yf[8];
-        unpack8(yy, yf);
+        dh_unpack8(yy, yf);
 #pragma unroll
         for (int i = 0; i < 8; ++i) if (!(yf[i] > 0.f)) f[i] = 0.f;
-        *reinterpret_cast<uint4*>(dy + o) = pack8(f);
+        *reinterpret_cast<uint4*>(dy + o) = dh_pack8(f);
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) s[i] += f[i];
@@ -94,13 +84,13 @@ __global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
         const int h = ho * 2 + dh, w = wo * 2 + dw;
         if (h < H && w < W) {
           float f[8];
-          unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), f);
+          dh_unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), f);
 #pragma unroll
           for (int i = 0; i < 8; ++i)
             if (f[i] > m[i]) { m[i] = f[i]; codes = (codes & ~(3u << (2 * i))) | ((unsigned)(dh * 2 + dw) << (2 * i)); }      // strict: the first maximum stays
         }
       }
-    *reinterpret_cast<uint4*>(y + idx * 8) = pack8(m);
+    *reinterpret_cast<uint4*>(y + idx * 8) = dh_pack8(m);
     if (arg) *reinterpret_cast<unsigned short*>(arg + (idx / cg) * (C / 4) + g * 2) = (unsigned short)codes;
   }
 }
@@ -122,13 +112,13 @@ __global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* _
     for (int t = 0; t < 4; ++t) {
       const int h = ho * 2 + (t >> 1), w = wo * 2 + (t & 1);
       in[t] = h < H && w < W;
-      if (in[t]) unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), v[t]);
+      if (in[t]) dh_unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), v[t]);
       else
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[t][i] = -INFINITY;
     }
     float gy[8];
-    unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), gy);
+    dh_unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), gy);
     float o[4][8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -146,11 +136,11 @@ __global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* _
         uint4* dst = reinterpret_cast<uint4*>(dx + (((long)n * H + h) * W + w) * C + g * 8);
         if (accumulate) {
           float old[8];
-          unpack8(*dst, old);
+          dh_unpack8(*dst, old);
 #pragma unroll
           for (int i = 0; i < 8; ++i) o[t][i] += old[i];
         }
-        *dst = pack8(o[t]);
+        *dst = dh_pack8(o[t]);
       }
     }
   }
@@ -185,7 +175,7 @@ __global__ void l2norm_fwd_kernel(const bf16_t* __restrict__ x, const float* __r
     float ss = 0.f;
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
-      if (ok) unpack8(*reinterpret_cast<const uint4*>(x + pix * C + (v * LPP + l) * 8), f[v]);
+      if (ok) dh_unpack8(*reinterpret_cast<const uint4*>(x + pix * C + (v * LPP + l) * 8), f[v]);
       else
 #pragma unroll
         for (int i = 0; i < 8; ++i) f[v][i] = 0.f;
@@ -199,7 +189,7 @@ __global__ void l2norm_fwd_kernel(const bf16_t* __restrict__ x, const float* __r
       for (int v = 0; v < VPL; ++v) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) f[v][i] = f[v][i] * inv * gm[v][i];
-        *reinterpret_cast<uint4*>(y + pix * C + (v * LPP + l) * 8) = pack8(f[v]);
+        *reinterpret_cast<uint4*>(y + pix * C + (v * LPP + l) * 8) = dh_pack8(f[v]);
       }
     }
   }
@@ -286,8 +276,8 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
     for (int v = 0; v < VPL; ++v) {
       const long o = pix * C + (v * LPP + l) * 8;
       if (ok) {
-        unpack8(*reinterpret_cast<const uint4*>(x + o), f[v]);
-        unpack8(*reinterpret_cast<const uint4*>(dy + o), g[v]);
+        dh_unpack8(*reinterpret_cast<const uint4*>(x + o), f[v]);
+        dh_unpack8(*reinterpret_cast<const uint4*>(dy + o), g[v]);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { f[v][i] = 0.f; g[v][i] = 0.f; }
@@ -303,7 +293,7 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
       for (int v = 0; v < VPL; ++v) {
         const long o = pix * C + (v * LPP + l) * 8;
         float r[8], old[8];
-        if (accumulate) unpack8(*reinterpret_cast<const uint4*>(dx + o), old);
+        if (accumulate) dh_unpack8(*reinterpret_cast<const uint4*>(dx + o), old);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           float t = l2_bwd_term(f[v][i], g[v][i], gm[v][i], inv, k, relu_mask);
@@ -311,7 +301,7 @@ __global__ void l2norm_bwd_kernel(const bf16_t* __restrict__ x, const float* __r
           r[i] = t;
           dg[v][i] = l2_bwd_dgamma(dg[v][i], f[v][i], g[v][i], inv);
         }
-        *reinterpret_cast<uint4*>(dx + o) = pack8(r);
+        *reinterpret_cast<uint4*>(dx + o) = dh_pack8(r);
       }
     }
   }
@@ -377,12 +367,12 @@ __global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16
       gyr = *reinterpret_cast<const uint4*>(pdy + win * C + l * 8);
     }
     float gy[8];
-    unpack8(gyr, gy);
+    dh_unpack8(gyr, gy);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       float f[8], g[8];
-      unpack8(xr[t], f);
-      unpack8(gr[t], g);
+      dh_unpack8(xr[t], f);
+      dh_unpack8(gr[t], g);
       float ss = 0.f, dot = 0.f;
       l2_bwd_sums(f, g, gm, ss, dot);
       ss = pixel_sum<LPP, 1>(ss);
@@ -391,7 +381,7 @@ __global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16
       const float k = (ss > 1e-10f) ? dot * inv * inv * inv : 0.f;
       if (ok[t]) {
         float a[8], b[8], old[8];
-        if (accumulate) unpack8(*reinterpret_cast<const uint4*>(dx + off[t]), old);
+        if (accumulate) dh_unpack8(*reinterpret_cast<const uint4*>(dx + off[t]), old);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           b[i] = l2_bwd_term(f[i], g[i], gm[i], inv, k, relu_mask);
@@ -407,10 +397,10 @@ __global__ __launch_bounds__(512) void l2norm_bwd_pool_scatter_kernel(const bf16
 #pragma unroll
           for (int i = 0; i < 8; ++i) a[i] += old[i];
         }
-        unpack8(pack8(a), a);                                // what the first launch would have stored
+        dh_unpack8(dh_pack8(a), a);                                // what the first launch would have stored
 #pragma unroll
         for (int i = 0; i < 8; ++i) b[i] += a[i];
-        *reinterpret_cast<uint4*>(dx + off[t]) = pack8(b);
+        *reinterpret_cast<uint4*>(dx + off[t]) = dh_pack8(b);
       }
     }
   }
@@ -427,7 +417,7 @@ __global__ void preprocess_kernel(const unsigned char* __restrict__ img, bf16_t*
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
     const float r = (float)img[p * 3] - 123.68f, g = (float)img[p * 3 + 1] - 116.78f, b = (float)img[p * 3 + 2] - 103.94f;
     float f[8] = {b, g, r, 0, 0, 0, 0, 0};
-    *reinterpret_cast<uint4*>(out + p * 8) = pack8(f);
+    *reinterpret_cast<uint4*>(out + p * 8) = dh_pack8(f);
   }
 }
 
@@ -441,13 +431,6 @@ __global__ void cast_pad_kernel(const float* __restrict__ src, const bf16_t* __r
     if (relu_y && c < c_src && !(bf2f(relu_y[r * c_src + c]) > 0.f)) v = 0.f;       // ReLU backward on the UNPADDED layout of y
     dst[i] = f2bf(v);
   }
-}
-
-inline int grid_for(long total, int block, int cap = 8192) {
-  long b = (total + block - 1) / block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace
@@ -494,21 +477,21 @@ __global__ void slice_deliver_vec_kernel(const bf16_t* __restrict__ dy, int ldy,
     const long m = idx / cg;
     const int g = (int)(idx - m * cg);
     float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(dy + m * ldy + c0 + g * 8), f);
+    dh_unpack8(*reinterpret_cast<const uint4*>(dy + m * ldy + c0 + g * 8), f);
     if (mask) {
       float k[8];
-      unpack8(*reinterpret_cast<const uint4*>(mask + idx * 8), k);
+      dh_unpack8(*reinterpret_cast<const uint4*>(mask + idx * 8), k);
 #pragma unroll
       for (int i = 0; i < 8; ++i) if (!(k[i] > 0.f)) f[i] = 0.f;
     }
     uint4* dst = reinterpret_cast<uint4*>(out + idx * 8);
     if (accumulate) {
       float old[8];
-      unpack8(*dst, old);
+      dh_unpack8(*dst, old);
 #pragma unroll
       for (int i = 0; i < 8; ++i) f[i] += old[i];
     }
-    *dst = pack8(f);
+    *dst = dh_pack8(f);
   }
 }
 // ragged form (C or c0 not a multiple of 8): one element per lane
@@ -563,7 +546,7 @@ __global__ void relu_bits_kernel(const bf16_t* __restrict__ x, unsigned char* __
     for (int b = 0; b < 4; ++b) {
       if (b < nb) {
         float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(x + m * C + (j * 4 + b) * 8), f);
+        dh_unpack8(*reinterpret_cast<const uint4*>(x + m * C + (j * 4 + b) * 8), f);
         unsigned byte = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) byte |= (f[i] > 0.f ? 1u : 0u) << i;
@@ -613,7 +596,7 @@ extern "C" int danhip_maxpool2x2_fwd_arg(const uint16_t* x, uint16_t* y, uint8_t
   DH_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "maxpool2x2_fwd: bad arguments (C%%8)");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const long total = (long)N * Ho * Wo * (C / 8);
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, Ho, Wo, arg);
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(dh_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, Ho, Wo, arg);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -638,7 +621,7 @@ __global__ void maxpool_bwd_arg_kernel(const unsigned char* __restrict__ arg, co
     const int n = (int)(p / Ho);
     const unsigned codes = *reinterpret_cast<const unsigned short*>(arg + ppix * (C / 4) + g * 2);
     float gy[8];
-    unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), gy);
+    dh_unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), gy);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int h = ho * 2 + (t >> 1), w = wo * 2 + (t & 1);
@@ -649,11 +632,11 @@ __global__ void maxpool_bwd_arg_kernel(const unsigned char* __restrict__ arg, co
         uint4* dst = reinterpret_cast<uint4*>(dx + (((long)n * H + h) * W + w) * C + g * 8);
         if (accumulate) {
           float old[8];
-          unpack8(*dst, old);
+          dh_unpack8(*dst, old);
 #pragma unroll
           for (int i = 0; i < 8; ++i) o[i] += old[i];
         }
-        *dst = pack8(o);
+        *dst = dh_pack8(o);
       }
     }
   }
@@ -665,7 +648,7 @@ extern "C" int danhip_maxpool2x2_bwd_arg(const uint8_t* arg, const uint16_t* dy,
   DH_REQUIRE(arg && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "maxpool2x2_bwd_arg: bad arguments (C%%8)");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const long total = (long)N * Ho * Wo * (C / 8);
-  hipLaunchKernelGGL(maxpool_bwd_arg_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, arg, dy, dx, N, H, W, C, Ho, Wo, accumulate);
+  hipLaunchKernelGGL(maxpool_bwd_arg_kernel, dim3(dh_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, arg, dy, dx, N, H, W, C, Ho, Wo, accumulate);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -675,7 +658,7 @@ extern "C" int danhip_maxpool2x2_bwd(const uint16_t* x, const uint16_t* dy, uint
   DH_REQUIRE(x && dy && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "maxpool2x2_bwd: bad arguments (C%%8)");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const long total = (long)N * Ho * Wo * (C / 8);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, N, H, W, C, Ho, Wo, accumulate);
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(dh_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, N, H, W, C, Ho, Wo, accumulate);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -795,7 +778,7 @@ extern "C" int danhip_l2norm_bwd_pool_scatter_ws(const uint16_t* x, const float*
 
 extern "C" int danhip_preprocess_u8(const uint8_t* img_rgb, uint16_t* out, int64_t npix, void* stream) {
   DH_REQUIRE(img_rgb && out && npix > 0, DANHIP_EINVAL, "preprocess_u8: bad arguments");
-  hipLaunchKernelGGL(preprocess_kernel, dim3(grid_for(npix, 256)), dim3(256), 0, (hipStream_t)stream, img_rgb, out, (long)npix);
+  hipLaunchKernelGGL(preprocess_kernel, dim3(dh_grid_for(npix, 256, 8192)), dim3(256), 0, (hipStream_t)stream, img_rgb, out, (long)npix);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -803,7 +786,7 @@ extern "C" int danhip_preprocess_u8(const uint8_t* img_rgb, uint16_t* out, int64
 extern "C" int danhip_cast_pad_f32_to_bf16(const float* src, const uint16_t* relu_y, uint16_t* dst, int64_t rows, int32_t c_src, int32_t c_dst,
                                            void* stream) {
   DH_REQUIRE(src && dst && rows > 0 && c_src > 0 && c_dst >= c_src, DANHIP_EINVAL, "cast_pad: bad arguments");
-  hipLaunchKernelGGL(cast_pad_kernel, dim3(grid_for(rows * c_dst, 256)), dim3(256), 0, (hipStream_t)stream, src, relu_y, dst, (long)rows, c_src, c_dst);
+  hipLaunchKernelGGL(cast_pad_kernel, dim3(dh_grid_for(rows * c_dst, 256, 8192)), dim3(256), 0, (hipStream_t)stream, src, relu_y, dst, (long)rows, c_src, c_dst);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }

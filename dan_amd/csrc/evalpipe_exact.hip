@@ -9,11 +9,6 @@
 
 namespace {
 
-inline int grid_for(long total, int block, int cap = 4096) {
-  long g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 // one thread per (dy, dx): the pixel arithmetic is resize_u8.h's, shared with the batched form (evalpipe_ragged_exact.hip)
 __global__ void resize_u8_linear_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, int Ho, int Wo, int C,
                                         double scale_x, double scale_y) {
@@ -120,7 +115,7 @@ extern "C" int danhip_resize_u8_linear(const uint8_t* src, int32_t H, int32_t W,
                                        double fy, void* stream) {
   DH_REQUIRE(src && dst && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && fx > 0 && fy > 0, DANHIP_EINVAL, "resize_u8_linear: bad arguments");
   const long total = (long)Ho * Wo;
-  hipLaunchKernelGGL(resize_u8_linear_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, Ho, Wo, C, 1. / fx,
+  hipLaunchKernelGGL(resize_u8_linear_kernel, dim3(dh_grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, Ho, Wo, C, 1. / fx,
                      1. / fy);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;

@@ -10,7 +10,7 @@
 // conv kernel: flat-M implicit GEMM, 64 pixels x 64 output channels per 256-thread workgroup, K walked in (tap, 16-channel) chunks
 // through LDS (register-staged loads; the activation tile is gathered with the tap's shift and zero padding); each wave owns 16 pixels
 // x 64 channels = four 16x16 accumulators.
-#include "common.h"
+#include "deform_sample.h"
 
 namespace {
 
@@ -217,34 +217,19 @@ __global__ void deform_sample_f32_kernel(const float* __restrict__ x, const floa
     const int h_in = ho * stride - pad_t, w_in = wo * stride - pad_l;
     const float* op = offs + m * offc + (grp * taps + t) * 2;
     const float off_h = op[0], off_w = op[1];
-    const float h_im = (float)(h_in + i * dil) + off_h;             // deform_conv.cu:261-262
-    const float w_im = (float)(w_in + j * dil) + off_w;
+    const DeformFwdTap s = deform_fwd_tap(h_in, w_in, i * dil, j * dil, off_h, off_w, H, W);
     float out = 0.f;
-    if (h_im >= 0 && w_im >= 0 && h_im < H && w_im < W) {           // :263
-      float mh = (float)(i * dil) + off_h, mw = (float)(j * dil) + off_w;
-      const int cur_h = H - h_in, cur_w = W - w_in;
-      int h_low = (int)floorf(mh), w_low = (int)floorf(mw), h_high, w_high;
-      if (h_low >= cur_h - 1) { h_high = h_low = cur_h - 1; mh = (float)h_low; } else h_high = h_low + 1;
-      if (w_low >= cur_w - 1) { w_high = w_low = cur_w - 1; mw = (float)w_low; } else w_high = w_low + 1;
-      const float lh = mh - h_low, lw = mw - w_low, hh = 1 - lh, hw = 1 - lw;
+    if (s.in) {
       const float* base = x + ((long)n * H * W) * C + c;
-      const float v1 = base[((long)(h_in + h_low) * W + (w_in + w_low)) * C], v2 = base[((long)(h_in + h_low) * W + (w_in + w_high)) * C];
-      const float v3 = base[((long)(h_in + h_high) * W + (w_in + w_low)) * C], v4 = base[((long)(h_in + h_high) * W + (w_in + w_high)) * C];
-      out = hh * hw * v1 + hh * lw * v2 + lh * hw * v3 + lh * lw * v4;
+      const float v1 = base[((long)(h_in + s.h_low) * W + (w_in + s.w_low)) * C], v2 = base[((long)(h_in + s.h_low) * W + (w_in + s.w_high)) * C];
+      const float v3 = base[((long)(h_in + s.h_high) * W + (w_in + s.w_low)) * C], v4 = base[((long)(h_in + s.h_high) * W + (w_in + s.w_high)) * C];
+      out = s.wq[0] * v1 + s.wq[1] * v2 + s.wq[2] * v3 + s.wq[3] * v4;
     }
     S[(m * taps + t) * C + c] = out;
   }
 }
 
-inline int f32_blocks(long total) {
-  long b = (total + 255) / 256;
-  return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
-}
-inline int f32_same_pad_before(int in, int out, int k, int s) {
-  int total = (out - 1) * s + k - in;
-  if (total < 0) total = 0;
-  return total / 2;
-}
+inline int f32_blocks(long total) { return dh_grid_for(total, 256, 16384); }
 
 }  // namespace
 
@@ -262,8 +247,8 @@ extern "C" int danhip_conv2d_fwd_f32(const danhip_conv_desc* d, const float* x, 
   F32ConvArgs a{};
   a.x = x; a.w = w_hwio; a.bias = bias; a.resid = residual; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Cout; a.kh = d->kh; a.kw = d->kw; a.stride = d->stride;
-  a.pad_t = f32_same_pad_before(d->H, d->Ho, d->kh, d->stride);
-  a.pad_l = f32_same_pad_before(d->W, d->Wo, d->kw, d->stride);
+  a.pad_t = dh_same_pad_before(d->H, d->Ho, d->kh, d->stride);
+  a.pad_l = dh_same_pad_before(d->W, d->Wo, d->kw, d->stride);
   a.M = d->N * d->Ho * d->Wo;
   a.relu = relu;
   a.div_wo = make_fastdiv(a.Wo);
@@ -311,7 +296,7 @@ extern "C" int danhip_deform_sample_fwd_f32(const float* x, const float* offsets
              DANHIP_EINVAL, "deform_sample_fwd_f32: bad dims");
   const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   // pad from the UNDILATED kernel, as the reference (deform_conv.cc:473-479)
-  const int pad_t = f32_same_pad_before(H, Ho, kh, stride), pad_l = f32_same_pad_before(W, Wo, kw, stride);
+  const int pad_t = dh_same_pad_before(H, Ho, kh, stride), pad_l = dh_same_pad_before(W, Wo, kw, stride);
   hipLaunchKernelGGL(deform_sample_f32_kernel, dim3(f32_blocks((long)N * Ho * Wo * kh * kw * C)), dim3(256), 0, (hipStream_t)stream, x, offsets, S, N,
                      H, W, C, Ho, Wo, kh, kw, stride, dilation, deformable_group, pad_t, pad_l);
   DH_LAUNCH_CHECK();

@@ -6,17 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const uint4& u, float* f) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) unpack2bf(w[i], f[2 * i], f[2 * i + 1]);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  uint4 u;
-  u.x = pack2bf(f[0], f[1]); u.y = pack2bf(f[2], f[3]); u.z = pack2bf(f[4], f[5]); u.w = pack2bf(f[6], f[7]);
-  return u;
-}
-
 // tf.image.resize_bilinear legacy source coordinate of destination index d: src = d * (in/out) in fp32
 struct Lerp { int lo, hi; float w; };
 __device__ __forceinline__ Lerp tf_legacy(int d, float scale, int in) {
@@ -42,11 +31,11 @@ __global__ void resize_add_fwd_kernel(const bf16_t* __restrict__ up, const bf16_
     const Lerp ly = tf_legacy(ho, sh, Hi), lx = tf_legacy(wo, sw, Wi);
     float tl[8], tr[8], bl[8], br[8], r[8];
     const bf16_t* base = up + (long)n * Hi * Wi * C + g * 8;
-    unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.lo * Wi + lx.lo) * C), tl);
-    unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.lo * Wi + lx.hi) * C), tr);
-    unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.hi * Wi + lx.lo) * C), bl);
-    unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.hi * Wi + lx.hi) * C), br);
-    if (lat) unpack8(*reinterpret_cast<const uint4*>(lat + idx * 8), r);
+    dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.lo * Wi + lx.lo) * C), tl);
+    dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.lo * Wi + lx.hi) * C), tr);
+    dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.hi * Wi + lx.lo) * C), bl);
+    dh_unpack8(*reinterpret_cast<const uint4*>(base + ((long)ly.hi * Wi + lx.hi) * C), br);
+    if (lat) dh_unpack8(*reinterpret_cast<const uint4*>(lat + idx * 8), r);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float t = tl[i] + (tr[i] - tl[i]) * lx.w;
@@ -54,7 +43,7 @@ __global__ void resize_add_fwd_kernel(const bf16_t* __restrict__ up, const bf16_
       const float v = t + (b - t) * ly.w;
       r[i] = lat ? r[i] + v : v;
     }
-    *reinterpret_cast<uint4*>(out + idx * 8) = pack8(r);
+    *reinterpret_cast<uint4*>(out + idx * 8) = dh_pack8(r);
   }
 }
 
@@ -89,7 +78,7 @@ __global__ void resize_bwd_kernel(const bf16_t* __restrict__ dout, bf16_t* __res
         if (lx.hi == wi) wx += lx.w;
         if (wx == 0.f) continue;
         float gy[8];
-        unpack8(*reinterpret_cast<const uint4*>(dout + (((long)n * Ho + ho) * Wo + wo) * C + g * 8), gy);
+        dh_unpack8(*reinterpret_cast<const uint4*>(dout + (((long)n * Ho + ho) * Wo + wo) * C + g * 8), gy);
         const float wgt = wy * wx;
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] += wgt * gy[i];
@@ -98,11 +87,11 @@ __global__ void resize_bwd_kernel(const bf16_t* __restrict__ dout, bf16_t* __res
     uint4* dst = reinterpret_cast<uint4*>(dup + idx * 8);
     if (accumulate) {
       float old[8];
-      unpack8(*dst, old);
+      dh_unpack8(*dst, old);
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] += old[i];
     }
-    *dst = pack8(acc);
+    *dst = dh_pack8(acc);
   }
 }
 
@@ -126,7 +115,7 @@ __global__ void avgpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
       for (int dw = 0; dw < 2; ++dw) {
         if (h + dh < H && w + dw < W) {
           float f[8];
-          unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h + dh) * W + w + dw) * ldx + g * 8), f);
+          dh_unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h + dh) * W + w + dw) * ldx + g * 8), f);
 #pragma unroll
           for (int i = 0; i < 8; ++i) s[i] += f[i];
           ++cnt;
@@ -139,7 +128,7 @@ __global__ void avgpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restr
 #pragma unroll
       for (int i = 0; i < 8; ++i) s[i] = fmaxf(s[i], 0.f);
     }
-    *reinterpret_cast<uint4*>(y + (idx / cg) * ldy + g * 8) = pack8(s);
+    *reinterpret_cast<uint4*>(y + (idx / cg) * ldy + g * 8) = dh_pack8(s);
   }
 }
 
@@ -162,7 +151,7 @@ __global__ void avgpool_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* 
         if (ho >= 0 && wo >= 0) {
           const int cnt = ((ho + 1 < H) ? 2 : 1) * ((wo + 1 < W) ? 2 : 1);
           float f[8];
-          unpack8(*reinterpret_cast<const uint4*>(dy + (((long)n * H + ho) * W + wo) * ldy + g * 8), f);
+          dh_unpack8(*reinterpret_cast<const uint4*>(dy + (((long)n * H + ho) * W + wo) * ldy + g * 8), f);
           const float d = (float)cnt;
 #pragma unroll
           for (int i = 0; i < 8; ++i) s[i] += f[i] / d;
@@ -171,17 +160,17 @@ __global__ void avgpool_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* 
     uint4* dst = reinterpret_cast<uint4*>(dx + (idx / cg) * ldx + g * 8);
     if (xmask) {                                          // x is a ReLU output: fold its backward in (x > 0)
       float m[8];
-      unpack8(*reinterpret_cast<const uint4*>(xmask + (idx / cg) * ldx + g * 8), m);
+      dh_unpack8(*reinterpret_cast<const uint4*>(xmask + (idx / cg) * ldx + g * 8), m);
 #pragma unroll
       for (int i = 0; i < 8; ++i) if (!(m[i] > 0.f)) s[i] = 0.f;
     }
     if (accumulate) {
       float old[8];
-      unpack8(*dst, old);
+      dh_unpack8(*dst, old);
 #pragma unroll
       for (int i = 0; i < 8; ++i) s[i] += old[i];
     }
-    *dst = pack8(s);
+    *dst = dh_pack8(s);
   }
 }
 
@@ -203,8 +192,8 @@ __global__ void bn_reduce_kernel(const bf16_t* __restrict__ a, const bf16_t* __r
   if (rsub < tpr) {
     for (long r = (long)blockIdx.x * tpr + rsub; r < M; r += (long)gridDim.x * tpr) {
       float fa[8], fb[8];
-      unpack8(*reinterpret_cast<const uint4*>(a + r * C + g * 8), fa);
-      if (b) unpack8(*reinterpret_cast<const uint4*>(b + r * C + g * 8), fb);
+      dh_unpack8(*reinterpret_cast<const uint4*>(a + r * C + g * 8), fa);
+      if (b) dh_unpack8(*reinterpret_cast<const uint4*>(b + r * C + g * 8), fb);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         t1[i] += fa[i];
@@ -238,7 +227,7 @@ __global__ void bn_stats_kernel(const bf16_t* __restrict__ x, double* __restrict
   if (rsub < tpr) {
     for (long r = (long)blockIdx.x * tpr + rsub; r < M; r += (long)gridDim.x * tpr) {
       float f[8];
-      unpack8(*reinterpret_cast<const uint4*>(x + r * C + g * 8), f);
+      dh_unpack8(*reinterpret_cast<const uint4*>(x + r * C + g * 8), f);
 #pragma unroll
       for (int i = 0; i < 8; ++i) { t1[i] += (double)f[i]; t2[i] += (double)(f[i] * f[i]); }
     }
@@ -288,14 +277,14 @@ __global__ void bn_apply_kernel(const bf16_t* __restrict__ x, const float* __res
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int g = (int)(idx % cg);
     float f[8];
-    unpack8(*reinterpret_cast<const uint4*>(x + idx * 8), f);
+    dh_unpack8(*reinterpret_cast<const uint4*>(x + idx * 8), f);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int c = g * 8 + i;
       float v = (f[i] - mean[c]) * rstd[c] * gamma[c] + beta[c];
       f[i] = relu ? fmaxf(v, 0.f) : v;
     }
-    *reinterpret_cast<uint4*>(y + idx * 8) = pack8(f);
+    *reinterpret_cast<uint4*>(y + idx * 8) = dh_pack8(f);
   }
 }
 
@@ -308,23 +297,16 @@ __global__ void bn_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* 
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int g = (int)(idx % cg);
     float fx[8], fd[8];
-    unpack8(*reinterpret_cast<const uint4*>(x + idx * 8), fx);
-    unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), fd);
+    dh_unpack8(*reinterpret_cast<const uint4*>(x + idx * 8), fx);
+    dh_unpack8(*reinterpret_cast<const uint4*>(dy + idx * 8), fd);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int c = g * 8 + i;
       const float xh = (fx[i] - mean[c]) * rstd[c];
       fd[i] = gamma[c] * rstd[c] * (fd[i] - sdy[c] * inv_m - xh * sdyx[c] * inv_m);
     }
-    *reinterpret_cast<uint4*>(dx + idx * 8) = pack8(fd);
+    *reinterpret_cast<uint4*>(dx + idx * 8) = dh_pack8(fd);
   }
-}
-
-inline int grid_for(long total, int block = 256, int cap = 8192) {
-  long b = (total + block - 1) / block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 }  // namespace
@@ -334,7 +316,7 @@ extern "C" int danhip_resize_bilinear_add_fwd(const uint16_t* up, const uint16_t
   DH_REQUIRE(up && out, DANHIP_EINVAL, "resize_bilinear_add_fwd: null pointer");
   DH_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "resize_bilinear_add_fwd: bad dims (C %% 8 == 0)");
   const long total = (long)N * Ho * Wo * (C / 8);
-  hipLaunchKernelGGL(resize_add_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, up, lateral, out, N, Hi, Wi, Ho, Wo, C,
+  hipLaunchKernelGGL(resize_add_fwd_kernel, dim3(dh_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, up, lateral, out, N, Hi, Wi, Ho, Wo, C,
                      (float)Hi / (float)Ho, (float)Wi / (float)Wo);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -345,7 +327,7 @@ extern "C" int danhip_resize_bilinear_add_bwd(const uint16_t* dout, uint16_t* du
   DH_REQUIRE(dout && dup, DANHIP_EINVAL, "resize_bilinear_add_bwd: null pointer");
   DH_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "resize_bilinear_add_bwd: bad dims (C %% 8 == 0)");
   const long total = (long)N * Hi * Wi * (C / 8);
-  hipLaunchKernelGGL(resize_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dout, dup, N, Hi, Wi, Ho, Wo, C,
+  hipLaunchKernelGGL(resize_bwd_kernel, dim3(dh_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dout, dup, N, Hi, Wi, Ho, Wo, C,
                      (float)Hi / (float)Ho, (float)Wi / (float)Wo, accumulate);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -356,11 +338,11 @@ namespace {
 __global__ void add16_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ out, long n8) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     float fa[8], fb[8];
-    unpack8(reinterpret_cast<const uint4*>(a)[i], fa);
-    unpack8(reinterpret_cast<const uint4*>(b)[i], fb);
+    dh_unpack8(reinterpret_cast<const uint4*>(a)[i], fa);
+    dh_unpack8(reinterpret_cast<const uint4*>(b)[i], fb);
 #pragma unroll
     for (int e = 0; e < 8; ++e) fa[e] += fb[e];
-    reinterpret_cast<uint4*>(out)[i] = pack8(fa);
+    reinterpret_cast<uint4*>(out)[i] = dh_pack8(fa);
   }
 }
 // backward of y = r + x with r = relu(.) in ONE pass over dy:  dr = dy * (r > 0)   and   dx (+)= dy * (xmask > 0 | no mask)
@@ -368,23 +350,23 @@ __global__ void residual_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t*
                                     bf16_t* __restrict__ dx, int accumulate, long n8) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     float g[8], m[8], t[8];
-    unpack8(reinterpret_cast<const uint4*>(dy)[i], g);
-    unpack8(reinterpret_cast<const uint4*>(r)[i], m);
+    dh_unpack8(reinterpret_cast<const uint4*>(dy)[i], g);
+    dh_unpack8(reinterpret_cast<const uint4*>(r)[i], m);
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = m[e] > 0.f ? g[e] : 0.f;
-    reinterpret_cast<uint4*>(dr)[i] = pack8(t);
+    reinterpret_cast<uint4*>(dr)[i] = dh_pack8(t);
     if (dx) {
       if (xmask) {
-        unpack8(reinterpret_cast<const uint4*>(xmask)[i], m);
+        dh_unpack8(reinterpret_cast<const uint4*>(xmask)[i], m);
 #pragma unroll
         for (int e = 0; e < 8; ++e) if (!(m[e] > 0.f)) g[e] = 0.f;
       }
       if (accumulate) {
-        unpack8(reinterpret_cast<const uint4*>(dx)[i], m);
+        dh_unpack8(reinterpret_cast<const uint4*>(dx)[i], m);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g[e] += m[e];
       }
-      reinterpret_cast<uint4*>(dx)[i] = pack8(g);
+      reinterpret_cast<uint4*>(dx)[i] = dh_pack8(g);
     }
   }
 }
@@ -392,7 +374,7 @@ __global__ void residual_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t*
 
 extern "C" int danhip_add16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, void* stream) {
   DH_REQUIRE(a && b && out && n > 0 && n % 8 == 0, DANHIP_EINVAL, "add16: null pointer or n not a multiple of 8");
-  hipLaunchKernelGGL(add16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)(n / 8));
+  hipLaunchKernelGGL(add16_kernel, dim3(dh_grid_for(n / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)(n / 8));
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -400,7 +382,7 @@ extern "C" int danhip_add16(const uint16_t* a, const uint16_t* b, uint16_t* out,
 extern "C" int danhip_residual_bwd(const uint16_t* dy, const uint16_t* r, const uint16_t* x_mask, uint16_t* dr, uint16_t* dx, int accumulate, int64_t n,
                                    void* stream) {
   DH_REQUIRE(dy && r && dr && n > 0 && n % 8 == 0, DANHIP_EINVAL, "residual_bwd: null pointer or n not a multiple of 8");
-  hipLaunchKernelGGL(residual_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, dy, r, x_mask, dr, dx, accumulate, (long)(n / 8));
+  hipLaunchKernelGGL(residual_bwd_kernel, dim3(dh_grid_for(n / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, r, x_mask, dr, dx, accumulate, (long)(n / 8));
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -408,7 +390,7 @@ extern "C" int danhip_residual_bwd(const uint16_t* dy, const uint16_t* r, const 
 extern "C" int danhip_avgpool2x2s1_same_fwd(const uint16_t* x, uint16_t* y, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
   DH_REQUIRE(x && y, DANHIP_EINVAL, "avgpool2x2s1_same_fwd: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "avgpool2x2s1_same_fwd: bad dims (C %% 8 == 0)");
-  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, C, C, 0);
+  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(dh_grid_for((long)N * H * W * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, C, C, 0);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -421,7 +403,7 @@ extern "C" int danhip_avgpool2x2s1_same_fwd_strided(const uint16_t* x, int32_t x
   DH_REQUIRE(x && y, DANHIP_EINVAL, "avgpool2x2s1_same_fwd_strided: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && x_pitch >= C && y_pitch >= C && ((x_pitch | y_pitch) & 7) == 0, DANHIP_EINVAL,
              "avgpool2x2s1_same_fwd_strided: bad dims (C and the pitches multiples of 8, pitch >= C)");
-  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, x_pitch, y_pitch,
+  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(dh_grid_for((long)N * H * W * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, x_pitch, y_pitch,
                      relu ? 1 : 0);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -432,7 +414,7 @@ extern "C" int danhip_avgpool2x2s1_same_bwd_strided(const uint16_t* dy, int32_t 
   DH_REQUIRE(dy && dx, DANHIP_EINVAL, "avgpool2x2s1_same_bwd_strided: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && x_pitch >= C && y_pitch >= C && ((x_pitch | y_pitch) & 7) == 0, DANHIP_EINVAL,
              "avgpool2x2s1_same_bwd_strided: bad dims (C and the pitches multiples of 8, pitch >= C)");
-  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, dy, (const bf16_t*)nullptr, dx, N, H, W, C, 0,
+  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(dh_grid_for((long)N * H * W * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, (const bf16_t*)nullptr, dx, N, H, W, C, 0,
                      y_pitch, x_pitch);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -442,7 +424,7 @@ extern "C" int danhip_avgpool2x2s1_same_bwd(const uint16_t* dy, const uint16_t* 
                                             int accumulate, void* stream) {
   DH_REQUIRE(dy && dx, DANHIP_EINVAL, "avgpool2x2s1_same_bwd: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, DANHIP_EINVAL, "avgpool2x2s1_same_bwd: bad dims (C %% 8 == 0)");
-  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((long)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, dy, x_mask, dx, N, H, W, C, accumulate, C, C);
+  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(dh_grid_for((long)N * H * W * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, x_mask, dx, N, H, W, C, accumulate, C, C);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -477,7 +459,7 @@ extern "C" int danhip_batchnorm_fwd_train(const uint16_t* x, const float* gamma,
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, sums, sums + C, save_mean, save_rstd, (float*)nullptr,
                      moving_mean, moving_var, (double)M, eps, momentum, C);
   DH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * cg)), dim3(256), 0, s, x, save_mean, save_rstd, gamma, beta, y, (long)M, C, relu);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(dh_grid_for(M * cg, 256, 8192)), dim3(256), 0, s, x, save_mean, save_rstd, gamma, beta, y, (long)M, C, relu);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -488,7 +470,7 @@ extern "C" int danhip_batchnorm_fwd_infer(const uint16_t* x, const float* gamma,
   int rc = bn_check(x, M, C, "batchnorm_fwd_infer");
   if (rc) return rc;
   DH_REQUIRE(gamma && beta && mean && rstd && y, DANHIP_EINVAL, "batchnorm_fwd_infer: null pointer");
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * (C / 8))), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, y, (long)M, C, relu);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(dh_grid_for(M * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, y, (long)M, C, relu);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -512,7 +494,7 @@ extern "C" int danhip_batchnorm_bwd(const uint16_t* x, const uint16_t* dy, const
   if (grid > 1024) grid = 1024;
   hipLaunchKernelGGL(bn_reduce_kernel, dim3(grid), dim3(block), sizeof(float) * block * 16, s, dy, x, save_mean, save_rstd, dbeta, dgamma, (long)M, C);
   DH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * cg)), dim3(256), 0, s, x, dy, save_mean, save_rstd, gamma, dbeta, dgamma, dx, (long)M, C,
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(dh_grid_for(M * cg, 256, 8192)), dim3(256), 0, s, x, dy, save_mean, save_rstd, gamma, dbeta, dgamma, dx, (long)M, C,
                      1.0f / (float)M);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -542,12 +524,12 @@ __global__ void maxpool3x3s2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __
         const int h = ho * 2 - pt + dh, w = wo * 2 - pl + dw;
         if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
           float f[8];
-          unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), f);
+          dh_unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + h) * W + w) * C + g * 8), f);
 #pragma unroll
           for (int i = 0; i < 8; ++i) m[i] = fmaxf(m[i], f[i]);
         }
       }
-    *reinterpret_cast<uint4*>(y + idx * 8) = pack8(m);
+    *reinterpret_cast<uint4*>(y + idx * 8) = dh_pack8(m);
   }
 }
 
@@ -578,17 +560,17 @@ __global__ void maxpool3x3s2_bwd_kernel(const bf16_t* __restrict__ x, const bf16
             if ((unsigned)hh >= (unsigned)H || (unsigned)ww >= (unsigned)W) continue;
             if (hh == h && ww == w) mine = dh * 3 + dw;
             float f[8];
-            unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + hh) * W + ww) * C + g * 8), f);
+            dh_unpack8(*reinterpret_cast<const uint4*>(x + (((long)n * H + hh) * W + ww) * C + g * 8), f);
 #pragma unroll
             for (int i = 0; i < 8; ++i) if (f[i] > best[i]) { best[i] = f[i]; bidx[i] = dh * 3 + dw; }
           }
         float gy[8];
-        unpack8(*reinterpret_cast<const uint4*>(dy + ((((long)n * Ho + ho) * Wo + wo) * C + g * 8)), gy);
+        dh_unpack8(*reinterpret_cast<const uint4*>(dy + ((((long)n * Ho + ho) * Wo + wo) * C + g * 8)), gy);
 #pragma unroll
         for (int i = 0; i < 8; ++i) if (bidx[i] == mine) acc[i] += gy[i];
       }
     }
-    *reinterpret_cast<uint4*>(dx + idx * 8) = pack8(acc);
+    *reinterpret_cast<uint4*>(dx + idx * 8) = dh_pack8(acc);
   }
 }
 }  // namespace

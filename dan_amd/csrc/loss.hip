@@ -471,13 +471,6 @@ __global__ void loss_scale_update_kernel(float* __restrict__ dyn) {
   dyn[3] = 0.f;
 }
 
-inline int grid_for(long total, int block, int cap = 4096) {
-  long b = (total + block - 1) / block;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" int danhip_head_split_fwd(const float* h, float* loc, float* cls, int32_t B, int32_t HW, int32_t Ch, int32_t nneg, int32_t npos,
@@ -485,7 +478,7 @@ extern "C" int danhip_head_split_fwd(const float* h, float* loc, float* cls, int
   DH_REQUIRE(h && loc && cls && B > 0 && HW > 0 && nneg >= 1 && npos >= 1 && Ch == 4 + nneg + npos, DANHIP_EINVAL,
              "head_split_fwd: bad arguments (Ch must be 4+nneg+npos, depth 1)");
   DH_REQUIRE(anchor_offset >= 0 && anchor_offset + HW <= A, DANHIP_EINVAL, "head_split_fwd: anchor range out of bounds");
-  hipLaunchKernelGGL(head_split_fwd_kernel, dim3(grid_for((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, h, loc, cls, B, HW, Ch, nneg,
+  hipLaunchKernelGGL(head_split_fwd_kernel, dim3(dh_grid_for((long)B * HW, 256, 4096)), dim3(256), 0, (hipStream_t)stream, h, loc, cls, B, HW, Ch, nneg,
                      npos, A, anchor_offset);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -496,7 +489,7 @@ extern "C" int danhip_head_split_bwd(const float* h, const float* dloc, const fl
   DH_REQUIRE(h && dloc && dcls && dy && B > 0 && HW > 0 && nneg >= 1 && npos >= 1 && Ch == 4 + nneg + npos, DANHIP_EINVAL,
              "head_split_bwd: bad arguments");
   DH_REQUIRE(anchor_offset >= 0 && anchor_offset + HW <= A, DANHIP_EINVAL, "head_split_bwd: anchor range out of bounds");
-  hipLaunchKernelGGL(head_split_bwd_kernel, dim3(grid_for((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, h, dloc, dcls, dy, B, HW, Ch,
+  hipLaunchKernelGGL(head_split_bwd_kernel, dim3(dh_grid_for((long)B * HW, 256, 4096)), dim3(256), 0, (hipStream_t)stream, h, dloc, dcls, dy, B, HW, Ch,
                      nneg, npos, A, anchor_offset);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -546,7 +539,7 @@ extern "C" int danhip_heads_split_fwd(const danhip_head_level* levels, int32_t n
   HeadsTable t;
   if (int rc = heads_table(levels, nlevels, B, A, false, "heads_split_fwd", &t)) return rc;
   const long rows = t.row0[t.n];
-  hipLaunchKernelGGL(heads_split_fwd_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, t, loc, cls, A);
+  hipLaunchKernelGGL(heads_split_fwd_kernel, dim3(dh_grid_for(rows, 256, 4096)), dim3(256), 0, (hipStream_t)stream, t, loc, cls, A);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -558,7 +551,7 @@ extern "C" int danhip_heads_grad_pad(const danhip_head_level* levels, int32_t nl
   HeadsTable t;
   if (int rc = heads_table(levels, nlevels, B, A, true, "heads_grad_pad", &t)) return rc;
   const long rows = t.row0[t.n];
-  hipLaunchKernelGGL(heads_grad_pad_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, t, dloc, dcls, A);
+  hipLaunchKernelGGL(heads_grad_pad_kernel, dim3(dh_grid_for(rows, 256, 4096)), dim3(256), 0, (hipStream_t)stream, t, dloc, dcls, A);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
 }
@@ -569,7 +562,7 @@ extern "C" int danhip_hard_neg_select(const float* cls, const int32_t* labels, f
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, sizeof(int32_t) * 2 * B, s) != hipSuccess) { danhip_set_error("hard_neg_select: memset failed"); return DANHIP_ELAUNCH; }
   // (few, fat blocks: the block totals end in atomics on two words per row - 64 blocks per row spent most of the kernel queueing on them)
-  hipLaunchKernelGGL(hard_neg_scores_kernel, dim3((unsigned)grid_for(A, 1024, 8), (unsigned)B), dim3(1024), 0, s, cls, labels, score, counts, A);
+  hipLaunchKernelGGL(hard_neg_scores_kernel, dim3((unsigned)dh_grid_for(A, 1024, 8), (unsigned)B), dim3(1024), 0, s, cls, labels, score, counts, A);
   DH_LAUNCH_CHECK();
   if (A <= 36 * 1024)
     hipLaunchKernelGGL(kth_largest_rows_kernel<36>, dim3((unsigned)B), dim3(1024), 0, s, score, counts, thr, k_out, A, negative_ratio, at_least_one);
@@ -590,7 +583,7 @@ static int detection_loss_fwd_impl(const float* cls, const float* loc, const int
   if (hipMemsetAsync(acc4, 0, sizeof(float) * 4, s) != hipSuccess) { danhip_set_error("detection_loss_fwd: memset failed"); return DANHIP_ELAUNCH; }
   const long total = (long)B * A;
   // (the four sums end in atomics on ONE 16-byte word: 1024 blocks spent ~40 of the kernel's 57 us queueing there; 128 fat blocks do not)
-  const int blocks = grid_for(total, 1024, 128);      // (the grid of the default launch below)
+  const int blocks = dh_grid_for(total, 1024, 128);      // (the grid of the default launch below)
   const bool det = danhip_option("deterministic") != 0;      // the block sums as rows of ws, finished in block order (danhip.h "Deterministic mode")
   if (det)
     DH_REQUIRE(ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= DANHIP_LOSS_WS_BYTES && ((uintptr_t)acc4 & 15) == 0, DANHIP_EINVAL,
@@ -599,7 +592,7 @@ static int detection_loss_fwd_impl(const float* cls, const float* loc, const int
     hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(blocks), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel, acc4, A, total,
                        reinterpret_cast<float*>(ws));
   else
-    hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(grid_for(total, 1024, 128)), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel,
+    hipLaunchKernelGGL(detection_loss_fwd_kernel, dim3(dh_grid_for(total, 1024, 128)), dim3(1024), 0, s, cls, loc, labels, loc_targets, score, thr, sel,
                        acc4, A, total, (float*)nullptr);
   DH_LAUNCH_CHECK();
   if (det) return dh_ordered_reduce(reinterpret_cast<const float*>(ws), 4, blocks, 4, acc4, 0, s);
@@ -618,7 +611,7 @@ extern "C" int danhip_detection_loss_bwd(const float* cls, const float* loc, con
                                          float* dcls, float* dloc, float ce_scale, float loc_scale, int32_t B, int32_t A, void* stream) {
   DH_REQUIRE(cls && loc && loc_targets && sel && acc4 && dcls && dloc && B > 0 && A > 0, DANHIP_EINVAL, "detection_loss_bwd: bad arguments");
   const long total = (long)B * A;
-  hipLaunchKernelGGL(detection_loss_bwd_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, (hipStream_t)stream, cls, loc, loc_targets, sel,
+  hipLaunchKernelGGL(detection_loss_bwd_kernel, dim3(dh_grid_for(total, 256, 2048)), dim3(256), 0, (hipStream_t)stream, cls, loc, loc_targets, sel,
                      acc4, dcls, dloc, ce_scale, loc_scale, total);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -631,7 +624,7 @@ extern "C" int danhip_cls_accuracy(const float* cls, const int32_t* labels, cons
   const int64_t total = (int64_t)B * A;
   DH_REQUIRE(total <= INT32_MAX, DANHIP_EINVAL, "cls_accuracy: B * A = %lld anchors exceeds the kernel's 32-bit index range (2^31 - 1)",
              (long long)total);
-  hipLaunchKernelGGL(cls_accuracy_kernel, dim3(grid_for(total, kAccThreads, kAccMaxBlocks)), dim3(kAccThreads), 0, (hipStream_t)stream, cls, labels,
+  hipLaunchKernelGGL(cls_accuracy_kernel, dim3(dh_grid_for(total, kAccThreads, kAccMaxBlocks)), dim3(kAccThreads), 0, (hipStream_t)stream, cls, labels,
                      sel, reinterpret_cast<unsigned long long*>(counts), (unsigned)total);
   DH_LAUNCH_CHECK();
   return DANHIP_OK;
@@ -660,7 +653,7 @@ static int sgd_momentum_flat_impl(float* w, const float* g, float* v, const int6
                        reinterpret_cast<const long*>(seg_starts), gmult, wd_coef, nseg, (long)total, lr, momentum, grad_scale, l2_out,
                        (const float*)nullptr, part);
   else
-    hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, v,
+    hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(dh_grid_for(total / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, v,
                        reinterpret_cast<const long*>(seg_starts), gmult, wd_coef, nseg, (long)total, lr, momentum, grad_scale, l2_out,
                        (const float*)nullptr, (float*)nullptr);
   DH_LAUNCH_CHECK();
@@ -693,8 +686,8 @@ extern "C" int danhip_sgd_momentum_flat_dynamic(float* w, const float* g, float*
   DH_REQUIRE(!(l2_out && danhip_option("deterministic") != 0), DANHIP_EINVAL,
              "sgd_momentum_flat_dynamic: l2_out has no deterministic form (pass NULL, or use danhip_sgd_momentum_flat_ws)");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(grad_nonfinite_kernel, dim3(grid_for(total / 4, 256, 2048)), dim3(256), 0, s, g, (long)total, loss_scale_state);
-  hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, 4096)), dim3(256), 0, s, w, g, v, reinterpret_cast<const long*>(seg_starts),
+  hipLaunchKernelGGL(grad_nonfinite_kernel, dim3(dh_grid_for(total / 4, 256, 2048)), dim3(256), 0, s, g, (long)total, loss_scale_state);
+  hipLaunchKernelGGL(sgd_momentum_flat_kernel, dim3(dh_grid_for(total / 4, 256, 4096)), dim3(256), 0, s, w, g, v, reinterpret_cast<const long*>(seg_starts),
                      gmult, wd_coef, nseg, (long)total, lr, momentum, 1.f, l2_out, (const float*)loss_scale_state, (float*)nullptr);
   hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, s, loss_scale_state);
   DH_LAUNCH_CHECK();

@@ -28,7 +28,7 @@ SIG_BITS = {torch.bfloat16: 8, torch.float16: 11}
 # ---------------------------------------------------------------------------------------------------------------- launch constants
 # Each mirrors the line of the launcher it names; the loop-trip conditions of the shape lists are computed from them (test_hbm_layers_cpu.py).
 BLOCK = 256                       # elementwise.hip / layers2.hip: dim3(256) of every grid_for launch
-GRID_FOR_CAP = 8192               # elementwise.hip `inline int grid_for(long total, int block, int cap = 8192)`; layers2.hip the same
+GRID_FOR_CAP = 8192               # elementwise.hip `dh_grid_for(total, 256, 8192)` at every such launch; layers2.hip the same
 POOL3_CAP = 4096                  # layers2.hip danhip_maxpool3x3s2_same_fwd/_bwd: `if (blocks > 4096) blocks = 4096;`
 L2_FWD_BLOCKS, L2_FWD_WAVES = 4096, 4        # elementwise.hip danhip_l2norm_fwd: `if (blocks > 4096) blocks = 4096;`, b(256)
 L2_BWD_BLOCKS, L2_BWD_WAVES = 512, 16        # elementwise.hip danhip_l2norm_bwd: `if (blocks > 512) blocks = 512;`, b(1024)

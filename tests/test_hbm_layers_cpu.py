@@ -1,6 +1,7 @@
 """Pins tests/hbm_layers.py itself (no GPU): the float64 references against the float32 oracle, the once-rounding helper, the exactness
 of the exact-case inputs, and the loop-trip conditions of the committed shape lists."""
 import os
+import re
 import sys
 
 import pytest
@@ -173,7 +174,9 @@ def test_constants_mirror_the_sources():
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dan_amd", "csrc")
     ew = open(os.path.join(root, "elementwise.hip")).read()
     l2 = open(os.path.join(root, "layers2.hip")).read()
-    assert "int cap = %d)" % HL.GRID_FOR_CAP in ew and "int cap = %d)" % HL.GRID_FOR_CAP in l2
+    for src in (ew, l2):                                         # dh_grid_for (common.h) has no default cap: every launch states its own
+        caps = re.findall(r"dh_grid_for\(.*?, 256, (\d+)\)\), dim3\(256\)", src)
+        assert caps and len(caps) == src.count("grid_for(") and set(caps) == {str(HL.GRID_FOR_CAP)}, caps
     assert l2.count("if (blocks > %d) blocks = %d;" % (HL.POOL3_CAP, HL.POOL3_CAP)) == 2
     assert l2.count("if (grid > %d) grid = %d;" % (HL.BN_REDUCE_BLOCKS, HL.BN_REDUCE_BLOCKS)) == 2
     for cap in (HL.L2_FWD_BLOCKS, HL.L2_BWD_BLOCKS, HL.RELU_BIAS_BLOCKS, HL.RELU_BITS_BLOCKS, HL.SLICE_BLOCKS):

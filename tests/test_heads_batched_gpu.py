@@ -36,8 +36,8 @@ SETS = {"four": FOUR, "one": ONE, "eight": EIGHT}
 
 def _trip():
     src = open(os.path.join(ROOT, "dan_amd", "csrc", "loss.hip")).read()
-    cap = int(re.search(r"inline int grid_for\(long total, int block, int cap = (\d+)\)", src).group(1))
-    assert "heads_grad_pad_kernel, dim3(grid_for(rows, 256)), dim3(256)" in src and "heads_split_fwd_kernel, dim3(grid_for(rows, 256)), dim3(256)" in src
+    cap = int(re.search(r"heads_grad_pad_kernel, dim3\(dh_grid_for\(rows, 256, (\d+)\)\), dim3\(256\)", src).group(1))
+    assert "heads_split_fwd_kernel, dim3(dh_grid_for(rows, 256, %d)), dim3(256)" % cap in src
     return cap * 256
 
 

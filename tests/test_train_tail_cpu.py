@@ -188,10 +188,10 @@ def test_constants_mirror_the_source():
     """The launch caps are read back from loss.hip, so a changed cap fails here and not silently in the shape conditions."""
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dan_amd", "csrc")
     src = open(os.path.join(root, "loss.hip")).read()
-    assert "int cap = %d)" % (TT.HEAD_TRIP // 256) in src and src.count("grid_for((long)B * HW, 256)), dim3(256)") == 2
+    assert src.count("dim3(dh_grid_for((long)B * HW, 256, %d)), dim3(256)" % (TT.HEAD_TRIP // 256)) == 2      # (no default cap: each launch states its own)
     assert "grid_for(A, 1024, %d)" % (TT.SCORE_ROW_TRIP // 1024) in src
     assert "grid_for(total, 1024, %d)), dim3(1024)" % (TT.LOSS_FWD_TRIP // 1024) in src
     assert "grid_for(total, 256, %d)), dim3(256)" % (TT.LOSS_BWD_TRIP // 256) in src
-    assert src.count("sgd_momentum_flat_kernel, dim3(grid_for(total / 4, 256, %d)), dim3(256)" % TT.SGD_BLOCKS) == 2
-    assert "grad_nonfinite_kernel, dim3(grid_for(total / 4, 256, %d)), dim3(256)" % (TT.NONFINITE_TRIP // 1024) in src
+    assert src.count("sgd_momentum_flat_kernel, dim3(dh_grid_for(total / 4, 256, %d)), dim3(256)" % TT.SGD_BLOCKS) == 2
+    assert "grad_nonfinite_kernel, dim3(dh_grid_for(total / 4, 256, %d)), dim3(256)" % (TT.NONFINITE_TRIP // 1024) in src
     assert "fmaxf(dyn[0] * 0.5f, 1.f)" in src and "fminf(dyn[0] * 2.f, 16777216.f)" in src
