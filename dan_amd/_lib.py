@@ -64,7 +64,13 @@ class ResizeItem(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("fx", "fy", "scale_x", "scale_y")]
 
 
+class CrcSegment(ctypes.Structure):
+    """danhip_crc_segment: one device byte range of danhip_crc32c_batch."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("bytes", ctypes.c_uint64)]
+
+
 DETECT_SELECT_LAUNCHES = 7     # DANHIP_DETECT_SELECT_LAUNCHES
+CRC32C_BATCH_LAUNCHES = 3      # DANHIP_CRC32C_BATCH_LAUNCHES
 
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
@@ -201,6 +207,7 @@ SIGNATURES = {
     "danhip_jpeg_scan_prepare_batch": [P, P, I32, P, ctypes.c_size_t, I64, P, P],
     "danhip_jpeg_huffman_decode_batch": [P, P, ctypes.c_size_t, I32, P, I64, P, P, P, ctypes.c_size_t, P, P, P],
     "danhip_jpeg_entropy_emulate_batch": [P, ctypes.c_size_t, I32, P, P, I64, I32, P, P],
+    "danhip_crc32c_batch": [P, I32, P, I32, P, ctypes.c_size_t, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
 }
@@ -323,11 +330,27 @@ def _load(so_path, act_name):
         L.danhip_jpeg_scan_device_bytes.argtypes = [P]
         L.danhip_jpeg_scan_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_jpeg_scan_workspace_bytes.argtypes = [P]
+        bind_crc32c_host(L)
+        L.danhip_crc_segment_bytes.restype, L.danhip_crc_segment_bytes.argtypes = ctypes.c_size_t, []
+        for fn in (L.danhip_crc32c_chunk_bytes, L.danhip_crc32c_group_bytes, L.danhip_crc32c_batch_last_launches):
+            fn.restype, fn.argtypes = I32, []
+        L.danhip_crc32c_batch_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_crc32c_batch_workspace_bytes.argtypes = [I32, ctypes.c_uint64]
         for name, args in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the export is missing
             fn.restype = ctypes.c_int
             fn.argtypes = args
     return L
+
+
+def bind_crc32c_host(L):
+    """Prototypes of the host CRC-32C entry points (no GPU call behind them; also bound by crc32c_host_lib on a bare handle)."""
+    L.danhip_crc32c_host.restype = ctypes.c_uint32
+    L.danhip_crc32c_host.argtypes = [P, ctypes.c_size_t, ctypes.c_uint32]
+    L.danhip_crc32c_host_form.restype = ctypes.c_uint32
+    L.danhip_crc32c_host_form.argtypes = [P, ctypes.c_size_t, ctypes.c_uint32, I32]
+    L.danhip_crc32c_combine.restype = ctypes.c_uint32
+    L.danhip_crc32c_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
 
 
 def check(rc, what):

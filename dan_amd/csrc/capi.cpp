@@ -20,7 +20,7 @@ void danhip_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* danhip_last_error(void) { return g_err; }
-extern "C" int danhip_version(void) { return 13; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch); 10: option "deterministic", danhip_ordered_reduce_f32, danhip_reduce_workspace_bytes and the _ws forms of the L2-norm / bias-gradient / loss / optimizer entry points; 11: danhip_augment_item_init / danhip_augment_preprocess_batch (the training input pass for a whole batch in a constant number of launches); 12: danhip_resize_item_init / danhip_resize_u8_linear_batch / danhip_detect_select (the test-time pipeline for images of different sizes); 13: danhip_cls_accuracy (the training metric, counted on the device)
+extern "C" int danhip_version(void) { return 14; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch); 10: option "deterministic", danhip_ordered_reduce_f32, danhip_reduce_workspace_bytes and the _ws forms of the L2-norm / bias-gradient / loss / optimizer entry points; 11: danhip_augment_item_init / danhip_augment_preprocess_batch (the training input pass for a whole batch in a constant number of launches); 12: danhip_resize_item_init / danhip_resize_u8_linear_batch / danhip_detect_select (the test-time pipeline for images of different sizes); 13: danhip_cls_accuracy (the training metric, counted on the device); 14: danhip_crc32c_host / _combine / _batch (CRC-32C of checkpoint tensors on the host and on the device)
 extern "C" int danhip_act_dtype(void) {
 #ifdef DANHIP_FP16
   return DANHIP_F16;
@@ -42,6 +42,8 @@ extern "C" int danhip_act_dtype(void) {
 //   "deterministic" DANHIP_DETERMINISTIC  0 (default) / 1: every cross-workgroup fp32 sum of the S3FD training step in a fixed order (partials
 //                as plain stores into the caller's workspace + ordered_reduce.hip) instead of float atomics: bit-reproducible per (library build,
 //                CU count).  Entry points that would need atomics return DANHIP_EINVAL (danhip.h "Deterministic mode")
+//   "crc_table"  DANHIP_CRC_TABLE   1 (default) / 0: danhip_crc32c_batch walks its chunks with a slicing-by-4 table in LDS (1) or with the
+//                table-free shift form (0) (crc32c_exact.hip; same bits; measured 1153 vs 764 GB/s on the S3FD shard)
 namespace {
 // Thread safety ("no mutable globals" on the data path): the table is filled from the environment exactly once
 // (std::call_once, before the first read or write), every value is a relaxed atomic, and the kernels' host launchers read an option
@@ -52,7 +54,7 @@ Opt g_opts[] = {{"splitk", "DANHIP_SPLITK", 1, {0}}, {"wgrad_slab", "DANHIP_WGRA
                 {"wgrad_b2", "DANHIP_WGRAD_B2", 0, {0}}, {"halo_general_epilogue", "DANHIP_HALO_GENERAL_EPILOGUE", 0, {0}},
                 {"deform_bwd_form", "DANHIP_DEFORM_BWD_FORM", 0, {0}}, {"pw_dgrad_ld_bn", "DANHIP_PW_DGRAD_LD_BN", 128, {0}},
                 {"wgrad_c8", "DANHIP_WGRAD_C8", 1, {0}}, {"deform_dx_untiled", "DANHIP_DEFORM_DX_UNTILED", 0, {0}},
-                {"deterministic", "DANHIP_DETERMINISTIC", 0, {0}}};
+                {"deterministic", "DANHIP_DETERMINISTIC", 0, {0}}, {"crc_table", "DANHIP_CRC_TABLE", 1, {0}}};
 std::once_flag g_opts_once;
 Opt* find_opt(const char* name) {
   std::call_once(g_opts_once, [] {

@@ -8,7 +8,9 @@ Flags carry the reference's names and defaults (each script's tf.app.flags block
 they configure TensorFlow's input threads, session and device placement: num_readers, num_preprocessing_threads, num_cpu_threads,
 gpu_memory_fraction, data_format, multi_gpu (and save_summary_steps / save_checkpoints_secs, which the reference itself leaves unused or
 feeds to summaries this port does not write).  Three flags are this port's own: --device, --deterministic, --decode_entropy; a fourth,
---no_prefetch, exists for measuring the loader thread against the plain generator (profiles/r15/train_driver.md).
+--no_prefetch, exists for measuring the loader thread against the plain generator (profiles/r15/train_driver.md).  Checkpoints are written
+with a CRC-32C on every tensor (checksums="device": packed and checksummed on the GPU, profiles/r16/checkpoint_crc.md) and every tensor CRC
+is checked on resume and on a warm start before a variable is written; --no_checkpoint_checksums turns both off.
 
 Out of scope: more than one rank (bench.py --gpus N is the multi-rank path; WORLD_SIZE > 1 is refused), average precision during training,
 and the position of the input stream across a resume (the reference restarts its queue as well)."""
@@ -108,6 +110,8 @@ def build_parser(model):
     p.add_argument("--device", default="cuda:0", help="the GPU to train on (default cuda:0)")
     p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (the trainer refuses models without an ordered form)")
     p.add_argument("--decode_entropy", choices=("host", "device"), default="host", help="where the JPEG Huffman stage runs (default host)")
+    p.add_argument("--no_checkpoint_checksums", action="store_true",
+                   help="write checkpoints without per-tensor CRCs and do not verify the ones that are read (default: both, on the device)")
     p.add_argument("--no_prefetch", action="store_true", help="prepare each batch between the steps instead of on the background thread")
     return p
 
@@ -354,12 +358,13 @@ def main(argv=None, model="sfd"):
     scope_in_ckpt = None if args.checkpoint_model_scope in (None, "None") else args.checkpoint_model_scope
     found = checkpoint.latest_checkpoint(args.model_dir)
     warm = None if found else _warm_start_path(args.checkpoint_path)
+    checked = not args.no_checkpoint_checksums                                # CRCs written ("device": the shard is checksummed on the GPU) and verified
     if found:
-        trainer.restore(found, args.model_scope)
+        trainer.restore(found, args.model_scope, verify=checked)
         print("resumed %s at step %d" % (found, trainer.step_no), flush=True)
     elif warm:
         names = checkpoint.init_from_checkpoint(trainer.model.vs, warm, args.model_scope, scope_in_ckpt, args.checkpoint_exclude_scopes,
-                                                args.ignore_missing_vars, name_remap=NAME_REMAP)
+                                                args.ignore_missing_vars, name_remap=NAME_REMAP, verify=checked)
         print("warm start from %s: %d variables" % (warm, len(names)), flush=True)
     else:
         print("no checkpoint in %s or at %s: seeded initialisers (%d)" % (args.model_dir, args.checkpoint_path, args.tf_random_seed), flush=True)
@@ -378,13 +383,13 @@ def main(argv=None, model="sfd"):
                 say("step %d: %s" % (step, format_log(setup.log_values())))
             done += 1
             if args.save_checkpoints_steps > 0 and step % args.save_checkpoints_steps == 0:
-                trainer.save(keeper.prefix(step), args.model_scope)
+                trainer.save(keeper.prefix(step), args.model_scope, checksums="device" if checked else False)
                 keeper.register(keeper.prefix(step))
                 saved_at = step
             if step >= args.max_number_of_steps:
                 break
         if saved_at != trainer.step_no:                                      # the Estimator's CheckpointSaverHook.end
-            trainer.save(keeper.prefix(trainer.step_no), args.model_scope)
+            trainer.save(keeper.prefix(trainer.step_no), args.model_scope, checksums="device" if checked else False)
             keeper.register(keeper.prefix(trainer.step_no))
     finally:
         if loader is not None:

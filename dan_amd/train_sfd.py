@@ -337,14 +337,17 @@ class DetectorTrainer(object):
 
     # ---- checkpoint / resume (the Estimator's save_checkpoints_steps + resume-from-model_dir behaviour, train_dan.py:549-556)
     def save(self, prefix, model_scope, checksums=False):
-        """Variables, batch-norm moving statistics, Momentum slots and global_step under the reference's names."""
+        """Variables, batch-norm moving statistics, Momentum slots and global_step under the reference's names.  checksums: False / True /
+        "device" as utility.checkpoint.save_checkpoint ("device": the shard is packed and checksummed on the GPU, one copy to the host;
+        `self.checkpoint_io.stats` counts its launches and copies)."""
         from .utility import checkpoint
         torch.cuda.synchronize() if self.flat.w.is_cuda else None
         checkpoint.save_checkpoint(self.model.vs, prefix, model_scope, checksums=checksums, trainer=self)
 
-    def restore(self, checkpoint_path, model_scope, strict=True):
+    def restore(self, checkpoint_path, model_scope, strict=True, verify=False):
+        """verify: every tensor CRC of the checkpoint is checked before anything is written (utility.checkpoint.restore_checkpoint)."""
         from .utility import checkpoint
-        return checkpoint.restore_checkpoint(self.model.vs, checkpoint_path, model_scope, trainer=self, strict=strict)
+        return checkpoint.restore_checkpoint(self.model.vs, checkpoint_path, model_scope, trainer=self, strict=strict, verify=verify)
 
     def loss_values(self):
         """{name: (cross_entropy, loc_loss)} per term + 'l2' + 'total' as python floats (synchronises)."""

@@ -61,6 +61,7 @@ int danhip_version(void);
  *                                           csrc/conv_wgrad_c8.hip
  *   "pw_dgrad_ld_bn" [DANHIP_PW_DGRAD_LD_BN, 128]  256: csrc/conv_pointwise.hip's data gradient with a ReLU mask / accumulation may take 256-wide tiles
  *   "deterministic" [DANHIP_DETERMINISTIC, 0]  1: deterministic mode, see below
+ *   "crc_table"  [DANHIP_CRC_TABLE, 1]   0: danhip_crc32c_batch walks with the table-free shift form instead of the slicing-by-4 table in LDS (same bits)
  * Results agree up to fp32 summation order whatever the setting.  danhip_set_option returns DANHIP_EINVAL for an unknown name. */
 int danhip_set_option(const char* name, int value);
 int danhip_get_option(const char* name);
@@ -993,6 +994,49 @@ int danhip_avgpool2x2s1_same_fwd_f32(const float* x, float* y, int32_t N, int32_
  * danhip_conv2d_fwd_f32 over S */
 int danhip_deform_sample_fwd_f32(const float* x, const float* offsets, float* S, int32_t N, int32_t H, int32_t W, int32_t C, int32_t kh,
                                  int32_t kw, int32_t stride, int32_t dilation, int32_t deformable_group, void* stream);
+
+/* --------------------------------------------------------------------------------------------------
+ * CRC-32C (Castagnoli; ABI version 14): the checksum of TF-V2 checkpoint tensors, index blocks and TFRecord frames
+ * (csrc/crc32c.cpp on the host, csrc/crc32c_exact.hip on the device; the arithmetic both share is csrc/crc32c.h).
+ * Polynomial 0x82F63B78 (reflected), init and final xor 0xFFFFFFFF.
+ *
+ * danhip_crc32c_host: the CRC of data[0, n) continued from `crc` (0 to start; (data, 0, crc) returns crc, so (.., 0, 0) is 0) - the
+ *   semantics of utility/checkpoint.py:crc32c.  Slicing-by-8 tables; on x86-64 with SSE4.2 (asked at run time) the crc32 instruction, same
+ *   bits.  danhip_crc32c_host_form(.., form): 0 the same, 1 always the tables (tests compare the two).  No GPU call, no error state.
+ * danhip_crc32c_combine: the CRC of A || B from crc(A), crc(B) and len(B): crc_a * x^(8 len_b) mod P, xor crc_b, the power by
+ *   square-and-multiply over all 64 bits of len_b.  The device path combines its pieces with this arithmetic.
+ *
+ * danhip_crc32c_batch: the CRCs of n DEVICE byte ranges of any length and byte alignment -> crc_out_dev uint32 [n] (masked != 0: TensorFlow's
+ *   crc32c::Mask, ((c >> 15) | (c << 17)) + 0xa282ead8).  An empty range gives 0 (masked: the mask of 0); n == 0 succeeds and launches nothing.
+ *   Table hand-over, as with danhip_resize_u8_linear_batch: the caller fills a host array of danhip_crc_segment and uploads it with ONE
+ *   copy - to the FRONT of the workspace, ordered before the call on `stream`.  table_host is validated before anything is launched and sizes
+ *   the grid; the kernels read the copy in the workspace; the call itself touches no other host memory, copies nothing and does not
+ *   synchronise.  Nothing outside a range is read.
+ *   KERNEL LAUNCHES PER CALL: DANHIP_CRC32C_BATCH_LAUNCHES = 3 whatever n and the sizes are (plan, walk, finish;
+ *   danhip_crc32c_batch_last_launches() returns what the calling thread's last call issued).  Pieces are combined by integer XOR (an ordinary
+ *   vector atomic on the range's word): the same bits in any order, deterministic mode is not concerned.
+ *   A lane walks danhip_crc32c_chunk_bytes() bytes, a workgroup danhip_crc32c_group_bytes() (of 16-byte aligned lines, so a range that starts
+ *   off alignment takes its windows from its pointer rounded down).
+ *   workspace: danhip_crc32c_batch_workspace_bytes(n, total_bytes) bytes, 16-byte aligned (total_bytes = the sum of the ranges' sizes; the
+ *   present form keeps one word per range, so the answer depends on n alone).
+ *   DANHIP_EINVAL: n < 0 or > 2^22, a null table / output / workspace, a range with bytes > 0 and a null pointer, more than 2^31 windows;
+ *   DANHIP_EWORKSPACE: a short workspace.  Option "crc_table" [DANHIP_CRC_TABLE]: the walk's form (csrc/crc32c_exact.hip).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  const void* ptr;                           /* device pointer, any alignment; may be NULL when bytes == 0 */
+  uint64_t bytes;
+} danhip_crc_segment;
+#define DANHIP_CRC32C_BATCH_LAUNCHES 3
+uint32_t danhip_crc32c_host(const void* data, size_t n, uint32_t crc);
+uint32_t danhip_crc32c_host_form(const void* data, size_t n, uint32_t crc, int32_t form);
+uint32_t danhip_crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+size_t danhip_crc_segment_bytes(void);       /* sizeof(danhip_crc_segment), for callers that bind the library without this header */
+int32_t danhip_crc32c_chunk_bytes(void);
+int32_t danhip_crc32c_group_bytes(void);
+int32_t danhip_crc32c_batch_last_launches(void);
+size_t danhip_crc32c_batch_workspace_bytes(int32_t n, uint64_t total_bytes);
+int danhip_crc32c_batch(const danhip_crc_segment* table_host, int32_t n, uint32_t* crc_out_dev, int32_t masked, void* ws, size_t ws_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }
