@@ -69,8 +69,25 @@ class CrcSegment(ctypes.Structure):
     _fields_ = [("ptr", ctypes.c_void_p), ("bytes", ctypes.c_uint64)]
 
 
+class JpegEncDesc(ctypes.Structure):
+    """danhip_jpeg_enc_desc: one image of an encode batch (filled by danhip_jpeg_encode_prepare)."""
+    _fields_ = [("src", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in ("width", "height", "mode", "quality")] + \
+               [(n, ctypes.c_int32 * 3) for n in ("blocks_w", "blocks_h", "comp_w", "comp_h")] + \
+               [(n, ctypes.c_int32) for n in ("real_bw", "real_bh", "color_groups", "fdct_groups")] + \
+               [("coef_offset", ctypes.c_int64), ("coef_count", ctypes.c_int64), ("plane_offset", ctypes.c_int64 * 3),
+                ("file_offset", ctypes.c_int64), ("file_capacity", ctypes.c_int64),
+                ("recip", (ctypes.c_uint16 * 64) * 2), ("corr", (ctypes.c_uint16 * 64) * 2),
+                ("shift", (ctypes.c_uint8 * 64) * 2), ("qtable", (ctypes.c_uint8 * 64) * 2)]
+
+
+class DrawItem(ctypes.Structure):
+    """danhip_draw_item: one image of danhip_draw_boxes_u8."""
+    _fields_ = [("image", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in ("width", "height", "first_box", "num_boxes", "groups", "reserved")]
+
+
 DETECT_SELECT_LAUNCHES = 7     # DANHIP_DETECT_SELECT_LAUNCHES
 CRC32C_BATCH_LAUNCHES = 3      # DANHIP_CRC32C_BATCH_LAUNCHES
+JPEG_ENCODE_LAUNCHES = 2       # DANHIP_JPEG_ENCODE_LAUNCHES
 
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
@@ -208,6 +225,8 @@ SIGNATURES = {
     "danhip_jpeg_huffman_decode_batch": [P, P, ctypes.c_size_t, I32, P, I64, P, P, P, ctypes.c_size_t, P, P, P],
     "danhip_jpeg_entropy_emulate_batch": [P, ctypes.c_size_t, I32, P, P, I64, I32, P, P],
     "danhip_crc32c_batch": [P, I32, P, I32, P, ctypes.c_size_t, P],
+    "danhip_jpeg_encode_pixels_batch": [P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
+    "danhip_draw_boxes_u8": [P, P, I32, P, P, I64, I32, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
 }
@@ -331,6 +350,8 @@ def _load(so_path, act_name):
         L.danhip_jpeg_scan_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_jpeg_scan_workspace_bytes.argtypes = [P]
         bind_crc32c_host(L)
+        bind_jpeg_encode_host(L)
+        L.danhip_draw_item_bytes.restype, L.danhip_draw_item_bytes.argtypes = ctypes.c_size_t, []
         L.danhip_crc_segment_bytes.restype, L.danhip_crc_segment_bytes.argtypes = ctypes.c_size_t, []
         for fn in (L.danhip_crc32c_chunk_bytes, L.danhip_crc32c_group_bytes, L.danhip_crc32c_batch_last_launches):
             fn.restype, fn.argtypes = I32, []
@@ -351,6 +372,18 @@ def bind_crc32c_host(L):
     L.danhip_crc32c_host_form.argtypes = [P, ctypes.c_size_t, ctypes.c_uint32, I32]
     L.danhip_crc32c_combine.restype = ctypes.c_uint32
     L.danhip_crc32c_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+
+
+def bind_jpeg_encode_host(L):
+    """Prototypes of the JPEG encoder's host entry points (csrc/jpeg_encode.cpp: no GPU call behind them)."""
+    L.danhip_jpeg_enc_desc_bytes.restype, L.danhip_jpeg_enc_desc_bytes.argtypes = ctypes.c_size_t, []
+    L.danhip_jpeg_encode_file_bound.restype, L.danhip_jpeg_encode_file_bound.argtypes = I64, [I32, I32, I32]
+    for name, args in (("danhip_jpeg_encode_prepare", [P, P, P, I32, I32, I32, P, P]),
+                       ("danhip_jpeg_encode_pixels_host", [P, I32, P, I64]),
+                       ("danhip_jpeg_encode_entropy_batch", [P, I64, P, I32, I32, P, I64, P]),
+                       ("danhip_jpeg_encode_host", [P, I32, I32, I32, I32, P, I64, P])):
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = ctypes.c_int, args
 
 
 def check(rc, what):

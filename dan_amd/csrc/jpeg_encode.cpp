@@ -1,0 +1,459 @@
+// Host half of the JPEG encoder (include/danhip.h, "Baseline JPEG encode"): descriptors, the Huffman stage, the file writer, and the pixel
+// stage once more on the host through the arithmetic of jpeg_encode.h.  Plain C++: no HIP call, usable in a process without a GPU.
+// The file is what libjpeg-turbo's jcmarker.c / jchuff.c write for Pillow's save(quality=q, subsampling=0 | 2): see jpeg_encode.h for the
+// places where that is not the textbook.
+#include <string.h>
+
+#include <atomic>
+#include <thread>
+#include <vector>
+
+#include "jpeg_encode.h"
+#include "jpeg_layout.h"
+
+void danhip_set_error(const char* fmt, ...);
+
+namespace {
+
+const uint8_t kZigColMajor[64] = {0,  8,  1,  2,  9,  16, 24, 17, 10, 3,  4,  11, 18, 25, 32, 40, 33, 26, 19, 12, 5,  6,
+                                  13, 20, 27, 34, 41, 48, 56, 49, 42, 35, 28, 21, 14, 7,  15, 22, 29, 36, 43, 50, 57, 58,
+                                  51, 44, 37, 30, 23, 31, 38, 45, 52, 59, 60, 53, 46, 39, 47, 54, 61, 62, 55, 63};   // k-th coded -> col * 8 + row
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};        // k-th coded -> row * 8 + col
+
+// T.81 K.1 / K.2, row-major
+const uint8_t kStdQuant[2][64] = {
+    {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+     18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// T.81 K.3 - K.6: code counts per length 1 .. 16, then the symbols.  Order: DC luma, AC luma, DC chroma, AC chroma (the order of the DHT segments)
+const uint8_t kBitsDcLuma[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+const uint8_t kBitsDcChroma[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+const uint8_t kValDc[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kBitsAcLuma[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+const uint8_t kValAcLuma[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+    0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+    0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+    0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+    0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+    0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+const uint8_t kBitsAcChroma[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+const uint8_t kValAcChroma[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+    0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+    0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+    0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+    0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+    0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+
+struct EncTable {
+  uint16_t code[256];
+  uint8_t len[256];                                       // 0: the table has no code for the symbol
+};
+
+struct StdTables {
+  EncTable dc[2], ac[2];
+  StdTables() {
+    build(kBitsDcLuma, kValDc, &dc[0]);
+    build(kBitsAcLuma, kValAcLuma, &ac[0]);
+    build(kBitsDcChroma, kValDc, &dc[1]);
+    build(kBitsAcChroma, kValAcChroma, &ac[1]);
+  }
+  static void build(const uint8_t* bits, const uint8_t* vals, EncTable* t) {
+    memset(t, 0, sizeof(*t));
+    unsigned code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+      for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code) {
+        t->code[vals[k]] = (uint16_t)code;
+        t->len[vals[k]] = (uint8_t)l;
+      }
+      code <<= 1;
+    }
+  }
+};
+
+const StdTables& std_tables() {
+  static const StdTables t;
+  return t;
+}
+
+const int64_t kHeaderBound = 1024;                        // the markers in front of the scan take 623 bytes
+const int64_t kBlockBound = 416;                          // (9 + 11) + 63 * (16 + 10) bits = 208 bytes, every one stuffed
+
+bool enc_mode_ok(int32_t mode) { return mode == DANHIP_JPEG_420 || mode == DANHIP_JPEG_444; }
+
+// everything of a descriptor that follows from (width, height, mode, quality); the offsets stay as they are
+bool derive_desc(int32_t width, int32_t height, int32_t mode, int32_t quality, danhip_jpeg_enc_desc* d) {
+  DhJpegGeom g;
+  if (!enc_mode_ok(mode) || quality < 1 || quality > 100 || !dh_jpeg_geometry(width, height, mode, &g)) return false;
+  d->width = width; d->height = height; d->mode = mode; d->quality = quality;
+  for (int c = 0; c < 3; ++c) {
+    d->blocks_w[c] = g.blocks_w[c]; d->blocks_h[c] = g.blocks_h[c]; d->comp_w[c] = g.comp_w[c]; d->comp_h[c] = g.comp_h[c];
+  }
+  d->real_bw = (width + 7) / 8;
+  d->real_bh = (height + 7) / 8;
+  const int64_t items = (int64_t)(g.blocks_h[0] * 8 / g.vs) * g.blocks_w[0];
+  d->color_groups = (int32_t)((items + 255) / 256);
+  d->fdct_groups = (int32_t)((g.blocks + DH_JPEG_IDCT_BLOCKS_PER_GROUP - 1) / DH_JPEG_IDCT_BLOCKS_PER_GROUP);
+  d->coef_count = g.coef_count;
+  d->file_capacity = kHeaderBound + g.blocks * kBlockBound;
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;          // jpeg_quality_scaling
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k) {
+      int q = (kStdQuant[t][k] * scale + 50) / 100;                             // jpeg_add_quant_table, force_baseline
+      q = q < 1 ? 1 : (q > 255 ? 255 : q);
+      d->qtable[t][k] = (uint8_t)q;
+      dh_jenc_reciprocal((unsigned)q * 8, &d->recip[t][k], &d->corr[t][k], &d->shift[t][k]);
+    }
+  return true;
+}
+
+// NULL = the descriptor is what derive_desc gives and its offsets lie inside the buffers, else what is wrong
+const char* check_desc(const danhip_jpeg_enc_desc* d, int64_t coef_count, int64_t workspace_bytes, int64_t file_bytes) {
+  danhip_jpeg_enc_desc w;
+  memset(&w, 0, sizeof(w));
+  if (!derive_desc(d->width, d->height, d->mode, d->quality, &w)) return "size, mode or quality outside the accepted range";
+  w.src = d->src; w.coef_offset = d->coef_offset; w.file_offset = d->file_offset;
+  for (int c = 0; c < 3; ++c) w.plane_offset[c] = d->plane_offset[c];
+  if (memcmp(&w, d, sizeof(w)) != 0) return "fields do not fit (width, height, mode, quality)";
+  if (d->coef_offset < 0 || d->coef_offset % 64 || d->coef_offset > coef_count || d->coef_count > coef_count - d->coef_offset)
+    return "coefficients leave the buffer";
+  if (workspace_bytes >= 0)
+    for (int c = 0; c < 3; ++c) {
+      const int64_t bytes = (int64_t)d->blocks_w[c] * d->blocks_h[c] * 64;
+      if (d->plane_offset[c] < 0 || d->plane_offset[c] % 256 || d->plane_offset[c] > workspace_bytes || bytes > workspace_bytes - d->plane_offset[c])
+        return "component plane leaves the workspace";
+    }
+  if (file_bytes >= 0 && (d->file_offset < 0 || d->file_offset > file_bytes || d->file_capacity > file_bytes - d->file_offset))
+    return "file leaves the file buffer";
+  return nullptr;
+}
+
+struct BitWriter {
+  uint8_t* p;
+  uint8_t* end;
+  uint64_t acc = 0;
+  int n = 0;                                              // bits held in acc
+  bool overflow = false;
+  void byte(unsigned b) {
+    if (p < end) *p++ = (uint8_t)b; else overflow = true;
+  }
+  void put(unsigned code, int len) {                      // len <= 27
+    acc = (acc << len) | (code & ((1u << len) - 1));
+    n += len;
+    while (n >= 8) {
+      const unsigned b = (unsigned)(acc >> (n - 8)) & 255;
+      byte(b);
+      if (b == 255) byte(0);
+      n -= 8;
+    }
+  }
+  void flush() {                                          // jchuff.c flush_bits: fill the last byte with ones
+    if (n > 0) put(0x7f, 8 - n);
+    acc = 0; n = 0;
+  }
+};
+
+int bit_length(unsigned v) {
+  int n = 0;
+  while (v) { ++n; v >>= 1; }
+  return n;
+}
+
+// one block (column-major, de-zigzagged) as jchuff.c encode_one_block codes it.  false: a value the baseline tables cannot carry
+bool encode_block(const int16_t* blk, int* last_dc, const EncTable& dc, const EncTable& ac, BitWriter* w) {
+  int diff = blk[0] - *last_dc;
+  *last_dc = blk[0];
+  int bits = diff < 0 ? diff - 1 : diff;                  // the low bits of the one's complement for a negative value
+  int nb = bit_length((unsigned)(diff < 0 ? -diff : diff));
+  if (nb > 11 || !dc.len[nb]) return false;
+  w->put(dc.code[nb], dc.len[nb]);
+  if (nb) w->put((unsigned)bits, nb);
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const int v = blk[kZigColMajor[k]];
+    if (v == 0) { ++run; continue; }
+    while (run > 15) { w->put(ac.code[0xf0], ac.len[0xf0]); run -= 16; }
+    bits = v < 0 ? v - 1 : v;
+    nb = bit_length((unsigned)(v < 0 ? -v : v));
+    if (nb > 10) return false;
+    const int sym = (run << 4) | nb;
+    w->put(ac.code[sym], ac.len[sym]);
+    w->put((unsigned)bits, nb);
+    run = 0;
+  }
+  if (run > 0) w->put(ac.code[0], ac.len[0]);
+  return true;
+}
+
+void put16(uint8_t*& p, unsigned v) { *p++ = (uint8_t)(v >> 8); *p++ = (uint8_t)v; }
+
+uint8_t* write_dht(uint8_t* p, int index, const uint8_t* bits, const uint8_t* vals) {
+  int n = 0;
+  for (int i = 0; i < 16; ++i) n += bits[i];
+  put16(p, 0xffc4); put16(p, (unsigned)(2 + 1 + 16 + n));
+  *p++ = (uint8_t)index;
+  memcpy(p, bits, 16); p += 16;
+  memcpy(p, vals, (size_t)n); p += n;
+  return p;
+}
+
+// jcmarker.c: write_file_header, write_frame_header, write_scan_header for three components, tables 0 (Y) and 1 (Cb, Cr)
+uint8_t* write_header(uint8_t* p, const danhip_jpeg_enc_desc& d) {
+  put16(p, 0xffd8);
+  put16(p, 0xffe0); put16(p, 16);
+  memcpy(p, "JFIF", 5); p += 5;
+  *p++ = 1; *p++ = 1;                                     // version 1.01
+  *p++ = 0; put16(p, 1); put16(p, 1);                     // density: unit 0, 1 : 1
+  *p++ = 0; *p++ = 0;                                     // no thumbnail
+  for (int t = 0; t < 2; ++t) {
+    put16(p, 0xffdb); put16(p, 67);
+    *p++ = (uint8_t)t;
+    for (int k = 0; k < 64; ++k) *p++ = d.qtable[t][kZigzag[k]];
+  }
+  put16(p, 0xffc0); put16(p, 17);
+  *p++ = 8; put16(p, (unsigned)d.height); put16(p, (unsigned)d.width); *p++ = 3;
+  *p++ = 1; *p++ = d.mode == DANHIP_JPEG_420 ? 0x22 : 0x11; *p++ = 0;
+  *p++ = 2; *p++ = 0x11; *p++ = 1;
+  *p++ = 3; *p++ = 0x11; *p++ = 1;
+  p = write_dht(p, 0x00, kBitsDcLuma, kValDc);
+  p = write_dht(p, 0x10, kBitsAcLuma, kValAcLuma);
+  p = write_dht(p, 0x01, kBitsDcChroma, kValDc);
+  p = write_dht(p, 0x11, kBitsAcChroma, kValAcChroma);
+  put16(p, 0xffda); put16(p, 12);
+  *p++ = 3; *p++ = 1; *p++ = 0x00; *p++ = 2; *p++ = 0x11; *p++ = 3; *p++ = 0x11;
+  *p++ = 0; *p++ = 63; *p++ = 0;
+  return p;
+}
+
+// the file of one image from its coefficient slot; -1: capacity, -2: a coefficient the tables cannot carry
+int64_t write_file(const danhip_jpeg_enc_desc& d, const int16_t* coef, uint8_t* out, int64_t capacity) {
+  if (capacity < kHeaderBound) return -1;
+  const StdTables& T = std_tables();
+  uint8_t* p = write_header(out, d);
+  BitWriter w;
+  w.p = p; w.end = out + capacity - 2;
+  const int hs = d.mode == DANHIP_JPEG_420 ? 2 : 1, vs = hs;
+  const int mcus_x = d.blocks_w[1], mcus_y = d.blocks_h[1];
+  const int16_t* plane[3];
+  plane[0] = coef;
+  plane[1] = plane[0] + (int64_t)d.blocks_w[0] * d.blocks_h[0] * 64;
+  plane[2] = plane[1] + (int64_t)d.blocks_w[1] * d.blocks_h[1] * 64;
+  int last_dc[3] = {0, 0, 0};
+  for (int my = 0; my < mcus_y; ++my)
+    for (int mx = 0; mx < mcus_x; ++mx) {
+      for (int v = 0; v < vs; ++v)
+        for (int h = 0; h < hs; ++h) {
+          const int64_t b = (int64_t)(my * vs + v) * d.blocks_w[0] + (mx * hs + h);
+          if (!encode_block(plane[0] + b * 64, &last_dc[0], T.dc[0], T.ac[0], &w)) return -2;
+        }
+      for (int c = 1; c < 3; ++c)
+        if (!encode_block(plane[c] + ((int64_t)my * mcus_x + mx) * 64, &last_dc[c], T.dc[1], T.ac[1], &w)) return -2;
+    }
+  w.flush();
+  if (w.overflow) return -1;
+  p = w.p;
+  put16(p, 0xffd9);
+  return p - out;
+}
+
+// the pixel stage of one image on the host: planes as the device makes them, then block by block
+void pixels_host(const danhip_jpeg_enc_desc& d, int16_t* coef) {
+  const int W = d.width, H = d.height;
+  const bool sub = d.mode == DANHIP_JPEG_420;
+  std::vector<uint8_t> planes[3];
+  int pitch[3];
+  for (int c = 0; c < 3; ++c) {
+    pitch[c] = d.blocks_w[c] * 8;
+    planes[c].resize((size_t)pitch[c] * d.blocks_h[c] * 8);
+  }
+  auto ycc = [&](int y, int x, int* yy, int* cb, int* cr) {
+    const uint8_t* px = d.src + ((int64_t)(y < H ? y : H - 1) * W + (x < W ? x : W - 1)) * 3;
+    dh_jenc_ycc(px[0], px[1], px[2], yy, cb, cr);
+  };
+  for (int y = 0; y < d.blocks_h[0] * 8; ++y)
+    for (int x = 0; x < pitch[0]; ++x) {
+      int yy, cb, cr;
+      ycc(y, x, &yy, &cb, &cr);
+      planes[0].at((size_t)y * pitch[0] + x) = (uint8_t)yy;
+      if (!sub) {
+        planes[1].at((size_t)y * pitch[1] + x) = (uint8_t)cb;
+        planes[2].at((size_t)y * pitch[2] + x) = (uint8_t)cr;
+      }
+    }
+  if (sub)
+    for (int cy = 0; cy < d.blocks_h[1] * 8; ++cy)
+      for (int cx = 0; cx < pitch[1]; ++cx) {
+        const int ry = cy < d.comp_h[1] ? cy : d.comp_h[1] - 1;                 // the component's last row, repeated
+        int yy, cb[4], cr[4];
+        for (int k = 0; k < 4; ++k) ycc(2 * ry + (k >> 1), 2 * cx + (k & 1), &yy, &cb[k], &cr[k]);
+        planes[1].at((size_t)cy * pitch[1] + cx) = (uint8_t)dh_jenc_h2v2(cb[0], cb[1], cb[2], cb[3], cx);
+        planes[2].at((size_t)cy * pitch[2] + cx) = (uint8_t)dh_jenc_h2v2(cr[0], cr[1], cr[2], cr[3], cx);
+      }
+  int16_t* out = coef;
+  for (int c = 0; c < 3; ++c) {
+    const int t = c == 0 ? 0 : 1;
+    for (int by = 0; by < d.blocks_h[c]; ++by)
+      for (int bx = 0; bx < d.blocks_w[c]; ++bx, out += 64) {
+        int sy = by, sx = bx;
+        const int dummy = c == 0 ? dh_jenc_block_source(by, bx, d.real_bw, d.real_bh, &sy, &sx) : 0;
+        int m[8][8];
+        for (int r = 0; r < 8; ++r) {
+          for (int k = 0; k < 8; ++k) m[r][k] = (int)planes[c].at((size_t)(sy * 8 + r) * pitch[c] + sx * 8 + k) - 128;
+          dh_jenc_fdct_1d(m[r], 1);
+        }
+        for (int j = 0; j < 8; ++j) {
+          int col[8];
+          for (int r = 0; r < 8; ++r) col[r] = m[r][j];
+          dh_jenc_fdct_1d(col, 0);
+          for (int r = 0; r < 8; ++r) {
+            const int k = r * 8 + j;
+            const int q = dh_jenc_quant(col[r], d.recip[t][k], d.corr[t][k], d.shift[t][k]);
+            out[j * 8 + r] = (int16_t)((dummy && k != 0) ? 0 : q);
+          }
+        }
+      }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t danhip_jpeg_enc_desc_bytes(void) { return sizeof(danhip_jpeg_enc_desc); }
+
+extern "C" int64_t danhip_jpeg_encode_file_bound(int32_t width, int32_t height, int32_t mode) {
+  DhJpegGeom g;
+  if (!enc_mode_ok(mode) || !dh_jpeg_geometry(width, height, mode, &g)) return 0;
+  return kHeaderBound + g.blocks * kBlockBound;
+}
+
+extern "C" int danhip_jpeg_encode_prepare(const int32_t* widths, const int32_t* heights, const void* const* srcs, int32_t B, int32_t mode,
+                                          int32_t quality, danhip_jpeg_enc_desc* descs_out, int64_t* totals_out) {
+  if (!widths || !heights || !descs_out || !totals_out || B < 1 || B > 65535) {
+    danhip_set_error("jpeg_encode_prepare: bad arguments (1 <= B <= 65535, no NULL table)");
+    return DANHIP_EINVAL;
+  }
+  if (!enc_mode_ok(mode) || quality < 1 || quality > 100) {
+    danhip_set_error("jpeg_encode_prepare: mode %d / quality %d (DANHIP_JPEG_444 or DANHIP_JPEG_420, quality 1 .. 100)", mode, quality);
+    return DANHIP_EINVAL;
+  }
+  int64_t coef = 0, ws = 0, file = 0;
+  for (int32_t i = 0; i < B; ++i) {
+    danhip_jpeg_enc_desc* d = &descs_out[i];
+    memset(d, 0, sizeof(*d));
+    if (!derive_desc(widths[i], heights[i], mode, quality, d)) {
+      danhip_set_error("jpeg_encode_prepare: image %d is %d x %d (sides 1 .. %d)", i, widths[i], heights[i], DANHIP_JPEG_MAX_DIM);
+      return DANHIP_EINVAL;
+    }
+    d->src = srcs ? (const uint8_t*)srcs[i] : nullptr;
+    d->coef_offset = coef;
+    coef += d->coef_count;
+    for (int c = 0; c < 3; ++c) {
+      d->plane_offset[c] = ws;
+      ws += dh_jpeg_align((int64_t)d->blocks_w[c] * d->blocks_h[c] * 64, 256);
+    }
+    d->file_offset = file;
+    file += d->file_capacity;
+  }
+  totals_out[0] = coef; totals_out[1] = ws; totals_out[2] = file;
+  return DANHIP_OK;
+}
+
+// the check of the device launcher (jpeg_encode_exact.hip), here because the derivation is
+extern "C" const char* danhip_jpeg_enc_desc_check(const danhip_jpeg_enc_desc* d, int64_t coef_count, int64_t workspace_bytes, int64_t file_bytes) {
+  return check_desc(d, coef_count, workspace_bytes, file_bytes);
+}
+
+extern "C" int danhip_jpeg_encode_pixels_host(const danhip_jpeg_enc_desc* descs, int32_t B, int16_t* coef_out, int64_t coef_count) {
+  if (!descs || !coef_out || B < 1 || B > 65535 || coef_count < 0) {
+    danhip_set_error("jpeg_encode_pixels_host: bad arguments");
+    return DANHIP_EINVAL;
+  }
+  for (int32_t i = 0; i < B; ++i) {
+    const char* why = check_desc(&descs[i], coef_count, -1, -1);
+    if (!why && !descs[i].src) why = "src is NULL";
+    if (why) {
+      danhip_set_error("jpeg_encode_pixels_host: descriptor %d: %s", i, why);
+      return DANHIP_EINVAL;
+    }
+  }
+  for (int32_t i = 0; i < B; ++i) pixels_host(descs[i], coef_out + descs[i].coef_offset);
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_count, const danhip_jpeg_enc_desc* descs, int32_t B,
+                                                int32_t threads, uint8_t* files_out, int64_t files_capacity, int64_t* sizes_out) {
+  if (!coef || !descs || !files_out || !sizes_out || B < 1 || B > 65535 || coef_count < 0 || files_capacity < 0) {
+    danhip_set_error("jpeg_encode_entropy_batch: bad arguments (1 <= B <= 65535, no NULL buffer)");
+    return DANHIP_EINVAL;
+  }
+  for (int32_t i = 0; i < B; ++i) {
+    const char* why = check_desc(&descs[i], coef_count, -1, files_capacity);
+    if (why) {
+      danhip_set_error("jpeg_encode_entropy_batch: descriptor %d: %s", i, why);
+      return DANHIP_EINVAL;
+    }
+  }
+  int T = threads < 1 ? 1 : threads;
+  if (T > DANHIP_JPEG_MAX_THREADS) T = DANHIP_JPEG_MAX_THREADS;
+  if (T > B) T = B;
+  std::atomic<int32_t> cursor(0);
+  auto work = [&]() {
+    for (;;) {
+      const int32_t i = cursor.fetch_add(1);
+      if (i >= B) return;
+      sizes_out[i] = write_file(descs[i], coef + descs[i].coef_offset, files_out + descs[i].file_offset, descs[i].file_capacity);
+    }
+  };
+  if (T == 1) {
+    work();
+  } else {
+    std::vector<std::thread> pool;
+    for (int t = 1; t < T; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+  }
+  for (int32_t i = 0; i < B; ++i)
+    if (sizes_out[i] < 0) {
+      danhip_set_error("jpeg_encode_entropy_batch: image %d: %s", i,
+                       sizes_out[i] == -2 ? "a coefficient outside what the baseline tables carry (DC difference 11 bits, AC 10 bits)" : "file capacity");
+      return DANHIP_EINVAL;
+    }
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_jpeg_encode_host(const uint8_t* rgb, int32_t width, int32_t height, int32_t mode, int32_t quality, uint8_t* out,
+                                       int64_t capacity, int64_t* size_out) {
+  if (!rgb || !out || !size_out || capacity < 0) {
+    danhip_set_error("jpeg_encode_host: NULL buffer");
+    return DANHIP_EINVAL;
+  }
+  danhip_jpeg_enc_desc d;
+  int64_t totals[3];
+  const void* src = rgb;
+  const int rc = danhip_jpeg_encode_prepare(&width, &height, &src, 1, mode, quality, &d, totals);
+  if (rc) return rc;
+  std::vector<int16_t> coef((size_t)totals[0]);
+  pixels_host(d, coef.data());
+  std::vector<uint8_t> file((size_t)d.file_capacity);
+  const int64_t n = write_file(d, coef.data(), file.data(), d.file_capacity);
+  if (n < 0) {
+    danhip_set_error("jpeg_encode_host: internal: the scan left its bound");
+    return DANHIP_EINVAL;
+  }
+  *size_out = n;
+  if (n > capacity) {
+    danhip_set_error("jpeg_encode_host: the file takes %lld bytes, capacity is %lld", (long long)n, (long long)capacity);
+    return DANHIP_EWORKSPACE;
+  }
+  memcpy(out, file.data(), (size_t)n);
+  return DANHIP_OK;
+}

@@ -21,13 +21,23 @@ script the validator does not take, is refused with reason "progression" and goe
 record then takes the fallback as before (reason "progressive").
 
     dec = JpegDecoder(torch.device("cuda:0"))
-    images = dec.decode_batch([record_bytes, ...])        # uint8 [H,W,3] device tensors: what preprocess_for_train takes"""
+    images = dec.decode_batch([record_bytes, ...])        # uint8 [H,W,3] device tensors: what preprocess_for_train takes
+
+JpegEncoder is the mirror: uint8 [H,W,3] RGB images -> baseline JFIF files, byte for byte what Pillow writes with
+save(f, "JPEG", quality=q, subsampling=s) (no optimize, no progressive).  Colour conversion, chroma downsampling, forward DCT and quantisation
+are two launches per BATCH on the device (csrc/jpeg_encode_exact.hip); the quantised coefficients come back in one download - in the layout the
+decoder's entropy stage produces - and host threads write the Huffman scan and the markers (csrc/jpeg_encode.cpp).  Images in host memory
+(numpy arrays, CPU tensors) run the same integer code on the host, which is also what a process without a GPU gets.
+
+    enc = JpegEncoder(quality=75, subsampling="4:2:0")
+    files = enc.encode_batch(images)                      # list of bytes; the images may be views into the decoder's output buffer"""
 import ctypes
 import time
 
+import numpy as np
 import torch
 
-from .._lib import JpegDesc, JpegInfo, call, lib, ptr, stream
+from .._lib import JpegDesc, JpegEncDesc, JpegInfo, call, lib, ptr, stream
 from . import dataset_common
 
 MAX_THREADS = 16                                          # DANHIP_JPEG_MAX_THREADS
@@ -208,3 +218,86 @@ class JpegDecoder(object):
             for i, image in zip(retry, again):
                 results[i] = image
         return self._fallback(datas, refused, results)
+
+
+MODE_444, MODE_420 = 1, 3                                 # DANHIP_JPEG_444, DANHIP_JPEG_420
+_SUBSAMPLING = {0: MODE_444, "4:4:4": MODE_444, 2: MODE_420, "4:2:0": MODE_420}      # Pillow's names for them
+
+
+class JpegEncoder(object):
+    def __init__(self, quality=75, subsampling="4:2:0", threads=4):
+        if subsampling not in _SUBSAMPLING:
+            raise ValueError("subsampling must be '4:2:0' (2) or '4:4:4' (0), got %r" % (subsampling,))
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality must be 1 .. 100, got %r" % (quality,))
+        self.quality = int(quality)
+        self.mode = _SUBSAMPLING[subsampling]
+        self.threads = max(1, min(int(threads), MAX_THREADS))
+        self.stats = {"device": 0, "host": 0, "launches": 0, "entropy_seconds": 0.0, "download_bytes": 0}
+        self.coef = None                                  # the last device batch's coefficients on the host (tests compare them)
+
+    def encode(self, image):
+        return self.encode_batch([image])[0]
+
+    def encode_batch(self, images):
+        """list of uint8 [H,W,3] RGB images -> list of bytes.  Device tensors (separate, or views into one buffer) take the device pixel
+        stage in one batch; numpy arrays and CPU tensors take the host's.  The two may be mixed."""
+        images = list(images)
+        results = [None] * len(images)
+        on_device = [i for i, im in enumerate(images) if torch.is_tensor(im) and im.is_cuda]
+        on_host = [i for i in range(len(images)) if i not in set(on_device)]
+        for at in range(0, len(on_device), 65535):
+            part = on_device[at:at + 65535]
+            for i, data in zip(part, self._encode([images[i] for i in part], True)):
+                results[i] = data
+        for at in range(0, len(on_host), 65535):
+            part = on_host[at:at + 65535]
+            host = [np.ascontiguousarray(im.numpy() if torch.is_tensor(im) else im) for im in (images[i] for i in part)]
+            for i, data in zip(part, self._encode(host, False)):
+                results[i] = data
+        return results
+
+    def _encode(self, images, device):
+        B = len(images)
+        for im in images:
+            if tuple(im.shape[2:]) != (3,) or len(im.shape) != 3 or str(im.dtype) not in ("torch.uint8", "uint8"):
+                raise ValueError("JpegEncoder takes uint8 [H,W,3] images, got %s %s" % (im.dtype, tuple(im.shape)))
+        if device:
+            images = [im.contiguous() for im in images]
+            if len(set(im.device for im in images)) != 1:
+                raise ValueError("JpegEncoder: the images of a batch lie on one device")
+        L = lib()
+        nbytes = B * ctypes.sizeof(JpegEncDesc)
+        table = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=device)
+        descs = (JpegEncDesc * B).from_address(table.data_ptr())
+        widths = (ctypes.c_int32 * B)(*[int(im.shape[1]) for im in images])
+        heights = (ctypes.c_int32 * B)(*[int(im.shape[0]) for im in images])
+        srcs = (ctypes.c_void_p * B)(*[im.data_ptr() if device else im.ctypes.data for im in images])
+        totals = (ctypes.c_int64 * 3)()
+        call("danhip_jpeg_encode_prepare", widths, heights, srcs, B, self.mode, self.quality, descs, totals)
+        ncoef = totals[0]
+        if device:
+            dev = images[0].device
+            with torch.cuda.device(dev):
+                table_dev = table.to(dev, non_blocking=True)
+                coef_dev = torch.empty(ncoef, dtype=torch.int16, device=dev)
+                ws = torch.empty(max(totals[1], 16), dtype=torch.uint8, device=dev)
+                launches = ctypes.c_int32(0)
+                call("danhip_jpeg_encode_pixels_batch", descs, ptr(table_dev), B, ptr(coef_dev), ncoef, ptr(ws), ws.numel(), ctypes.byref(launches),
+                     stream())
+                coef = coef_dev.cpu()                     # the one download
+            self.coef = coef
+            self.stats["launches"] += launches.value
+            self.stats["download_bytes"] += 2 * ncoef
+            self.stats["device"] += B
+        else:
+            coef = torch.empty(ncoef, dtype=torch.int16)
+            call("danhip_jpeg_encode_pixels_host", descs, B, ctypes.c_void_p(coef.data_ptr()), ncoef)
+            self.stats["host"] += B
+        files = np.empty(totals[2], dtype=np.uint8)       # the bound of every file; pages a file does not reach are never touched
+        sizes = (ctypes.c_int64 * B)()
+        t0 = time.perf_counter()
+        call("danhip_jpeg_encode_entropy_batch", ctypes.c_void_p(coef.data_ptr()), ncoef, descs, B, self.threads, ctypes.c_void_p(files.ctypes.data),
+             totals[2], sizes)
+        self.stats["entropy_seconds"] += time.perf_counter() - t0
+        return [files[descs[i].file_offset:descs[i].file_offset + sizes[i]].tobytes() for i in range(B)]

@@ -186,14 +186,15 @@ def get_shrink(height, width, memory_limit=MEMORY_LIMIT):
     return (m if m < 1 else 1), m
 
 
-def write_to_txt(f, det, event, im_name, select_threshold=SELECT_THRESHOLD):
+def write_to_txt(f, det, event, im_name, select_threshold=SELECT_THRESHOLD, min_height=10):
     """eval_dan.py:243-261 (same text format); det may be a device tensor.  `event` is the WIDER-FACE event entry
-    (event[0][0] is its name) or a plain string."""
+    (event[0][0] is its name) or a plain string.  min_height: the row filter ceil(height) >= 10 of eval_dan.py / eval_sfd.py;
+    eval_pb.py:252 has 9 (dan_amd/eval_pb.py passes it)."""
     det = det.detach().cpu().numpy() if torch.is_tensor(det) else np.asarray(det)
     name = event if isinstance(event, str) else event[0][0]
     xmin, ymin, xmax, ymax, sc = (det[:, i] for i in range(5))
     bh, bw = ymax - ymin + 1, xmax - xmin + 1
-    valid = np.logical_and(np.logical_and(np.ceil(bh) >= 10, bw > 1), sc > select_threshold)
+    valid = np.logical_and(np.logical_and(np.ceil(bh) >= min_height, bw > 1), sc > select_threshold)
     f.write('{:s}\n'.format(name + '/' + im_name + '.jpg'))
     f.write('{}\n'.format(np.count_nonzero(valid)))
     for i in range(valid.shape[0]):
@@ -312,9 +313,9 @@ def detect_image(net, image, pyramid=True):
 FILTER_NONE, FILTER_BIG, FILTER_SMALL = 0, 1, 2          # danhip_detect_select's filter: none / max(w, h) > 30 / min(w, h) < 100
 
 
-def scale_passes(height, width, pyramid=True):
+def scale_passes(height, width, pyramid=True, memory_limit=MEMORY_LIMIT):
     """The passes detect_image walks for an image of this size, in its order: [(scale, mirrored, filter)] (host arithmetic on the size)."""
-    shrink, max_shrink = get_shrink(height, width)
+    shrink, max_shrink = get_shrink(height, width, memory_limit)
     passes = [(shrink, 0, FILTER_NONE), (shrink, 1, FILTER_NONE)]              # detect_face, flip_test
     st = 0.5 if max_shrink >= 0.75 else 0.5 * max_shrink                      # multi_scale_test
     passes.append((st, 0, FILTER_BIG))
@@ -376,7 +377,7 @@ def detect_select(bboxes, scores, shrink, top, rows, valid, filter=FILTER_NONE, 
     return launches.value
 
 
-def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
+def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):
     """detect_image for a list of uint8 [H_i,W_i,3] device tensors of ANY sizes (they may be views into one buffer, the JPEG decoder's)
     -> (dets fp32 [B, max_per_image, 5], num int32 [B]) on the device, the layout WiderEvaluator.add takes; rows beyond num[b] are
     unspecified.  Per image the result equals detect_image(net, images[b], pyramid): the forwards are the same batch-1 calls.  No device
@@ -386,7 +387,7 @@ def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, ma
     device = images[0].device
     images = [im.contiguous() for im in images]
     cap = int(max_per_image * 1.5)
-    plans = [scale_passes(int(im.shape[0]), int(im.shape[1]), pyramid) for im in images]
+    plans = [scale_passes(int(im.shape[0]), int(im.shape[1]), pyramid, memory_limit) for im in images]
     requests, where = [], {}                                                   # one copy per distinct (image, scale, mirrored)
     for i, plan in enumerate(plans):
         for scale, mirror, _ in plan:
@@ -420,7 +421,17 @@ def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, ma
     return out, num
 
 
-def detect_encoded(net, datas, decoder, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
+def detect_encoded(net, datas, decoder, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):
     """JPEG byte strings -> detections: dataset.jpeg.JpegDecoder.decode_batch (device decode; a stream the decoder refuses, a progressive one
     by default, takes its Pillow fallback) -> detect_image_list on the decoder's views."""
-    return detect_image_list(net, decoder.decode_batch(list(datas)), pyramid, nms_threshold, max_per_image)
+    return detect_image_list(net, decoder.decode_batch(list(datas)), pyramid, nms_threshold, max_per_image, memory_limit)
+
+
+def main(argv=None, **kw):
+    """`python -m dan_amd.eval_dan --data_dir WIDER_ROOT --checkpoint_path M`: the reference's `python eval_dan.py` (dan_amd/eval_cli.py)."""
+    from .eval_cli import main as run
+    return run(argv, model="dan", **kw)
+
+
+if __name__ == "__main__":
+    main()

@@ -25,3 +25,13 @@ def detect_encoded(net, datas, decoder):
     """JPEG byte strings -> detections (eval_dan.detect_encoded) without the pyramid pass."""
     from .eval_dan import detect_encoded as _detect_encoded
     return _detect_encoded(net, datas, decoder, pyramid=False)
+
+
+def main(argv=None, **kw):
+    """`python -m dan_amd.eval_sfd --data_dir WIDER_ROOT --checkpoint_path M`: the reference's `python eval_sfd.py` (dan_amd/eval_cli.py)."""
+    from .eval_cli import main as run
+    return run(argv, model="sfd", **kw)
+
+
+if __name__ == "__main__":
+    main()

@@ -1038,6 +1038,88 @@ size_t danhip_crc32c_batch_workspace_bytes(int32_t n, uint64_t total_bytes);
 int danhip_crc32c_batch(const danhip_crc_segment* table_host, int32_t n, uint32_t* crc_out_dev, int32_t masked, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* --------------------------------------------------------------------------------------------------
+ * Baseline JPEG encode (ABI version 15): uint8 [H,W,3] RGB -> a JFIF file that is byte for byte what Pillow (libjpeg-turbo) writes with
+ * Image.save(f, "JPEG", quality=q, subsampling=s) - the mirror of the decoder above, made for the debug images of the evaluation
+ * command.  The pixel stage runs on the device (csrc/jpeg_encode_exact.hip), the Huffman stage and the file writer on host threads
+ * (csrc/jpeg_encode.cpp, no HIP call); the integer arithmetic both share is csrc/jpeg_encode.h, which also says where libjpeg-turbo
+ * parts from the textbook (edges and dummy blocks, the reciprocal quantiser, the quality scaling, APP0).
+ *
+ * Scope: quality 1 .. 100; mode DANHIP_JPEG_420 (Pillow's default, subsampling=2) or DANHIP_JPEG_444 (subsampling=0); sides 1 ..
+ * DANHIP_JPEG_MAX_DIM; no optimize, no progressive.  The file is SOI, JFIF APP0, two DQT, SOF0, four DHT (the standard tables of T.81
+ * K.3), SOS, the stuffed scan padded with 1 bits, EOI.  Grey input, 4:2:2, restart intervals and optimised tables are not made.
+ *
+ * danhip_jpeg_encode_prepare: one descriptor per image from (width, height) and the call's (mode, quality): geometry by the rules of the
+ *   decoder (whole MCUs), reciprocal quantisation tables, and offsets handed out in order into the coefficient buffer (int16 elements), the
+ *   device workspace (bytes) and the file buffer (bytes; file_capacity is a bound no image can exceed).  srcs[i] is image i's first byte -
+ *   a device pointer for danhip_jpeg_encode_pixels_batch, a host pointer for danhip_jpeg_encode_pixels_host; rows are width * 3 bytes
+ *   apart (views into one buffer, the decoder's, or separate tensors).  srcs may be NULL for descriptors that only feed the entropy stage.
+ *   totals_out[3] = {coefficients, workspace bytes, file bytes}.
+ * danhip_jpeg_encode_pixels_batch: the device pixel stage, DANHIP_JPEG_ENCODE_LAUNCHES launches whatever B and the sizes are, each a
+ *   (workgroup, image) grid through the descriptor table (the host copy is re-derived from (width, height, mode) and checked against the
+ *   buffer sizes before a launch; the kernels read the device copy).
+ *     1 colour and downsample: RGB -> YCbCr, planar component planes in the workspace (pitch = block-grid width * 8), edges replicated;
+ *       4:2:0 chroma by (a + b + c + d + bias) >> 2, bias 1, 2 alternating along the row.
+ *     2 forward DCT and quantisation: eight lanes own a block - level shift, the jfdctint row pass, the transpose through LDS, the column
+ *       pass, the reciprocal quantiser.
+ *   Coefficients leave as int16 IN THE LAYOUT danhip_jpeg_entropy_decode_batch PRODUCES (component planes, raster blocks over whole MCUs,
+ *   de-zigzagged, column-major), so either stage can be tested against the decoder's.
+ * danhip_jpeg_encode_pixels_host: the same stage on the host through the same arithmetic (checked indexing, one thread).
+ * danhip_jpeg_encode_entropy_batch: coefficients in host memory -> files.  min(threads, B, DANHIP_JPEG_MAX_THREADS) threads; image i's
+ *   file is files_out[descs[i].file_offset ...], sizes_out[i] bytes long.
+ * danhip_jpeg_encode_host: the whole encoder on the host for one image; *size_out = the file's size.  DANHIP_EWORKSPACE when capacity is
+ *   below it (danhip_jpeg_encode_file_bound gives a capacity that always suffices).
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_ENCODE_LAUNCHES 2
+typedef struct danhip_jpeg_enc_desc {
+  const uint8_t* src;                 /* RGB, rows width * 3 bytes apart */
+  int32_t width, height, mode, quality;
+  int32_t blocks_w[3], blocks_h[3];   /* block grid of each component over whole MCUs: the coefficient layout; a plane's pitch is blocks_w * 8 */
+  int32_t comp_w[3], comp_h[3];       /* the component's own size */
+  int32_t real_bw, real_bh;           /* luma blocks that carry samples: ceil(width / 8) x ceil(height / 8); the rest are dummy blocks */
+  int32_t color_groups, fdct_groups;  /* workgroups of launch 1 (256 lanes x 8 luma columns x 1 | 2 rows) and launch 2 (32 blocks each) */
+  int64_t coef_offset, coef_count;    /* int16 elements */
+  int64_t plane_offset[3];            /* bytes into the workspace, multiples of 256 */
+  int64_t file_offset, file_capacity; /* bytes into the file buffer */
+  uint16_t recip[2][64], corr[2][64]; /* luma | chroma quantiser, row-major (de-zigzagged): csrc/jpeg_encode.h dh_jenc_quant */
+  uint8_t shift[2][64];
+  uint8_t qtable[2][64];              /* the tables the file carries, row-major */
+} danhip_jpeg_enc_desc;
+size_t danhip_jpeg_enc_desc_bytes(void);                                         /* sizeof(danhip_jpeg_enc_desc) */
+int64_t danhip_jpeg_encode_file_bound(int32_t width, int32_t height, int32_t mode);   /* 0: outside the scope */
+int danhip_jpeg_encode_prepare(const int32_t* widths, const int32_t* heights, const void* const* srcs, int32_t B, int32_t mode, int32_t quality,
+                               danhip_jpeg_enc_desc* descs_out, int64_t* totals_out);
+int danhip_jpeg_encode_pixels_batch(const danhip_jpeg_enc_desc* descs_host, const danhip_jpeg_enc_desc* descs_dev, int32_t B, int16_t* coef_dev,
+                                    int64_t coef_count, void* workspace, size_t workspace_bytes, int32_t* launches, void* stream);
+int danhip_jpeg_encode_pixels_host(const danhip_jpeg_enc_desc* descs, int32_t B, int16_t* coef_out, int64_t coef_count);
+int danhip_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_count, const danhip_jpeg_enc_desc* descs, int32_t B, int32_t threads,
+                                     uint8_t* files_out, int64_t files_capacity, int64_t* sizes_out);
+int danhip_jpeg_encode_host(const uint8_t* rgb, int32_t width, int32_t height, int32_t mode, int32_t quality, uint8_t* out, int64_t capacity,
+                            int64_t* size_out);
+
+/* --------------------------------------------------------------------------------------------------
+ * Box drawing on uint8 [H,W,3] device images (ABI version 15; csrc/draw_exact.hip): the rectangles of utility/draw_toolbox.py
+ * bboxes_draw_on_img for every image of a list in ONE launch.  The rule is this project's own (no OpenCV to compare with):
+ *   box i of an image is skipped when classes[i] < 1 or a coordinate is not finite; corners x1, y1, x2, y2 = the floats bbox[0..3]
+ *   truncated toward zero (Python's int(); clamped to +-2^30); skipped when x2 < x1 or y2 < y1;
+ *   with t = thickness, a pixel (x, y) of the image is painted (203, 71, 119) when x1 - t/2 <= x <= x2 + t/2 and y1 - t/2 <= y <= y2 + t/2
+ *   and it is not in the interior x1 + (t+1)/2 <= x <= x2 - (t+1)/2, y1 + (t+1)/2 <= y <= y2 - (t+1)/2 (integer divisions).  For t = 2 the
+ *   band is the two pixels x1 - 1, x1 on the left, x2, x2 + 1 on the right, likewise above and below.
+ * One colour, so the result does not depend on the order of the boxes; one lane per pixel tests the image's boxes, staged in LDS in
+ * chunks; no atomics.  THE SCORE LABEL IS NOT DRAWN (it needs Hershey-font text rendering, which nothing here could check).
+ * items: one per image, in host memory (validated, sizes the grid) and in device memory (read by the kernel); boxes float [n,4] and
+ * classes int32 [n] of all images back to back, an item names its range.  thickness 1 .. 64.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct danhip_draw_item {
+  uint8_t* image;                     /* device, uint8 [height, width, 3], rows width * 3 bytes apart */
+  int32_t width, height;
+  int32_t first_box, num_boxes;       /* rows of boxes / classes */
+  int32_t groups, reserved;           /* workgroups of 256 pixels: ceil(width * height / 256) */
+} danhip_draw_item;
+size_t danhip_draw_item_bytes(void);
+int danhip_draw_boxes_u8(const danhip_draw_item* items_host, const danhip_draw_item* items_dev, int32_t n_images, const float* boxes_dev,
+                         const int32_t* classes_dev, int64_t n_boxes, int32_t thickness, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
