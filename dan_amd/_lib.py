@@ -88,6 +88,8 @@ class DrawItem(ctypes.Structure):
 DETECT_SELECT_LAUNCHES = 7     # DANHIP_DETECT_SELECT_LAUNCHES
 CRC32C_BATCH_LAUNCHES = 3      # DANHIP_CRC32C_BATCH_LAUNCHES
 JPEG_ENCODE_LAUNCHES = 2       # DANHIP_JPEG_ENCODE_LAUNCHES
+JPEG_ENCODE_ENTROPY_LAUNCHES = 6   # DANHIP_JPEG_ENCODE_ENTROPY_LAUNCHES
+JPEG_HOSTONLY = -1             # DANHIP_JPEG_HOSTONLY
 
 P = ctypes.c_void_p
 I32 = ctypes.c_int32
@@ -226,6 +228,7 @@ SIGNATURES = {
     "danhip_jpeg_entropy_emulate_batch": [P, ctypes.c_size_t, I32, P, P, I64, I32, P, P],
     "danhip_crc32c_batch": [P, I32, P, I32, P, ctypes.c_size_t, P],
     "danhip_jpeg_encode_pixels_batch": [P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
+    "danhip_jpeg_encode_huffman_batch": [P, P, ctypes.c_size_t, P, I32, P, I64, P, I64, P, P, P, ctypes.c_size_t, P, P],
     "danhip_draw_boxes_u8": [P, P, I32, P, P, I64, I32, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
@@ -378,10 +381,14 @@ def bind_jpeg_encode_host(L):
     """Prototypes of the JPEG encoder's host entry points (csrc/jpeg_encode.cpp: no GPU call behind them)."""
     L.danhip_jpeg_enc_desc_bytes.restype, L.danhip_jpeg_enc_desc_bytes.argtypes = ctypes.c_size_t, []
     L.danhip_jpeg_encode_file_bound.restype, L.danhip_jpeg_encode_file_bound.argtypes = I64, [I32, I32, I32]
+    L.danhip_jpeg_encode_scan_staging_bytes.restype, L.danhip_jpeg_encode_scan_staging_bytes.argtypes = ctypes.c_size_t, [I32]
+    L.danhip_jpeg_encode_scan_workspace_bytes.restype, L.danhip_jpeg_encode_scan_workspace_bytes.argtypes = ctypes.c_size_t, [P]
     for name, args in (("danhip_jpeg_encode_prepare", [P, P, P, I32, I32, I32, P, P]),
                        ("danhip_jpeg_encode_pixels_host", [P, I32, P, I64]),
                        ("danhip_jpeg_encode_entropy_batch", [P, I64, P, I32, I32, P, I64, P]),
-                       ("danhip_jpeg_encode_host", [P, I32, I32, I32, I32, P, I64, P])):
+                       ("danhip_jpeg_encode_host", [P, I32, I32, I32, I32, P, I64, P]),
+                       ("danhip_jpeg_encode_scan_prepare", [P, I32, I64, I64, P, ctypes.c_size_t, P]),
+                       ("danhip_jpeg_encode_entropy_emulate_batch", [P, ctypes.c_size_t, P, I32, P, I64, P, I64, P, P, P])):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = ctypes.c_int, args
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jpeg_encode.h"
+#include "jpeg_encode_huffman.h"
 #include "jpeg_layout.h"
 
 void danhip_set_error(const char* fmt, ...);
@@ -325,6 +326,204 @@ void pixels_host(const danhip_jpeg_enc_desc& d, int16_t* coef) {
   }
 }
 
+
+// ---- Huffman stage on the device: the staging buffer (jpeg_encode_huffman.h) and the phases on the host ----
+
+int64_t align16(int64_t v) { return dh_jpeg_align(v, 16); }
+
+size_t scan_staging_bytes(int32_t B) {
+  return (size_t)(align16(sizeof(DhJencHeader)) + align16((int64_t)B * (int64_t)sizeof(DhJencImage)) + 4 * 256 * 4 + (int64_t)B * DH_JHUF_HEADER_SLOT);
+}
+
+// fills `staging` (scan_staging_bytes(B) bytes) from checked descriptors; status may be NULL
+void fill_staging(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, uint8_t* staging, int32_t* status) {
+  const size_t bytes = scan_staging_bytes(B);
+  memset(staging, 0, bytes);
+  DhJencHeader* H = (DhJencHeader*)staging;
+  H->magic = DH_JHUF_MAGIC;
+  H->B = B;
+  H->off_images = align16(sizeof(DhJencHeader));
+  H->off_tabs = H->off_images + align16((int64_t)B * (int64_t)sizeof(DhJencImage));
+  H->off_headers = H->off_tabs + 4 * 256 * 4;
+  H->used_bytes = (int64_t)bytes;
+  H->coef_count = coef_count;
+  H->file_bytes = file_bytes;
+  const StdTables& T = std_tables();
+  const EncTable* tabs[4] = {&T.dc[0], &T.ac[0], &T.dc[1], &T.ac[1]};
+  uint32_t* tab = (uint32_t*)(staging + H->off_tabs);
+  for (int t = 0; t < 4; ++t)
+    for (int k = 0; k < 256; ++k) tab[t * 256 + k] = (uint32_t)tabs[t]->code[k] | ((uint32_t)tabs[t]->len[k] << 16);
+  DhJencImage* images = (DhJencImage*)(staging + H->off_images);
+  int64_t ws = 0;
+  for (int32_t i = 0; i < B; ++i) {
+    const danhip_jpeg_enc_desc& d = descs[i];
+    DhJencImage& im = images[i];
+    im.coef_offset = d.coef_offset; im.coef_count = d.coef_count;
+    im.file_offset = d.file_offset; im.file_capacity = d.file_capacity;
+    if (d.file_capacity >= DH_JHUF_MAX_FILE) {
+      if (status) status[i] = DANHIP_JPEG_HOSTONLY;
+      continue;
+    }
+    if (status) status[i] = 0;
+    im.prepared = 1;
+    im.hs = d.mode == DANHIP_JPEG_420 ? 2 : 1;
+    im.nl = im.hs * im.hs;
+    im.bpm = im.nl + 2;
+    im.mcus_x = d.blocks_w[1]; im.mcus_y = d.blocks_h[1];
+    im.bw0 = d.blocks_w[0];
+    im.nblocks = (int64_t)im.mcus_x * im.mcus_y * im.bpm;
+    im.plane[0] = d.coef_offset;
+    im.plane[1] = im.plane[0] + (int64_t)d.blocks_w[0] * d.blocks_h[0] * 64;
+    im.plane[2] = im.plane[1] + (int64_t)d.blocks_w[1] * d.blocks_h[1] * 64;
+    im.header_off = H->off_headers + (int64_t)i * DH_JHUF_HEADER_SLOT;
+    im.header_len = (int32_t)(write_header(staging + im.header_off, d) - (staging + im.header_off));
+    im.len_groups = (int32_t)((im.nblocks + DH_JHUF_GROUP - 1) / DH_JHUF_GROUP);
+    im.bits_bytes = (int64_t)im.len_groups * DH_JHUF_GROUP * DH_JHUF_BLOCK_BYTES;
+    im.stuff_groups = (int32_t)((im.bits_bytes + DH_JHUF_CHUNK_BYTES - 1) / DH_JHUF_CHUNK_BYTES);
+    im.ws_gsum = ws; ws += align16((int64_t)im.len_groups * 8);
+    im.ws_goff = ws; ws += align16(((int64_t)im.len_groups + 1) * 8);
+    im.ws_bits = ws; ws += align16(im.bits_bytes);
+    im.ws_ff = ws; ws += align16((int64_t)im.stuff_groups * 4);
+    im.ws_ffoff = ws; ws += align16((int64_t)im.stuff_groups * 4);
+    H->nprepared += 1;
+    H->max_len_groups = im.len_groups > H->max_len_groups ? im.len_groups : H->max_len_groups;
+    H->max_stuff_groups = im.stuff_groups > H->max_stuff_groups ? im.stuff_groups : H->max_stuff_groups;
+  }
+  H->workspace_bytes = ws;
+}
+
+static_assert(623 <= DH_JHUF_HEADER_SLOT, "the markers fit their staged slot");
+
+// NULL = staging is what fill_staging makes of these descriptors and buffer sizes, else what is wrong
+const char* check_staging(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count,
+                          int64_t file_bytes) {
+  if (staging_bytes < scan_staging_bytes(B)) return "staging buffer shorter than danhip_jpeg_encode_scan_staging_bytes(B)";
+  for (int32_t i = 0; i < B; ++i) {
+    const char* why = check_desc(&descs[i], coef_count, -1, file_bytes);
+    if (why) return why;
+  }
+  std::vector<uint8_t> again(scan_staging_bytes(B));
+  fill_staging(descs, B, coef_count, file_bytes, again.data(), nullptr);
+  if (memcmp(again.data(), staging, again.size()) != 0) return "staging buffer is not what danhip_jpeg_encode_scan_prepare makes of the descriptors";
+  return nullptr;
+}
+
+// the context of jpeg_encode_huffman.h over host arrays: every index checked, a refused one counted
+struct EmuCtx {
+  const uint8_t* staging;
+  const DhJencHeader* H;
+  const int16_t* coef;
+  std::vector<uint8_t>* ws;
+  uint8_t* files;
+  int64_t errors = 0;
+  void load_block(int64_t el, int16_t v[64]) {
+    if (el < 0 || el + 64 > H->coef_count) { ++errors; memset(v, 0, 128); return; }
+    memcpy(v, coef + el, 128);
+  }
+  int dc(int64_t el) {
+    if (el < 0 || el >= H->coef_count) { ++errors; return 0; }
+    return coef[el];
+  }
+  uint32_t tab(int t, int sym) {
+    if (t < 0 || t > 3 || sym < 0 || sym > 255) { ++errors; return 0; }
+    return ((const uint32_t*)(staging + H->off_tabs))[t * 256 + sym];
+  }
+  void or_word(const DhJencImage& im, int64_t w, uint32_t v) {
+    if (w < 0 || w >= im.bits_bytes / 4) { ++errors; return; }
+    uint8_t* p = &ws->at((size_t)(im.ws_bits + w * 4));
+    p[0] |= (uint8_t)(v >> 24); p[1] |= (uint8_t)(v >> 16); p[2] |= (uint8_t)(v >> 8); p[3] |= (uint8_t)v;
+  }
+  uint32_t ubyte(const DhJencImage& im, int64_t i) {
+    if (i < 0 || i >= im.bits_bytes) { ++errors; return 0; }
+    return ws->at((size_t)(im.ws_bits + i));
+  }
+  void file_store(const DhJencImage& im, int64_t i, uint32_t b) {
+    if (i < 0 || i >= im.file_capacity || im.file_offset + i >= H->file_bytes) { ++errors; return; }
+    files[im.file_offset + i] = (uint8_t)b;
+  }
+  uint32_t header_byte(const DhJencImage& im, int i) {
+    if (i < 0 || i >= im.header_len) { ++errors; return 0; }
+    return staging[im.header_off + i];
+  }
+  template <class T>
+  T* array(int64_t off, int64_t n) {                      // n elements of the workspace at byte off; NULL and an error when they leave it
+    if (off < 0 || n < 0 || off % (int64_t)sizeof(T) || off + n * (int64_t)sizeof(T) > (int64_t)ws->size()) { ++errors; return nullptr; }
+    return (T*)(ws->data() + off);
+  }
+};
+
+// the six launches of jpeg_encode_huffman_exact.hip for one image, workgroup by workgroup and lane by lane
+void emulate_image(EmuCtx& c, const DhJencImage& im, int64_t* size_out, int32_t* status_out) {
+  uint64_t* gsum = c.array<uint64_t>(im.ws_gsum, im.len_groups);
+  uint64_t* goff = c.array<uint64_t>(im.ws_goff, (int64_t)im.len_groups + 1);
+  uint32_t* ff = c.array<uint32_t>(im.ws_ff, im.stuff_groups);
+  uint32_t* ffoff = c.array<uint32_t>(im.ws_ffoff, im.stuff_groups);
+  uint8_t* bits = c.array<uint8_t>(im.ws_bits, im.bits_bytes);
+  if (!gsum || !goff || !ff || !ffoff || !bits) { *size_out = 0; *status_out = DANHIP_JPEG_ENC_DEV_CAPACITY; return; }
+  // 1 length (and the zero fill)
+  memset(bits, 0, (size_t)im.bits_bytes);
+  for (int32_t g = 0; g < im.len_groups; ++g) {
+    uint64_t sum = 0;
+    for (int lane = 0; lane < DH_JHUF_GROUP; ++lane) {
+      const int64_t s = (int64_t)g * DH_JHUF_GROUP + lane;
+      if (s >= im.nblocks) break;
+      const uint64_t len = dh_jhuf_lane_length(c, im, s);
+      if (len & DH_JHUF_INVALID) sum |= DH_JHUF_INVALID;             // the flag is OR-ed, the bits (0 for such a block) are added
+      else sum += len;
+    }
+    gsum[g] = sum;
+  }
+  // 2 offsets
+  uint64_t at = 0;
+  int32_t status = 0;
+  for (int32_t g = 0; g < im.len_groups; ++g) {
+    goff[g] = at;
+    if (gsum[g] & DH_JHUF_INVALID) status |= DANHIP_JPEG_ENC_DEV_RANGE;
+    at += gsum[g] & ~DH_JHUF_INVALID;
+  }
+  goff[im.len_groups] = at;
+  // 3 write
+  for (int32_t g = 0; g < im.len_groups; ++g) {
+    uint64_t bit = goff[g];
+    for (int lane = 0; lane < DH_JHUF_GROUP; ++lane) {
+      const int64_t s = (int64_t)g * DH_JHUF_GROUP + lane;
+      if (s >= im.nblocks) break;
+      const uint64_t len = dh_jhuf_lane_length(c, im, s);
+      dh_jhuf_lane_write(c, im, s, bit, len);
+      bit += len & ~DH_JHUF_INVALID;
+    }
+  }
+  // 4 count
+  const int64_t scan_bytes = dh_jhuf_scan_bytes(im, goff[im.len_groups]);
+  const int32_t chunks = (int32_t)((scan_bytes + DH_JHUF_CHUNK_BYTES - 1) / DH_JHUF_CHUNK_BYTES);
+  for (int32_t g = 0; g < chunks && g < im.stuff_groups; ++g) {
+    uint32_t n = 0;
+    for (int lane = 0; lane < DH_JHUF_GROUP; ++lane)
+      n += dh_jhuf_lane_ffcount(c, im, scan_bytes, (int64_t)g * DH_JHUF_CHUNK_BYTES + (int64_t)lane * DH_JHUF_LANE_BYTES);
+    ff[g] = n;
+  }
+  // 5 finish
+  uint32_t total_ff = 0;
+  for (int32_t g = 0; g < chunks && g < im.stuff_groups; ++g) { ffoff[g] = total_ff; total_ff += ff[g]; }
+  int64_t size = 0;
+  const bool fits = (int64_t)im.header_len + scan_bytes + total_ff + 2 <= im.file_capacity;
+  if (!fits) status |= DANHIP_JPEG_ENC_DEV_CAPACITY;
+  else
+    for (int lane = 0; lane < DH_JHUF_GROUP; ++lane) size = dh_jhuf_lane_finish(c, im, scan_bytes, total_ff, lane, DH_JHUF_GROUP);
+  // 6 stuff
+  if (fits)
+    for (int32_t g = 0; g < chunks && g < im.stuff_groups; ++g) {
+      uint32_t before = ffoff[g];
+      for (int lane = 0; lane < DH_JHUF_GROUP; ++lane) {
+        const int64_t byte0 = (int64_t)g * DH_JHUF_CHUNK_BYTES + (int64_t)lane * DH_JHUF_LANE_BYTES;
+        dh_jhuf_lane_scatter(c, im, scan_bytes, byte0, before);
+        before += dh_jhuf_lane_ffcount(c, im, scan_bytes, byte0);
+      }
+    }
+  *status_out = status;
+  *size_out = status ? 0 : size;
+}
+
 }  // namespace
 
 extern "C" size_t danhip_jpeg_enc_desc_bytes(void) { return sizeof(danhip_jpeg_enc_desc); }
@@ -455,5 +654,65 @@ extern "C" int danhip_jpeg_encode_host(const uint8_t* rgb, int32_t width, int32_
     return DANHIP_EWORKSPACE;
   }
   memcpy(out, file.data(), (size_t)n);
+  return DANHIP_OK;
+}
+
+extern "C" size_t danhip_jpeg_encode_scan_staging_bytes(int32_t B) { return B < 1 || B > 65535 ? 0 : scan_staging_bytes(B); }
+
+extern "C" int danhip_jpeg_encode_scan_prepare(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, void* staging,
+                                               size_t staging_bytes, int32_t* status_out) {
+  if (!descs || !staging || !status_out || B < 1 || B > 65535 || coef_count < 0 || file_bytes < 0 || ((uintptr_t)staging & 15) ||
+      staging_bytes < scan_staging_bytes(B)) {
+    danhip_set_error("jpeg_encode_scan_prepare: bad arguments (1 <= B <= 65535, no NULL table, staging 16-byte aligned and at least "
+                     "danhip_jpeg_encode_scan_staging_bytes(B) bytes)");
+    return DANHIP_EINVAL;
+  }
+  for (int32_t i = 0; i < B; ++i) {
+    const char* why = check_desc(&descs[i], coef_count, -1, file_bytes);
+    if (why) {
+      danhip_set_error("jpeg_encode_scan_prepare: descriptor %d: %s", i, why);
+      return DANHIP_EINVAL;
+    }
+  }
+  fill_staging(descs, B, coef_count, file_bytes, (uint8_t*)staging, status_out);
+  return DANHIP_OK;
+}
+
+extern "C" size_t danhip_jpeg_encode_scan_workspace_bytes(const void* staging) {
+  const DhJencHeader* H = (const DhJencHeader*)staging;
+  if (!H || H->magic != DH_JHUF_MAGIC || H->workspace_bytes < 0) return 0;
+  return (size_t)H->workspace_bytes;
+}
+
+// the check of the device launcher (jpeg_encode_huffman_exact.hip), here because the derivation is
+extern "C" const char* danhip_jpeg_encode_scan_check(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B,
+                                                     int64_t coef_count, int64_t file_bytes) {
+  return check_staging(staging, staging_bytes, descs, B, coef_count, file_bytes);
+}
+
+extern "C" int danhip_jpeg_encode_entropy_emulate_batch(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B,
+                                                        const int16_t* coef, int64_t coef_count, uint8_t* files_out, int64_t file_bytes,
+                                                        int64_t* sizes_out, int32_t* status_out, int64_t* range_errors) {
+  if (range_errors) *range_errors = 0;
+  if (!staging || !descs || !coef || !files_out || !sizes_out || !status_out || B < 1 || B > 65535 || coef_count < 0 || file_bytes < 0 ||
+      ((uintptr_t)staging & 15)) {
+    danhip_set_error("jpeg_encode_entropy_emulate_batch: bad arguments (1 <= B <= 65535, no NULL buffer, staging 16-byte aligned)");
+    return DANHIP_EINVAL;
+  }
+  const char* why = check_staging(staging, staging_bytes, descs, B, coef_count, file_bytes);
+  if (why) {
+    danhip_set_error("jpeg_encode_entropy_emulate_batch: %s", why);
+    return DANHIP_EINVAL;
+  }
+  const DhJencHeader* H = (const DhJencHeader*)staging;
+  const DhJencImage* images = (const DhJencImage*)((const uint8_t*)staging + H->off_images);
+  std::vector<uint8_t> ws((size_t)H->workspace_bytes, (uint8_t)0xa5);       // exactly the queried size, not zeroed: the phases own every byte they read
+  EmuCtx c;
+  c.staging = (const uint8_t*)staging; c.H = H; c.coef = coef; c.ws = &ws; c.files = files_out;
+  for (int32_t i = 0; i < B; ++i) {
+    if (!images[i].prepared) { sizes_out[i] = 0; status_out[i] = DANHIP_JPEG_HOSTONLY; continue; }
+    emulate_image(c, images[i], &sizes_out[i], &status_out[i]);
+  }
+  if (range_errors) *range_errors = c.errors;
   return DANHIP_OK;
 }

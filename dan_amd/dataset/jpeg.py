@@ -30,7 +30,13 @@ decoder's entropy stage produces - and host threads write the Huffman scan and t
 (numpy arrays, CPU tensors) run the same integer code on the host, which is also what a process without a GPU gets.
 
     enc = JpegEncoder(quality=75, subsampling="4:2:0")
-    files = enc.encode_batch(images)                      # list of bytes; the images may be views into the decoder's output buffer"""
+    files = enc.encode_batch(images)                      # list of bytes; the images may be views into the decoder's output buffer
+
+With entropy="device" (opt-in; device images only) the Huffman stage runs on the device as well (csrc/jpeg_encode_huffman_exact.hip, six
+launches per BATCH): block lengths, prefix sums, the codes written at their bit offsets, FF stuffing, markers and EOI.  The files are the
+same bytes.  No coefficient comes back: one download brings sizes and status words, one more the files themselves, packed back to back on
+the device first.  An image the device stage flags, or leaves to the host for its size, goes through the host stage, which stays the
+authority (stats["entropy_retry"])."""
 import ctypes
 import time
 
@@ -225,7 +231,9 @@ _SUBSAMPLING = {0: MODE_444, "4:4:4": MODE_444, 2: MODE_420, "4:2:0": MODE_420} 
 
 
 class JpegEncoder(object):
-    def __init__(self, quality=75, subsampling="4:2:0", threads=4):
+    def __init__(self, quality=75, subsampling="4:2:0", threads=4, entropy="host"):
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device', got %r" % (entropy,))
         if subsampling not in _SUBSAMPLING:
             raise ValueError("subsampling must be '4:2:0' (2) or '4:4:4' (0), got %r" % (subsampling,))
         if not 1 <= int(quality) <= 100:
@@ -233,8 +241,11 @@ class JpegEncoder(object):
         self.quality = int(quality)
         self.mode = _SUBSAMPLING[subsampling]
         self.threads = max(1, min(int(threads), MAX_THREADS))
-        self.stats = {"device": 0, "host": 0, "launches": 0, "entropy_seconds": 0.0, "download_bytes": 0}
+        self.entropy = entropy
+        self.stats = {"device": 0, "host": 0, "launches": 0, "entropy_seconds": 0.0, "download_bytes": 0, "entropy_device": 0,
+                      "entropy_launches": 0, "entropy_retry": 0}
         self.coef = None                                  # the last device batch's coefficients on the host (tests compare them)
+        self._buffers = {}                                # entropy="device": workspace, files and result words, kept and grown across calls
 
     def encode(self, image):
         return self.encode_batch([image])[0]
@@ -248,7 +259,7 @@ class JpegEncoder(object):
         on_host = [i for i in range(len(images)) if i not in set(on_device)]
         for at in range(0, len(on_device), 65535):
             part = on_device[at:at + 65535]
-            for i, data in zip(part, self._encode([images[i] for i in part], True)):
+            for i, data in zip(part, self._encode([images[i] for i in part], True, self.entropy == "device")):
                 results[i] = data
         for at in range(0, len(on_host), 65535):
             part = on_host[at:at + 65535]
@@ -257,7 +268,58 @@ class JpegEncoder(object):
                 results[i] = data
         return results
 
-    def _encode(self, images, device):
+    def _buffer(self, name, nbytes, dev):
+        """A device byte buffer of at least nbytes, kept across calls and grown by half as much again when it is too small."""
+        t = self._buffers.get(name)
+        if t is None or t.device != dev or t.numel() < nbytes:
+            t = torch.empty(max(nbytes + nbytes // 2, 256), dtype=torch.uint8, device=dev)
+            self._buffers[name] = t
+        return t
+
+    def _entropy_device(self, images, descs, totals, coef_dev, dev):
+        """The device Huffman stage behind the pixel stage (called under torch.cuda.device(dev)) -> list of bytes."""
+        L = lib()
+        B, ncoef, nfile = len(images), totals[0], totals[2]
+        nstaging = L.danhip_jpeg_encode_scan_staging_bytes(B)
+        staging = torch.empty(nstaging, dtype=torch.uint8, pin_memory=True)
+        prepared = (ctypes.c_int32 * B)()
+        call("danhip_jpeg_encode_scan_prepare", descs, B, ncoef, nfile, ctypes.c_void_p(staging.data_ptr()), nstaging, prepared)
+        staging_dev = staging.to(dev, non_blocking=True)
+        ws = self._buffer("workspace", max(L.danhip_jpeg_encode_scan_workspace_bytes(ctypes.c_void_p(staging.data_ptr())), 16), dev)
+        files = self._buffer("files", nfile, dev)
+        words = self._buffer("words", 12 * B, dev)        # int64 sizes[B], then int32 status[B]
+        launches = ctypes.c_int32(0)
+        call("danhip_jpeg_encode_huffman_batch", ctypes.c_void_p(staging.data_ptr()), ptr(staging_dev), nstaging, descs, B, ptr(coef_dev), ncoef,
+             ptr(files), nfile, ctypes.c_void_p(words.data_ptr()), ctypes.c_void_p(words.data_ptr() + 8 * B), ptr(ws), ws.numel(),
+             ctypes.byref(launches), stream())
+        self.stats["entropy_launches"] += launches.value
+        if launches.value:
+            host_words = words[:12 * B].cpu()             # download 1: sizes and status
+            self.stats["download_bytes"] += 12 * B
+            sizes = host_words[:8 * B].view(torch.int64).tolist()
+            status = host_words[8 * B:].view(torch.int32).tolist()
+        else:                                             # nothing was prepared: every status is the prepare call's
+            sizes, status = [0] * B, list(prepared)
+        good = [i for i in range(B) if status[i] == 0]
+        results = [None] * B
+        if good:
+            packed = torch.cat([files[descs[i].file_offset:descs[i].file_offset + sizes[i]] for i in good]).cpu()     # download 2: the files
+            self.stats["download_bytes"] += packed.numel()
+            data = packed.numpy().tobytes()
+            at = 0
+            for i in good:
+                results[i] = data[at:at + sizes[i]]
+                at += sizes[i]
+        self.stats["entropy_device"] += len(good)
+        retry = [i for i in range(B) if status[i] != 0]
+        if retry:                                         # the host stage has the last word (and raises for a value no baseline code carries)
+            self.stats["entropy_retry"] += len(retry)
+            self.stats["device"] -= len(retry)            # _encode counts them again
+            for i, data in zip(retry, self._encode([images[i] for i in retry], True, False)):
+                results[i] = data
+        return results
+
+    def _encode(self, images, device, entropy_device=False):
         B = len(images)
         for im in images:
             if tuple(im.shape[2:]) != (3,) or len(im.shape) != 3 or str(im.dtype) not in ("torch.uint8", "uint8"):
@@ -285,11 +347,16 @@ class JpegEncoder(object):
                 launches = ctypes.c_int32(0)
                 call("danhip_jpeg_encode_pixels_batch", descs, ptr(table_dev), B, ptr(coef_dev), ncoef, ptr(ws), ws.numel(), ctypes.byref(launches),
                      stream())
+                self.stats["launches"] += launches.value
+                self.stats["device"] += B
+                if entropy_device:
+                    t0 = time.perf_counter()
+                    results = self._entropy_device(images, descs, totals, coef_dev, dev)
+                    self.stats["entropy_seconds"] += time.perf_counter() - t0
+                    return results
                 coef = coef_dev.cpu()                     # the one download
             self.coef = coef
-            self.stats["launches"] += launches.value
             self.stats["download_bytes"] += 2 * ncoef
-            self.stats["device"] += B
         else:
             coef = torch.empty(ncoef, dtype=torch.int16)
             call("danhip_jpeg_encode_pixels_host", descs, B, ctypes.c_void_p(coef.data_ptr()), ncoef)

@@ -1098,6 +1098,65 @@ int danhip_jpeg_encode_host(const uint8_t* rgb, int32_t width, int32_t height, i
                             int64_t* size_out);
 
 /* --------------------------------------------------------------------------------------------------
+ * JPEG encode: Huffman stage on the device (ABI version 16), opt-in: the coefficient buffer danhip_jpeg_encode_pixels_batch leaves on the
+ * device -> the complete files in ONE device buffer, image i's at descs[i].file_offset, plus int64 sizes[B] and int32 status[B] in device
+ * memory.  Every byte of every file is what danhip_jpeg_encode_entropy_batch writes from the same coefficients and descriptors; the scope
+ * is that stage's (4:2:0 and 4:4:4, quality 1 .. 100, the tables of T.81 K.3, one interleaved scan, no restart intervals).
+ *
+ * The host keeps what is O(B) and makes no HIP call: danhip_jpeg_encode_scan_prepare checks the descriptors and packs into one staging
+ * buffer, per image, the scan geometry (MCU counts, blocks in scan order), the offsets into the device workspace (workgroup bit sums and
+ * bit offsets, the unstuffed bit buffer, the FF counts and offsets), the four code / length tables, and the markers in front of the scan
+ * (SOI, APP0, DQT, SOF0, DHT, SOS - a function of (width, height, mode, quality), written by the writer the host stage uses).  An image
+ * whose file bound reaches 1 GiB gets the status DANHIP_JPEG_HOSTONLY and is left to the host stage.
+ *
+ * csrc/jpeg_encode_huffman_exact.hip then runs DANHIP_JPEG_ENCODE_ENTROPY_LAUNCHES launches whatever B, the sizes and the data are; each
+ * is a (workgroup, image) grid or one workgroup per image, and no workgroup waits for another inside a launch:
+ *   1 length   one lane per block in scan order (MCU-interleaved): the DC difference against the component's previous block, the 63 AC
+ *              values in zig-zag order, ZRL for runs of 16 and more, EOB -> the block's bits; a workgroup's sum; the workgroup also zeroes
+ *              its share of the unstuffed buffer
+ *   2 offsets  one workgroup per image: the prefix sum of the workgroup sums as 64-bit bit offsets, the scan's total, status[i]
+ *   3 write    the same walk emits the codes MSB first at the block's bit offset (workgroup prefix sum + the workgroup's offset), whole
+ *              32-bit words OR-ed into the zeroed buffer (atomicOr: the bytes do not depend on timing); the last block pads with 1 bits
+ *   4 count    the FF bytes of every DANHIP_JPEG_ENCODE_STUFF_LANE_BYTES * 256 bytes of the unstuffed scan
+ *   5 finish   one workgroup per image: prefix sum of the counts, the markers copied in front, FF D9 behind, sizes[i]
+ *   6 stuff    every byte to file_offset + marker length + its index + the FF bytes in front of it, 00 behind every FF
+ * Every index comes from the staging buffer, which danhip_jpeg_encode_huffman_batch re-derives from the host descriptors and compares
+ * before a launch.  Coefficient values change counts only: a block counts at most 1658 bits, word indices are checked against the unstuffed
+ * buffer and byte indices against the slot's file_capacity (danhip_jpeg_encode_file_bound covers 1658 bits per block, every byte stuffed).
+ * A value no baseline code carries (a DC difference of more than 11 bits, an AC value of more than 10) sets DANHIP_JPEG_ENC_DEV_RANGE in
+ * status[i], a file that would leave its slot DANHIP_JPEG_ENC_DEV_CAPACITY; sizes[i] is then 0, nothing is written outside image i's slot,
+ * and the caller hands the image to danhip_jpeg_encode_entropy_batch, which has the last word (it refuses such a value).
+ * danhip_jpeg_encode_entropy_emulate_batch runs the same phases through the same routines (csrc/jpeg_encode_huffman.h) on the host with
+ * checked indexing.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_ENCODE_ENTROPY_LAUNCHES 6
+#define DANHIP_JPEG_ENCODE_STUFF_LANE_BYTES 16
+#define DANHIP_JPEG_ENC_DEV_RANGE 1     /* status bits of the device stage: a coefficient without a baseline code */
+#define DANHIP_JPEG_ENC_DEV_CAPACITY 2  /* the file would leave its slot */
+size_t danhip_jpeg_encode_scan_staging_bytes(int32_t B);                            /* 0: B outside 1 .. 65535 */
+/* descs as danhip_jpeg_encode_prepare fills them (src is not read); coef_count / file_bytes: the sizes of the coefficient and file buffers
+ * the launches will be given.  staging: 16-byte aligned, at least danhip_jpeg_encode_scan_staging_bytes(B) bytes.  status_out[i]: 0 =
+ * prepared, or DANHIP_JPEG_HOSTONLY.  DANHIP_EINVAL for a descriptor that does not follow from its (width, height, mode, quality) or
+ * leaves a buffer. */
+int danhip_jpeg_encode_scan_prepare(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, void* staging,
+                                    size_t staging_bytes, int32_t* status_out);
+size_t danhip_jpeg_encode_scan_workspace_bytes(const void* staging);                /* device workspace of the launches; 0: not a staging buffer */
+/* The launches.  staging_host / staging_dev: the same prepared bytes in host and device memory (the host copy is validated against
+ * descs_host, the kernels read the device copy); coef_dev: int16 [coef_count]; files_dev: file_bytes bytes; sizes_dev: int64 [B];
+ * status_dev: int32 [B], 0 = written, DANHIP_JPEG_HOSTONLY as prepared, else DANHIP_JPEG_ENC_DEV_* bits; workspace: 16-byte aligned.
+ * launches (may be NULL) receives the number of kernels launched: DANHIP_JPEG_ENCODE_ENTROPY_LAUNCHES, or 0 when no image is prepared (the
+ * caller then knows every status from the prepare call; nothing is written). */
+int danhip_jpeg_encode_huffman_batch(const void* staging_host, const void* staging_dev, size_t staging_bytes,
+                                     const danhip_jpeg_enc_desc* descs_host, int32_t B, const int16_t* coef_dev, int64_t coef_count,
+                                     uint8_t* files_dev, int64_t file_bytes, int64_t* sizes_dev, int32_t* status_dev, void* workspace,
+                                     size_t workspace_bytes, int32_t* launches, void* stream);
+/* The same phases on the host, everything in host memory.  range_errors (may be NULL) receives the number of indices the checked accessors
+ * refused: 0 unless the encoder is wrong (an out-of-range coefficient is a status, not a refused index). */
+int danhip_jpeg_encode_entropy_emulate_batch(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B,
+                                             const int16_t* coef, int64_t coef_count, uint8_t* files_out, int64_t file_bytes,
+                                             int64_t* sizes_out, int32_t* status_out, int64_t* range_errors);
+
+/* --------------------------------------------------------------------------------------------------
  * Box drawing on uint8 [H,W,3] device images (ABI version 15; csrc/draw_exact.hip): the rectangles of utility/draw_toolbox.py
  * bboxes_draw_on_img for every image of a list in ONE launch.  The rule is this project's own (no OpenCV to compare with):
  *   box i of an image is skipped when classes[i] < 1 or a coordinate is not finite; corners x1, y1, x2, y2 = the floats bbox[0..3]

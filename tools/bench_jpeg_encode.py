@@ -1,12 +1,14 @@
 """The JPEG encoder and the evaluation command, measured (no threshold is set on either; profiles/r17/eval_driver.md keeps the results).
 
-    python tools/bench_jpeg_encode.py [--repeats 7] [--workdir DIR] [--out FILE.json]
+    python tools/bench_jpeg_encode.py [--repeats 7] [--workdir DIR] [--out FILE.json] [--encode_only]
 
 1. Encode of 8 decoded 1024-wide images - the ragged set of tools/bench_eval_ragged.py, smooth content so that the files have a photograph's
    size - from the SAME device tensors: JpegEncoder.encode_batch (device pixel stage, one download of the coefficients, host Huffman threads)
-   against Pillow on the host (one download per image, Image.save at the same quality).  `repeats` timed runs of each in the order
-   device -> pillow and again pillow -> device; a run is bracketed by torch.cuda.synchronize(); the figure is the median, the spread
-   (min .. max) is printed with it.  The bytes of both are compared.
+   against JpegEncoder(entropy="device") (the Huffman stage on the device too: sizes, status words and the files come back, no
+   coefficient) and against Pillow on the host (one download per image, Image.save at the same quality).  2 x `repeats` timed runs of
+   each, the three alternating inside every repeat in a rotating order; a run is bracketed by torch.cuda.synchronize(); the figure is the
+   median, the spread (min .. max) and the bytes each arm downloads are printed with it.  The bytes of all three are compared.
+   profiles/r18/jpeg_encode_entropy.md keeps the device-entropy arm's results.
 2. The command's images/s on a synthetic WIDER tree (2 events x 8 images, 640 x 480, seeded S3FD initialisers as the checkpoint):
    `dan_amd.eval_sfd.main` with --debug_dir, with --debug_dir "" and with --log_every_n_steps 1 (every image drawn and encoded), and
    eval_sfd.detect_encoded alone over the same files - alternating, median of `repeats` runs each."""
@@ -53,6 +55,7 @@ def bench_encode(dev, repeats):
     from dan_amd.dataset.jpeg import JpegEncoder
     imgs = [torch.from_numpy(_smooth(h, WIDTH, k)).to(dev) for k, h in enumerate(HEIGHTS)]
     enc = JpegEncoder(quality=75, threads=8)
+    enc_dev = JpegEncoder(quality=75, threads=8, entropy="device")
 
     def pillow():
         out = []
@@ -61,18 +64,29 @@ def bench_encode(dev, repeats):
             Image.fromarray(im.cpu().numpy()).save(b, "JPEG", quality=75)
             out.append(b.getvalue())
         return out
-    device = lambda: enc.encode_batch(imgs)
-    same = device() == pillow()                                  # also the warm-up of both
-    times = {"device": [], "pillow": []}
-    for order in (("device", "pillow"), ("pillow", "device")):
-        for _ in range(repeats):
-            for name in order:
-                times[name].append(_timed_once(device if name == "device" else pillow))
-    entry = {"bytes_equal": bool(same), "images": len(imgs), "file_bytes": sum(len(d) for d in device()),
-             "device": _stats(times["device"]), "pillow": _stats(times["pillow"])}
+    arms = {"device": lambda: enc.encode_batch(imgs), "device_entropy": lambda: enc_dev.encode_batch(imgs), "pillow": pillow}
+    first = {name: fn() for name, fn in arms.items()}            # also the warm-up of all three
+    same = first["device"] == first["pillow"] == first["device_entropy"]
+    downloads = {}
+    for name, e in (("device", enc), ("device_entropy", enc_dev)):
+        before = e.stats["download_bytes"]
+        arms[name]()
+        downloads[name] = e.stats["download_bytes"] - before
+    downloads["pillow"] = sum(int(im.numel()) for im in imgs)
+    times = {name: [] for name in arms}
+    names = list(arms)
+    for r in range(2 * repeats):                                 # the three arms alternate inside every repeat, the order rotates
+        for k in range(len(names)):
+            name = names[(k + r) % len(names)]
+            times[name].append(_timed_once(arms[name]))
+    entry = {"bytes_equal": bool(same), "images": len(imgs), "file_bytes": sum(len(d) for d in first["device"]), "download_bytes": downloads,
+             "entropy_retry": enc_dev.stats["entropy_retry"]}
+    for name in names:
+        entry[name] = _stats(times[name])
+        print("encode %s: median %.2f ms for %d images (min %.2f, max %.2f), %d bytes downloaded" %
+              (name, entry[name]["median"], len(imgs), entry[name]["min"], entry[name]["max"], downloads[name]))
     entry["pillow_over_device"] = entry["pillow"]["median"] / entry["device"]["median"]
-    for name in ("device", "pillow"):
-        print("encode %s: median %.2f ms for %d images (min %.2f, max %.2f)" % (name, entry[name]["median"], len(imgs), entry[name]["min"], entry[name]["max"]))
+    entry["device_over_device_entropy"] = entry["device"]["median"] / entry["device_entropy"]["median"]
     return entry
 
 
@@ -124,11 +138,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--encode_only", action="store_true", help="part 1 alone")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     result = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "encode": bench_encode(dev, args.repeats)}
-    with tempfile.TemporaryDirectory(dir=args.workdir) as d:
-        result["command"] = bench_command(dev, args.repeats, d)
+    if not args.encode_only:
+        with tempfile.TemporaryDirectory(dir=args.workdir) as d:
+            result["command"] = bench_command(dev, args.repeats, d)
     line = json.dumps(result)
     print(line)
     if args.out:
