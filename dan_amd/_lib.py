@@ -186,6 +186,8 @@ SIGNATURES = {
     "danhip_wider_ap": [P, ctypes.c_size_t, P, I64, I32, I32, I32, P, P, P, P, P, P],
     "danhip_deform_sample_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
     "danhip_deform_sample_bwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
+    "danhip_deform_far_ordered": [P, P, I32, I32, I32, I32, I32, I32, P, ctypes.c_size_t, P],
+    "danhip_deform_far_ordered_emulate": [P, P, P, ctypes.c_int64, I32, I32, I32, I32, I32, I32, P, P],
     "danhip_deform_conv_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
     "danhip_deform_conv_bwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
     "danhip_deform_conv_bwd_with_col": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
@@ -317,6 +319,10 @@ def _load(so_path, act_name):
         L.danhip_deform_conv_workspace_bytes.argtypes = [I32, I32, I32, I32, I32, I32, I32, ctypes.c_int]
         L.danhip_deform_sample_bwd_workspace_bytes.restype = ctypes.c_size_t
         L.danhip_deform_sample_bwd_workspace_bytes.argtypes = [I32, I32, I32, I32]
+        L.danhip_deform_sample_bwd_ordered_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_deform_sample_bwd_ordered_workspace_bytes.argtypes = [I32] * 5
+        L.danhip_deform_conv_bwd_ordered_workspace_bytes.restype = ctypes.c_size_t
+        L.danhip_deform_conv_bwd_ordered_workspace_bytes.argtypes = [I32] * 9
         L.danhip_conv2d_fwd_pool_only.restype = ctypes.c_int
         L.danhip_conv2d_fwd_pool_only.argtypes = [DESC]
         L.danhip_conv2d_fwd_concat2_supported.restype = ctypes.c_int

@@ -531,7 +531,7 @@ __device__ __forceinline__ void deform_bwd_doff_tile_c64_body(const bf16_t* __re
       const int which = (b0 ? 4 : 0) + (b1 ? 2 : 0) + (b2 ? 1 : 0);
       if (live && which < 6) dp[tb * 6 + which] = f2bf(r1);
     }
-    doff_far_corners<R>(farm, live, uo, ud, far_dx, g, n, h_in, w_in, grp, l8);
+    if (far_dx) doff_far_corners<R>(farm, live, uo, ud, far_dx, g, n, h_in, w_in, grp, l8);   // (NULL: deterministic mode, deform_far.hip has them)
   }
 }
 
@@ -756,12 +756,86 @@ extern "C" size_t danhip_deform_sample_bwd_workspace_bytes(int32_t N, int32_t H,
   return ((size_t)N * H * W * C + 64) * sizeof(float);
 }
 
+// deform_far.hip: the ordered far-corner path of deterministic mode
+const char* danhip_deform_far_shape_error(int N, int H, int W, int C, int dg);
+size_t danhip_deform_far_region_bytes(int N, int H, int W, int C, int dg);
+int danhip_launch_deform_far_ordered(const uint16_t* offsets, const uint16_t* dS, float* far_dx, const unsigned* stat, uint32_t* region, int N, int H,
+                                     int W, int C, int dg, int window, int always, hipStream_t s);
+
+extern "C" size_t danhip_deform_sample_bwd_ordered_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t deformable_group) {
+  if (danhip_deform_far_shape_error(N, H, W, C, deformable_group)) return 0;
+  return danhip_deform_sample_bwd_workspace_bytes(N, H, W, C) + danhip_deform_far_region_bytes(N, H, W, C, deformable_group);
+}
+
+// zero the statistic and the count words behind it, count the statistic, run the far path: far_dx = workspace[0 .. N*H*W*C)
+static int deform_far_ordered_run(const uint16_t* offsets, const uint16_t* dS, int N, int H, int W, int C, int dg, int window, int always, float* workspace,
+                                  hipStream_t s) {
+  const long nx = (long)N * H * W * C, pairs = (long)N * H * W * dg * 9;
+  unsigned* stat = reinterpret_cast<unsigned*>(workspace + nx);
+  const int zrc = danhip_zero_async(stat, sizeof(unsigned) * (64 + (size_t)N * H * W * dg), s);
+  if (zrc) return zrc;
+  hipLaunchKernelGGL(deform_far_stat_kernel, dim3(dh_grid_for(pairs, 256, 1024)), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(offsets), pairs, stat);
+  return danhip_launch_deform_far_ordered(offsets, dS, workspace, stat, stat + 64, N, H, W, C, dg, window, always, s);
+}
+
+/* Deterministic mode: 3 x 3, stride 1, dilation 1 (SAME padding of 1), C / deformable_group == 64 alone.  The tile kernels as in default mode,
+ * never the scatter form; the far corners through deform_far.hip instead of float atomics. */
+static int deform_sample_bwd_ordered(const uint16_t* x, const uint16_t* offsets, const uint16_t* dS, uint16_t* dx, uint16_t* d_offsets, int32_t N,
+                                     int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t stride, int32_t dilation, int32_t dg,
+                                     int accumulate, int relu_x, float* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(x && offsets && dS && dx && d_offsets && workspace, DANHIP_EINVAL, "deform_sample_bwd: null pointer");
+  DeformGeom g;
+  int rc = make_geom(&g, N, H, W, C, kh, kw, stride, dilation, dg, "deform_sample_bwd");
+  if (rc) return rc;
+  const char* why = danhip_deform_far_shape_error(N, H, W, C, dg);
+  const int tiles_h = (H + DT_H - 1) / DT_H, tiles_w = (W + DT_W - 1) / DT_W;
+  const long tile_blocks = (long)N * tiles_h * tiles_w * dg;
+  if (!why && !(kh == 3 && kw == 3 && stride == 1 && dilation == 1 && g.pad_t == 1 && g.pad_l == 1)) why = "3 x 3 taps, stride 1, dilation 1 only";
+  if (!why && !(dg <= 9 && tile_blocks < (1l << 31) - 8)) why = "deformable_group <= 9 and fewer than 2^31 tiles";
+  DH_REQUIRE(!why, DANHIP_EINVAL, "deform_sample_bwd: this shape class has no ordered form (option \"deterministic\" is set): %s", why);
+  const int force = danhip_option("deform_bwd_form");
+  DH_REQUIRE(force != 2, DANHIP_EINVAL, "deform_sample_bwd: the scatter form (option \"deform_bwd_form\" = 2) has no ordered form (option \"deterministic\" is set)");
+  DH_REQUIRE(!danhip_option("deform_dx_untiled"), DANHIP_EINVAL, "deform_sample_bwd: option \"deform_dx_untiled\" has no ordered form (option \"deterministic\" is set)");
+  const size_t need = danhip_deform_sample_bwd_ordered_workspace_bytes(N, H, W, C, dg);
+  DH_REQUIRE(workspace_bytes >= need, DANHIP_EWORKSPACE, "deform_sample_bwd: workspace of %zu bytes, deterministic mode needs %zu (danhip_deform_sample_bwd_ordered_workspace_bytes)",
+             workspace_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const long nx = (long)N * H * W * C, pairs = (long)N * H * W * dg * 9;
+  const unsigned* stat = reinterpret_cast<const unsigned*>(workspace + nx);
+  rc = deform_far_ordered_run(offsets, dS, N, H, W, C, dg, force == 3 ? 1 : (force == 1 ? 2 : 0), 0, workspace, s);
+  if (rc) return rc;
+  const BwdGate gate{stat, 0xffffffffu, (unsigned)(pairs / 128), force};         // (never the scatter form; the window as in default mode)
+  const unsigned tgrid = (unsigned)((tile_blocks + 7) / 8 * 8);
+  hipLaunchKernelGGL(deform_bwd_doff_tile_c64_kernel, dim3(tgrid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(offsets),
+                     reinterpret_cast<const bf16_t*>(dS), (float*)nullptr, reinterpret_cast<bf16_t*>(d_offsets), g, gate, tiles_h, tiles_w);
+  hipLaunchKernelGGL(deform_bwd_dx_tile_c64_kernel, dim3(tgrid), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(offsets), reinterpret_cast<const bf16_t*>(dS),
+                     workspace, reinterpret_cast<bf16_t*>(dx), g, accumulate, gate, relu_x ? reinterpret_cast<const bf16_t*>(x) : nullptr, tiles_h, tiles_w);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}
+
+/* Test and measurement hook: the ordered far path alone.  workspace as danhip_deform_sample_bwd takes it in deterministic mode; on return (stream
+ * order) its first N*H*W*C floats are far_dx - zeros where no far corner lands, also when the statistic reports none at all.  window: 0 by the
+ * statistic, 1 / 2 fixed. */
+extern "C" int danhip_deform_far_ordered(const uint16_t* offsets, const uint16_t* dS, int32_t N, int32_t H, int32_t W, int32_t C, int32_t deformable_group,
+                                         int32_t window, float* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(offsets && dS && workspace, DANHIP_EINVAL, "deform_far_ordered: null pointer");
+  const char* why = danhip_deform_far_shape_error(N, H, W, C, deformable_group);
+  DH_REQUIRE(!why, DANHIP_EINVAL, "deform_far_ordered: this shape class has no ordered form: %s", why);
+  DH_REQUIRE(window >= 0 && window <= 2, DANHIP_EINVAL, "deform_far_ordered: window %d (0 by the statistic, 1, 2)", window);
+  const size_t need = danhip_deform_sample_bwd_ordered_workspace_bytes(N, H, W, C, deformable_group);
+  DH_REQUIRE(workspace_bytes >= need, DANHIP_EWORKSPACE, "deform_far_ordered: workspace of %zu bytes, needs %zu", workspace_bytes, need);
+  return deform_far_ordered_run(offsets, dS, N, H, W, C, deformable_group, window, 1, workspace, (hipStream_t)stream);
+}
+
 /* dS [N*Ho*Wo, kh*kw*C] -> d_offsets bf16 [N,Ho,Wo,dg*2*kh*kw] (overwritten) and dx bf16 [N,H,W,C] (=|+= if accumulate).
  * workspace: N*H*W*C + 64 floats (fp32 scatter target + the far-corner statistic), zeroed inside. */
 static int deform_sample_bwd_impl(const uint16_t* x, const uint16_t* offsets, const uint16_t* dS, uint16_t* dx, uint16_t* d_offsets,
                                   int32_t N, int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t stride, int32_t dilation,
                                   int32_t deformable_group, int accumulate, int relu_x, float* workspace, size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "deform_sample_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
+  if (danhip_option("deterministic") != 0)
+    return deform_sample_bwd_ordered(x, offsets, dS, dx, d_offsets, N, H, W, C, kh, kw, stride, dilation, deformable_group, accumulate, relu_x, workspace,
+                                     workspace_bytes, stream);
   const bf16_t* rx = relu_x ? x : nullptr;              // dx *= (x > 0): x is a ReLU output whose producer takes dx as delivered
   DH_REQUIRE(x && offsets && dS && dx && d_offsets && workspace, DANHIP_EINVAL, "deform_sample_bwd: null pointer");
   DH_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && workspace_bytes >= danhip_deform_sample_bwd_workspace_bytes(N, H, W, C), DANHIP_EWORKSPACE,
@@ -856,6 +930,18 @@ static int deform_gemm_desc(danhip_conv_desc* d, int32_t N, int32_t H, int32_t W
   return 0;
 }
 
+/* Deterministic mode's workspace of danhip_deform_conv_bwd*: answered with the option SET (the weight-gradient part is the active mode's).
+ * 0: the shape class has no ordered form. */
+extern "C" size_t danhip_deform_conv_bwd_ordered_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t kh, int32_t kw,
+                                                                 int32_t stride, int32_t deformable_group) {
+  if (Cout <= 0 || kh != 3 || kw != 3 || stride != 1) return 0;
+  const size_t sample = danhip_deform_sample_bwd_ordered_workspace_bytes(N, H, W, C, deformable_group);
+  if (!sample) return 0;
+  danhip_conv_desc d;
+  deform_gemm_desc(&d, N, H, W, C, Cout, kh, kw, stride);
+  return 2 * danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 0) + align256(sample) + align256(danhip_conv2d_bwd_weight_workspace_bytes(&d));
+}
+
 bool danhip_deform_fused_eligible(int N, int H, int W, int C, int Cout, int kh, int kw, int stride, int dg);
 int danhip_launch_deform_fused_fwd(const uint16_t* x, const uint16_t* wf_packed, int kpad, const float* bias, const uint16_t* offsets, uint16_t* y,
                                    uint16_t* col, int N, int H, int W, int C, int Cout, int stride, int dil, int dg, int relu, hipStream_t s);
@@ -900,25 +986,33 @@ static int deform_conv_bwd_impl(const uint16_t* x, const uint16_t* wb_packed, co
                                 int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t kh, int32_t kw, int32_t stride,
                                 int32_t dilation, int32_t deformable_group, int accumulate_dx, int relu_x, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(danhip_option("deterministic") == 0, DANHIP_EINVAL, "deform_conv_bwd: no deterministic form (option \"deterministic\" is set; its float atomics are out of that mode's scope)");
   DH_REQUIRE(x && wb_packed && offsets && dy && dx && d_offsets && dw && workspace, DANHIP_EINVAL, "deform_conv_bwd: null pointer");
-  const size_t need = danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1);
-  DH_REQUIRE(workspace_bytes >= need && need > 0, DANHIP_EWORKSPACE, "deform_conv_bwd: workspace too small");
+  const bool det = danhip_option("deterministic") != 0;
+  danhip_conv_desc d;
+  deform_gemm_desc(&d, N, H, W, C, Cout, kh, kw, stride);
   const size_t colb = danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 0);
+  size_t need = danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1), sample_ws = 0, wgrad_ws = 0;
+  if (det) {        // [col | dcol | side buffer + statistic + ordered region | weight-gradient partial rows]
+    need = danhip_deform_conv_bwd_ordered_workspace_bytes(N, H, W, C, Cout, kh, kw, stride, deformable_group);
+    DH_REQUIRE(need > 0, DANHIP_EINVAL, "deform_conv_bwd: this shape class has no ordered form (option \"deterministic\" is set): 3 x 3 taps, stride 1, dilation 1, C / deformable_group == 64 only");
+    sample_ws = align256(danhip_deform_sample_bwd_ordered_workspace_bytes(N, H, W, C, deformable_group));
+    wgrad_ws = danhip_conv2d_bwd_weight_workspace_bytes(&d);
+  }
+  DH_REQUIRE(workspace_bytes >= need && need > 0, DANHIP_EWORKSPACE, "deform_conv_bwd: workspace of %zu bytes, needs %zu%s", workspace_bytes, need,
+             det ? " (deterministic mode: danhip_deform_conv_bwd_ordered_workspace_bytes)" : "");
   uint16_t* col = (uint16_t*)workspace;
   uint16_t* dcol = (uint16_t*)((char*)workspace + colb);
   float* scatter = (float*)((char*)workspace + 2 * colb);
-  danhip_conv_desc d;
-  deform_gemm_desc(&d, N, H, W, C, Cout, kh, kw, stride);
   int rc = danhip_conv2d_bwd_data(&d, dy, wb_packed, nullptr, dcol, 0, stream);                       // col gradient = W^T dOut (:700-712)
   if (rc) return rc;
   rc = deform_sample_bwd_impl(x, offsets, dcol, dx, d_offsets, N, H, W, C, kh, kw, stride, dilation, deformable_group, accumulate_dx, relu_x, scatter,
-                              workspace_bytes - 2 * colb, stream);                                                                // col2im_coord + col2im (:716-741)
+                              det ? sample_ws : workspace_bytes - 2 * colb, stream);                                              // col2im_coord + col2im (:716-741)
   if (rc) return rc;
   if (!col_saved) {
     rc = danhip_deform_sample_fwd(x, offsets, col, N, H, W, C, kh, kw, stride, dilation, deformable_group, stream);   // re-im2col (:744-748)
     if (rc) return rc;
   }
+  if (det) return danhip_conv2d_bwd_weight_ws(&d, col_saved ? col_saved : col, dy, dw, db, kh * kw * C, (char*)workspace + 2 * colb + sample_ws, wgrad_ws, stream);
   return danhip_conv2d_bwd_weight(&d, col_saved ? col_saved : col, dy, dw, db, kh * kw * C, stream);  // dW += dOut col^T (:750-768)
 }
 

@@ -4,6 +4,7 @@
 // backward forms give the same dOffset because they call the same function, and a change to a seam rule is made in one place.
 #pragma once
 #include "common.h"
+#include "deform_far.h"
 
 // The (dh, dw) pair of one tap, stored as one 32-bit word of the offsets tensor
 struct DeformOffset {
@@ -72,34 +73,8 @@ __device__ __forceinline__ void deform_coord_sum8(const DeformCoordWeights& c, c
   }
 }
 
-// ---- dX: get_gradient_weight (:130-173) + the guards of deformable_col2im_gpu_kernel (:311-326) for one sampling position
-struct CornerSet {
-  int rh[4], rw[4];
-  float wg[4];
-  bool ok[4];
-};
-__device__ __forceinline__ CornerSet corner_set(float inv_h, float inv_w, int H, int W) {
-  CornerSet cs;
-  const bool in = !(inv_h < 0 || inv_h > (float)H || inv_w < 0 || inv_w > (float)W);
-  float ah = fmaxf(inv_h, 0.f), aw = fmaxf(inv_w, 0.f);
-  if (!in) { ah = 0.f; aw = 0.f; }
-  int hl = (int)ah, wl = (int)aw, hh, wh;
-  const bool ch = hl >= H - 1, cw = wl >= W - 1;
-  if (ch) { hh = hl = H - 1; ah = (float)hl; } else hh = hl + 1;
-  if (cw) { wh = wl = W - 1; aw = (float)wl; } else wh = wl + 1;
-  cs.rh[0] = hl; cs.rh[1] = hl; cs.rh[2] = hh; cs.rh[3] = hh;
-  cs.rw[0] = wl; cs.rw[1] = wh; cs.rw[2] = wl; cs.rw[3] = wh;
-  cs.wg[0] = ((float)(hl + 1) - ah) * ((float)(wl + 1) - aw);
-  cs.wg[1] = ((float)(hl + 1) - ah) * (aw + 1.f - (float)wh);
-  cs.wg[2] = (ah + 1.f - (float)hh) * ((float)(wl + 1) - aw);
-  cs.wg[3] = (ah + 1.f - (float)hh) * (aw + 1.f - (float)wh);
-  const bool dup[4] = {false, cw, ch, ch || cw};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    cs.ok[k] = in && !dup[k] && fabsf(inv_h - (float)cs.rh[k]) < 1.f && fabsf(inv_w - (float)cs.rw[k]) < 1.f && cs.rh[k] >= 0 && cs.rh[k] < H &&
-               cs.rw[k] >= 0 && cs.rw[k] < W;
-  return cs;
-}
+// ---- dX: get_gradient_weight (:130-173) + the guards of deformable_col2im_gpu_kernel (:311-326): CornerSet / corner_set live in deform_far.h,
+// which the host emulation of the ordered far-corner path compiles too
 
 // The weight corner_set() gives the corner that IS pixel (h, w), or 0: wg[k] and ok[k] factor into a row part and a column part
 // (dup[1] = cw, dup[2] = ch, dup[3] = ch || cw), so the gather evaluates the two 1-D factors directly.

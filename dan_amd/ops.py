@@ -63,7 +63,8 @@ class OpsContext(object):
                        purpose: a fixed one).  use_context sets libdanhip's option "deterministic" while this context is active; every
                        gradient / loss sum over workgroups then goes through a workspace this module allocates and the library's ordered
                        reduction (include/danhip.h "Deterministic mode") instead of float atomics, and conv1_1's weight gradient is a launch
-                       of its own.  Ops without an ordered form (deformable conv, batch norm, PS-ROI pooling backward) raise.  One rank only.
+                       of its own.  The deformable backward of DAN-Deform's shape class (3 x 3, stride 1, C / group == 64) sums its far corners in key order;
+                       ops without an ordered form (other deformable shapes, batch norm, PS-ROI pooling backward) raise.  One rank only.
                        A trainer passes the flag on to FlatParams.sgd_step (the optimizer's L2 term).
       SPLIT_EVAL       True: convolutions of the fp32 inference path run as split-operand products on the fp16 MFMA (csrc/split_infer.hip;
                        models set it for precision "split"): fp32-accurate boxes at a third of the 16-bit rate instead of a tenth
@@ -121,6 +122,16 @@ def use_context(ctx):
     finally:
         _CTX = prev
         _sync_deterministic(ctx, prev)
+
+
+def deterministic_context(src=None):
+    """A copy of `src` (default: the active context) with OpsContext.deterministic set - what DetectorTrainer(deterministic=True) builds
+    for itself, and the way to ask for the mode where a trainer's flag refuses the model: DANTrainer(DANModel(deform=True), anchors,
+    ops_ctx=ops.deterministic_context())."""
+    src = src if src is not None else _CTX
+    ctx = OpsContext(**{k: getattr(src, k) for k in OpsContext.__slots__ if k != "wgrad"})
+    ctx.deterministic = True
+    return ctx
 
 
 def _sync_deterministic(old, new):
@@ -1960,7 +1971,11 @@ class _DeformSample(torch.autograd.Function):
         N, H, W, C = x.shape
         dx = torch.empty_like(x)
         doff = torch.empty_like(offsets)
-        ws = torch.empty(x.numel() + 64, dtype=torch.float32, device=x.device)      # scatter target + the far-corner statistic
+        if _CTX.deterministic:      # + the ordered far-corner region (records, counts, starts); 0: the shape class has no ordered form
+            nws = int(_lib.lib().danhip_deform_sample_bwd_ordered_workspace_bytes(N, H, W, C, dg))
+            ws = torch.empty(max(nws // 4, x.numel() + 64), dtype=torch.float32, device=x.device)
+        else:
+            ws = torch.empty(x.numel() + 64, dtype=torch.float32, device=x.device)      # scatter target + the far-corner statistic
         call("danhip_deform_sample_bwd", ptr(x), ptr(offsets), ptr(dS.contiguous()), ptr(dx), ptr(doff), N, H, W, C, kh, kw, stride, dilation, dg, 0,
              ptr(ws), ws.numel() * 4, stream())
         return dx, doff, None, None, None, None, None
@@ -2024,6 +2039,8 @@ class _DeformConv(torch.autograd.Function):
         dw, dw_ret = _grad_target(ctx.w_param, (1, 1, kh * kw * C, cout), x.device)       # (a sink: the flat gradient buffer's block)
         doff = torch.empty_like(offsets)
         nws = _lib.lib().danhip_deform_conv_workspace_bytes(N, H, W, C, kh, kw, stride, 1)
+        if _CTX.deterministic:      # + the ordered far-corner region and the weight gradient's partial rows; 0 (the call then raises): no ordered form
+            nws = int(_lib.lib().danhip_deform_conv_bwd_ordered_workspace_bytes(N, H, W, C, cout, kh, kw, stride, dg)) or nws
         ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
         # x's gradient goes straight into its producer's slot - times (x > 0) when x is a ReLU output, added to what other consumers (the
         # offset convolution) delivered - instead of through an autograd tensor the producer would clone, mask and add (three map-sized passes)

@@ -108,7 +108,7 @@ def build_parser(model):
         else:
             p.add_argument("--" + name, type=type(default), default=default, help=text + " (default %r)" % default)
     p.add_argument("--device", default="cuda:0", help="the GPU to train on (default cuda:0)")
-    p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (the trainer refuses models without an ordered form)")
+    p.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (every model of these drivers has an ordered form; dan_deform takes it through ops.deterministic_context())")
     p.add_argument("--decode_entropy", choices=("host", "device"), default="host", help="where the JPEG Huffman stage runs (default host)")
     p.add_argument("--no_checkpoint_checksums", action="store_true",
                    help="write checkpoints without per-tensor CRCs and do not verify the ones that are read (default: both, on the device)")
@@ -192,7 +192,8 @@ class _Setup(object):
             from .preprocessing import dan_preprocessing as P
             from .train_dan import DANModel, DANTrainer, encode_batch_dan
             anchors = AnchorConfig(size, size, device, args.match_threshold, args.neg_threshold, ratios=_dan_ratios())
-            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform")), anchors, routing_seed=seed, **trainer_kw)
+            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform")), anchors, routing_seed=seed,
+                                      **deterministic_route(model, trainer_kw))
             self.preprocess = lambda images, boxes, draws: P.preprocess_batch_for_train(images, boxes, shape, ANCHOR_SCALES, draws=draws)
             self.encode = lambda boxes: encode_batch_dan(anchors, boxes)
         self.model = model
@@ -210,6 +211,18 @@ class _Setup(object):
         else:
             vals = (lr, v["stage1"][0], v["stage1"][1], v["stage2"][0], v["stage2"][1], v["total"], v["l2"], acc)
         return collections.OrderedDict(zip(LOG_KEYS[self.model], vals))
+
+
+def deterministic_route(model, trainer_kw):
+    """The trainer keywords --deterministic turns into.  The trainer's own flag covers the models whose every op had an ordered form when it
+    was introduced; DAN-Deform (the deformable backward's ordered far-corner path) takes the context route instead: the same mode, asked for
+    with ops_ctx=ops.deterministic_context()."""
+    kw = dict(trainer_kw)
+    if model == "dan_deform" and kw.get("deterministic"):
+        from . import ops
+        kw["deterministic"] = False
+        kw["ops_ctx"] = ops.deterministic_context(kw.get("ops_ctx"))
+    return kw
 
 
 def _dan_ratios():

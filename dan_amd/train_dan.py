@@ -19,7 +19,7 @@ def dan_anchor_config(height, width, device):
 class DANModel(object):
     def __init__(self, device="cuda", seed=20180817, deform=False):
         self.vs = VariableStore(device=device, seed=seed)
-        self.deform = bool(deform)                            # (the deformable backward has no deterministic form: DetectorTrainer refuses the flag)
+        self.deform = bool(deform)                            # (DetectorTrainer refuses deterministic=True for it; ops_ctx=ops.deterministic_context() is its spelling of the mode)
         if deform:
             from .net import danet_deform
             self.backbone = danet_deform.VGG16Backbone("channels_last", variables=self.vs)
@@ -102,7 +102,7 @@ class DANTrainer(DetectorTrainer):
     """dan_model_fn (train_dan.py:386-532): stage-1 loss against the encoded anchors, dynamic anchor routing of the decoded
     stage-1 boxes into stage-2 targets (x [20,20,10,10], :452), stage-2 loss; mining keeps at least one negative (:302)."""
 
-    DETERMINISTIC = True          # (the VGG model; the deformable one is refused: tests/test_deterministic_gpu.py holds the two-trainer check)
+    DETERMINISTIC = True          # (the VGG model: tests/test_deterministic_gpu.py; the deformable one through ops.deterministic_context(): tests/test_deterministic_deform_gpu.py)
 
     def __init__(self, model, anchors, routing_seed=20180817, **kw):
         super().__init__(model, **kw)

@@ -104,7 +104,9 @@ class DetectorTrainer(object):
     deterministic=True: the step is bit-reproducible - two trainers built from one seed hold the same bits in weights, momenta and loss terms
     after any number of steps (per library build and CU count; one rank).  The trainer then owns a copy of its ops context with
     OpsContext.deterministic set and runs every step inside it.  Only trainers whose every reduction has an ordered form accept the flag
-    (DETERMINISTIC below); the others raise NotImplementedError("deterministic")."""
+    (DETERMINISTIC below); the others raise NotImplementedError("deterministic").  A model the flag refuses whose ops do have ordered forms -
+    DAN-Deform - is built with ops_ctx=ops.deterministic_context() instead: every step runs inside that context, the optimizer takes its
+    ordered L2 sum, DANHIP_OPT_OVERLAP is ignored and the dynamic loss scale is refused, exactly as under the flag."""
 
     DETERMINISTIC = False
 
@@ -123,14 +125,18 @@ class DetectorTrainer(object):
             if world != 1:
                 raise NotImplementedError("deterministic: one rank only (the all-reduce order is not covered)")
             src = ops_ctx if ops_ctx is not None else ops.context()
-            ops_ctx = ops.OpsContext(**{k: getattr(src, k) for k in ops.OpsContext.__slots__ if k != "wgrad"})
-            ops_ctx.deterministic = True
+            ops_ctx = ops.deterministic_context(src)
         # the ops' steering state this trainer runs under (kernel-form switches, diagnostic sinks, the per-step hooks armed below): the
         # context active at construction unless one is handed in - every step runs inside it (ops.OpsContext)
         self.ops_ctx = ops_ctx if ops_ctx is not None else ops.context()
         # a context handed in explicitly is entered by every step; otherwise a step runs in whatever context is active at CALL time, so
         # `with ops.use_context(...): tr.train_step(...)` steers it as the OpsContext docstring promises
         self._own_ctx = ops_ctx is not None
+        # A context handed in with OpsContext.deterministic set (ops.deterministic_context()) is the other spelling of the mode - the one a
+        # model outside DETERMINISTIC takes, DAN-Deform for one: what the flag switches off below follows it too
+        ordered = self.deterministic or (self._own_ctx and bool(ops_ctx.deterministic))
+        if ordered and world != 1:
+            raise NotImplementedError("deterministic: one rank only (the all-reduce order is not covered)")
         # fp16 build: activation gradients below 6e-8 flush to zero, so the backward pass runs on loss * loss_scale (the factor enters
         # through the loss terms' `scale`: their backward ignores the upstream seed) and the
         # fused optimizer divides the (fp32) weight gradients again; bf16 has fp32's exponent range and needs none
@@ -145,7 +151,7 @@ class DetectorTrainer(object):
         if dynamic_loss_scale:
             self.ls_state = torch.tensor([self.loss_scale, 0.0, float(loss_scale_growth_interval), 0.0], dtype=torch.float32, device=model.vs.device)
             self.loss_scale = 1.0                             # host-side factor of the loss terms; the device scalar carries the scale
-            if self.deterministic:
+            if ordered:
                 raise NotImplementedError("deterministic: the dynamic loss scale's optimizer entry has no ordered L2 sum (pass loss_scale=...)")
         self.world = world
         self.towers = 1                                       # towers of THIS rank inside one step (train_step_towers)
@@ -167,7 +173,7 @@ class DetectorTrainer(object):
         # the persistent convolution kernels leave no CU for the update to hide on, so it only adds launches and HBM traffic mid-backward.
         # With more than one rank the end of the step is exposed to the last all-reduce anyway and the form may pay; nobody has measured it
         # (one-GPU boxes), so the default stays the single pass.
-        self.opt_overlap = (os.environ.get("DANHIP_OPT_OVERLAP", "0") == "1" and not self.deterministic and self.ls_state is None and self.flat.g.is_cuda
+        self.opt_overlap = (os.environ.get("DANHIP_OPT_OVERLAP", "0") == "1" and not ordered and self.ls_state is None and self.flat.g.is_cuda
                             and (not self.buckets.enabled or self.buckets.device_collectives))
         if self.opt_overlap:
             self.buckets.enable_local()

@@ -91,9 +91,46 @@ int danhip_act_dtype(void);   /* DANHIP_BF16 or DANHIP_F16 */
  *   - danhip_conv2d_bwd_data_first_supported answers 0 (callers take danhip_conv2d_bwd_data_bits + danhip_conv2d_bwd_weight_ws);
  *   - danhip_relu_bwd_bias_grad (db != NULL), danhip_l2norm_bwd, danhip_l2norm_bwd_pool_scatter, danhip_detection_loss_fwd and
  *     danhip_sgd_momentum_flat[_dynamic] (l2_out != NULL) return DANHIP_EINVAL: call their _ws forms (declared next to them);
- *   - out of scope, DANHIP_EINVAL: danhip_conv2d_bwd_data_bits_first, danhip_batchnorm_fwd_train, danhip_batchnorm_bwd, danhip_deform_sample_bwd,
- *     danhip_deform_conv_bwd*, danhip_deform_psroi_pool_bwd (their float atomics have no ordered form).
- * With the option at 0 the _ws forms behave exactly as the plain calls (the workspace is ignored). */
+ *   - danhip_deform_sample_bwd and danhip_deform_conv_bwd* run their ordered form for ONE shape class (below) and need its larger workspace;
+ *   - out of scope, DANHIP_EINVAL: danhip_conv2d_bwd_data_bits_first, danhip_batchnorm_fwd_train, danhip_batchnorm_bwd, the deformable backward
+ *     of every other shape class, danhip_deform_psroi_pool_bwd (their float atomics have no ordered form).
+ * With the option at 0 the _ws forms behave exactly as the plain calls (the workspace is ignored).
+ *
+ * Deformable backward in deterministic mode (ABI version 17).  Shape class: 3 x 3 taps, stride 1, dilation 1, SAME padding of 1,
+ * C / deformable_group == 64 - what DAN-Deform uses; any other shape returns DANHIP_EINVAL with a message that says the shape class has no
+ * ordered form.  dOffset and the gather part of dX come from the tile kernels of default mode, which were ordered already (candidates in
+ * ascending index, fixed shuffle trees).  The all-atomics scatter form is never chosen (option "deform_bwd_form" = 2 is DANHIP_EINVAL in
+ * the mode, as is "deform_dx_untiled"); the gather window is +-1 while at most 1 / 128 of the offset pairs leave [-1, 1), else +-2 - the
+ * integer statistic of default mode, a function of the offsets alone ("deform_bwd_form" = 3 / 1 still pins it).  No float atomic runs.
+ * FAR CORNERS (bilinear corners more than R pixels from their tap's nominal position, R = the window) leave through records, not atomics:
+ *   record       one far corner: source row m * 9 + t of dS (m = output pixel, t = tap) and corner index k of corner_set (0..3);
+ *                key = (m * 9 + t) * 4 + k.  Corners that coincide under the high-edge clamp are separate records: k is part of the key.
+ *   destination  (n, h, w, group): the 64 fp32 sums of the side buffer far_dx the corner lands on.
+ * THE ORDER CONTRACT for one far_dx element:  F = ((0 + c_1) + c_2) + ... in fp32, c_i = w_i * dS_i over the destination's far records in
+ * ASCENDING (m, t, k), w = the weight corner_set gives the corner (the weights default mode's atomics add).  Each step is one fused
+ * multiply-add F <- fma(w_i, dS_i, F) in this build.  far_dx is stored plainly (zeros where no record lands) and the dX tile kernel reads
+ * it as before: ONE add onto the gather sum, then the ReLU mask, the accumulate and the 16-bit store.  The result is a function of the
+ * inputs alone - not of the grid size, the CU count or timing.
+ * Mechanism (csrc/deform_far.hip): count per destination (integer atomics), exclusive prefix sum, fill (a segment's order is arbitrary
+ * here), then per destination repeated selection of the smallest key not yet taken - that removes the fill order - and the sum.  Six launches
+ * whatever the offsets are, no host synchronisation: the step stays capturable.  Segments of any length are summed correctly; the selection
+ * costs L^2 / 8 loads for a segment of L records, short segments are the fast case.
+ * Workspace, sized from the shape alone (worst case: four records per (pixel, tap, group), a count and a start word per destination; about
+ * 250 MB at 160 x 160 x 256, batch 16): danhip_deform_sample_bwd_ordered_workspace_bytes = the default workspace + that region, 0 outside the
+ * shape class; danhip_deform_conv_bwd_ordered_workspace_bytes = 2 column buffers + that + the weight gradient's partial rows
+ * (danhip_conv2d_bwd_weight_workspace_bytes of the GEMM: ask with the option SET).  A smaller buffer is DANHIP_EWORKSPACE.  Shapes with
+ * N * H * W * deformable_group * 9 >= 2^30 are refused (32-bit record ids).
+ * danhip_deform_far_ordered runs the far path alone into the workspace's first N*H*W*C floats (zeros where nothing lands; window: 0 by the
+ * statistic, 1, 2) and danhip_deform_far_ordered_emulate is the same computation on the host - the per-record routines are one header
+ * (csrc/deform_far.h) compiled for both sides - with every index checked (*range_errors, NULL allowed; DANHIP_EINVAL when any) and the
+ * sums formed in the contract's order: the two far_dx agree bit for bit.  *records_out (NULL allowed) = the number of far records. */
+size_t danhip_deform_sample_bwd_ordered_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t deformable_group);
+size_t danhip_deform_conv_bwd_ordered_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t kh, int32_t kw, int32_t stride,
+                                                      int32_t deformable_group);
+int danhip_deform_far_ordered(const uint16_t* offsets, const uint16_t* dS, int32_t N, int32_t H, int32_t W, int32_t C, int32_t deformable_group,
+                              int32_t window, float* workspace, size_t workspace_bytes, void* stream);
+int danhip_deform_far_ordered_emulate(const uint16_t* offsets, const uint16_t* dS, float* far_dx, int64_t far_dx_elems, int32_t N, int32_t H, int32_t W,
+                                      int32_t C, int32_t deformable_group, int32_t window, int64_t* records_out, int64_t* range_errors);
 #define DANHIP_ORDERED_REDUCE_SEQ_MAX 64
 int danhip_ordered_reduce_f32(const float* part, int32_t P, int64_t C, float* out, int accumulate, void* stream);
 /* Workspace of the _ws forms of danhip_relu_bwd_bias_grad / danhip_l2norm_bwd / danhip_l2norm_bwd_pool_scatter over M pixels (N*H*W) of C channels:

@@ -1,7 +1,10 @@
 """What deterministic mode costs: the S3FD training step (640 x 640, bf16, batch 16) with the switch off and on, alternating in one process on
 one device, plus the kernel launches the mode adds per step (a count).
 
-    python tools/bench_deterministic.py [--batch 16] [--size 640] [--steps 20] [--rounds 3] [--out profiles/r12/deterministic.md]
+    python tools/bench_deterministic.py [--model sfd|dan_deform] [--batch 16] [--size 640] [--steps 20] [--rounds 3] [--out profiles/r12/deterministic.md]
+
+--model dan_deform times the DAN-Deform step instead (DANTrainer(DANModel(deform=True), anchors) against the same with
+ops_ctx=ops.deterministic_context(): the deformable backward's ordered far-corner path, profiles/r19/deterministic_deform.md).
 
 Two trainers are built from one seed (SFDTrainer(model) and SFDTrainer(model, deterministic=True)); each round times `steps` eager steps of
 one, then of the other (device events around the window, one synchronise at its end).  Launches are counted at the library boundary: every _lib.call of a step by entry point, and for each call of the deterministic step the
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", choices=("sfd", "dan_deform"), default="sfd")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_deterministic: no GPU")
@@ -33,11 +37,19 @@ def main():
     dev = torch.device("cuda:0")
     B, S = a.batch, a.size
     imgs = synthetic.make_images(B, S, S, dev, seed=17)
-    loc_t, cls_t, _ = AnchorConfig(S, S, dev).encode_batch(synthetic.make_gt_boxes(B, S, S, seed=5, max_faces=6))
-    trainers = {"default": SFDTrainer(SFDModel(device=dev, seed=11)), "deterministic": SFDTrainer(SFDModel(device=dev, seed=11), deterministic=True)}
+    if a.model == "sfd":
+        loc_t, cls_t, _ = AnchorConfig(S, S, dev).encode_batch(synthetic.make_gt_boxes(B, S, S, seed=5, max_faces=6))
+        targets = (loc_t, cls_t)
+        trainers = {"default": SFDTrainer(SFDModel(device=dev, seed=11)), "deterministic": SFDTrainer(SFDModel(device=dev, seed=11), deterministic=True)}
+    else:
+        from dan_amd.train_dan import DANModel, DANTrainer, dan_anchor_config, encode_batch_dan
+        anchors = dan_anchor_config(S, S, dev)
+        targets = encode_batch_dan(anchors, synthetic.make_gt_boxes(B, S, S, seed=5, max_faces=6))
+        trainers = {"default": DANTrainer(DANModel(device=dev, seed=11, deform=True), anchors),
+                    "deterministic": DANTrainer(DANModel(device=dev, seed=11, deform=True), anchors, ops_ctx=ops.deterministic_context())}
     for tr in trainers.values():
         for _ in range(a.warmup):
-            tr.train_step(imgs, loc_t, cls_t)
+            tr.train_step(imgs, *targets)
     torch.cuda.synchronize()
     # ---- entry-point calls of one step, by name; for the deterministic step also what each call adds in kernel launches
     L = _lib.lib()
@@ -51,6 +63,8 @@ def main():
             simple[fn] += 1                                   # one ordered reduction
         elif fn == "danhip_relu_bwd_bias_grad_ws" and args[2] is not None:
             simple[fn] += 1
+        elif fn == "danhip_deform_conv_bwd_deliver":
+            simple[fn + " (far corners: count, 3 x scan, fill, sum instead of the lazy zero and the two empty scatter-form launches)"] += 3
         elif fn == "danhip_sgd_momentum_flat_ws":
             simple[fn] += 2                                   # [rows][64] -> 64 -> 1
 
@@ -69,7 +83,7 @@ def main():
         import dan_amd.trainer as trainer_mod
         trainer_mod.call = counting
         try:
-            tr.train_step(imgs, loc_t, cls_t)
+            tr.train_step(imgs, *targets)
         finally:
             _lib.call = ops.call = trainer_mod.call = real_call
         torch.cuda.synchronize()
@@ -93,13 +107,13 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(a.steps):
-                tr.train_step(imgs, loc_t, cls_t)
+                tr.train_step(imgs, *targets)
             e1.record()
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / a.steps)
-    lines = ["# Deterministic mode: cost of the S3FD step (%d x %d, batch %d, %s)" % (S, S, B, _lib.ACT_NAME), "",
-             "`python tools/bench_deterministic.py --batch %d --size %d --steps %d --rounds %d`, one process, alternating windows of %d eager steps." % (
-                 B, S, a.steps, a.rounds, a.steps), "", "| mode | ms / step per round | median | img/s |", "|---|---|---|---|"]
+    lines = ["# Deterministic mode: cost of the %s step (%d x %d, batch %d, %s)" % ({"sfd": "S3FD", "dan_deform": "DAN-Deform"}[a.model], S, S, B, _lib.ACT_NAME), "",
+             "`python tools/bench_deterministic.py --model %s --batch %d --size %d --steps %d --rounds %d`, one process, alternating windows of %d eager steps." % (
+                 a.model, B, S, a.steps, a.rounds, a.steps), "", "| mode | ms / step per round | median | img/s |", "|---|---|---|---|"]
     med = {}
     for name, ts in times.items():
         med[name] = sorted(ts)[len(ts) // 2]
