@@ -90,6 +90,13 @@ def main():
     conv_seconds = time.time() - t0
     n += 1
 
+    # the training input pass, equal to the oracle chain rounded to IEEE half (tests/augment_exact.py: float32 arithmetic in both builds, the
+    # 16-bit convert and the 16-byte store are what this build changes): the palette under every chain, the geometry cases at two output shapes
+    import augment_exact as AE
+    augment_cases = AE.run_fp16_group(dev)
+    assert augment_cases == 2 * len(AE.PALETTE_CHAINS) + 2 * 5 * 2 * len(AE.GEOMETRY_WINDOWS)      # both entry points; flips 0, 1 and 0, 1, 2
+    n += 1
+
     # S3FD forward against the oracle in fp16-storage emulation
     from dan_amd.train_sfd import AnchorConfig, SFDModel
     P = ON.Params(create=True, seed=1234)
@@ -169,7 +176,7 @@ def main():
     assert checked > 100
     n += 1
     print("FP16-OK", n, "groups; DAN-Deform losses", ["%.4f" % t for t in totals], "; hbm_layers group: %d cases in %.0f s" % (len(HL.FP16_IDS), hbm_seconds),
-          "; conv_exact group: %d cases in %.0f s" % (len(conv_cases), conv_seconds))
+          "; conv_exact group: %d cases in %.0f s" % (len(conv_cases), conv_seconds), "; augment_exact group: %d cases" % augment_cases)
 
 
 if __name__ == "__main__":

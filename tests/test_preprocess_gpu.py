@@ -1,11 +1,17 @@
 """On-device training input pipeline (dan_amd/preprocessing) against the oracle restatement (oracle/preprocess.py): with the same
 random draws the two produce the same crop window / boxes / flip, and the fused device pass (colour chain, mean-filled crop,
-legacy bilinear resize, flip, uint8 saturation, means, BGR) reproduces the materialised numpy pipeline."""
+legacy bilinear resize, flip, uint8 saturation, means, BGR) reproduces the materialised numpy pipeline: by equality, no value of the
+oracle's result rounded to the 16-bit type may differ (tests/augment_exact.py says why, and what was measured)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import preprocess as O
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import augment_exact as AE  # noqa: E402
+from oracle import preprocess as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ANCHOR_SCALES = [16., 32., 64., 128., 256., 512.]
@@ -31,12 +37,8 @@ def test_preprocess_for_train_matches_oracle(seed, h, w, n, dev):
     ref_img, ref_boxes, info = O.preprocess_for_train(img, boxes, out_shape, ANCHOR_SCALES, O.Draws(100 + seed))
     got_img, got_boxes = P.preprocess_for_train(torch.from_numpy(img).to(dev), boxes, out_shape, ANCHOR_SCALES, draws=P.Draws(100 + seed))
     assert got_boxes.shape == ref_boxes.shape and np.array_equal(got_boxes, ref_boxes), info
-    g = got_img.float().cpu().numpy()
-    assert g.shape == (out_shape[0], out_shape[1], 8) and np.all(g[..., 3:] == 0)
-    ref16 = torch.from_numpy(ref_img).to(got_img.dtype).float().numpy()                 # the network input is stored in 16 bits
-    diff = np.abs(g[..., :3] - ref16)
-    # identical integer pixel levels except where a float op order differs by an ulp right at a uint8 truncation boundary
-    assert (diff > 0).mean() < 2e-3 and diff.max() <= 1.01, (info, (diff > 0).mean(), diff.max())
+    assert tuple(got_img.shape) == (out_shape[0], out_shape[1], 8)
+    AE.assert_exact(got_img, ref_img, info)                                            # the network input is stored in 16 bits
 
 
 def test_colour_chain_each_op_alone(dev):
@@ -47,10 +49,7 @@ def test_colour_chain_each_op_alone(dev):
                 [("contrast", 0.5), ("hue", 0.1), ("brightness", -0.05), ("saturation", 1.2)], []):
         dist, _ = O.distort_color((img.astype(np.float32) * np.float32(1.0 / 255)).astype(np.float32), ops)
         ref = O.finish(O.resize_bilinear_legacy(O.crop_with_mean_fill(dist, (0, 0, 64, 96)), 64, 96), False)
-        got = P.augment_image(timg, ops, (0, 0, 64, 96), False, (64, 96)).float().cpu().numpy()[..., :3]
-        ref16 = torch.from_numpy(ref).to(torch.bfloat16).float().numpy()
-        d = np.abs(got - ref16)
-        assert (d > 0).mean() < 2e-3 and d.max() <= 1.01, (ops, (d > 0).mean(), d.max())
+        AE.assert_exact(P.augment_image(timg, ops, (0, 0, 64, 96), False, (64, 96)), ref, ops)
 
 
 def test_window_outside_the_image_is_mean_filled_and_flip(dev):
@@ -60,13 +59,12 @@ def test_window_outside_the_image_is_mean_filled_and_flip(dev):
     dist = (img.astype(np.float32) * np.float32(1.0 / 255)).astype(np.float32)
     for flip in (False, True):
         ref = O.finish(O.resize_bilinear_legacy(O.crop_with_mean_fill(dist, win), 80, 80), flip)
-        got = P.augment_image(torch.from_numpy(img).to(dev), [], win, flip, (80, 80)).float().cpu().numpy()[..., :3]
-        ref16 = torch.from_numpy(ref).to(torch.bfloat16).float().numpy()
-        assert np.abs(got - ref16).max() <= 1.01 and (np.abs(got - ref16) > 0).mean() < 2e-3
+        AE.assert_exact(P.augment_image(torch.from_numpy(img).to(dev), [], win, flip, (80, 80)), ref, "flip %s" % flip)
     # far outside: exactly the mean colour -> (B, G, R) - means = trunc(mean*255.5/255) - mean
-    far = P.augment_image(torch.from_numpy(img).to(dev), [], (500, 500, 16, 16), False, (8, 8)).float().cpu().numpy()
+    far16 = P.augment_image(torch.from_numpy(img).to(dev), [], (500, 500, 16, 16), False, (8, 8))
+    far = far16.float().cpu().numpy()
     exp = np.trunc(np.asarray([103.94, 116.78, 123.68], np.float32) / np.float32(255.) * np.float32(255.5)) - np.asarray([103.94, 116.78, 123.68], np.float32)
-    assert np.allclose(far[0, 0, :3], torch.tensor(exp).to(torch.bfloat16).float().numpy())
+    assert np.array_equal(far[..., :3], np.broadcast_to(torch.tensor(exp).to(far16.dtype).float().numpy(), (8, 8, 3)))
 
 
 def test_augmented_image_feeds_the_network(dev):
