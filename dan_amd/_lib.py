@@ -232,6 +232,9 @@ SIGNATURES = {
     "danhip_jpeg_encode_pixels_batch": [P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
     "danhip_jpeg_encode_huffman_batch": [P, P, ctypes.c_size_t, P, I32, P, I64, P, I64, P, P, P, ctypes.c_size_t, P, P],
     "danhip_draw_boxes_u8": [P, P, I32, P, P, I64, I32, P],
+    "danhip_draw_boxes_labels_u8": [P, P, I32, P, P, P, I64, I32, P],
+    "danhip_draw_glyph": [I32, P],
+    "danhip_draw_format_score": [FL, P],
     "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
                                                  ctypes.c_size_t, P],
 }

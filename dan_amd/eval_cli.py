@@ -9,12 +9,13 @@ data_format, num_classes, train_image_size and batch_size (the reference's graph
 there either).  The port's own: --device, --precision, --batch_images (JPEGs read, decoded and detected as one group), --decode_entropy, --encode_entropy,
 --image_list (one `event/name` per line instead of wider_face_split/wider_face_<subset>.mat, which needs scipy), --gt_dir (the directory
 of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat / wider_hard_<subset>.mat: the average precision is
-computed on the device and printed) and --debug_quality.
+computed on the device and printed), --debug_quality and --debug_labels (draw each box's score on a tab above it; off by default).
 
 Per group: the files are read, decoded on the device (dataset.jpeg.JpegDecoder; a stream it refuses takes its Pillow fallback) and
 detected (eval_dan.detect_image_list); ONE download brings (dets, num) to the host for the text files; the evaluator takes the device
-tensors; the debug images of the group are drawn in one launch where the decoder left them (utility.draw_toolbox: rectangles only, the
-score label is not drawn) and encoded in one batch (dataset.jpeg.JpegEncoder: byte for byte Pillow's JPEG at --debug_quality).
+tensors; the debug images of the group are drawn in one launch where the decoder left them (utility.draw_toolbox: rectangles, and with
+--debug_labels the score labels by the module's own rule) and encoded in one batch (dataset.jpeg.JpegEncoder: byte for byte Pillow's JPEG
+at --debug_quality).
 --debug_dir "" writes no images and never touches the encoder."""
 import argparse
 import collections
@@ -76,6 +77,8 @@ def build_parser(model):
     p.add_argument("--image_list", default=None, help="text file with one event/name per line, instead of wider_face_split/wider_face_<subset>.mat")
     p.add_argument("--gt_dir", default=None, help="directory of wider_face_<subset>.mat and wider_{easy,medium,hard}_<subset>.mat: compute and print the AP")
     p.add_argument("--debug_quality", type=int, default=75, help="JPEG quality of the debug images (default 75)")
+    p.add_argument("--debug_labels", action="store_true",
+                   help="draw each box's score ('%%.1f%%%%' of score * 100) in white on a filled tab above it (default: rectangles only)")
     return p
 
 
@@ -234,7 +237,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
                 boxes = [dets[b, :counts[b], :4] for b in drawn]
                 classes = [(dets[b, :counts[b], 4] > DEBUG_SCORE).to(torch.int32) for b in drawn]
                 pictures = draw_toolbox.bboxes_draw_on_img_list([images[b].contiguous() for b in drawn], classes, [dets[b, :counts[b], 4] for b in drawn],
-                                                                boxes, thickness=2)
+                                                                boxes, thickness=2, labels=args.debug_labels)
                 for b, data in zip(drawn, encoder.encode_batch(pictures)):
                     debug_paths.append(os.path.join(args.debug_dir, group[b] + ".jpg"))
                     with open(debug_paths[-1], "wb") as f:

@@ -1202,7 +1202,27 @@ int danhip_jpeg_encode_entropy_emulate_batch(const void* staging, size_t staging
  *   and it is not in the interior x1 + (t+1)/2 <= x <= x2 - (t+1)/2, y1 + (t+1)/2 <= y <= y2 - (t+1)/2 (integer divisions).  For t = 2 the
  *   band is the two pixels x1 - 1, x1 on the left, x2, x2 + 1 on the right, likewise above and below.
  * One colour, so the result does not depend on the order of the boxes; one lane per pixel tests the image's boxes, staged in LDS in
- * chunks; no atomics.  THE SCORE LABEL IS NOT DRAWN (it needs Hershey-font text rendering, which nothing here could check).
+ * chunks; no atomics.  danhip_draw_boxes_u8 draws these rectangles and nothing else.
+ *
+ * The score label (ABI version 18; danhip_draw_boxes_labels_u8, csrc/draw_font.h): the reference's '%.1f%%' % (score * 100) in white on a
+ * filled tab above each box, by this project's own rule (OpenCV's Hershey font and getTextSize are not matched):
+ *   text: v = score * 100 in ONE float32 multiply; tenths = v * 10 rounded to the nearest integer, ties to even, on the exact value
+ *   (computed in double, where the product is exact; v * 10 in float32 would round twice).  The string is the decimal digits of
+ *   tenths / 10, '.', the digit tenths % 10, '%': what printf("%.1f%%", v) prints.  The label is drawn only when 0 <= tenths <= 9999
+ *   (4 to 6 characters; NaN, the infinities, a negative tenths and 1000.0 and above draw the rectangle only); -0.0 and the negatives that
+ *   round to it print as 0.0%, without printf's sign.  A skipped box has no label;
+ *   font: 5 x 7 bitmap glyphs, advance 6: n characters have text_w = 6 n - 1; text_h = 7, baseline = 2;
+ *   tab: (203, 71, 119) for x1 - t/2 <= x <= x1 + text_w and y1 - text_h - t - baseline <= y <= y1 (the reference's arithmetic,
+ *   draw_toolbox.py:60-65, with these metrics);
+ *   text: (255, 255, 255); the bottom glyph row is y = y1 - text_h + baseline, the top one 6 above it; the left column of character k
+ *   is x = x1 + 6 k.  Everything is clipped to the image: a label that leaves the top or the right edge is cut, not moved;
+ *   order: the reference's loop.  Box i paints its band, then its tab, then its text, and box i + 1 paints over all of it: a pixel shows
+ *   what the highest-index box that touches it paints there, and within that box the text beats the tab beats the band.
+ * One lane per pixel walks ALL staged boxes in index order (no early-out) and stores once; the score is formatted once per box.
+ * scores float [n] beside boxes and classes, required when n_boxes > 0; everything else is validated as danhip_draw_boxes_u8 does.
+ * danhip_draw_glyph: the 7 row bytes of glyph `index` (0 - 9 the digits, 10 '.', 11 '%'), top row first, bit 4 the left column.
+ * danhip_draw_format_score (host): the string of a score by the rule above, or "" when no label is drawn - the same inline function the
+ * kernel runs.
  * items: one per image, in host memory (validated, sizes the grid) and in device memory (read by the kernel); boxes float [n,4] and
  * classes int32 [n] of all images back to back, an item names its range.  thickness 1 .. 64.
  * ------------------------------------------------------------------------------------------------ */
@@ -1215,6 +1235,11 @@ typedef struct danhip_draw_item {
 size_t danhip_draw_item_bytes(void);
 int danhip_draw_boxes_u8(const danhip_draw_item* items_host, const danhip_draw_item* items_dev, int32_t n_images, const float* boxes_dev,
                          const int32_t* classes_dev, int64_t n_boxes, int32_t thickness, void* stream);
+int danhip_draw_boxes_labels_u8(const danhip_draw_item* items_host, const danhip_draw_item* items_dev, int32_t n_images,
+                                const float* boxes_dev, const int32_t* classes_dev, const float* scores_dev, int64_t n_boxes,
+                                int32_t thickness, void* stream);
+int danhip_draw_glyph(int32_t index, uint8_t rows_out[7]);       /* 0-9 digits, 10 '.', 11 '%' */
+int danhip_draw_format_score(float score, char out[8]);          /* host: the string, or "" when no label is drawn */
 
 #ifdef __cplusplus
 }
