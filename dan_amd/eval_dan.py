@@ -4,6 +4,7 @@ flip test, multi-scale tests and box voting, with the same function names, argum
 (xmin, ymin, xmax, ymax, score).  The image resize (cv2.resize in the reference) and the voting loop (numpy in the
 reference) are libdanhip kernels; everything stays on the device until write_to_txt."""
 import ctypes
+import itertools
 
 import numpy as np
 import torch
@@ -15,6 +16,7 @@ NMS_THRESHOLD = 0.3          # eval_dan.py:69-70
 MEMORY_LIMIT = 577.0         # :71-72
 MAX_PER_IMAGE = 750          # :73-74
 SELECT_THRESHOLD = 0.01      # :75-76
+FILTER_NONE, FILTER_BIG, FILTER_SMALL = 0, 1, 2          # a pass's size filter (danhip_detect_select's codes): none / max(w, h) > 30 / min(w, h) < 100
 
 
 class Detector(object):
@@ -84,52 +86,111 @@ def detect_face(net, image, shrink, max_per_image=MAX_PER_IMAGE):
     return det[_order_desc(det[:, 4])[:top]]
 
 
-def _keep_big(det):
-    return det[torch.maximum(det[:, 2] - det[:, 0] + 1, det[:, 3] - det[:, 1] + 1) > 30]
+def _mirror_back(det, width):
+    """flip_test's map back (eval_dan.py:191-198) on det fp32 [..., 5]: fp32 arithmetic (w - x) - 1 in a float64 container."""
+    w = torch.tensor(float(width), dtype=torch.float32, device=det.device)
+    det_t = torch.empty(det.shape, dtype=torch.float64, device=det.device)
+    det_t[..., 0] = (w - det[..., 2]) - 1
+    det_t[..., 1] = det[..., 1]
+    det_t[..., 2] = (w - det[..., 0]) - 1
+    det_t[..., 3] = det[..., 3]
+    det_t[..., 4] = det[..., 4]
+    return det_t
 
 
-def _keep_small(det):
-    return det[torch.minimum(det[:, 2] - det[:, 0] + 1, det[:, 3] - det[:, 1] + 1) < 100]
+def flip_test(net, image, shrink, max_per_image=MAX_PER_IMAGE):
+    """eval_dan.py:188-199: detections of the mirrored image mapped back."""
+    return _mirror_back(detect_face(net, image.flip(1).contiguous(), shrink, max_per_image), image.shape[1])
+
+
+def _big_mask(det):
+    return torch.maximum(det[..., 2] - det[..., 0] + 1, det[..., 3] - det[..., 1] + 1) > 30
+
+
+def _small_mask(det):
+    return torch.minimum(det[..., 2] - det[..., 0] + 1, det[..., 3] - det[..., 1] + 1) < 100
+
+
+def _filter_mask(det, filt):
+    """The rows of det [..., 5] a FILTER_* code keeps (eval_dan.py:126,147-148,153,160-170), in det's own precision -> bool [...]."""
+    if filt == FILTER_NONE:
+        return torch.ones(det.shape[:-1], dtype=torch.bool, device=det.device)
+    return _big_mask(det) if filt == FILTER_BIG else _small_mask(det)
+
+
+# ---- the scale plan: which passes an image of a given size gets.  Stated once; the three forms below (per image, B images of one size,
+# images of any sizes) are three ways of walking it.
+def _multi_scale_passes(max_shrink):
+    """multi_scale_test's passes (eval_dan.py:121-148): the st pass, then the bt passes, whose common filter is decided by the bt the
+    doubling loop ends on."""
+    st = 0.5 if max_shrink >= 0.75 else 0.5 * max_shrink
+    bt = min(2, max_shrink) if max_shrink > 1 else (st + max_shrink) / 2
+    bs = [bt]
+    if max_shrink > 2:
+        bt *= 2
+        while bt < max_shrink:
+            bs.append(bt)
+            bt *= 2
+        bs.append(max_shrink)
+    return [(st, 0, FILTER_BIG)] + [(b, 0, FILTER_SMALL if bt > 1 else FILTER_BIG) for b in bs]
+
+
+def _pyramid_passes(max_shrink):
+    """multi_scale_test_pyramid's passes (eval_dan.py:151-175)."""
+    return [(0.25, 0, FILTER_BIG)] + [(st, 0, FILTER_SMALL if st > 1 else FILTER_BIG) for st in (0.75, 1.25, 1.5, 1.75) if st <= max_shrink]
+
+
+def scale_passes(height, width, pyramid=True, memory_limit=MEMORY_LIMIT):
+    """The passes of eval_dan.py:452-459 for an image of this size, in its order: [(scale, mirrored, filter)] (host arithmetic on the
+    size).  The mirrored pass carries no filter."""
+    shrink, max_shrink = get_shrink(height, width, memory_limit)
+    passes = [(shrink, 0, FILTER_NONE), (shrink, 1, FILTER_NONE)] + _multi_scale_passes(max_shrink)      # detect_face, flip_test
+    return passes + _pyramid_passes(max_shrink) if pyramid else passes
+
+
+def _serial_walk(net, image, passes, max_per_image=MAX_PER_IMAGE):
+    """The passes on one image -> their kept rows in the passes' order, one compacted tensor per run of passes that share a filter (the
+    boolean index reads its count on the host: once per run).  Filtering a run's concatenation gives the same rows in the same order as
+    filtering pass by pass and concatenating, whichever of the two the reference does at that place."""
+    out = []
+    for (mirrored, filt), run in itertools.groupby(passes, key=lambda p: p[1:]):
+        dets = [(flip_test if mirrored else detect_face)(net, image, scale, max_per_image) for scale, _, _ in run]
+        det = dets[0] if len(dets) == 1 else torch.cat(dets, dim=0)
+        out.append(det[_filter_mask(det, filt)] if filt else det)
+    return out
 
 
 def multi_scale_test(net, image, max_im_shrink):
     """eval_dan.py:121-148 -> (det_s, det_b)."""
-    st = 0.5 if max_im_shrink >= 0.75 else 0.5 * max_im_shrink
-    det_s = _keep_big(detect_face(net, image, st))
-    bt = min(2, max_im_shrink) if max_im_shrink > 1 else (st + max_im_shrink) / 2
-    det_b = detect_face(net, image, bt)
-    if max_im_shrink > 2:
-        bt *= 2
-        while bt < max_im_shrink:
-            det_b = torch.cat((det_b, detect_face(net, image, bt)), dim=0)
-            bt *= 2
-        det_b = torch.cat((det_b, detect_face(net, image, max_im_shrink)), dim=0)
-    det_b = _keep_small(det_b) if bt > 1 else _keep_big(det_b)
-    return det_s, det_b
+    passes = _multi_scale_passes(max_im_shrink)
+    return _serial_walk(net, image, passes[:1])[0], _serial_walk(net, image, passes[1:])[0]
 
 
 def multi_scale_test_pyramid(net, image, max_shrink):
     """eval_dan.py:151-175."""
-    det_b = _keep_big(detect_face(net, image, 0.25))
-    for st in (0.75, 1.25, 1.5, 1.75):
-        if st <= max_shrink:
-            d = detect_face(net, image, st)
-            d = _keep_small(d) if st > 1 else _keep_big(d)
-            det_b = torch.cat((det_b, d), dim=0)
-    return det_b
+    return torch.cat(_serial_walk(net, image, _pyramid_passes(max_shrink)), dim=0)
 
 
-def flip_test(net, image, shrink):
-    """eval_dan.py:188-199: detections of the mirrored image mapped back (float32 arithmetic, float64 container)."""
-    det_f = detect_face(net, image.flip(1).contiguous(), shrink)
-    w = torch.tensor(float(image.shape[1]), dtype=torch.float32, device=det_f.device)
-    det_t = torch.empty(det_f.shape, dtype=torch.float64, device=det_f.device)
-    det_t[:, 0] = (w - det_f[:, 2]) - 1
-    det_t[:, 1] = det_f[:, 1]
-    det_t[:, 2] = (w - det_f[:, 0]) - 1
-    det_t[:, 3] = det_f[:, 3]
-    det_t[:, 4] = det_f[:, 4]
-    return det_t
+def _vote(packed, counts, nms_threshold, max_per_image):
+    """The library call: packed float64 [B, n, 5] contiguous, each image's first counts[b] rows in voting order, counts int32 [B]
+    -> (out fp32 [B, max_per_image, 5], num int32 [B]) on the device."""
+    B, n = packed.shape[:2]
+    out = torch.empty((B, max_per_image, 5), dtype=torch.float32, device=packed.device)
+    num = torch.empty((B,), dtype=torch.int32, device=packed.device)
+    ws = torch.empty((lib().danhip_bbox_vote_workspace_bytes(B, n),), dtype=torch.uint8, device=packed.device)
+    call("danhip_bbox_vote", ptr(packed), ptr(counts), B, n, float(nms_threshold), int(max_per_image), ptr(out), ptr(num), ptr(ws), ws.numel(), stream())
+    return out, num
+
+
+def _vote_masked(det, valid, nms_threshold, max_per_image):
+    """Box voting over fixed-size blocks: det float64 [B, n, 5], valid bool [B, n] -> (out, num) as _vote; nothing is read on the host.
+    The voting input is the valid rows in descending score order (ties: higher index first, as np.argsort()[::-1]); invalid rows carry
+    -inf and fall behind every real score (scores are softmax outputs >= 0), and the relative index order of the valid rows is the order
+    of the serial concatenation, so ties resolve alike."""
+    key = torch.where(valid, det[..., 4].to(torch.float32), torch.full((), float("-inf"), dtype=torch.float32, device=det.device))
+    order = torch.stack([ops.argsort_desc(key[b].contiguous(), ties_high_index_first=True) for b in range(det.shape[0])])
+    packed = torch.gather(det, 1, order.unsqueeze(2).expand(-1, -1, 5)).contiguous()
+    return _vote(packed, valid.sum(dim=1).to(torch.int32), nms_threshold, max_per_image)
 
 
 def bbox_vote_batch(dets, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
@@ -143,11 +204,7 @@ def bbox_vote_batch(dets, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMA
         d = d.to(torch.float64)
         packed[i, :d.shape[0]] = d[_order_desc(d[:, 4])]
     counts = torch.tensor([d.shape[0] for d in dets], dtype=torch.int32, device=dev)
-    out = torch.empty((B, max_per_image, 5), dtype=torch.float32, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws = torch.empty((lib().danhip_bbox_vote_workspace_bytes(B, nmax),), dtype=torch.uint8, device=dev)
-    call("danhip_bbox_vote", ptr(packed), ptr(counts), B, nmax, float(nms_threshold), int(max_per_image), ptr(out), ptr(num), ptr(ws), ws.numel(),
-         stream())
+    out, num = _vote(packed, counts, nms_threshold, max_per_image)
     n = num.tolist()
     return [out[i, :n[i]] for i in range(B)]
 
@@ -202,10 +259,9 @@ def write_to_txt(f, det, event, im_name, select_threshold=SELECT_THRESHOLD, min_
             f.write('{:.1f} {:.1f} {:.1f} {:.1f} {:.3f}\n'.format(np.floor(xmin[i]), np.floor(ymin[i]), np.ceil(bw[i]), np.ceil(bh[i]), sc[i]))
 
 
-# ---- the same pipeline for B images of ONE size, without a host round trip.  get_shrink and the scale lists of
-# multi_scale_test / multi_scale_test_pyramid depend on the image SIZE only, so every pass of eval_dan.py:452-459 runs as one batched
-# forward; the size filters (eval_dan.py:126,147-148,153,160-170) become validity masks over fixed-size [B, top] blocks instead of
-# boolean compactions (whose output shape the host would have to read), and the voting kernel takes the per-image counts from the device.
+# ---- B images of ONE size, without a host round trip: the plan depends on the image SIZE only, so every pass runs as one batched forward;
+# the size filters become validity masks over fixed-size [B, top] blocks instead of boolean compactions (whose output shape the host would
+# have to read), and the voting kernel takes the per-image counts from the device.
 def resize_images(images, fx, fy):
     B, H, W, C = images.shape
     Wo, Ho = int(np.rint(W * fx)), int(np.rint(H * fy))
@@ -228,112 +284,29 @@ def detect_face_batch(net, images, shrink, max_per_image=MAX_PER_IMAGE):
     return torch.gather(det, 1, order.unsqueeze(2).expand(-1, -1, 5))
 
 
-def _big_mask(det):
-    return torch.maximum(det[..., 2] - det[..., 0] + 1, det[..., 3] - det[..., 1] + 1) > 30
-
-
-def _small_mask(det):
-    return torch.minimum(det[..., 2] - det[..., 0] + 1, det[..., 3] - det[..., 1] + 1) < 100
-
-
-def detect_images(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE):
+def detect_images(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):
     """detect_image for a batch: uint8 [B,H,W,3] -> (dets fp32 [B, max_per_image, 5], num int32 [B]) on the device; rows beyond num[b]
-    are unspecified.  Per image the result equals detect_image(net, images[b], pyramid) whenever the forward passes agree (a batched
+    are unspecified.  Per image the result equals detect_image(net, images[b], ...) whenever the forward passes agree (a batched
     forward may take another split-K plan than a single image: same math, another fp32 summation order)."""
-    B, H, W, _ = images.shape
-    shrink, max_shrink = get_shrink(H, W)
-    parts = []                                             # (det [B, k, 5] float64, valid [B, k])
-    def add(det, mask=None):
-        parts.append((det.to(torch.float64), torch.ones(det.shape[:2], dtype=torch.bool, device=det.device) if mask is None else mask))
-    add(detect_face_batch(net, images, shrink))
-    # flip_test (eval_dan.py:188-199)
-    det_f = detect_face_batch(net, images.flip(2).contiguous(), shrink)
-    w = torch.tensor(float(W), dtype=torch.float32, device=det_f.device)
-    det_t = torch.empty(det_f.shape, dtype=torch.float64, device=det_f.device)
-    det_t[..., 0] = (w - det_f[..., 2]) - 1
-    det_t[..., 1] = det_f[..., 1]
-    det_t[..., 2] = (w - det_f[..., 0]) - 1
-    det_t[..., 3] = det_f[..., 3]
-    det_t[..., 4] = det_f[..., 4]
-    add(det_t)
-    # multi_scale_test (eval_dan.py:121-148)
-    st = 0.5 if max_shrink >= 0.75 else 0.5 * max_shrink
-    d = detect_face_batch(net, images, st)
-    add(d, _big_mask(d))
-    bt = min(2, max_shrink) if max_shrink > 1 else (st + max_shrink) / 2
-    bs = [detect_face_batch(net, images, bt)]
-    if max_shrink > 2:
-        bt *= 2
-        while bt < max_shrink:
-            bs.append(detect_face_batch(net, images, bt))
-            bt *= 2
-        bs.append(detect_face_batch(net, images, max_shrink))
-    for d in bs:
-        add(d, _small_mask(d) if bt > 1 else _big_mask(d))
-    # multi_scale_test_pyramid (eval_dan.py:151-175)
-    if pyramid:
-        d = detect_face_batch(net, images, 0.25)
-        add(d, _big_mask(d))
-        for sc in (0.75, 1.25, 1.5, 1.75):
-            if sc <= max_shrink:
-                d = detect_face_batch(net, images, sc)
-                add(d, _small_mask(d) if sc > 1 else _big_mask(d))
-    det = torch.cat([p[0] for p in parts], dim=1)
-    valid = torch.cat([p[1] for p in parts], dim=1)
-    n = det.shape[1]
-    # voting input: the valid rows in descending score order (ties: higher index first, as np.argsort()[::-1]); invalid rows carry -inf
-    # and fall behind every real score (scores are softmax outputs >= 0), and the relative index order of the valid rows is the order of
-    # the serial concatenation, so ties resolve alike
-    key = torch.where(valid, det[..., 4].to(torch.float32), torch.full((), float("-inf"), dtype=torch.float32, device=det.device))
-    order = torch.stack([ops.argsort_desc(key[b].contiguous(), ties_high_index_first=True) for b in range(B)])
-    packed = torch.gather(det, 1, order.unsqueeze(2).expand(-1, -1, 5)).contiguous()
-    counts = valid.sum(dim=1).to(torch.int32)
-    out = torch.empty((B, max_per_image, 5), dtype=torch.float32, device=det.device)
-    num = torch.empty((B,), dtype=torch.int32, device=det.device)
-    ws = torch.empty((lib().danhip_bbox_vote_workspace_bytes(B, n),), dtype=torch.uint8, device=det.device)
-    call("danhip_bbox_vote", ptr(packed), ptr(counts), B, n, float(nms_threshold), int(max_per_image), ptr(out), ptr(num), ptr(ws), ws.numel(), stream())
-    return out, num
+    H, W = int(images.shape[1]), int(images.shape[2])
+    dets, valid = [], []
+    for scale, mirrored, filt in scale_passes(H, W, pyramid, memory_limit):
+        det = detect_face_batch(net, images.flip(2).contiguous() if mirrored else images, scale, max_per_image)
+        valid.append(_filter_mask(det, filt))
+        dets.append(_mirror_back(det, W) if mirrored else det.to(torch.float64))
+    return _vote_masked(torch.cat(dets, dim=1), torch.cat(valid, dim=1), nms_threshold, max_per_image)
 
 
-def detect_image(net, image, pyramid=True):
+def detect_image(net, image, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):
     """The per-image body of eval_dan.py:452-459 (eval_sfd.py:323-328 without the pyramid pass)."""
-    shrink, max_shrink = get_shrink(image.shape[0], image.shape[1])
-    dets = [detect_face(net, image, shrink), flip_test(net, image, shrink)]
-    dets += list(multi_scale_test(net, image, max_shrink))
-    if pyramid:
-        dets.append(multi_scale_test_pyramid(net, image, max_shrink))
-    return bbox_vote(torch.cat([d.to(torch.float64) for d in dets], dim=0))
+    dets = _serial_walk(net, image, scale_passes(int(image.shape[0]), int(image.shape[1]), pyramid, memory_limit), max_per_image)
+    return bbox_vote(torch.cat([d.to(torch.float64) for d in dets], dim=0), nms_threshold, max_per_image)
 
 
-# ---- the same pipeline for B images of DIFFERENT sizes, without a host round trip.  The forward passes stay per (image, scale); everything
-# around them is size-agnostic: ONE launch makes every resized / mirrored copy of every image (danhip_resize_u8_linear_batch), one library
-# call per pass does detect_face's cut and order, the size filter and flip_test's mirror map into the image's rows of the packed voting
-# buffer (danhip_detect_select: a radix select instead of the arg-sort of all A anchors, no boolean compaction), and ONE voting launch takes
-# the per-image counts from the device.
-FILTER_NONE, FILTER_BIG, FILTER_SMALL = 0, 1, 2          # danhip_detect_select's filter: none / max(w, h) > 30 / min(w, h) < 100
-
-
-def scale_passes(height, width, pyramid=True, memory_limit=MEMORY_LIMIT):
-    """The passes detect_image walks for an image of this size, in its order: [(scale, mirrored, filter)] (host arithmetic on the size)."""
-    shrink, max_shrink = get_shrink(height, width, memory_limit)
-    passes = [(shrink, 0, FILTER_NONE), (shrink, 1, FILTER_NONE)]              # detect_face, flip_test
-    st = 0.5 if max_shrink >= 0.75 else 0.5 * max_shrink                      # multi_scale_test
-    passes.append((st, 0, FILTER_BIG))
-    bt = min(2, max_shrink) if max_shrink > 1 else (st + max_shrink) / 2
-    bs = [bt]
-    if max_shrink > 2:
-        bt *= 2
-        while bt < max_shrink:
-            bs.append(bt)
-            bt *= 2
-        bs.append(max_shrink)
-    passes += [(b, 0, FILTER_SMALL if bt > 1 else FILTER_BIG) for b in bs]
-    if pyramid:                                                               # multi_scale_test_pyramid
-        passes.append((0.25, 0, FILTER_BIG))
-        passes += [(sc, 0, FILTER_SMALL if sc > 1 else FILTER_BIG) for sc in (0.75, 1.25, 1.5, 1.75) if sc <= max_shrink]
-    return passes
-
-
+# ---- images of DIFFERENT sizes, without a host round trip.  The forward passes stay per (image, scale); everything around them is
+# size-agnostic: ONE launch makes every resized / mirrored copy of every image (danhip_resize_u8_linear_batch), one library call per pass does
+# detect_face's cut and order, the size filter and flip_test's mirror map into the image's rows of the packed voting buffer
+# (danhip_detect_select: a radix select instead of the arg-sort of all A anchors, no boolean compaction), and the voting tail is detect_images'.
 def resize_image_batch(images, requests):
     """Every resized / mirrored copy in ONE launch: images = list of contiguous uint8 [H,W,3] device tensors (separate tensors or views into
     one buffer, at any byte offset), requests = [(image index, fx, fy, mirror)] -> list of uint8 [Ho,Wo,3] tensors (views into one buffer),
@@ -380,7 +353,7 @@ def detect_select(bboxes, scores, shrink, top, rows, valid, filter=FILTER_NONE, 
 def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):
     """detect_image for a list of uint8 [H_i,W_i,3] device tensors of ANY sizes (they may be views into one buffer, the JPEG decoder's)
     -> (dets fp32 [B, max_per_image, 5], num int32 [B]) on the device, the layout WiderEvaluator.add takes; rows beyond num[b] are
-    unspecified.  Per image the result equals detect_image(net, images[b], pyramid): the forwards are the same batch-1 calls.  No device
+    unspecified.  Per image the result equals detect_image(net, images[b], ...): the forwards are the same batch-1 calls.  No device
     value is read on the host between the first launch and the return."""
     B = len(images)
     assert B > 0
@@ -408,17 +381,7 @@ def detect_image_list(net, images, pyramid=True, nms_threshold=NMS_THRESHOLD, ma
                 detect_select(bboxes, scores, scale, top, det[i, at:at + top], valid[i, at:at + top], filt,
                               float(images[i].shape[1]) if mirror else None)
             at += max(top, 0)
-    valid = valid.bool()
-    # the voting input as detect_images builds it: valid rows by descending score, ties higher index first; invalid rows carry -inf
-    key = torch.where(valid, det[..., 4].to(torch.float32), torch.full((), float("-inf"), dtype=torch.float32, device=device))
-    order = torch.stack([ops.argsort_desc(key[b].contiguous(), ties_high_index_first=True) for b in range(B)])
-    packed = torch.gather(det, 1, order.unsqueeze(2).expand(-1, -1, 5)).contiguous()
-    counts = valid.sum(dim=1).to(torch.int32)
-    out = torch.empty((B, max_per_image, 5), dtype=torch.float32, device=device)
-    num = torch.empty((B,), dtype=torch.int32, device=device)
-    ws = torch.empty((lib().danhip_bbox_vote_workspace_bytes(B, n),), dtype=torch.uint8, device=device)
-    call("danhip_bbox_vote", ptr(packed), ptr(counts), B, n, float(nms_threshold), int(max_per_image), ptr(out), ptr(num), ptr(ws), ws.numel(), stream())
-    return out, num
+    return _vote_masked(det, valid.bool(), nms_threshold, max_per_image)
 
 
 def detect_encoded(net, datas, decoder, pyramid=True, nms_threshold=NMS_THRESHOLD, max_per_image=MAX_PER_IMAGE, memory_limit=MEMORY_LIMIT):

@@ -1,11 +1,17 @@
 """Test-time pipeline (eval_dan.py:95-297) on the GPU against oracle/evalpipe.py: the image resize is bit-exact, box voting
 has exact cluster membership / scores and float32-rounded float64 means, and the whole multi-scale pipeline — driven by a
 deterministic stand-in for the network so both sides see identical raw detections — matches detection for detection."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import evalpipe as E
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from evalpipe_standin import FakeNet as _FakeBatchNet, fake_net_np as _fake_net_np, fake_net_torch as _fake_net_torch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -67,31 +73,7 @@ def test_bbox_vote_batch_and_empty(dev):
     assert got.shape == ref.shape == (100, 5) and np.array_equal(got[:, 4], ref[:, 4])
 
 
-def _fake_net_np(image):
-    """Deterministic stand-in for sess.run: boxes / scores derived from the image content with integer arithmetic only."""
-    h, w = image.shape[:2]
-    key = (int(image.astype(np.int64).sum()) + 7919 * h + 104729 * w) % (2 ** 31 - 1)
-    rng = np.random.RandomState(key)
-    n = 1500
-    cy, cx = rng.rand(n) * h, rng.rand(n) * w
-    s = np.exp(rng.rand(n) * np.log(40)) * 6
-    face = rng.randint(0, 12, n)                                              # 12 "faces" get many hits -> clusters across scales
-    fy, fx, fs = (np.arange(12) * 37 % 11 + 1) / 12.0 * h, (np.arange(12) * 53 % 11 + 1) / 12.0 * w, (np.arange(12) % 4 + 1) * 0.06 * min(h, w)
-    hit = rng.rand(n) < 0.5
-    cy = np.where(hit, fy[face] + rng.randn(n) * fs[face] * 0.05, cy)
-    cx = np.where(hit, fx[face] + rng.randn(n) * fs[face] * 0.05, cx)
-    s = np.where(hit, fs[face] * (1 + rng.randn(n) * 0.05), s)
-    boxes = np.stack([cy - s / 2, cx - s / 2, cy + s / 2, cx + s / 2], 1).astype(np.float32)
-    scores = np.where(hit, 0.5 + rng.rand(n) * 0.5, rng.rand(n) * 0.3).astype(np.float32)
-    return boxes, scores
-
-
-def _fake_net_torch(image):
-    b, s = _fake_net_np(image.cpu().numpy())
-    return torch.from_numpy(b).to(image.device), torch.from_numpy(s).to(image.device)
-
-
-@pytest.mark.parametrize("h,w", [(240, 320), (683, 1024), (1400, 2000)])
+@pytest.mark.parametrize("h,w", [(240, 320), (683, 1024), (1100, 1500), (1400, 2000)])     # max_shrink 5.21 (capped below) / 1.59 / 0.99 / 0.69: the four branches
 def test_pipeline_matches_oracle_with_identical_raw_detections(h, w, dev):
     from dan_amd import eval_dan as P
     rng = np.random.RandomState(h + w)
@@ -141,17 +123,6 @@ def test_detect_image_real_network_odd_size(model, dev):
     k = int(torch.argmax(s))
     if int((s == s.max()).sum()) == 1:
         assert torch.equal(got[0, :4], torch.stack((b[k, 1], b[k, 0], b[k, 3], b[k, 2])) / torch.tensor(0.5, device=dev))
-
-
-class _FakeBatchNet(object):
-    """The deterministic stand-in as a `net` with the Detector's two entry points: per image, or B images of one size in one call."""
-
-    def __call__(self, image):
-        return _fake_net_torch(image)
-
-    def batch(self, images):
-        outs = [_fake_net_torch(images[b]) for b in range(images.shape[0])]
-        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
 
 
 @pytest.mark.parametrize("h,w,pyramid", [(240, 320, True), (400, 300, False), (683, 1024, True)])

@@ -109,3 +109,32 @@ def test_scale_passes_are_those_detect_image_walks():
             assert [m for _, m, _ in got] == [0, 1] + [0] * (len(got) - 2)
             assert got[0][2] == got[1][2] == P.FILTER_NONE and got[2][2] == P.FILTER_BIG
     assert len(P.scale_passes(120, 160, False)) > 4                          # max_shrink > 2: the loop branch of multi_scale_test
+
+
+FORM_LIMITS = (577, 40000, 80000, 115000, 150000)
+FORM_SIZES = ((120, 160), (96, 136))
+FORM_MAX_SHRINK = {(120, 160): (11.22, 1.37, 0.88, 0.68, 0.56), (96, 136): (13.78, 1.62, 1.13, 0.89, 0.74)}
+
+
+def test_scale_passes_is_origin_flip_and_the_two_pass_lists():
+    """The ten (size, memory_limit) pairs tests/test_evalpipe_forms_gpu.py runs: between them every branch of multi_scale_test's schedule.
+    scale_passes equals the two private pass lists composed by hand, and each branch's list is spelled out once."""
+    from dan_amd import eval_dan as P
+    N, BIG, SMALL = P.FILTER_NONE, P.FILTER_BIG, P.FILTER_SMALL
+    for size in FORM_SIZES:
+        for ml, want in zip(FORM_LIMITS, FORM_MAX_SHRINK[size]):
+            shrink, m = P.get_shrink(size[0], size[1], ml)
+            assert round(m, 2) == want and shrink == min(m, 1), (size, ml, m)
+            head = [(shrink, 0, N), (shrink, 1, N)]
+            assert P.scale_passes(size[0], size[1], False, ml) == head + P._multi_scale_passes(m)
+            assert P.scale_passes(size[0], size[1], True, ml) == head + P._multi_scale_passes(m) + P._pyramid_passes(m)
+    m = P.get_shrink(120, 160, 577)[1]                                       # the loop: 2, 4, 8 and max_shrink itself, all small-filtered
+    assert P._multi_scale_passes(m) == [(0.5, 0, BIG), (2, 0, SMALL), (4, 0, SMALL), (8, 0, SMALL), (m, 0, SMALL)]
+    m = P.get_shrink(120, 160, 40000)[1]                                     # 1 < m <= 2
+    assert P._multi_scale_passes(m) == [(0.5, 0, BIG), (m, 0, SMALL)]
+    m = P.get_shrink(120, 160, 80000)[1]                                     # 0.75 <= m <= 1: bt = (0.5 + m) / 2 <= 1, the BIG filter
+    assert P._multi_scale_passes(m) == [(0.5, 0, BIG), ((0.5 + m) / 2, 0, BIG)] and P.scale_passes(120, 160, True, 80000)[1] == (m, 1, N)
+    m = P.get_shrink(120, 160, 115000)[1]                                    # m < 0.75: st = 0.5 m
+    assert P._multi_scale_passes(m) == [(0.5 * m, 0, BIG), ((0.5 * m + m) / 2, 0, BIG)]
+    assert P._pyramid_passes(0.74) == [(0.25, 0, BIG)] and P._pyramid_passes(0.75) == [(0.25, 0, BIG), (0.75, 0, BIG)]
+    assert P._pyramid_passes(1.62) == [(0.25, 0, BIG), (0.75, 0, BIG), (1.25, 0, SMALL), (1.5, 0, SMALL)]

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import launch_trace  # noqa: E402
+from evalpipe_standin import FakeNet as _FakeNet, fake_net_np as _fake_net_np, traced as _traced  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -105,31 +105,6 @@ def test_batched_resize_equals_resize_image_per_item(dev):
 
 
 # ------------------------------------------------------------------------------------------------- 3. the list pipeline, stand-in net
-def _fake_net_np(image):
-    """Deterministic stand-in for the network (the idiom of tests/test_evalpipe_gpu.py): boxes / scores derived from the image content."""
-    h, w = image.shape[:2]
-    key = (int(image.astype(np.int64).sum()) + 7919 * h + 104729 * w) % (2 ** 31 - 1)
-    rng = np.random.RandomState(key)
-    n = 1500
-    cy, cx = rng.rand(n) * h, rng.rand(n) * w
-    s = np.exp(rng.rand(n) * np.log(40)) * 6
-    face = rng.randint(0, 12, n)
-    fy, fx, fs = (np.arange(12) * 37 % 11 + 1) / 12.0 * h, (np.arange(12) * 53 % 11 + 1) / 12.0 * w, (np.arange(12) % 4 + 1) * 0.06 * min(h, w)
-    hit = rng.rand(n) < 0.5
-    cy = np.where(hit, fy[face] + rng.randn(n) * fs[face] * 0.05, cy)
-    cx = np.where(hit, fx[face] + rng.randn(n) * fs[face] * 0.05, cx)
-    s = np.where(hit, fs[face] * (1 + rng.randn(n) * 0.05), s)
-    boxes = np.stack([cy - s / 2, cx - s / 2, cy + s / 2, cx + s / 2], 1).astype(np.float32)
-    scores = np.where(hit, 0.5 + rng.rand(n) * 0.5, rng.rand(n) * 0.3).astype(np.float32)
-    return boxes, scores
-
-
-class _FakeNet(object):
-    def __call__(self, image):
-        b, s = _fake_net_np(image.cpu().numpy())
-        return torch.from_numpy(b).to(image.device), torch.from_numpy(s).to(image.device)
-
-
 class _CachedNet(object):
     """A stand-in that reads nothing back: its answer depends on the image SIZE only and is built once per size (the warm-up call)."""
 
@@ -203,25 +178,6 @@ def test_no_host_read_between_the_first_launch_and_the_return(dev):
     finally:
         torch.cuda.set_sync_debug_mode("default")
     assert torch.equal(num, warm[1]) and int(num.min()) > 5
-
-
-def _traced(P, fn):
-    """fn() with every library call of eval_dan / ops recorded by tests/launch_trace.py's Recorder AND carried out."""
-    from dan_amd import ops
-    rec = launch_trace.Recorder()
-    real_p, real_o = P.call, ops.call
-
-    def both(real):
-        def call(name, *args):
-            rec.call(name, *args)
-            return real(name, *args)
-        return call
-    P.call, ops.call = both(real_p), both(real_o)
-    try:
-        result = fn()
-    finally:
-        P.call, ops.call = real_p, real_o
-    return result, [e[1] for e in rec.events if e[0] == "call"]
 
 
 def test_one_resize_call_and_one_vote_call_whatever_the_list(dev):
