@@ -21,6 +21,7 @@ F32, BF16 = 0, 1      # BF16 = "the build's 16-bit activation type" in out_dtype
 SPLIT3 = 3            # fp16 build, forward convolutions: the [hi | lo | hi] half-limb layout of csrc/split_infer.hip
 
 
+# ---- struct mirrors: field for field the typedefs of include/danhip.h (tests/test_abi_header_cpu.py compares them with the header)
 class ConvDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("N", "H", "W", "Cin", "Ho", "Wo", "Cout", "kh", "kw", "stride")]
 
@@ -96,148 +97,252 @@ I32 = ctypes.c_int32
 I64 = ctypes.c_int64
 FL = ctypes.c_float
 DESC = ctypes.POINTER(ConvDesc)
+INT = ctypes.c_int
+U32 = ctypes.c_uint32
+U64 = ctypes.c_uint64
+DBL = ctypes.c_double
+SZ = ctypes.c_size_t
+STR = ctypes.c_char_p
+PI32 = ctypes.POINTER(I32)
+PFL = ctypes.POINTER(FL)
+PITCH = ctypes.POINTER(ConvPitch)
+LEVELS = ctypes.POINTER(HeadLevel)
+JINFO = ctypes.POINTER(JpegInfo)
+STATUS = "status"     # return class of the table below: an int that is 0 or a negative DANHIP_E* code (bound as INT, listed in SIGNATURES)
 
-# name -> argtypes (every function returns int status except the two noted below)
-SIGNATURES = {
-    "danhip_conv_packed_dims": [DESC, ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I64)],
-    "danhip_pack_conv_weight": [DESC, P, I32, P, P, P],
-    "danhip_conv2d_fwd_pool": [DESC, P, P, P, P, P, P],
-    "danhip_pack_entry_init": [ctypes.POINTER(PackEntry), DESC, P, I32, P, P, I32, ctypes.POINTER(ctypes.c_int32)],
-    "danhip_pack_conv_weights_batched": [P, I32, I32, P],
-    "danhip_conv2d_fwd": [DESC, P, P, P, P, ctypes.c_int, ctypes.c_int, P, P],
-    "danhip_conv2d_fwd_ws": [DESC, P, P, P, P, ctypes.c_int, ctypes.c_int, P, P, ctypes.c_size_t, P],
-    "danhip_conv2d_fwd_f32": [DESC, P, P, P, P, ctypes.c_int, P, P],
-    "danhip_maxpool2x2_fwd_f32": [P, P, I32, I32, I32, I32, P],
-    "danhip_split_set_range_flag": [P],
-    "danhip_split3_f32": [P, P, I64, I32, I32, ctypes.c_int, I32, P],
-    "danhip_unsplit3_f32": [P, P, I64, I32, I32, P],
-    "danhip_unsplit3_scaled_f32": [P, P, I64, I32, I32, I32, P],
-    "danhip_maxpool2x2_split3": [P, P, I32, I32, I32, I32, P],
-    "danhip_l2norm_split3": [P, P, P, I64, I32, I32, I32, P],
-    "danhip_conv3x3_c3_f32_split3": [P, P, P, P, I32, I32, I32, I32, ctypes.c_int, I32, P],
-    "danhip_conv2d_fwd_split": [DESC, P, P, P, P, ctypes.c_int, ctypes.c_int, I32, P, ctypes.c_size_t, P],
-    "danhip_l2norm_fwd_f32": [P, P, P, I64, I32, P],
-    "danhip_resize_bilinear_add_fwd_f32": [P, P, P, I32, I32, I32, I32, I32, I32, P],
-    "danhip_avgpool2x2s1_same_fwd_f32": [P, P, I32, I32, I32, I32, P],
-    "danhip_deform_sample_fwd_f32": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
-    "danhip_conv2d_bwd_data": [DESC, P, P, P, P, ctypes.c_int, P],
-    "danhip_conv2d_bwd_data_ws": [DESC, P, P, P, P, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_conv2d_bwd_data_bits": [DESC, P, P, P, P, ctypes.c_int, P],
-    "danhip_conv2d_bwd_data_bits_first": [DESC, P, P, P, P, I32, P, P, P],
-    "danhip_relu_bits": [P, P, I64, I32, P],
-    "danhip_conv2d_fwd_relu_bits": [DESC, P, P, P, P, P, P, P, P],
-    "danhip_conv2d_bwd_weight": [DESC, P, P, P, P, I32, P],
-    "danhip_conv2d_bwd_weight_ws": [DESC, P, P, P, P, I32, P, ctypes.c_size_t, P],
-    "danhip_avgpool2x2s1_same_fwd_strided": [P, I32, P, I32, I32, I32, I32, I32, ctypes.c_int, P],
-    "danhip_avgpool2x2s1_same_bwd_strided": [P, I32, P, I32, I32, I32, I32, I32, P],
-    "danhip_add16": [P, P, P, I64, P],
-    "danhip_residual_bwd": [P, P, P, P, P, ctypes.c_int, I64, P],
-    "danhip_conv2d_fwd_strided": [DESC, P, P, P, P, ctypes.c_int, I32, ctypes.POINTER(ConvPitch), P, ctypes.c_size_t, P],
-    "danhip_conv2d_bwd_data_strided": [DESC, P, P, P, P, ctypes.c_int, ctypes.POINTER(ConvPitch), P, ctypes.c_size_t, P],
-    "danhip_conv2d_fwd_concat2": [DESC, P, P, I32, I32, P, P, P, ctypes.c_int, P],
-    "danhip_conv2d_bwd_weight_strided": [DESC, P, P, P, P, I32, ctypes.POINTER(ConvPitch), P, ctypes.c_size_t, P],
-    "danhip_relu_bwd_bias_grad": [P, P, P, I64, I32, P],
-    "danhip_relu_bwd_bias_grad_ws": [P, P, P, I64, I32, P, ctypes.c_size_t, P],
-    "danhip_l2norm_bwd_ws": [P, P, P, P, P, I64, I32, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_l2norm_bwd_pool_scatter_ws": [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_detection_loss_fwd_ws": [P, P, P, P, P, P, P, P, I32, I32, P, ctypes.c_size_t, P],
-    "danhip_sgd_momentum_flat_ws": [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P, ctypes.c_size_t, P],
-    "danhip_ordered_reduce_f32": [P, I32, I64, P, ctypes.c_int, P],
-    "danhip_maxpool2x2_fwd": [P, P, I32, I32, I32, I32, P],
-    "danhip_maxpool2x2_fwd_arg": [P, P, P, I32, I32, I32, I32, P],
-    "danhip_maxpool2x2_bwd_arg": [P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
-    "danhip_conv2d_fwd_pool_arg": [DESC, P, P, P, P, P, P, P],
-    "danhip_conv2d_fwd_relu_bits_arg": [DESC, P, P, P, P, P, P, P, P, P],
-    "danhip_maxpool2x2_bwd": [P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
-    "danhip_l2norm_fwd": [P, P, P, I64, I32, P],
-    "danhip_l2norm_bwd": [P, P, P, P, P, I64, I32, ctypes.c_int, ctypes.c_int, P],
-    "danhip_l2norm_bwd_pool_scatter": [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_int, ctypes.c_int, ctypes.c_int, P],
-    "danhip_preprocess_u8": [P, P, I64, P],
-    "danhip_resize_bilinear_add_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, P],
-    "danhip_resize_bilinear_add_bwd": [P, P, I32, I32, I32, I32, I32, I32, ctypes.c_int, P],
-    "danhip_avgpool2x2s1_same_fwd": [P, P, I32, I32, I32, I32, P],
-    "danhip_avgpool2x2s1_same_bwd": [P, P, P, I32, I32, I32, I32, ctypes.c_int, P],
-    "danhip_slice_deliver": [P, I32, I32, I32, P, I32, P, I32, ctypes.c_int, I64, P],
-    "danhip_batchnorm_fwd_train": [P, P, P, P, P, P, P, P, I64, I32, FL, FL, ctypes.c_int, P, P],
-    "danhip_batchnorm_fwd_infer": [P, P, P, P, P, P, I64, I32, ctypes.c_int, P],
-    "danhip_batchnorm_bwd": [P, P, P, P, P, P, P, P, I64, I32, P],
-    "danhip_dynamic_anchor_routing_eval": [P, P, P, P, I64, I32, I32, I32, I32, I32, P, P, P, ctypes.c_size_t, P],
-    "danhip_dynamic_anchor_routing_train": [P, P, P, P, I64, I32, I32, I32, I32, I32, FL, FL, ctypes.c_uint64, ctypes.c_uint64, P, P, P, P,
-                                            ctypes.c_size_t, P],
-    "danhip_nms": [P, I32, I32, I32, FL, P, P, P],
-    "danhip_argsort_desc_f32": [P, I64, I32, P, P, ctypes.c_size_t, P],
-    "danhip_augment_preprocess": [P, I32, I32, I32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), I32, I32, I32, I32, I32, P, I32, I32,
-                                  P, ctypes.c_size_t, P],
-    "danhip_augment_item_init": [P, P, I32, I32, I32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), I32, I32, I32, I32, I32, I32,
-                                 ctypes.POINTER(ctypes.c_int32)],
-    "danhip_augment_preprocess_batch": [P, I32, I32, P, I32, I32, P, ctypes.c_size_t, P],
-    "danhip_deform_psroi_pool_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P],
-    "danhip_deform_psroi_pool_bwd": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P],
-    "danhip_maxpool3x3s2_same_fwd": [P, P, I32, I32, I32, I32, P],
-    "danhip_maxpool3x3s2_same_bwd": [P, P, P, I32, I32, I32, I32, P],
-    "danhip_resize_u8_linear": [P, I32, I32, P, I32, I32, I32, ctypes.c_double, ctypes.c_double, P],
-    "danhip_bbox_vote": [P, P, I32, I32, ctypes.c_double, I32, P, P, P, ctypes.c_size_t, P],
-    "danhip_resize_item_init": [P, I64, I32, I32, I32, I64, I32, I32, ctypes.c_double, ctypes.c_double, I32, I32, ctypes.POINTER(ctypes.c_int32)],
-    "danhip_resize_u8_linear_batch": [P, P, I32, P, I64, P, I64, P],
-    "danhip_detect_select": [P, P, I32, I32, FL, I32, FL, P, P, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), P],
-    "danhip_wider_quantize": [P, ctypes.c_int, P, P, I32, I32, I32, P, P, I32, I32, P, P],
-    "danhip_wider_score_range": [P, I64, P, P, ctypes.c_size_t, P],
-    "danhip_wider_eval": [P, P, I64, P, P, P, I64, P, I32, I32, I32, I32, ctypes.c_double, P, ctypes.c_size_t, P, P],
-    "danhip_wider_ap": [P, ctypes.c_size_t, P, I64, I32, I32, I32, P, P, P, P, P, P],
-    "danhip_deform_sample_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
-    "danhip_deform_sample_bwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_deform_far_ordered": [P, P, I32, I32, I32, I32, I32, I32, P, ctypes.c_size_t, P],
-    "danhip_deform_far_ordered_emulate": [P, P, P, ctypes.c_int64, I32, I32, I32, I32, I32, I32, P, P],
-    "danhip_deform_conv_fwd": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_deform_conv_bwd": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_deform_conv_bwd_with_col": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_deform_conv_bwd_deliver": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P],
-    "danhip_cast_pad_f32_to_bf16": [P, P, P, I64, I32, I32, P],
-    "danhip_head_split_fwd": [P, P, P, I32, I32, I32, I32, I32, I32, I32, P],
-    "danhip_head_split_bwd": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P],
-    "danhip_heads_split_fwd": [ctypes.POINTER(HeadLevel), I32, P, P, I32, I32, P],
-    "danhip_heads_grad_pad": [ctypes.POINTER(HeadLevel), I32, P, P, I32, I32, P],
-    "danhip_hard_neg_select": [P, P, P, P, P, P, I32, I32, FL, ctypes.c_int, P],
-    "danhip_detection_loss_fwd": [P, P, P, P, P, P, P, P, I32, I32, P],
-    "danhip_detection_loss_bwd": [P, P, P, P, P, P, P, FL, FL, I32, I32, P],
-    "danhip_cls_accuracy": [P, P, P, P, I32, I32, P],
-    "danhip_sgd_momentum_flat": [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P],
-    "danhip_sgd_momentum_flat_dynamic": [P, P, P, P, P, P, I32, I64, FL, FL, P, P, P],
-    "danhip_anchors_generate": [P, P, P, P, P, P, I32, I32, I32, FL, FL, FL, I32, P],
-    "danhip_iou_matrix": [P, P, P, P, P, P, P, I32, I32, P],
-    "danhip_dual_max_match": [P, I32, I32, FL, FL, ctypes.c_int, P, P, P, ctypes.c_size_t, P],
-    "danhip_small_mining_match": [P, I32, I32, FL, FL, FL, I32, FL, P, P, P, ctypes.c_size_t, P],
-    "danhip_encode_anchors": [P, P, P, P, P, P, P, P, P, I32, FL, FL, FL, FL, FL, P],
-    "danhip_decode_anchors": [P, P, P, P, P, P, I32, I32, FL, FL, FL, FL, P],
-    "danhip_face_scores": [P, P, P, FL, I64, P],
-    "danhip_comm_load": [ctypes.c_char_p],
-    "danhip_comm_rccl_version": [ctypes.POINTER(ctypes.c_int)],
-    "danhip_comm_unique_id": [P],
-    "danhip_comm_create": [P, I32, I32, I32, ctypes.POINTER(ctypes.c_void_p)],
-    "danhip_comm_destroy": [P],
-    "danhip_comm_info": [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32)],
-    "danhip_comm_async_error": [P, ctypes.POINTER(I32)],
-    "danhip_comm_abort": [P],
-    "danhip_comm_allreduce_sum": [P, P, I64, ctypes.c_int, P],
-    "danhip_comm_reduce_scatter_sum": [P, P, P, I64, ctypes.c_int, P],
-    "danhip_comm_allgather": [P, P, P, I64, ctypes.c_int, P],
-    "danhip_jpeg_entropy_decode_batch": [P, P, I32, I32, P, I64, P, P],
-    "danhip_jpeg_entropy_decode_batch_ex": [P, P, I32, I32, ctypes.c_uint32, P, I64, P, P],
-    "danhip_jpeg_scan_prepare_batch_ex": [P, P, I32, ctypes.c_uint32, P, ctypes.c_size_t, I64, P, P],
-    "danhip_jpeg_reconstruct_batch": [P, I64, P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
-    "danhip_jpeg_scan_prepare_batch": [P, P, I32, P, ctypes.c_size_t, I64, P, P],
-    "danhip_jpeg_huffman_decode_batch": [P, P, ctypes.c_size_t, I32, P, I64, P, P, P, ctypes.c_size_t, P, P, P],
-    "danhip_jpeg_entropy_emulate_batch": [P, ctypes.c_size_t, I32, P, P, I64, I32, P, P],
-    "danhip_crc32c_batch": [P, I32, P, I32, P, ctypes.c_size_t, P],
-    "danhip_jpeg_encode_pixels_batch": [P, P, I32, P, I64, P, ctypes.c_size_t, P, P],
-    "danhip_jpeg_encode_huffman_batch": [P, P, ctypes.c_size_t, P, I32, P, I64, P, I64, P, P, P, ctypes.c_size_t, P, P],
-    "danhip_draw_boxes_u8": [P, P, I32, P, P, I64, I32, P],
-    "danhip_draw_boxes_labels_u8": [P, P, I32, P, P, P, I64, I32, P],
-    "danhip_draw_glyph": [I32, P],
-    "danhip_draw_format_score": [FL, P],
-    "danhip_encode_anchors_batched": [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P,
-                                                 ctypes.c_size_t, P],
+# name -> (return type, argtypes): ONE line per function include/danhip.h declares, in the header's order.  tests/test_abi_header_cpu.py
+# parses the header and holds every return type, parameter and struct field here to it.
+_TABLE = {
+    # ---- library state
+    "danhip_last_error": (STR, []),
+    "danhip_version": (INT, []),
+    "danhip_set_option": (STATUS, [STR, INT]),
+    "danhip_get_option": (INT, [STR]),
+    "danhip_act_dtype": (INT, []),
+    # ---- deterministic mode
+    "danhip_deform_sample_bwd_ordered_workspace_bytes": (SZ, [I32] * 5),
+    "danhip_deform_conv_bwd_ordered_workspace_bytes": (SZ, [I32] * 9),
+    "danhip_deform_far_ordered": (STATUS, [P, P, I32, I32, I32, I32, I32, I32, P, SZ, P]),
+    "danhip_deform_far_ordered_emulate": (STATUS, [P, P, P, I64, I32, I32, I32, I32, I32, I32, P, P]),
+    "danhip_ordered_reduce_f32": (STATUS, [P, I32, I64, P, INT, P]),
+    "danhip_reduce_workspace_bytes": (SZ, [I64, I32]),
+    "danhip_loss_workspace_bytes": (SZ, []),
+    "danhip_sgd_workspace_bytes": (SZ, []),
+    # ---- dense convolution
+    "danhip_conv_packed_dims": (STATUS, [DESC, INT, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+    "danhip_pack_conv_weight": (STATUS, [DESC, P, I32, P, P, P]),
+    "danhip_pack_entry_init": (STATUS, [ctypes.POINTER(PackEntry), DESC, P, I32, P, P, I32, PI32]),
+    "danhip_pack_conv_weights_batched": (STATUS, [P, I32, I32, P]),
+    "danhip_conv2d_fwd": (STATUS, [DESC, P, P, P, P, INT, INT, P, P]),
+    "danhip_conv2d_fwd_pool": (STATUS, [DESC, P, P, P, P, P, P]),
+    "danhip_conv2d_fwd_pool_arg": (STATUS, [DESC, P, P, P, P, P, P, P]),
+    "danhip_conv2d_fwd_relu_bits_arg": (STATUS, [DESC, P, P, P, P, P, P, P, P, P]),
+    "danhip_conv2d_fwd_pool_only": (INT, [DESC]),                       # 0 / 1
+    "danhip_conv2d_bwd_data": (STATUS, [DESC, P, P, P, P, INT, P]),
+    "danhip_conv2d_workspace_bytes": (SZ, [DESC, INT]),
+    "danhip_conv2d_fwd_ws": (STATUS, [DESC, P, P, P, P, INT, INT, P, P, SZ, P]),
+    "danhip_conv2d_bwd_data_ws": (STATUS, [DESC, P, P, P, P, INT, P, SZ, P]),
+    "danhip_relu_bits": (STATUS, [P, P, I64, I32, P]),
+    "danhip_conv2d_fwd_emits_bits": (INT, [DESC, INT]),                 # 0 / 1
+    "danhip_conv2d_fwd_relu_bits": (STATUS, [DESC, P, P, P, P, P, P, P, P]),
+    "danhip_conv2d_bwd_data_takes_bits": (INT, [DESC]),                 # 0 / 1
+    "danhip_conv2d_bwd_data_first_supported": (INT, [DESC]),            # 0 / 1
+    "danhip_conv2d_bwd_data_bits_first": (STATUS, [DESC, P, P, P, P, I32, P, P, P]),
+    "danhip_conv2d_bwd_data_bits": (STATUS, [DESC, P, P, P, P, INT, P]),
+    "danhip_conv2d_fwd_concat2_supported": (INT, [DESC, I32, I32]),     # 0 / 1
+    "danhip_conv2d_fwd_concat2": (STATUS, [DESC, P, P, I32, I32, P, P, P, INT, P]),
+    "danhip_conv2d_fwd_strided": (STATUS, [DESC, P, P, P, P, INT, I32, PITCH, P, SZ, P]),
+    "danhip_conv2d_bwd_data_strided": (STATUS, [DESC, P, P, P, P, INT, PITCH, P, SZ, P]),
+    "danhip_conv2d_bwd_weight_strided": (STATUS, [DESC, P, P, P, P, I32, PITCH, P, SZ, P]),
+    "danhip_conv2d_bwd_weight": (STATUS, [DESC, P, P, P, P, I32, P]),
+    "danhip_conv2d_bwd_weight_workspace_bytes": (SZ, [DESC]),
+    "danhip_conv2d_bwd_weight_ws": (STATUS, [DESC, P, P, P, P, I32, P, SZ, P]),
+    "danhip_relu_bwd_bias_grad": (STATUS, [P, P, P, I64, I32, P]),
+    "danhip_relu_bwd_bias_grad_ws": (STATUS, [P, P, P, I64, I32, P, SZ, P]),
+    "danhip_conv_kernel_label": (STR, [DESC, INT]),
+    "danhip_conv_wgrad_kernel_label": (STR, [DESC]),
+    "danhip_conv_last_launch_label": (STR, []),
+    # ---- HBM-bound layer kernels
+    "danhip_maxpool2x2_fwd": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_maxpool2x2_bwd": (STATUS, [P, P, P, I32, I32, I32, I32, INT, P]),
+    "danhip_maxpool2x2_fwd_arg": (STATUS, [P, P, P, I32, I32, I32, I32, P]),
+    "danhip_maxpool2x2_bwd_arg": (STATUS, [P, P, P, I32, I32, I32, I32, INT, P]),
+    "danhip_l2norm_fwd": (STATUS, [P, P, P, I64, I32, P]),
+    "danhip_l2norm_bwd": (STATUS, [P, P, P, P, P, I64, I32, INT, INT, P]),
+    "danhip_l2norm_bwd_ws": (STATUS, [P, P, P, P, P, I64, I32, INT, INT, P, SZ, P]),
+    "danhip_l2norm_bwd_pool_scatter": (STATUS, [P, P, P, P, P, P, P, I32, I32, I32, I32, INT, INT, INT, P]),
+    "danhip_l2norm_bwd_pool_scatter_ws": (STATUS, [P, P, P, P, P, P, P, I32, I32, I32, I32, INT, INT, INT, P, SZ, P]),
+    "danhip_resize_bilinear_add_fwd": (STATUS, [P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "danhip_resize_bilinear_add_bwd": (STATUS, [P, P, I32, I32, I32, I32, I32, I32, INT, P]),
+    "danhip_avgpool2x2s1_same_fwd": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_avgpool2x2s1_same_bwd": (STATUS, [P, P, P, I32, I32, I32, I32, INT, P]),
+    "danhip_add16": (STATUS, [P, P, P, I64, P]),
+    "danhip_residual_bwd": (STATUS, [P, P, P, P, P, INT, I64, P]),
+    "danhip_avgpool2x2s1_same_fwd_strided": (STATUS, [P, I32, P, I32, I32, I32, I32, I32, INT, P]),
+    "danhip_avgpool2x2s1_same_bwd_strided": (STATUS, [P, I32, P, I32, I32, I32, I32, I32, P]),
+    "danhip_slice_deliver": (STATUS, [P, I32, I32, I32, P, I32, P, I32, INT, I64, P]),
+    "danhip_batchnorm_fwd_train": (STATUS, [P, P, P, P, P, P, P, P, I64, I32, FL, FL, INT, P, P]),
+    "danhip_batchnorm_fwd_infer": (STATUS, [P, P, P, P, P, P, I64, I32, INT, P]),
+    "danhip_batchnorm_bwd": (STATUS, [P, P, P, P, P, P, P, P, I64, I32, P]),
+    "danhip_preprocess_u8": (STATUS, [P, P, I64, P]),
+    "danhip_cast_pad_f32_to_bf16": (STATUS, [P, P, P, I64, I32, I32, P]),
+    # ---- detection heads, hard-negative mining, losses, optimizer
+    "danhip_head_split_fwd": (STATUS, [P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
+    "danhip_head_split_bwd": (STATUS, [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P]),
+    "danhip_heads_split_fwd": (STATUS, [LEVELS, I32, P, P, I32, I32, P]),
+    "danhip_heads_grad_pad": (STATUS, [LEVELS, I32, P, P, I32, I32, P]),
+    "danhip_hard_neg_select": (STATUS, [P, P, P, P, P, P, I32, I32, FL, INT, P]),
+    "danhip_detection_loss_fwd": (STATUS, [P, P, P, P, P, P, P, P, I32, I32, P]),
+    "danhip_detection_loss_fwd_ws": (STATUS, [P, P, P, P, P, P, P, P, I32, I32, P, SZ, P]),
+    "danhip_detection_loss_bwd": (STATUS, [P, P, P, P, P, P, P, FL, FL, I32, I32, P]),
+    "danhip_cls_accuracy": (STATUS, [P, P, P, P, I32, I32, P]),
+    "danhip_sgd_momentum_flat": (STATUS, [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P]),
+    "danhip_sgd_momentum_flat_ws": (STATUS, [P, P, P, P, P, P, I32, I64, FL, FL, FL, P, P, SZ, P]),
+    "danhip_sgd_momentum_flat_dynamic": (STATUS, [P, P, P, P, P, P, I32, I64, FL, FL, P, P, P]),
+    # ---- anchors and boxes
+    "danhip_anchors_generate": (STATUS, [P, P, P, P, P, P, I32, I32, I32, FL, FL, FL, I32, P]),
+    "danhip_iou_matrix": (STATUS, [P, P, P, P, P, P, P, I32, I32, P]),
+    "danhip_match_workspace_bytes": (SZ, [I32, I32]),
+    "danhip_dual_max_match": (STATUS, [P, I32, I32, FL, FL, INT, P, P, P, SZ, P]),
+    "danhip_small_mining_match": (STATUS, [P, I32, I32, FL, FL, FL, I32, FL, P, P, P, SZ, P]),
+    "danhip_encode_anchors": (STATUS, [P, P, P, P, P, P, P, P, P, I32, FL, FL, FL, FL, FL, P]),
+    "danhip_encode_anchors_batched_workspace_bytes": (SZ, [I32, I32, I32]),
+    "danhip_encode_anchors_batched": (STATUS, [P] * 11 + [I32, I32, I32, I32, I32, FL, FL, FL, I32, FL, FL, FL, FL, FL, FL, P, P, P, P, P, SZ, P]),
+    "danhip_decode_anchors": (STATUS, [P, P, P, P, P, P, I32, I32, FL, FL, FL, FL, P]),
+    "danhip_face_scores": (STATUS, [P, P, P, FL, I64, P]),
+    # ---- deformable convolution
+    "danhip_deform_sample_fwd": (STATUS, [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
+    "danhip_deform_sample_bwd_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "danhip_deform_sample_bwd": (STATUS, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, INT, P, SZ, P]),
+    "danhip_deform_conv_workspace_bytes": (SZ, [I32, I32, I32, I32, I32, I32, I32, INT]),
+    "danhip_deform_conv_fused": (INT, [I32] * 9),                       # 0 / 1
+    "danhip_deform_conv_fwd": (STATUS, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, INT, P, SZ, P]),
+    "danhip_deform_conv_bwd": (STATUS, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, INT, P, SZ, P]),
+    "danhip_deform_conv_bwd_with_col": (STATUS, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, INT, P, SZ, P]),
+    "danhip_deform_conv_bwd_deliver": (STATUS, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, INT, INT, P, SZ, P]),
+    # ---- anchor routing, NMS, arg-sort, PS-ROI pooling, the 3x3 pool
+    "danhip_routing_workspace_bytes": (SZ, [I64, I32, INT]),
+    "danhip_dynamic_anchor_routing_eval": (STATUS, [P, P, P, P, I64, I32, I32, I32, I32, I32, P, P, P, SZ, P]),
+    "danhip_dynamic_anchor_routing_train": (STATUS, [P, P, P, P, I64, I32, I32, I32, I32, I32, FL, FL, U64, U64, P, P, P, P, SZ, P]),
+    "danhip_nms": (STATUS, [P, I32, I32, I32, FL, P, P, P]),
+    "danhip_argsort_workspace_bytes": (SZ, [I64]),
+    "danhip_argsort_desc_f32": (STATUS, [P, I64, I32, P, P, SZ, P]),
+    "danhip_deform_psroi_pool_fwd": (STATUS, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P]),
+    "danhip_deform_psroi_pool_bwd": (STATUS, [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, FL, FL, I32, I32, P]),
+    "danhip_maxpool3x3s2_same_fwd": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_maxpool3x3s2_same_bwd": (STATUS, [P, P, P, I32, I32, I32, I32, P]),
+    # ---- test-time pipeline
+    "danhip_resize_u8_linear": (STATUS, [P, I32, I32, P, I32, I32, I32, DBL, DBL, P]),
+    "danhip_bbox_vote_workspace_bytes": (SZ, [I32, I32]),
+    "danhip_bbox_vote": (STATUS, [P, P, I32, I32, DBL, I32, P, P, P, SZ, P]),
+    # ---- WIDER FACE evaluation
+    "danhip_wider_quantize": (STATUS, [P, INT, P, P, I32, I32, I32, P, P, I32, I32, P, P]),
+    "danhip_wider_score_range_workspace_bytes": (SZ, []),
+    "danhip_wider_score_range": (STATUS, [P, I64, P, P, SZ, P]),
+    "danhip_wider_eval_workspace_bytes": (SZ, [I32, I32, I32]),
+    "danhip_wider_eval": (STATUS, [P, P, I64, P, P, P, I64, P, I32, I32, I32, I32, DBL, P, SZ, P, P]),
+    "danhip_wider_ap": (STATUS, [P, SZ, P, I64, I32, I32, I32, P, P, P, P, P, P]),
+    # ---- training input pipeline
+    "danhip_augment_workspace_bytes": (SZ, []),
+    "danhip_augment_preprocess": (STATUS, [P, I32, I32, I32, PI32, PFL, I32, I32, I32, I32, I32, P, I32, I32, P, SZ, P]),
+    "danhip_augment_item_bytes": (SZ, []),
+    "danhip_augment_item_init": (STATUS, [P, P, I32, I32, I32, PI32, PFL, I32, I32, I32, I32, I32, I32, PI32]),
+    "danhip_augment_batch_workspace_bytes": (SZ, [I32]),
+    "danhip_augment_preprocess_batch": (STATUS, [P, I32, I32, P, I32, I32, P, SZ, P]),
+    # ---- test-time pipeline for images of different sizes
+    "danhip_resize_item_bytes": (SZ, []),
+    "danhip_resize_item_init": (STATUS, [P, I64, I32, I32, I32, I64, I32, I32, DBL, DBL, I32, I32, PI32]),
+    "danhip_resize_u8_linear_batch": (STATUS, [P, P, I32, P, I64, P, I64, P]),
+    "danhip_detect_select_workspace_bytes": (SZ, [I64]),
+    "danhip_detect_select": (STATUS, [P, P, I32, I32, FL, I32, FL, P, P, P, SZ, PI32, P]),
+    # ---- JPEG decode: host entropy stage and the two device launches
+    "danhip_jpeg_inspect": (INT, [P, I64, JINFO]),                      # a reason code (>= 0), not a status
+    "danhip_jpeg_entropy_decode_batch": (STATUS, [P, P, I32, I32, P, I64, P, P]),
+    "danhip_jpeg_workspace_bytes": (SZ, [P, I32]),
+    "danhip_jpeg_output_bytes": (I64, [P, I32]),
+    "danhip_jpeg_reconstruct_batch": (STATUS, [P, I64, P, P, I32, P, I64, P, SZ, P, P]),
+    # ---- JPEG decode: Huffman stage on the device
+    "danhip_jpeg_scan_staging_bytes": (SZ, [P, P, I32]),
+    "danhip_jpeg_scan_prepare_batch": (STATUS, [P, P, I32, P, SZ, I64, P, P]),
+    "danhip_jpeg_scan_device_bytes": (SZ, [P]),
+    "danhip_jpeg_scan_workspace_bytes": (SZ, [P]),
+    "danhip_jpeg_huffman_decode_batch": (STATUS, [P, P, SZ, I32, P, I64, P, P, P, SZ, P, P, P]),
+    "danhip_jpeg_entropy_emulate_batch": (STATUS, [P, SZ, I32, P, P, I64, I32, P, P]),
+    # ---- JPEG decode: progressive streams
+    "danhip_jpeg_inspect_ex": (INT, [P, I64, U32, JINFO]),              # a reason code likewise (DANHIP_EINVAL for unknown flag bits)
+    "danhip_jpeg_entropy_decode_batch_ex": (STATUS, [P, P, I32, I32, U32, P, I64, P, P]),
+    "danhip_jpeg_scan_prepare_batch_ex": (STATUS, [P, P, I32, U32, P, SZ, I64, P, P]),
+    # ---- data-parallel gradient exchange
+    "danhip_comm_load": (STATUS, [STR]),
+    "danhip_comm_rccl_version": (STATUS, [ctypes.POINTER(INT)]),
+    "danhip_comm_unique_id": (STATUS, [P]),
+    "danhip_comm_create": (STATUS, [P, I32, I32, I32, ctypes.POINTER(P)]),
+    "danhip_comm_destroy": (STATUS, [P]),
+    "danhip_comm_info": (STATUS, [P, PI32, PI32, PI32]),
+    "danhip_comm_async_error": (STATUS, [P, PI32]),
+    "danhip_comm_abort": (STATUS, [P]),
+    "danhip_comm_allreduce_sum": (STATUS, [P, P, I64, INT, P]),
+    "danhip_comm_reduce_scatter_sum": (STATUS, [P, P, P, I64, INT, P]),
+    "danhip_comm_allgather": (STATUS, [P, P, P, I64, INT, P]),
+    # ---- split-operand inference
+    "danhip_split_set_range_flag": (STATUS, [P]),
+    "danhip_split3_f32": (STATUS, [P, P, I64, I32, I32, INT, I32, P]),
+    "danhip_unsplit3_f32": (STATUS, [P, P, I64, I32, I32, P]),
+    "danhip_unsplit3_scaled_f32": (STATUS, [P, P, I64, I32, I32, I32, P]),
+    "danhip_maxpool2x2_split3": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_l2norm_split3": (STATUS, [P, P, P, I64, I32, I32, I32, P]),
+    "danhip_conv3x3_c3_f32_split3": (STATUS, [P, P, P, P, I32, I32, I32, I32, INT, I32, P]),
+    "danhip_conv2d_fwd_split": (STATUS, [DESC, P, P, P, P, INT, INT, I32, P, SZ, P]),
+    # ---- fp32 inference path
+    "danhip_conv2d_fwd_f32": (STATUS, [DESC, P, P, P, P, INT, P, P]),
+    "danhip_maxpool2x2_fwd_f32": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_l2norm_fwd_f32": (STATUS, [P, P, P, I64, I32, P]),
+    "danhip_resize_bilinear_add_fwd_f32": (STATUS, [P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "danhip_avgpool2x2s1_same_fwd_f32": (STATUS, [P, P, I32, I32, I32, I32, P]),
+    "danhip_deform_sample_fwd_f32": (STATUS, [P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
+    # ---- CRC-32C (the three host functions make no GPU call)
+    "danhip_crc32c_host": (U32, [P, SZ, U32]),
+    "danhip_crc32c_host_form": (U32, [P, SZ, U32, I32]),
+    "danhip_crc32c_combine": (U32, [U32, U32, U64]),
+    "danhip_crc_segment_bytes": (SZ, []),
+    "danhip_crc32c_chunk_bytes": (I32, []),
+    "danhip_crc32c_group_bytes": (I32, []),
+    "danhip_crc32c_batch_last_launches": (I32, []),
+    "danhip_crc32c_batch_workspace_bytes": (SZ, [I32, U64]),
+    "danhip_crc32c_batch": (STATUS, [P, I32, P, I32, P, SZ, P]),
+    # ---- JPEG encode (csrc/jpeg_encode.cpp: all but danhip_jpeg_encode_pixels_batch make no GPU call)
+    "danhip_jpeg_enc_desc_bytes": (SZ, []),
+    "danhip_jpeg_encode_file_bound": (I64, [I32, I32, I32]),
+    "danhip_jpeg_encode_prepare": (STATUS, [P, P, P, I32, I32, I32, P, P]),
+    "danhip_jpeg_encode_pixels_batch": (STATUS, [P, P, I32, P, I64, P, SZ, P, P]),
+    "danhip_jpeg_encode_pixels_host": (STATUS, [P, I32, P, I64]),
+    "danhip_jpeg_encode_entropy_batch": (STATUS, [P, I64, P, I32, I32, P, I64, P]),
+    "danhip_jpeg_encode_host": (STATUS, [P, I32, I32, I32, I32, P, I64, P]),
+    # ---- JPEG encode: Huffman stage on the device
+    "danhip_jpeg_encode_scan_staging_bytes": (SZ, [I32]),
+    "danhip_jpeg_encode_scan_prepare": (STATUS, [P, I32, I64, I64, P, SZ, P]),
+    "danhip_jpeg_encode_scan_workspace_bytes": (SZ, [P]),
+    "danhip_jpeg_encode_huffman_batch": (STATUS, [P, P, SZ, P, I32, P, I64, P, I64, P, P, P, SZ, P, P]),
+    "danhip_jpeg_encode_entropy_emulate_batch": (STATUS, [P, SZ, P, I32, P, I64, P, I64, P, P, P]),
+    # ---- box drawing
+    "danhip_draw_item_bytes": (SZ, []),
+    "danhip_draw_boxes_u8": (STATUS, [P, P, I32, P, P, I64, I32, P]),
+    "danhip_draw_boxes_labels_u8": (STATUS, [P, P, I32, P, P, P, I64, I32, P]),
+    "danhip_draw_glyph": (STATUS, [I32, P]),
+    "danhip_draw_format_score": (STATUS, [FL, P]),
 }
+PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
+SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for
+
+
+def bind(handle, names=None):
+    """Sets restype and argtypes from PROTOTYPES on a ctypes.CDLL handle: of every function, or of `names` alone (a handle of the other
+    build, a stand-in library, another commit's build)."""
+    for name in PROTOTYPES if names is None else names:
+        fn = getattr(handle, name)          # AttributeError if the export is missing
+        fn.restype, fn.argtypes = PROTOTYPES[name]
+    return handle
+
 
 _lib = None
 
@@ -275,131 +380,12 @@ def call_f16(name, *args):
 
 
 def _load(so_path, act_name):
-    if True:
-        if not os.path.exists(so_path):
-            raise DanhipError("libdanhip.so not found at %s — run `python -m dan_amd.build` (there is no fallback path)" % so_path)
-        L = ctypes.CDLL(so_path)
-        L.danhip_last_error.restype = ctypes.c_char_p
-        L.danhip_last_error.argtypes = []
-        L.danhip_version.restype = ctypes.c_int
-        L.danhip_act_dtype.restype = ctypes.c_int
-        if L.danhip_act_dtype() != (2 if act_name == "fp16" else 1):
-            raise DanhipError("%s was built for another activation dtype than %s" % (so_path, act_name))
-        L.danhip_match_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_conv_kernel_label.restype = ctypes.c_char_p
-        L.danhip_conv_kernel_label.argtypes = [DESC, ctypes.c_int]
-        L.danhip_conv_wgrad_kernel_label.restype = ctypes.c_char_p
-        L.danhip_conv_wgrad_kernel_label.argtypes = [DESC]
-        L.danhip_conv_last_launch_label.restype = ctypes.c_char_p
-        L.danhip_conv_last_launch_label.argtypes = []
-        L.danhip_match_workspace_bytes.argtypes = [I32, I32]
-        L.danhip_encode_anchors_batched_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_encode_anchors_batched_workspace_bytes.argtypes = [I32, I32, I32]
-        L.danhip_routing_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_routing_workspace_bytes.argtypes = [I64, I32, ctypes.c_int]
-        L.danhip_bbox_vote_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_augment_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_argsort_workspace_bytes.argtypes = [I64]
-        L.danhip_argsort_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_augment_workspace_bytes.argtypes = []
-        L.danhip_augment_item_bytes.restype = ctypes.c_size_t
-        L.danhip_augment_item_bytes.argtypes = []
-        L.danhip_augment_batch_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_augment_batch_workspace_bytes.argtypes = [I32]
-        L.danhip_set_option.restype = ctypes.c_int
-        L.danhip_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
-        L.danhip_get_option.restype = ctypes.c_int
-        L.danhip_get_option.argtypes = [ctypes.c_char_p]
-        L.danhip_conv2d_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_conv2d_workspace_bytes.argtypes = [DESC, ctypes.c_int]
-        L.danhip_conv2d_bwd_weight_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_conv2d_bwd_weight_workspace_bytes.argtypes = [DESC]
-        for fn in (L.danhip_loss_workspace_bytes, L.danhip_sgd_workspace_bytes):
-            fn.restype, fn.argtypes = ctypes.c_size_t, []
-        L.danhip_reduce_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_reduce_workspace_bytes.argtypes = [I64, I32]
-        L.danhip_deform_conv_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_deform_conv_workspace_bytes.argtypes = [I32, I32, I32, I32, I32, I32, I32, ctypes.c_int]
-        L.danhip_deform_sample_bwd_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_deform_sample_bwd_workspace_bytes.argtypes = [I32, I32, I32, I32]
-        L.danhip_deform_sample_bwd_ordered_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_deform_sample_bwd_ordered_workspace_bytes.argtypes = [I32] * 5
-        L.danhip_deform_conv_bwd_ordered_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_deform_conv_bwd_ordered_workspace_bytes.argtypes = [I32] * 9
-        L.danhip_conv2d_fwd_pool_only.restype = ctypes.c_int
-        L.danhip_conv2d_fwd_pool_only.argtypes = [DESC]
-        L.danhip_conv2d_fwd_concat2_supported.restype = ctypes.c_int
-        L.danhip_conv2d_fwd_concat2_supported.argtypes = [DESC, I32, I32]
-        L.danhip_conv2d_fwd_emits_bits.restype = ctypes.c_int
-        L.danhip_conv2d_fwd_emits_bits.argtypes = [DESC, ctypes.c_int]
-        L.danhip_conv2d_bwd_data_takes_bits.restype = ctypes.c_int
-        L.danhip_conv2d_bwd_data_takes_bits.argtypes = [DESC]
-        L.danhip_conv2d_bwd_data_first_supported.restype = ctypes.c_int
-        L.danhip_conv2d_bwd_data_first_supported.argtypes = [DESC]
-        L.danhip_deform_conv_fused.restype = ctypes.c_int
-        L.danhip_deform_conv_fused.argtypes = [I32] * 9
-        L.danhip_bbox_vote_workspace_bytes.argtypes = [I32, I32]
-        L.danhip_resize_item_bytes.restype = ctypes.c_size_t
-        L.danhip_resize_item_bytes.argtypes = []
-        L.danhip_detect_select_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_detect_select_workspace_bytes.argtypes = [I64]
-        L.danhip_wider_score_range_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_wider_score_range_workspace_bytes.argtypes = []
-        L.danhip_wider_eval_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_wider_eval_workspace_bytes.argtypes = [I32, I32, I32]
-        L.danhip_jpeg_inspect.restype = ctypes.c_int           # a reason code (>= 0), not a status
-        L.danhip_jpeg_inspect.argtypes = [P, I64, ctypes.POINTER(JpegInfo)]
-        L.danhip_jpeg_inspect_ex.restype = ctypes.c_int        # likewise (DANHIP_EINVAL for unknown flag bits)
-        L.danhip_jpeg_inspect_ex.argtypes = [P, I64, ctypes.c_uint32, ctypes.POINTER(JpegInfo)]
-        L.danhip_jpeg_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_jpeg_workspace_bytes.argtypes = [P, I32]
-        L.danhip_jpeg_output_bytes.restype = I64
-        L.danhip_jpeg_output_bytes.argtypes = [P, I32]
-        L.danhip_jpeg_scan_staging_bytes.restype = ctypes.c_size_t
-        L.danhip_jpeg_scan_staging_bytes.argtypes = [P, P, I32]
-        L.danhip_jpeg_scan_device_bytes.restype = ctypes.c_size_t
-        L.danhip_jpeg_scan_device_bytes.argtypes = [P]
-        L.danhip_jpeg_scan_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_jpeg_scan_workspace_bytes.argtypes = [P]
-        bind_crc32c_host(L)
-        bind_jpeg_encode_host(L)
-        L.danhip_draw_item_bytes.restype, L.danhip_draw_item_bytes.argtypes = ctypes.c_size_t, []
-        L.danhip_crc_segment_bytes.restype, L.danhip_crc_segment_bytes.argtypes = ctypes.c_size_t, []
-        for fn in (L.danhip_crc32c_chunk_bytes, L.danhip_crc32c_group_bytes, L.danhip_crc32c_batch_last_launches):
-            fn.restype, fn.argtypes = I32, []
-        L.danhip_crc32c_batch_workspace_bytes.restype = ctypes.c_size_t
-        L.danhip_crc32c_batch_workspace_bytes.argtypes = [I32, ctypes.c_uint64]
-        for name, args in SIGNATURES.items():
-            fn = getattr(L, name)          # AttributeError if the export is missing
-            fn.restype = ctypes.c_int
-            fn.argtypes = args
+    if not os.path.exists(so_path):
+        raise DanhipError("libdanhip.so not found at %s — run `python -m dan_amd.build` (there is no fallback path)" % so_path)
+    L = bind(ctypes.CDLL(so_path))
+    if L.danhip_act_dtype() != (2 if act_name == "fp16" else 1):
+        raise DanhipError("%s was built for another activation dtype than %s" % (so_path, act_name))
     return L
-
-
-def bind_crc32c_host(L):
-    """Prototypes of the host CRC-32C entry points (no GPU call behind them; also bound by crc32c_host_lib on a bare handle)."""
-    L.danhip_crc32c_host.restype = ctypes.c_uint32
-    L.danhip_crc32c_host.argtypes = [P, ctypes.c_size_t, ctypes.c_uint32]
-    L.danhip_crc32c_host_form.restype = ctypes.c_uint32
-    L.danhip_crc32c_host_form.argtypes = [P, ctypes.c_size_t, ctypes.c_uint32, I32]
-    L.danhip_crc32c_combine.restype = ctypes.c_uint32
-    L.danhip_crc32c_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
-
-
-def bind_jpeg_encode_host(L):
-    """Prototypes of the JPEG encoder's host entry points (csrc/jpeg_encode.cpp: no GPU call behind them)."""
-    L.danhip_jpeg_enc_desc_bytes.restype, L.danhip_jpeg_enc_desc_bytes.argtypes = ctypes.c_size_t, []
-    L.danhip_jpeg_encode_file_bound.restype, L.danhip_jpeg_encode_file_bound.argtypes = I64, [I32, I32, I32]
-    L.danhip_jpeg_encode_scan_staging_bytes.restype, L.danhip_jpeg_encode_scan_staging_bytes.argtypes = ctypes.c_size_t, [I32]
-    L.danhip_jpeg_encode_scan_workspace_bytes.restype, L.danhip_jpeg_encode_scan_workspace_bytes.argtypes = ctypes.c_size_t, [P]
-    for name, args in (("danhip_jpeg_encode_prepare", [P, P, P, I32, I32, I32, P, P]),
-                       ("danhip_jpeg_encode_pixels_host", [P, I32, P, I64]),
-                       ("danhip_jpeg_encode_entropy_batch", [P, I64, P, I32, I32, P, I64, P]),
-                       ("danhip_jpeg_encode_host", [P, I32, I32, I32, I32, P, I64, P]),
-                       ("danhip_jpeg_encode_scan_prepare", [P, I32, I64, I64, P, ctypes.c_size_t, P]),
-                       ("danhip_jpeg_encode_entropy_emulate_batch", [P, ctypes.c_size_t, P, I32, P, I64, P, I64, P, P, P])):
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = ctypes.c_int, args
 
 
 def check(rc, what):

@@ -151,7 +151,6 @@ def window_of(off, dg):
 
 # ---- the host emulation (needs the library, no GPU)
 GUARD = 64
-EMU_ARGTYPES = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 2
 
 
 def act_dtype():
@@ -168,7 +167,6 @@ def emulate16(off16, dS16, N, H, W, C, dg, window=0):
     n = N * H * W * C
     buf = np.full(n + 2 * GUARD, np.float32(-777.25), np.float32)
     rec, err = ctypes.c_int64(-1), ctypes.c_int64(-1)
-    L.danhip_deform_far_ordered_emulate.argtypes = EMU_ARGTYPES
     rc = L.danhip_deform_far_ordered_emulate(off16.data_ptr(), dS16.data_ptr(), buf.ctypes.data + 4 * GUARD, n, N, H, W, C, dg, window,
                                             ctypes.addressof(rec), ctypes.addressof(err))
     assert rc == 0, L.danhip_last_error()

@@ -20,6 +20,10 @@ import argparse
 import ctypes
 import json
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))      # run as a script: the repository root
+from dan_amd._lib import ConvDesc, bind as bind_prototypes
 
 NS = (1, 2, 16)
 MAPS = ((5, 5), (8, 8), (10, 10), (16, 16), (20, 20), (24, 32), (32, 32), (40, 40), (48, 48), (32, 64), (64, 64), (160, 160))
@@ -40,10 +44,6 @@ VALUE_COLUMNS = ["ws_fwd_q", "ws_fwd_r", "ws_bwd_q", "ws_bwd_r", "ws_wgrad", "po
 BIAS_BLIND = ("conv3x3_c8_kernel<true>", "conv3x3_halo_kernel<8, 32, 64, 8, 1, 3, 3, false, 1, false>", "conv3x3_halo_kernel<16, 16, 64, 8, 1, 3, 3, false, 1, false>")
 
 
-class ConvDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "H", "W", "Cin", "Ho", "Wo", "Cout", "kh", "kw", "stride")]
-
-
 def descriptors():
     """The grid, in the order the columns are recorded: (N, H, W, Cin, Ho, Wo, Cout, k, k, stride)."""
     out = []
@@ -62,21 +62,11 @@ def descriptors():
 
 
 def bind(L):
-    D = ctypes.POINTER(ConvDesc)
-    for name, res, args in (("danhip_conv_kernel_label", ctypes.c_char_p, [D, ctypes.c_int]),
-                            ("danhip_conv_wgrad_kernel_label", ctypes.c_char_p, [D]),
-                            ("danhip_conv2d_workspace_bytes", ctypes.c_size_t, [D, ctypes.c_int]),
-                            ("danhip_conv2d_bwd_weight_workspace_bytes", ctypes.c_size_t, [D]),
-                            ("danhip_conv2d_fwd_pool_only", ctypes.c_int, [D]),
-                            ("danhip_conv2d_fwd_emits_bits", ctypes.c_int, [D, ctypes.c_int]),
-                            ("danhip_conv2d_bwd_data_takes_bits", ctypes.c_int, [D]),
-                            ("danhip_conv2d_bwd_data_first_supported", ctypes.c_int, [D]),
-                            ("danhip_conv2d_fwd_concat2_supported", ctypes.c_int, [D, ctypes.c_int32, ctypes.c_int32]),
-                            ("danhip_conv_packed_dims", ctypes.c_int, [D, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)])):
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    return L
+    """The functions sweep() calls and nothing else: the parent commit's build need not export everything the present header declares."""
+    return bind_prototypes(L, ["danhip_conv_kernel_label", "danhip_conv_wgrad_kernel_label", "danhip_conv2d_workspace_bytes",
+                               "danhip_conv2d_bwd_weight_workspace_bytes", "danhip_conv2d_fwd_pool_only", "danhip_conv2d_fwd_emits_bits",
+                               "danhip_conv2d_bwd_data_takes_bits", "danhip_conv2d_bwd_data_first_supported",
+                               "danhip_conv2d_fwd_concat2_supported", "danhip_conv_packed_dims"])
 
 
 def sweep(L):

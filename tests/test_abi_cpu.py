@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol():
     L16 = ctypes.CDLL(build.OUT_F16)
     for n in names:
         assert hasattr(L16, n), "fp16 build misses export " + n
-    L16.danhip_act_dtype.restype = ctypes.c_int
+    _lib.bind(L16, ["danhip_act_dtype"])
     assert L16.danhip_act_dtype() == 2
 
 
@@ -51,7 +51,6 @@ def test_invalid_arguments_are_reported_not_thrown():
     assert rc == -1
     # ABI 2: danhip_deform_sample_bwd refuses a workspace sized to the version-1 contract (N*H*W*C floats, without the 64 statistic words)
     # before anything is launched (the pointers are never dereferenced on the host)
-    L.danhip_deform_sample_bwd_workspace_bytes.restype = ctypes.c_size_t
     need = L.danhip_deform_sample_bwd_workspace_bytes(1, 8, 8, 64)
     assert need == (8 * 8 * 64 + 64) * 4
     buf = (ctypes.c_char * 64)()

@@ -254,13 +254,9 @@ def test_launch_plans_restate_the_sources_by_hand():
 def test_launch_plans_equal_the_library_queries():
     """Without a device the library plans for 256 CUs (dh_cu_count), the MI355X's count: every listed shape, both directions."""
     from dan_amd import build as B
-    from dan_amd._lib import ConvDesc
+    from dan_amd._lib import ConvDesc, bind
     B.build()
-    L = ctypes.CDLL(B.OUT)
-    L.danhip_conv2d_workspace_bytes.restype = ctypes.c_size_t
-    L.danhip_conv2d_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), ctypes.c_int]
-    L.danhip_conv2d_bwd_weight_workspace_bytes.restype = ctypes.c_size_t
-    L.danhip_conv2d_bwd_weight_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
+    L = bind(ctypes.CDLL(B.OUT))
     shapes = sorted({c[2] for c in CASES} | {(16, 160, 160, 256, 256, 3, 3, 1), (2, 80, 80, 512, 64, 1, 1, 1), (4, 40, 40, 1024, 1024, 1, 1, 1)})
     for shp in shapes:
         N, H, W, Cin, Cout, kh, kw, s = shp

@@ -1,7 +1,6 @@
 """The ordered far-corner path of the deformable backward without a GPU: the host emulation (danhip_deform_far_ordered_emulate, the
 per-record routines of csrc/deform_far.h run over checked host arrays) against a plain Python loop with an np.float32 running sum in key
 order, and the command-line route of `train_dan_deform --deterministic`."""
-import ctypes
 import os
 import sys
 
@@ -45,10 +44,8 @@ def test_emulation_refuses_other_shape_classes():
     L = _lib.lib()
     a = np.zeros(16, np.int16)
     f = np.zeros(16, np.float32)
-    L.danhip_deform_far_ordered_emulate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 2
     assert L.danhip_deform_far_ordered_emulate(a.ctypes.data, a.ctypes.data, f.ctypes.data, 16, 1, 1, 1, 32, 1, 0, None, None) == -1      # C / dg = 32
     assert L.danhip_version() >= 17
-    L.danhip_deform_sample_bwd_ordered_workspace_bytes.restype = ctypes.c_size_t
     assert L.danhip_deform_sample_bwd_ordered_workspace_bytes(2, 8, 16, 128, 4) == 0
     nx, nd = 16 * 160 * 160 * 256, 16 * 160 * 160 * 4
     want = (nx + 64) * 4 + 4 * ((2 * nd + 1 + (nd + 2047) // 2048 + 3) // 4 * 4 + 4 * 9 * nd)

@@ -103,11 +103,9 @@ def test_split_selection_restates_the_sources_by_hand():
 def test_split_plans_equal_the_fp16_library_query():
     """danhip_conv2d_workspace_bytes of the fp16 build on the limb descriptor (256 CUs without a device)."""
     from dan_amd import build as B
-    from dan_amd._lib import ConvDesc
+    from dan_amd._lib import ConvDesc, bind
     B.build()
-    L = ctypes.CDLL(os.path.join(os.path.dirname(B.OUT), "libdanhip_f16.so"))
-    L.danhip_conv2d_workspace_bytes.restype = ctypes.c_size_t
-    L.danhip_conv2d_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), ctypes.c_int]
+    L = bind(ctypes.CDLL(os.path.join(os.path.dirname(B.OUT), "libdanhip_f16.so")), ["danhip_conv2d_workspace_bytes"])
     for c in IE.SPLIT_CASES:
         o = IE.case_opts(c)
         p = IE.plan_split_call(c[1], not o["f32"], o["padding"], 256)

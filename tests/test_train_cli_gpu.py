@@ -132,8 +132,12 @@ def test_metric_is_read_only(dev):
 
 def _step_launches(dev, build):
     """Every library call of one eager step, by name (ops.call and _lib.call are the two doors; recorded, then passed on)."""
+    import gc
     from dan_amd import _lib, ops, trainer as T
     from dan_amd.utility import anchor_manipulator, custom_op
+    # Earlier trainers' parameters die NOW, not when the collector happens to run: a packed parameter that dies between the two steps below
+    # clears ops' packing tables, and the recorded step would carry the danhip_pack_entry_init calls of their rebuild.
+    gc.collect()
     tr, args = build()
     tr.train_step(*args)                                                          # (first step: packings, scratch, lazy initialisation)
     names = []

@@ -94,7 +94,7 @@ def test_new_symbols_are_declared_bound_and_exported_by_both_builds():
         if not n.endswith("_workspace_bytes"):
             assert n in _lib.SIGNATURES, n
     assert L.danhip_version() >= 5
-    L16.danhip_version.restype = ctypes.c_int
+    _lib.bind(L16, ["danhip_version"])
     assert L16.danhip_version() >= 5
 
 
