@@ -330,6 +330,14 @@ _TABLE = {
     "danhip_draw_boxes_labels_u8": (STATUS, [P, P, I32, P, P, P, I64, I32, P]),
     "danhip_draw_glyph": (STATUS, [I32, P]),
     "danhip_draw_format_score": (STATUS, [FL, P]),
+    # ---- transposed convolution 4x4 / stride 2 (the LFPN's learnable upsampling)
+    "danhip_conv_transpose4x4s2_pack_weight": (STATUS, [P, P, P, I32, I32, P]),
+    "danhip_conv_transpose4x4s2_add_fwd": (STATUS, [P, P, P, P, P] + [I32] * 7 + [P]),
+    "danhip_conv_transpose4x4s2_dgrad": (STATUS, [P, P, P] + [I32] * 7 + [INT, P]),
+    "danhip_conv_transpose4x4s2_wgrad_workspace_bytes": (SZ, [I32] * 7),
+    "danhip_conv_transpose4x4s2_wgrad_slabs": (I32, [I32] * 7),
+    "danhip_conv_transpose4x4s2_wgrad": (STATUS, [P, P, P, P] + [I32] * 7 + [P, SZ, P]),
+    "danhip_conv_transpose4x4s2_add_fwd_f32": (STATUS, [P, P, P, P, P] + [I32] * 7 + [P]),
 }
 PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
 SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for

@@ -9,7 +9,9 @@ data_format, num_classes, train_image_size and batch_size (the reference's graph
 there either).  The port's own: --device, --precision, --batch_images (JPEGs read, decoded and detected as one group), --decode_entropy, --encode_entropy,
 --image_list (one `event/name` per line instead of wider_face_split/wider_face_<subset>.mat, which needs scipy), --gt_dir (the directory
 of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat / wider_hard_<subset>.mat: the average precision is
-computed on the device and printed), --debug_quality and --debug_labels (draw each box's score on a tab above it; off by default).
+computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default) and
+--lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
+train_*'s flag of the same name.  transposed has no split-operand form: with --precision split the command exits with a message.
 
 Per group: the files are read, decoded on the device (dataset.jpeg.JpegDecoder; a stream it refuses takes its Pillow fallback) and
 detected (eval_dan.detect_image_list); ONE download brings (dets, num) to the host for the text files; the evaluator takes the device
@@ -51,6 +53,7 @@ _HELP = {
 DEBUG_SCORE = 0.2            # eval_dan.py:456
 PYRAMID = {"sfd": False, "pb": True, "dan": True, "dan_deform": True}       # eval_sfd.py:323-328 has no multi_scale_test_pyramid
 MIN_HEIGHT = {"sfd": 10, "pb": 9, "dan": 10, "dan_deform": 10}              # write_to_txt's row filter (eval_pb.py:252)
+LFPN_UPSAMPLE = ("bilinear", "transposed")                                  # --lfpn_upsample (net/pb_net.py LFPN_UPSAMPLE)
 
 
 def flag_defaults(model):
@@ -79,6 +82,10 @@ def build_parser(model):
     p.add_argument("--debug_quality", type=int, default=75, help="JPEG quality of the debug images (default 75)")
     p.add_argument("--debug_labels", action="store_true",
                    help="draw each box's score ('%%.1f%%%%' of score * 100) in white on a filled tab above it (default: rectangles only)")
+    if model != "sfd":                                                      # (S3FD has no LFPN)
+        p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
+                       help="the LFPN of the checkpoint's graph: bilinear resize (default) or the learnable 4x4 stride-2 transposed convolution "
+                            "(train_*'s --lfpn_upsample transposed); transposed does not run with --precision split")
     return p
 
 
@@ -131,7 +138,7 @@ def ground_truth(args):
 
 
 # ------------------------------------------------------------------------------------------------------------ the models
-def build_detector(model, device, precision, seed=20180817):
+def build_detector(model, device, precision, seed=20180817, lfpn_upsample="bilinear"):
     """eval_dan.Detector around the model's inference graph with its script's anchors.  The variables are created here, by one forward
     of a 64 x 64 image (their shapes do not depend on the image size), so that a checkpoint finds them: the store makes a variable when a
     layer first asks for it."""
@@ -143,10 +150,10 @@ def build_detector(model, device, precision, seed=20180817):
         net = eval_dan.Detector(SFDModel(device=device, seed=seed), lambda h, w, d: AnchorConfig(h, w, d), precision)
     elif model == "pb":
         from .train_pb import PBModel
-        net = eval_dan.Detector(PBModel(device=device, seed=seed), lambda h, w, d: AnchorConfig(h, w, d), precision)     # ratios (1.,): eval_pb.py:311
+        net = eval_dan.Detector(PBModel(device=device, seed=seed, lfpn_upsample=lfpn_upsample), lambda h, w, d: AnchorConfig(h, w, d), precision)     # ratios (1.,): eval_pb.py:311
     else:
         from .train_dan import DANModel, dan_anchor_config
-        net = eval_dan.Detector(DANModel(device=device, seed=seed, deform=(model == "dan_deform")), dan_anchor_config, precision)
+        net = eval_dan.Detector(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=lfpn_upsample), dan_anchor_config, precision)
     with torch.no_grad():
         net.model.forward(torch.zeros((1, 64, 64, 3), dtype=torch.uint8, device=device))
     return net
@@ -173,6 +180,9 @@ def main(argv=None, model="sfd", gt=None, out=None):
         raise SystemExit("--batch_images %d: at least 1" % args.batch_images)
     if not 1 <= args.debug_quality <= 100:
         raise SystemExit("--debug_quality %d: 1 .. 100" % args.debug_quality)
+    lfpn_upsample = getattr(args, "lfpn_upsample", "bilinear")
+    if lfpn_upsample == "transposed" and args.precision == "split":
+        raise SystemExit("--lfpn_upsample transposed has no split-operand form: use --precision act or fp32")
     import torch
     from . import eval_dan
     from .dataset.jpeg import JpegDecoder, JpegEncoder
@@ -184,7 +194,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     if gt is None and args.gt_dir:
         gt = ground_truth(args)
 
-    net = build_detector(model, device, args.precision)
+    net = build_detector(model, device, args.precision, lfpn_upsample=lfpn_upsample)
     path = args.checkpoint_path
     if os.path.isdir(path):
         path = checkpoint.latest_checkpoint(path)

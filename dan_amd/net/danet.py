@@ -10,9 +10,9 @@ from . import pb_net
 
 
 class VGG16Backbone(pb_net.VGG16Backbone):
-    def build_lfpn(self, feature_layers, skip_last=3, name=None):
-        """net/danet.py:339-380: as PyramidBox's LFPN but the fused 3x3 conv always has 256 filters."""
-        return super().build_lfpn(feature_layers, skip_last, name, fused_channels=256)
+    def build_lfpn(self, feature_layers, skip_last=3, name=None, upsample="bilinear"):
+        """net/danet.py:339-380: as PyramidBox's LFPN but the fused 3x3 conv always has 256 filters.  upsample: pb_net.build_lfpn's option."""
+        return super().build_lfpn(feature_layers, skip_last, name, fused_channels=256, upsample=upsample)
 
     def build_bi_lfpn(self, feature_layers, skip_last=3, name=None):
         """net/danet.py:191-249 (defined on the backbone, used by no script): EVERY level but the last is merged with its

@@ -5,11 +5,25 @@ import torch
 from .. import ops
 from . import sfd_net
 
+LFPN_UPSAMPLE = ("bilinear", "transposed")     # build_lfpn(upsample=...)
+
 
 class VGG16Backbone(sfd_net.VGG16Backbone):
-    def build_lfpn(self, feature_layers, skip_last=3, name=None, fused_channels=None):
+    def build_lfpn(self, feature_layers, skip_last=3, name=None, fused_channels=None, upsample="bilinear"):
         """net/pb_net.py:185-226.  No activation on any of the three convs; the running `up_sampling` is the SUM
-        (lateral + upsampled), not the fused output.  (fused_channels: DAN's variant fixes the fused conv to 256.)"""
+        (lateral + upsampled), not the fused output.  (fused_channels: DAN's variant fixes the fused conv to 256.)
+
+        upsample (this port's own option; the reference's README names it as the next step: "transposed convolution in LFPN"):
+          "bilinear"    the reference's graph: lateral + resize_bilinear(upsample_conv(up)).
+          "transposed"  lateral + conv2d_transpose(upsample_conv(up), C, (4, 4), strides 2, 'same') (ops.conv_transpose_add), cropped
+                        top-left to the lateral's size where a 'same' pool halved an odd map.  The 1x1 upsample_conv in front stays.  New
+                        variables per level: <name>/fpn_k/upsample_deconv/kernel [4, 4, C, C] (TensorFlow's conv2d_transpose layout
+                        [ky, kx, out, in]) and /bias [C].  Initialiser: bias zero, kernel[ky, kx, co, ci] = f[ky] f[kx] delta(co, ci)
+                        with f = (0.25, 0.75, 0.75, 0.25): the initial operator is a half-pixel 2x bilinear interpolation in the
+                        interior; the border rows and columns carry 0.75 or 0.25 of ONE sample (no edge replication, so they are
+                        darker than resize_bilinear's).  With "bilinear" no such variable exists."""
+        if upsample not in LFPN_UPSAMPLE:
+            raise ValueError("lfpn upsample must be one of %s, got %r" % (", ".join(LFPN_UPSAMPLE), upsample))
         name = name or "lfpn"
         output_layers = []
         up_sampling = None
@@ -20,7 +34,12 @@ class VGG16Backbone(sfd_net.VGG16Backbone):
                 up_sampling = feature_layers[ind]
             up_sampling = self.conv2d(up_sampling, down_channels, (1, 1), 1, sc + "/upsample_conv", relu=False)
             lateral = self.conv2d(feature_layers[ind - 1], down_channels, (1, 1), 1, sc + "/lateral", relu=False)
-            up_sampling = ops.resize_bilinear_add(up_sampling, lateral)         # lateral + resize_bilinear(up, size(lateral))
+            if upsample == "transposed":
+                wt = self.vs.get(sc + "/upsample_deconv/kernel", (4, 4, down_channels, down_channels), "bilinear_deconv")
+                bt = self.vs.get(sc + "/upsample_deconv/bias", (down_channels,), "zeros")
+                up_sampling = ops.conv_transpose_add(up_sampling, wt, bt, lateral)      # lateral + conv2d_transpose(up), cropped to size(lateral)
+            else:
+                up_sampling = ops.resize_bilinear_add(up_sampling, lateral)         # lateral + resize_bilinear(up, size(lateral))
             featmap = self.conv2d(up_sampling, fused_channels or down_channels, (3, 3), 1, sc + "/fused_conv", relu=False)
             output_layers.append(featmap)
         return list(reversed(output_layers)) + list(feature_layers[skip_last:])

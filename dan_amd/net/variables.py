@@ -3,6 +3,8 @@ import math
 
 import torch
 
+DECONV_TAPS = (0.25, 0.75, 0.75, 0.25)     # initialiser "bilinear_deconv": the taps of a half-pixel 2x linear interpolation
+
 
 class VariableStore(torch.nn.Module):
     """Creates fp32 nn.Parameters on first use with the reference's initialisers and keeps them under their TF
@@ -33,6 +35,11 @@ class VariableStore(torch.nn.Module):
                 co, ci, kh, kw = shape
                 lim = math.sqrt(6.0 / (co * ci * kh + co * ci * kw))
                 v = (torch.rand(shape, generator=self.gen) * 2.0 - 1.0) * lim
+            elif init == "bilinear_deconv":            # transposed 4x4/2 kernel [4, 4, Cout, Cin]: f[ky] f[kx] on the channel diagonal
+                f = torch.tensor(DECONV_TAPS)
+                v = torch.zeros(shape)
+                d = torch.arange(min(shape[2], shape[3]))
+                v[:, :, d, d] = (f[:, None] * f[None, :])[:, :, None]
             elif init == "zeros":
                 v = torch.zeros(shape)
             else:

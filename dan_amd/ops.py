@@ -485,7 +485,8 @@ def _grad_target(p, shape, device):
 
 
 def _launch_wgrad(d, on_side, issue, keep):
-    """Issues a weight gradient of descriptor d - issue(stream handle) makes the library call - with its profiling bracket.  on_side and
+    """Issues a weight gradient of descriptor d - issue(stream handle) makes the library call - with its profiling bracket (d = None: a call
+    without a conv descriptor, no bracket).  on_side and
     the trainer's second stream on: on that stream, ordered behind everything issued so far on the current one (dY is final there, and
     the sinks are zeroed), with explicit stream handles (no stream-context switch per layer on the host) and `keep` (what the call
     reads) alive until the join.  -> went to the side stream"""
@@ -494,12 +495,12 @@ def _launch_wgrad(d, on_side, issue, keep):
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         side.wait_event(ev)
-        e0 = _prof_begin(side)
+        e0 = _prof_begin(side) if d is not None else None
         issue(ctypes.c_void_p(side.cuda_stream))
         _prof_end(e0, d, 2, side)
         _CTX.wgrad["keep"].append(keep)
         return True
-    e0 = _prof_begin()
+    e0 = _prof_begin() if d is not None else None
     issue(stream())
     _prof_end(e0, d, 2)
     return False
@@ -1458,6 +1459,125 @@ def resize_bilinear_add(up, lateral=None, size=None):
     track = torch.is_grad_enabled() and (up.requires_grad or (lateral is not None and lateral.requires_grad))
     yslot = _new_slot(track)
     return _publish(_ResizeAdd.apply(up, lateral, size, yslot), yslot, False)
+
+
+# ---- transposed convolution 4 x 4 / stride 2 with the lateral add (csrc/conv_transpose.hip): the LFPN's learnable upsampling
+_CT_PACKED = {}              # id(variable) -> [weakref, stamp, wf, wb]: the two 16-bit operands, keyed on the weight epoch like _PACKED
+
+
+def _ct_pack(wd, need_bwd):
+    if not (wd.dtype == torch.float32 and wd.is_contiguous()):
+        raise RuntimeError("conv_transpose_add: the kernel variable must be a contiguous fp32 [4, 4, Cout, Cin] tensor")
+    cout, cin = wd.shape[2], wd.shape[3]
+    wf = torch.empty((4, 4, cout, cin), dtype=ACT, device=wd.device)
+    wb = torch.empty((4, 4, cin, cout), dtype=ACT, device=wd.device) if need_bwd else None
+    call("danhip_conv_transpose4x4s2_pack_weight", ptr(wd), ptr(wf), ptr(wb), cin, cout, stream())
+    return wf, wb
+
+
+def _ct_packed(w, w_param, need_bwd):
+    """-> (wf [4,4,Cout,Cin], wb [4,4,Cin,Cout] or None), 16-bit: cached per variable while it is unchanged (_stamp), packed on the spot
+    for a plain tensor."""
+    if w_param is None:
+        return _ct_pack(w.detach(), need_bwd)
+    import weakref
+    pid = id(w_param)
+    e = _CT_PACKED.get(pid)
+    st = _stamp(w_param) + (tuple(w_param.shape),)
+    if e is None or e[0]() is not w_param or e[1] != st or (need_bwd and e[3] is None):
+        wf, wb = _ct_pack(w_param.detach(), need_bwd or (e is not None and e[0]() is w_param and e[3] is not None))
+        e = _CT_PACKED[pid] = [weakref.ref(w_param, lambda _r, pid=pid: _CT_PACKED.pop(pid, None)), st, wf, wb]
+    return e[2], (e[3] if need_bwd else None)
+
+
+def _ct_wgrad_scratch(dims, dev):
+    key = ("ct",) + tuple(dims)
+    n = _SCRATCH_BYTES.get(key)
+    if n is None:
+        n = _SCRATCH_BYTES[key] = int(_lib.lib().danhip_conv_transpose4x4s2_wgrad_workspace_bytes(*dims))
+    return torch.empty(n, dtype=torch.uint8, device=dev), n
+
+
+class _ConvTransposeAdd(torch.autograd.Function):
+    """out = lateral + tf.layers.conv2d_transpose(up, Cout, (4, 4), strides=(2, 2), padding='same'), cropped top-left to the lateral's size
+    (include/danhip.h has the rule).  One node: forward, data gradient (into the producer's slot) and weight / bias gradient (into the
+    trainer's sinks, on the weight-gradient stream)."""
+
+    @staticmethod
+    def forward(ctx, up, w, b, lateral, size, w_param, b_param, xslot, yslot):
+        N, Hi, Wi, Cin = up.shape
+        Cout = w.shape[2]
+        Ho, Wo = (lateral.shape[1], lateral.shape[2]) if lateral is not None else size
+        assert up.dtype == ACT and up.is_contiguous(), "conv_transpose_add input must be contiguous NHWC 16-bit"
+        need_bwd = up.requires_grad or w.requires_grad
+        wf, wb = _ct_packed(w, w_param, need_bwd)
+        out = torch.empty((N, Ho, Wo, Cout), dtype=ACT, device=up.device)
+        call("danhip_conv_transpose4x4s2_add_fwd", ptr(up), ptr(wf), ptr(b.detach()) if b is not None else None,
+             ptr(lateral.contiguous()) if lateral is not None else None, ptr(out), N, Hi, Wi, Ho, Wo, Cin, Cout, stream())
+        ctx.dims = (N, Hi, Wi, Ho, Wo, Cin, Cout)
+        ctx.xslot, ctx.yslot = xslot, yslot
+        ctx.w_param, ctx.b_param = w_param, b_param
+        ctx.has_lat, ctx.has_bias = lateral is not None, b is not None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(up, wb)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        up, wb = ctx.saved_tensors
+        dims = ctx.dims
+        N, Hi, Wi, Ho, Wo, Cin, Cout = dims
+        # the merged map feeds two convolutions in the LFPN (this level's fused 3x3 and the next level's upsample 1x1): both deliver into its slot
+        g = _incoming(ctx.yslot, dout)
+        if g is None:
+            return (None,) * 9
+        dup = None
+        if ctx.needs_input_grad[0]:
+            def data_grad(buf, acc):
+                call("danhip_conv_transpose4x4s2_dgrad", ptr(g), ptr(wb), ptr(buf), N, Hi, Wi, Ho, Wo, Cin, Cout, acc, stream())
+
+            dup = _deliver(ctx.xslot, up.shape, up, data_grad)
+        wp, bp = ctx.w_param, ctx.b_param
+        need_dw = ctx.needs_input_grad[1]
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        dw = db_ret = None
+        if need_dw or need_db:
+            dw_to, dw = _grad_target(wp, (4, 4, Cout, Cin), g.device) if need_dw else (None, None)
+            db_to, db_ret = _grad_target(bp, (Cout,), g.device) if need_db else (None, None)
+            ws, nws = _ct_wgrad_scratch(dims, g.device)
+
+            def issue(st):
+                call("danhip_conv_transpose4x4s2_wgrad", ptr(up), ptr(g), ptr(dw_to), ptr(db_to), N, Hi, Wi, Ho, Wo, Cin, Cout, ptr(ws), nws, st)
+
+            # (the side stream only when both gradients go to sinks: one handed back to autograd is consumed on this stream)
+            _launch_wgrad(None, dw is None and db_ret is None, issue, (g, up, ws))
+            if _CTX.GRAD_READY_HOOK is not None and wp is not None:
+                _CTX.GRAD_READY_HOOK(wp)
+        return dup, dw, db_ret, (g if ctx.has_lat else None), None, None, None, None, None
+
+
+def conv_transpose_add(up, w, b, lateral=None, size=None):
+    """lateral + conv2d_transpose(up; w [4, 4, Cout, Cin], b [Cout]; 4 x 4, stride 2, 'same'), at the lateral's size or `size` = (Ho, Wo):
+    2 Hi x 2 Wi or one less each way (top-left crop).  The learnable counterpart of resize_bilinear_add."""
+    if _is_limbs(up) or (lateral is not None and _is_limbs(lateral)) or (_CTX.SPLIT_EVAL and up.dtype == torch.float32):
+        raise ValueError("conv_transpose_add (lfpn_upsample='transposed') has no split-operand form: precision='split' is not supported with it")
+    N, Hi, Wi, Cin = up.shape
+    if tuple(w.shape[:2]) != (4, 4) or w.shape[3] != Cin:
+        raise ValueError("conv_transpose_add: the kernel must be [4, 4, Cout, %d], got %s" % (Cin, tuple(w.shape)))
+    if lateral is None and size is None:
+        size = (2 * Hi, 2 * Wi)
+    if _f32_infer(up):
+        Ho, Wo = (lateral.shape[1], lateral.shape[2]) if lateral is not None else size
+        out = torch.empty((N, Ho, Wo, w.shape[2]), dtype=torch.float32, device=up.device)
+        call("danhip_conv_transpose4x4s2_add_fwd_f32", ptr(up.contiguous()), ptr(w.detach().contiguous()), ptr(b.detach()) if b is not None else None,
+             ptr(lateral.contiguous()) if lateral is not None else None, ptr(out), N, Hi, Wi, Ho, Wo, Cin, w.shape[2], stream())
+        return out
+    track = torch.is_grad_enabled() and (up.requires_grad or w.requires_grad or (lateral is not None and lateral.requires_grad))
+    yslot = _new_slot(track)
+    xs = _slot_of(up) if track else None
+    if xs is not None and xs.is_relu:
+        xs = None                # (no ReLU mask in this data gradient's epilogue: the gradient of a ReLU output travels through autograd)
+    return _publish(_ConvTransposeAdd.apply(up, w, b, lateral, size, _param_handle(w), _param_handle(b), xs, yslot), yslot, False)
 
 
 class _AvgPool2x2S1(torch.autograd.Function):

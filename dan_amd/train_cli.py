@@ -8,7 +8,10 @@ Flags carry the reference's names and defaults (each script's tf.app.flags block
 they configure TensorFlow's input threads, session and device placement: num_readers, num_preprocessing_threads, num_cpu_threads,
 gpu_memory_fraction, data_format, multi_gpu (and save_summary_steps / save_checkpoints_secs, which the reference itself leaves unused or
 feeds to summaries this port does not write).  Three flags are this port's own: --device, --deterministic, --decode_entropy; a fourth,
---no_prefetch, exists for measuring the loader thread against the plain generator (profiles/r15/train_driver.md).  Checkpoints are written
+--no_prefetch, exists for measuring the loader thread against the plain generator (profiles/r15/train_driver.md); a fifth,
+--lfpn_upsample {bilinear,transposed} (train_pb, train_dan, train_dan_deform; default bilinear: the reference's graph), makes the LFPN merge
+through a learnable 4x4 / stride-2 transposed convolution (net/pb_net.py build_lfpn) - a checkpoint written without it resumes or warm-starts
+with the new variables at their initialiser.  Checkpoints are written
 with a CRC-32C on every tensor (checksums="device": packed and checksummed on the GPU, profiles/r16/checkpoint_crc.md) and every tensor CRC
 is checked on resume and on a warm start before a variable is written; --no_checkpoint_checksums turns both off.
 
@@ -79,6 +82,7 @@ ANCHOR_SCALES = [16, 32, 64, 128, 256, 512]                                 # da
 KEEP_CHECKPOINT_MAX = 5                                                     # RunConfig(keep_checkpoint_max=5), train_sfd.py:476
 PREFETCH_DEPTH = 2
 MAX_THREADS = 16
+LFPN_UPSAMPLE = ("bilinear", "transposed")                                  # --lfpn_upsample (net/pb_net.py LFPN_UPSAMPLE)
 
 
 def flag_defaults(model):
@@ -113,6 +117,10 @@ def build_parser(model):
     p.add_argument("--no_checkpoint_checksums", action="store_true",
                    help="write checkpoints without per-tensor CRCs and do not verify the ones that are read (default: both, on the device)")
     p.add_argument("--no_prefetch", action="store_true", help="prepare each batch between the steps instead of on the background thread")
+    if model != "sfd":                                                      # (S3FD has no LFPN)
+        p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
+                       help="how the LFPN brings the upper level to the lateral's size: bilinear resize (the reference's graph, default) or a "
+                            "learnable 4x4 stride-2 transposed convolution (new variables <lfpn>/fpn_k/upsample_deconv/{kernel,bias})")
     return p
 
 
@@ -185,14 +193,14 @@ class _Setup(object):
             targets = PBAnchorTargets(size, size, device)
             if (args.match_threshold, args.neg_threshold) != (0.4, 0.4):
                 targets.face = AnchorConfig(size, size, device, args.match_threshold, args.neg_threshold)
-            self.trainer = PBTrainer(PBModel(device=device, seed=seed), **trainer_kw)
+            self.trainer = PBTrainer(PBModel(device=device, seed=seed, lfpn_upsample=args.lfpn_upsample), **trainer_kw)
             self.preprocess = lambda images, boxes, draws: P.preprocess_batch_for_train(images, boxes, shape, ANCHOR_SCALES, draws=draws)
             self.encode = lambda boxes: (targets.encode_batch(boxes),)
         else:
             from .preprocessing import dan_preprocessing as P
             from .train_dan import DANModel, DANTrainer, encode_batch_dan
             anchors = AnchorConfig(size, size, device, args.match_threshold, args.neg_threshold, ratios=_dan_ratios())
-            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform")), anchors, routing_seed=seed,
+            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=args.lfpn_upsample), anchors, routing_seed=seed,
                                       **deterministic_route(model, trainer_kw))
             self.preprocess = lambda images, boxes, draws: P.preprocess_batch_for_train(images, boxes, shape, ANCHOR_SCALES, draws=draws)
             self.encode = lambda boxes: encode_batch_dan(anchors, boxes)

@@ -3,7 +3,7 @@ train_dan.py / train_dan_deform.py (dan_model_fn :386-532) and eval_dan.py (:299
 import torch
 
 from . import ops
-from .net import danet, sfd_net
+from .net import danet, pb_net, sfd_net
 from .net.variables import VariableStore
 from .train_sfd import ALL_ANCHOR_SCALES, ALL_EXTRA_SCALES, ALL_LAYER_STRIDES, AnchorConfig
 from .utility import custom_op
@@ -17,7 +17,12 @@ def dan_anchor_config(height, width, device):
 
 
 class DANModel(object):
-    def __init__(self, device="cuda", seed=20180817, deform=False):
+    def __init__(self, device="cuda", seed=20180817, deform=False, lfpn_upsample="bilinear"):
+        """lfpn_upsample (the command lines' --lfpn_upsample {bilinear,transposed}): "bilinear" (the reference's graph) or "transposed" - the three LFPNs merge through a learnable 4x4 / stride-2
+        transposed convolution (net/pb_net.py build_lfpn; new variables <lfpn scope>/fpn_k/upsample_deconv/{kernel,bias})."""
+        if lfpn_upsample not in pb_net.LFPN_UPSAMPLE:
+            raise ValueError("lfpn_upsample must be one of %s, got %r" % (", ".join(pb_net.LFPN_UPSAMPLE), lfpn_upsample))
+        self.lfpn_upsample = lfpn_upsample
         self.vs = VariableStore(device=device, seed=seed)
         self.deform = bool(deform)                            # (DetectorTrainer refuses deterministic=True for it; ops_ctx=ops.deterministic_context() is its spelling of the mode)
         if deform:
@@ -33,13 +38,13 @@ class DANModel(object):
             b = self.backbone
             x = sfd_net.prepare_input(images_u8, prec)
             feats = b.get_featmaps(x, training=True)
-            feats = b.build_lfpn(feats, skip_last=3)
+            feats = b.build_lfpn(feats, skip_last=3, upsample=self.lfpn_upsample)
             s1 = b.get_features_stage1(feats, name="prediction_modules_stage1")
-            s1 = b.build_lfpn(s1, skip_last=3, name="lfpn_stage1")
+            s1 = b.build_lfpn(s1, skip_last=3, name="lfpn_stage1", upsample=self.lfpn_upsample)
             n = len(feats)
             stage1 = b.get_predict_module(s1, [1] * n, [1] * n, [1] * n, name="predict_face")
             s2 = b.get_features_stage2(s1, feats, name="prediction_modules_stage2")
-            s2 = b.build_lfpn(s2, skip_last=3, name="lfpn_stage2")
+            s2 = b.build_lfpn(s2, skip_last=3, name="lfpn_stage2", upsample=self.lfpn_upsample)
             stage2 = b.get_predict_module(s2, [1] * n, [3] + [1] * (n - 1), [1] * n, name="predict_cascade")
             return stage1, stage2, [(f.shape[1], f.shape[2]) for f in feats]
 

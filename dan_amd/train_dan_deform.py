@@ -7,8 +7,8 @@ from .train_dan import DANModel, DANTrainer, dan_anchor_config, encode_batch_dan
 
 
 class DANDeformModel(DANModel):
-    def __init__(self, device="cuda", seed=20180817):
-        super().__init__(device=device, seed=seed, deform=True)
+    def __init__(self, device="cuda", seed=20180817, lfpn_upsample="bilinear"):
+        super().__init__(device=device, seed=seed, deform=True, lfpn_upsample=lfpn_upsample)
 
 
 def main(argv=None):

@@ -1,5 +1,7 @@
 """PyramidBox training / inference graph on libdanhip — the MI355X equivalent of the reference's train_pb.py
-(pb_model_fn :350-520: forward :396-420, three-head loss :422-470) and eval_pb.py's inference graph."""
+(pb_model_fn :350-520: forward :396-420, three-head loss :422-470) and eval_pb.py's inference graph.
+The port's own flag --lfpn_upsample {bilinear,transposed} (default bilinear; PBModel(lfpn_upsample=...)) makes the LFPN merge through a
+learnable 4x4 / stride-2 transposed convolution instead of the bilinear resize (dan_amd/train_cli.py, net/pb_net.py build_lfpn)."""
 import torch
 
 from . import ops
@@ -9,7 +11,12 @@ from .train_sfd import AnchorConfig  # noqa: F401  (same anchor layout: train_pb
 
 
 class PBModel(object):
-    def __init__(self, device="cuda", seed=20180817):
+    def __init__(self, device="cuda", seed=20180817, lfpn_upsample="bilinear"):
+        """lfpn_upsample: "bilinear" (the reference's graph) or "transposed" - the LFPN merges through a learnable 4x4 / stride-2
+        transposed convolution (net/pb_net.py build_lfpn; new variables lfpn/fpn_k/upsample_deconv/{kernel,bias})."""
+        if lfpn_upsample not in pb_net.LFPN_UPSAMPLE:
+            raise ValueError("lfpn_upsample must be one of %s, got %r" % (", ".join(pb_net.LFPN_UPSAMPLE), lfpn_upsample))
+        self.lfpn_upsample = lfpn_upsample
         self.vs = VariableStore(device=device, seed=seed)
         self.backbone = pb_net.VGG16Backbone("channels_last", variables=self.vs)
 
@@ -21,7 +28,7 @@ class PBModel(object):
             b = self.backbone
             x = sfd_net.prepare_input(images_u8, prec)
             feats = b.get_featmaps(x, training=True)
-            feats = b.build_lfpn(feats, skip_last=3)
+            feats = b.build_lfpn(feats, skip_last=3, upsample=self.lfpn_upsample)
             feats = b.context_pred_module(feats)
             n = len(feats)
             face = b.get_predict_module(feats, [1] + [3] * (n - 1), [3] + [1] * (n - 1), [1] * n, name="predict_face")

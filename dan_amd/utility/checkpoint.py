@@ -653,7 +653,7 @@ def init_from_checkpoint(variables, checkpoint_path, model_scope, checkpoint_mod
     restored, params = [], dict(variables.named())
     for ck_name, var_name in mapping.items():
         if not reader.has_tensor(ck_name):
-            if ignore_missing_vars:
+            if ignore_missing_vars or _optional(ck_name):
                 continue
             raise CheckpointError("variable %s missing in checkpoint %s" % (ck_name, checkpoint_path))
         p = params[full[var_name]]
@@ -665,6 +665,16 @@ def init_from_checkpoint(variables, checkpoint_path, model_scope, checkpoint_mod
         restored.append(full[var_name])
     _bump_weight_epoch()
     return restored
+
+
+# Variables of this port's own options (the LFPN's transposed convolution, lfpn_upsample="transposed"): a checkpoint written without the
+# option lacks them and their Momentum slots, and restores or warm-starts with ignore_missing_vars semantics whatever the caller asked for -
+# they keep their initialiser (zero momentum).
+OPTIONAL_VARIABLE_SCOPES = ("/upsample_deconv/",)
+
+
+def _optional(ck_name):
+    return any(s in ck_name for s in OPTIONAL_VARIABLE_SCOPES)
 
 
 def _bump_weight_epoch():
@@ -805,7 +815,7 @@ def restore_checkpoint(variables, checkpoint_path, model_scope, trainer=None, st
 
     def load(ck_name, dst):
         if not reader.has_tensor(ck_name):
-            if strict:
+            if strict and not _optional(ck_name):
                 raise CheckpointError("variable %s missing in checkpoint %s" % (ck_name, checkpoint_path))
             return
         t = shard.device_tensor(ck_name) if shard is not None and dst.device == shard.image.device else None

@@ -1241,6 +1241,46 @@ int danhip_draw_boxes_labels_u8(const danhip_draw_item* items_host, const danhip
 int danhip_draw_glyph(int32_t index, uint8_t rows_out[7]);       /* 0-9 digits, 10 '.', 11 '%' */
 int danhip_draw_format_score(float score, char out[8]);          /* host: the string, or "" when no label is drawn */
 
+/* --------------------------------------------------------------------------------------------------
+ * Transposed convolution 4x4 / stride 2 with the LFPN's lateral add (ABI version 19; csrc/conv_transpose.hip):
+ * tf.layers.conv2d_transpose(x, Cout, (4, 4), strides=(2, 2), padding='same') on NHWC, written out:
+ *
+ *   full[n, oy, ox, co] = b[co] + sum over ky, kx in 0..3 and ci of x[n, iy, ix, ci] * W[ky, kx, co, ci]
+ *                         with oy = 2 iy + ky - 1, ox = 2 ix + kx - 1, 0 <= iy < Hi, 0 <= ix < Wi
+ *   out [n, oy, ox, co] = lateral[n, oy, ox, co] + full[n, oy, ox, co]        for oy < Ho, ox < Wo
+ *
+ *   - full is 2 Hi x 2 Wi; Ho is 2 Hi or 2 Hi - 1 and Wo is 2 Wi or 2 Wi - 1: the odd sizes are a top-left crop (a 'same' pool halved an
+ *     odd map).  Any other Ho / Wo is DANHIP_EINVAL, not a silent result;
+ *   - lateral and bias may be NULL;
+ *   - products are accumulated in fp32; ONE rounding to the activation type, at the end, after bias and lateral;
+ *   - every output has 1, 2 or 4 contributing taps per input channel (corner, edge, interior);
+ *   - the variable is W [4, 4, Cout, Cin] fp32 (TensorFlow's conv2d_transpose layout) and b [Cout] fp32.
+ * Cin and Cout: multiples of 64 up to 1024, anything else is DANHIP_EINVAL.  No call here uses float atomics: each result is a fixed
+ * function of the call's inputs, in deterministic mode and out of it.
+ *
+ * danhip_conv_transpose4x4s2_pack_weight: W -> wf (16-bit, [4,4,Cout,Cin], the forward's operand) and, unless NULL, wb (16-bit,
+ *   [4,4,Cin,Cout], the data gradient's operand); 16 Cin Cout elements each.
+ * danhip_conv_transpose4x4s2_add_fwd: x [N,Hi,Wi,Cin], lateral / out [N,Ho,Wo,Cout], 16-bit activations; on the MFMA, by output parity.
+ * danhip_conv_transpose4x4s2_dgrad: dx [N,Hi,Wi,Cin] (+)= the gradient of x for dout [N,Ho,Wo,Cout] (a cropped row / column of full carries
+ *   no gradient); accumulate != 0: dx = dx + gradient in fp32, one rounding (the second delivery into a gradient slot).
+ * danhip_conv_transpose4x4s2_wgrad: dw [4,4,Cout,Cin] += sum over pixels of dout x; db [Cout] += sum over pixels of dout (fp32; either
+ *   may be NULL).  Partial sums over pixel slabs are stored in the workspace (danhip_conv_transpose4x4s2_wgrad_workspace_bytes bytes for the
+ *   same shape, 16-byte aligned; a smaller one is DANHIP_EWORKSPACE) and added in slab order by the ordered reduction.
+ *   danhip_conv_transpose4x4s2_wgrad_slabs: how many partial sums of dw that is (0 for an unsupported shape, like the byte count).
+ * danhip_conv_transpose4x4s2_add_fwd_f32: the same rule on fp32 tensors with the fp32 variable as it is (fp32 inference path; FMA chains).
+ * ------------------------------------------------------------------------------------------------ */
+int danhip_conv_transpose4x4s2_pack_weight(const float* w, void* wf, void* wb, int32_t Cin, int32_t Cout, void* stream);
+int danhip_conv_transpose4x4s2_add_fwd(const void* x, const void* wf, const float* bias, const void* lateral, void* out, int32_t N, int32_t Hi,
+                                       int32_t Wi, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout, void* stream);
+int danhip_conv_transpose4x4s2_dgrad(const void* dout, const void* wb, void* dx, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo,
+                                     int32_t Cin, int32_t Cout, int accumulate, void* stream);
+size_t danhip_conv_transpose4x4s2_wgrad_workspace_bytes(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout);
+int32_t danhip_conv_transpose4x4s2_wgrad_slabs(int32_t N, int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout);
+int danhip_conv_transpose4x4s2_wgrad(const void* x, const void* dout, float* dw, float* db, int32_t N, int32_t Hi, int32_t Wi, int32_t Ho,
+                                     int32_t Wo, int32_t Cin, int32_t Cout, void* workspace, size_t workspace_bytes, void* stream);
+int danhip_conv_transpose4x4s2_add_fwd_f32(const float* x, const float* w, const float* bias, const float* lateral, float* out, int32_t N,
+                                           int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
