@@ -90,6 +90,8 @@ DETECT_SELECT_LAUNCHES = 7     # DANHIP_DETECT_SELECT_LAUNCHES
 CRC32C_BATCH_LAUNCHES = 3      # DANHIP_CRC32C_BATCH_LAUNCHES
 JPEG_ENCODE_LAUNCHES = 2       # DANHIP_JPEG_ENCODE_LAUNCHES
 JPEG_ENCODE_ENTROPY_LAUNCHES = 6   # DANHIP_JPEG_ENCODE_ENTROPY_LAUNCHES
+JPEG_ENCODE_OPTIMIZE_LAUNCHES = 3  # DANHIP_JPEG_ENCODE_OPTIMIZE_LAUNCHES
+JPEG_ENC_OPTIMIZE = 1              # DANHIP_JPEG_ENC_OPTIMIZE
 JPEG_HOSTONLY = -1             # DANHIP_JPEG_HOSTONLY
 
 P = ctypes.c_void_p
@@ -324,6 +326,12 @@ _TABLE = {
     "danhip_jpeg_encode_scan_workspace_bytes": (SZ, [P]),
     "danhip_jpeg_encode_huffman_batch": (STATUS, [P, P, SZ, P, I32, P, I64, P, I64, P, P, P, SZ, P, P]),
     "danhip_jpeg_encode_entropy_emulate_batch": (STATUS, [P, SZ, P, I32, P, I64, P, I64, P, P, P]),
+    # ---- JPEG encode, optimize=True (csrc/jpeg_encode.cpp; the launch in csrc/jpeg_encode_huffman_exact.hip)
+    "danhip_jpeg_optimal_table_host": (STATUS, [P, P, P]),
+    "danhip_jpeg_encode_entropy_batch_ex": (STATUS, [P, I64, P, I32, I32, I32, P, I64, P]),
+    "danhip_jpeg_encode_scan_prepare_ex": (STATUS, [P, I32, I64, I64, I32, P, SZ, P]),
+    "danhip_jpeg_encode_optimize_layout": (INT, [P]),
+    "danhip_jpeg_optimal_tables_device": (STATUS, [P, I32, P]),
     # ---- box drawing
     "danhip_draw_item_bytes": (SZ, []),
     "danhip_draw_boxes_u8": (STATUS, [P, P, I32, P, P, I64, I32, P]),

@@ -87,6 +87,16 @@ const StdTables& std_tables() {
   return t;
 }
 
+struct HuffSpec {                                         // one DHT segment's content: bits[l] codes of length l (bits[0] = 0), then the symbols
+  uint8_t bits[17], vals[256];
+};
+
+// the four tables of one image in DHT order (DC luma, AC luma, DC chroma, AC chroma): what the markers carry and what the scan is coded with
+struct ImageTables {
+  HuffSpec spec[4];
+  EncTable enc[4];
+};
+
 const int64_t kHeaderBound = 1024;                        // the markers in front of the scan take 623 bytes
 const int64_t kBlockBound = 416;                          // (9 + 11) + 63 * (16 + 10) bits = 208 bytes, every one stuffed
 
@@ -208,8 +218,9 @@ uint8_t* write_dht(uint8_t* p, int index, const uint8_t* bits, const uint8_t* va
   return p;
 }
 
-// jcmarker.c: write_file_header, write_frame_header, write_scan_header for three components, tables 0 (Y) and 1 (Cb, Cr)
-uint8_t* write_header(uint8_t* p, const danhip_jpeg_enc_desc& d) {
+// jcmarker.c: write_file_header, write_frame_header, write_scan_header for three components, tables 0 (Y) and 1 (Cb, Cr).
+// own: the image's own tables (optimize), NULL: the standard ones.  The DHT segments keep their place and order either way.
+uint8_t* write_header(uint8_t* p, const danhip_jpeg_enc_desc& d, const ImageTables* own = nullptr) {
   put16(p, 0xffd8);
   put16(p, 0xffe0); put16(p, 16);
   memcpy(p, "JFIF", 5); p += 5;
@@ -226,40 +237,94 @@ uint8_t* write_header(uint8_t* p, const danhip_jpeg_enc_desc& d) {
   *p++ = 1; *p++ = d.mode == DANHIP_JPEG_420 ? 0x22 : 0x11; *p++ = 0;
   *p++ = 2; *p++ = 0x11; *p++ = 1;
   *p++ = 3; *p++ = 0x11; *p++ = 1;
-  p = write_dht(p, 0x00, kBitsDcLuma, kValDc);
-  p = write_dht(p, 0x10, kBitsAcLuma, kValAcLuma);
-  p = write_dht(p, 0x01, kBitsDcChroma, kValDc);
-  p = write_dht(p, 0x11, kBitsAcChroma, kValAcChroma);
+  if (own) {
+    for (int t = 0; t < 4; ++t) p = write_dht(p, ((t & 1) << 4) | (t >> 1), own->spec[t].bits + 1, own->spec[t].vals);
+  } else {
+    p = write_dht(p, 0x00, kBitsDcLuma, kValDc);
+    p = write_dht(p, 0x10, kBitsAcLuma, kValAcLuma);
+    p = write_dht(p, 0x01, kBitsDcChroma, kValDc);
+    p = write_dht(p, 0x11, kBitsAcChroma, kValAcChroma);
+  }
   put16(p, 0xffda); put16(p, 12);
   *p++ = 3; *p++ = 1; *p++ = 0x00; *p++ = 2; *p++ = 0x11; *p++ = 3; *p++ = 0x11;
   *p++ = 0; *p++ = 63; *p++ = 0;
   return p;
 }
 
-// the file of one image from its coefficient slot; -1: capacity, -2: a coefficient the tables cannot carry
-int64_t write_file(const danhip_jpeg_enc_desc& d, const int16_t* coef, uint8_t* out, int64_t capacity) {
-  if (capacity < kHeaderBound) return -1;
-  const StdTables& T = std_tables();
-  uint8_t* p = write_header(out, d);
-  BitWriter w;
-  w.p = p; w.end = out + capacity - 2;
+// every block of the image's one interleaved scan in the order it is written, dummy blocks included: f(block, component) until it is false
+template <class F>
+bool for_each_scan_block(const danhip_jpeg_enc_desc& d, const int16_t* coef, F f) {
   const int hs = d.mode == DANHIP_JPEG_420 ? 2 : 1, vs = hs;
   const int mcus_x = d.blocks_w[1], mcus_y = d.blocks_h[1];
   const int16_t* plane[3];
   plane[0] = coef;
   plane[1] = plane[0] + (int64_t)d.blocks_w[0] * d.blocks_h[0] * 64;
   plane[2] = plane[1] + (int64_t)d.blocks_w[1] * d.blocks_h[1] * 64;
-  int last_dc[3] = {0, 0, 0};
   for (int my = 0; my < mcus_y; ++my)
     for (int mx = 0; mx < mcus_x; ++mx) {
       for (int v = 0; v < vs; ++v)
         for (int h = 0; h < hs; ++h) {
           const int64_t b = (int64_t)(my * vs + v) * d.blocks_w[0] + (mx * hs + h);
-          if (!encode_block(plane[0] + b * 64, &last_dc[0], T.dc[0], T.ac[0], &w)) return -2;
+          if (!f(plane[0] + b * 64, 0)) return false;
         }
       for (int c = 1; c < 3; ++c)
-        if (!encode_block(plane[c] + ((int64_t)my * mcus_x + mx) * 64, &last_dc[c], T.dc[1], T.ac[1], &w)) return -2;
+        if (!f(plane[c] + ((int64_t)my * mcus_x + mx) * 64, c)) return false;
     }
+  return true;
+}
+
+struct CountSink {                                        // dh_jhuf_symbols' sink over counts[4][257]
+  int32_t (*counts)[257];
+  void add(int t, int sym) { ++counts[t][sym]; }
+};
+
+// the gather pass of optimize: the statistics of the scan as it will be written.  false: a coefficient no baseline code carries
+bool count_symbols(const danhip_jpeg_enc_desc& d, const int16_t* coef, int32_t counts[4][257]) {
+  memset(counts, 0, sizeof(int32_t) * 4 * 257);
+  CountSink sink{counts};
+  int last_dc[3] = {0, 0, 0};
+  return for_each_scan_block(d, coef, [&](const int16_t* blk, int c) {
+    const int pred = last_dc[c];
+    last_dc[c] = blk[0];
+    return dh_jhuf_symbols(blk, pred, c, sink);
+  });
+}
+
+// false: a merge chain longer than libjpeg takes (it fails there as well)
+bool optimal_tables(const int32_t counts[4][257], ImageTables* T) {
+  int32_t work[DH_JENC_TABLE_WORK];
+  for (int t = 0; t < 4; ++t) {
+    if (!dh_jenc_optimal_table(counts[t], T->spec[t].bits, T->spec[t].vals, work)) return false;
+    StdTables::build(T->spec[t].bits + 1, T->spec[t].vals, &T->enc[t]);
+  }
+  return true;
+}
+
+// the file of one image from its coefficient slot; -1: capacity, -2: a coefficient the tables cannot carry, -3: no optimal table.
+// optimize: the image's own tables from two passes over its coefficients (jchuff.c's gather pass, then the scan), else the standard ones.
+// The capacity is checked, not assumed, in both forms.  The bound of danhip_jpeg_encode_file_bound covers the standard tables by
+// construction; own tables carry at most as many symbols (12 DC, 162 AC), so their markers are no longer, and their scan is shorter.
+int64_t write_file(const danhip_jpeg_enc_desc& d, const int16_t* coef, uint8_t* out, int64_t capacity, bool optimize = false) {
+  if (capacity < kHeaderBound) return -1;
+  const StdTables& S = std_tables();
+  const EncTable* dc[2] = {&S.dc[0], &S.dc[1]};
+  const EncTable* ac[2] = {&S.ac[0], &S.ac[1]};
+  ImageTables own;
+  if (optimize) {
+    int32_t counts[4][257];
+    if (!count_symbols(d, coef, counts)) return -2;
+    if (!optimal_tables(counts, &own)) return -3;
+    dc[0] = &own.enc[0]; ac[0] = &own.enc[1]; dc[1] = &own.enc[2]; ac[1] = &own.enc[3];
+  }
+  uint8_t* p = write_header(out, d, optimize ? &own : nullptr);
+  BitWriter w;
+  w.p = p; w.end = out + capacity - 2;
+  int last_dc[3] = {0, 0, 0};
+  const bool coded = for_each_scan_block(d, coef, [&](const int16_t* blk, int c) {
+    const int t = c == 0 ? 0 : 1;
+    return encode_block(blk, &last_dc[c], *dc[t], *ac[t], &w);
+  });
+  if (!coded) return -2;
   w.flush();
   if (w.overflow) return -1;
   p = w.p;
@@ -335,13 +400,17 @@ size_t scan_staging_bytes(int32_t B) {
   return (size_t)(align16(sizeof(DhJencHeader)) + align16((int64_t)B * (int64_t)sizeof(DhJencImage)) + 4 * 256 * 4 + (int64_t)B * DH_JHUF_HEADER_SLOT);
 }
 
-// fills `staging` (scan_staging_bytes(B) bytes) from checked descriptors; status may be NULL
-void fill_staging(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, uint8_t* staging, int32_t* status) {
+// fills `staging` (scan_staging_bytes(B) bytes) from checked descriptors; status may be NULL.  optimize (0 | 1) changes two things: the
+// header's word, and the workspace, whose first B * DH_JHUF_OPT_STRIDE bytes then hold the images' statistics, tables and markers (the
+// staged standard tables and markers stay: the table launch takes the markers around the DHT segments from them).
+void fill_staging(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, uint8_t* staging, int32_t* status,
+                  int32_t optimize = 0) {
   const size_t bytes = scan_staging_bytes(B);
   memset(staging, 0, bytes);
   DhJencHeader* H = (DhJencHeader*)staging;
   H->magic = DH_JHUF_MAGIC;
   H->B = B;
+  H->optimize = optimize;
   H->off_images = align16(sizeof(DhJencHeader));
   H->off_tabs = H->off_images + align16((int64_t)B * (int64_t)sizeof(DhJencImage));
   H->off_headers = H->off_tabs + 4 * 256 * 4;
@@ -354,7 +423,7 @@ void fill_staging(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_cou
   for (int t = 0; t < 4; ++t)
     for (int k = 0; k < 256; ++k) tab[t * 256 + k] = (uint32_t)tabs[t]->code[k] | ((uint32_t)tabs[t]->len[k] << 16);
   DhJencImage* images = (DhJencImage*)(staging + H->off_images);
-  int64_t ws = 0;
+  int64_t ws = optimize ? (int64_t)B * DH_JHUF_OPT_STRIDE : 0;
   for (int32_t i = 0; i < B; ++i) {
     const danhip_jpeg_enc_desc& d = descs[i];
     DhJencImage& im = images[i];
@@ -393,6 +462,7 @@ void fill_staging(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_cou
 }
 
 static_assert(623 <= DH_JHUF_HEADER_SLOT, "the markers fit their staged slot");
+static_assert(DH_JHUF_HEADER_PRE + 2 * (21 + 12) + 2 * (21 + 162) + DH_JHUF_HEADER_SOS == 623, "the markers around the DHT segments");
 
 // NULL = staging is what fill_staging makes of these descriptors and buffer sizes, else what is wrong
 const char* check_staging(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count,
@@ -402,8 +472,10 @@ const char* check_staging(const void* staging, size_t staging_bytes, const danhi
     const char* why = check_desc(&descs[i], coef_count, -1, file_bytes);
     if (why) return why;
   }
+  const int32_t optimize = ((const DhJencHeader*)staging)->optimize;
+  if (optimize != 0 && optimize != 1) return "staging buffer is not what danhip_jpeg_encode_scan_prepare makes of the descriptors";
   std::vector<uint8_t> again(scan_staging_bytes(B));
-  fill_staging(descs, B, coef_count, file_bytes, again.data(), nullptr);
+  fill_staging(descs, B, coef_count, file_bytes, again.data(), nullptr, optimize);
   if (memcmp(again.data(), staging, again.size()) != 0) return "staging buffer is not what danhip_jpeg_encode_scan_prepare makes of the descriptors";
   return nullptr;
 }
@@ -588,12 +660,45 @@ extern "C" int danhip_jpeg_encode_pixels_host(const danhip_jpeg_enc_desc* descs,
   return DANHIP_OK;
 }
 
+extern "C" int danhip_jpeg_optimal_table_host(const int32_t counts[257], uint8_t bits_out[17], uint8_t vals_out[256]) {
+  if (!counts || !bits_out || !vals_out) {
+    danhip_set_error("jpeg_optimal_table_host: NULL table");
+    return DANHIP_EINVAL;
+  }
+  int64_t sum = 0;
+  for (int i = 0; i < 256; ++i) sum += counts[i] > 0 ? counts[i] : 0;
+  int32_t work[DH_JENC_TABLE_WORK];
+  if (sum >= 0x7fffffff || !dh_jenc_optimal_table(counts, bits_out, vals_out, work)) {
+    danhip_set_error("jpeg_optimal_table_host: the counts sum to 2^31 - 1 or more, or give a code of more than 32 bits before the cut to 16");
+    return DANHIP_EINVAL;
+  }
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_jpeg_encode_optimize_layout(int32_t out[8]) {
+  if (!out) return DH_JHUF_OPT_STRIDE;
+  out[0] = DH_JHUF_OPT_STRIDE; out[1] = DH_JHUF_OPT_COUNTS; out[2] = DH_JHUF_OPT_TABS; out[3] = DH_JHUF_OPT_BITSVALS;
+  out[4] = DH_JHUF_OPT_WORDS; out[5] = DH_JHUF_OPT_HEADER; out[6] = DH_JHUF_HIST_BLOCKS; out[7] = DH_JHUF_OPT_HEADER_MAX;
+  return DH_JHUF_OPT_STRIDE;
+}
+
 extern "C" int danhip_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_count, const danhip_jpeg_enc_desc* descs, int32_t B,
                                                 int32_t threads, uint8_t* files_out, int64_t files_capacity, int64_t* sizes_out) {
+  return danhip_jpeg_encode_entropy_batch_ex(coef, coef_count, descs, B, threads, 0, files_out, files_capacity, sizes_out);
+}
+
+extern "C" int danhip_jpeg_encode_entropy_batch_ex(const int16_t* coef, int64_t coef_count, const danhip_jpeg_enc_desc* descs, int32_t B,
+                                                   int32_t threads, int32_t flags, uint8_t* files_out, int64_t files_capacity,
+                                                   int64_t* sizes_out) {
   if (!coef || !descs || !files_out || !sizes_out || B < 1 || B > 65535 || coef_count < 0 || files_capacity < 0) {
     danhip_set_error("jpeg_encode_entropy_batch: bad arguments (1 <= B <= 65535, no NULL buffer)");
     return DANHIP_EINVAL;
   }
+  if (flags & ~DANHIP_JPEG_ENC_OPTIMIZE) {
+    danhip_set_error("jpeg_encode_entropy_batch_ex: flags %d (DANHIP_JPEG_ENC_OPTIMIZE or 0)", flags);
+    return DANHIP_EINVAL;
+  }
+  const bool optimize = (flags & DANHIP_JPEG_ENC_OPTIMIZE) != 0;
   for (int32_t i = 0; i < B; ++i) {
     const char* why = check_desc(&descs[i], coef_count, -1, files_capacity);
     if (why) {
@@ -609,7 +714,7 @@ extern "C" int danhip_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coe
     for (;;) {
       const int32_t i = cursor.fetch_add(1);
       if (i >= B) return;
-      sizes_out[i] = write_file(descs[i], coef + descs[i].coef_offset, files_out + descs[i].file_offset, descs[i].file_capacity);
+      sizes_out[i] = write_file(descs[i], coef + descs[i].coef_offset, files_out + descs[i].file_offset, descs[i].file_capacity, optimize);
     }
   };
   if (T == 1) {
@@ -623,7 +728,9 @@ extern "C" int danhip_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coe
   for (int32_t i = 0; i < B; ++i)
     if (sizes_out[i] < 0) {
       danhip_set_error("jpeg_encode_entropy_batch: image %d: %s", i,
-                       sizes_out[i] == -2 ? "a coefficient outside what the baseline tables carry (DC difference 11 bits, AC 10 bits)" : "file capacity");
+                       sizes_out[i] == -2   ? "a coefficient outside what the baseline tables carry (DC difference 11 bits, AC 10 bits)"
+                       : sizes_out[i] == -3 ? "symbol statistics without an optimal table (a code of more than 32 bits before the cut to 16)"
+                                            : "file capacity");
       return DANHIP_EINVAL;
     }
   return DANHIP_OK;
@@ -661,6 +768,15 @@ extern "C" size_t danhip_jpeg_encode_scan_staging_bytes(int32_t B) { return B < 
 
 extern "C" int danhip_jpeg_encode_scan_prepare(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, void* staging,
                                                size_t staging_bytes, int32_t* status_out) {
+  return danhip_jpeg_encode_scan_prepare_ex(descs, B, coef_count, file_bytes, 0, staging, staging_bytes, status_out);
+}
+
+extern "C" int danhip_jpeg_encode_scan_prepare_ex(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes,
+                                                  int32_t flags, void* staging, size_t staging_bytes, int32_t* status_out) {
+  if (flags & ~DANHIP_JPEG_ENC_OPTIMIZE) {
+    danhip_set_error("jpeg_encode_scan_prepare_ex: flags %d (DANHIP_JPEG_ENC_OPTIMIZE or 0)", flags);
+    return DANHIP_EINVAL;
+  }
   if (!descs || !staging || !status_out || B < 1 || B > 65535 || coef_count < 0 || file_bytes < 0 || ((uintptr_t)staging & 15) ||
       staging_bytes < scan_staging_bytes(B)) {
     danhip_set_error("jpeg_encode_scan_prepare: bad arguments (1 <= B <= 65535, no NULL table, staging 16-byte aligned and at least "
@@ -674,7 +790,7 @@ extern "C" int danhip_jpeg_encode_scan_prepare(const danhip_jpeg_enc_desc* descs
       return DANHIP_EINVAL;
     }
   }
-  fill_staging(descs, B, coef_count, file_bytes, (uint8_t*)staging, status_out);
+  fill_staging(descs, B, coef_count, file_bytes, (uint8_t*)staging, status_out, (flags & DANHIP_JPEG_ENC_OPTIMIZE) ? 1 : 0);
   return DANHIP_OK;
 }
 
@@ -705,6 +821,11 @@ extern "C" int danhip_jpeg_encode_entropy_emulate_batch(const void* staging, siz
     return DANHIP_EINVAL;
   }
   const DhJencHeader* H = (const DhJencHeader*)staging;
+  if (H->optimize) {
+    danhip_set_error("jpeg_encode_entropy_emulate_batch: a staging buffer prepared with DANHIP_JPEG_ENC_OPTIMIZE is not emulated (the "
+                     "statistics and the table rule have host entry points of their own)");
+    return DANHIP_EINVAL;
+  }
   const DhJencImage* images = (const DhJencImage*)((const uint8_t*)staging + H->off_images);
   std::vector<uint8_t> ws((size_t)H->workspace_bytes, (uint8_t)0xa5);       // exactly the queried size, not zeroed: the phases own every byte they read
   EmuCtx c;

@@ -15,6 +15,12 @@
 //   quality   jpeg_quality_scaling: 5000 / q below 50, 200 - 2 q from 50 on; (base * scale + 50) / 100 clamped to [1, 255]
 //             (force_baseline), so quality 100 gives tables of ones.
 //   APP0      JFIF 1.01, density unit 0 with a 1 : 1 aspect (Pillow passes no dpi), no thumbnail.
+//   optimize  the tables of save(optimize=True) are jchuff.c jpeg_gen_optimal_table's, not the textbook Huffman code (dh_jenc_optimal_table):
+//             a 257th pseudo-symbol of count 1 keeps the all-ones code free; of two equal counts the LARGER symbol is merged first; the
+//             lengths are cut to 16 by the counting rule of T.81 K.2 figure K.3, which is not an optimal length-limited code; and the DHT
+//             lists the symbols by the length they had BEFORE that cut, then by value, so a symbol can stand in front of one whose final
+//             code is shorter.  libjpeg skips counts above 10^9; no image here reaches them.  The statistics are those of the scan as it is
+//             written: dummy blocks count (a DC difference of 0 and EOB each), ZRL and EOB are symbols 0xF0 and 0x00 of the AC tables.
 #pragma once
 #include <stdint.h>
 
@@ -104,4 +110,61 @@ DH_JENC_HD int dh_jenc_block_source(int by, int bx, int real_bw, int real_bh, in
     return 1;
   }
   return 0;
+}
+
+// ---- optimize=True: jchuff.c jpeg_gen_optimal_table over the counts of one table ----
+// counts[257]: occurrences of symbol 0 .. 255 (entry 256 is not read: it is the pseudo-symbol, whose count is 1 by rule); their sum stays
+// below 2^31 (a 16384 x 16384 image has 2^28 coefficients).  bits[17]: bits[l] = codes of length l, bits[0] = 0; vals[256]: the symbols in
+// DHT order, zero behind the last.  work: DH_JENC_TABLE_WORK int32 of scratch (LDS in a kernel).  Returns 0 - bits and vals all zero - when
+// a merge chain is longer than libjpeg's 32 (it raises JERR_HUFF_CLEN_OVERFLOW there), else 1.
+#define DH_JENC_TABLE_WORK (3 * 257 + 33)
+DH_JENC_HD int dh_jenc_optimal_table(const int32_t* counts, uint8_t* bits, uint8_t* vals, int32_t* work) {
+  int32_t* freq = work;
+  int32_t* others = work + 257;
+  int32_t* codesize = work + 2 * 257;
+  int32_t* nbits = work + 3 * 257;                          // [33]
+  for (int i = 0; i < 256; ++i) freq[i] = counts[i] > 0 ? counts[i] : 0;
+  freq[256] = 1;                                            // step 1: the reserved symbol, so that no code is all ones
+  for (int i = 0; i < 257; ++i) { others[i] = -1; codesize[i] = 0; }
+  for (int i = 0; i < 33; ++i) nbits[i] = 0;
+  for (int i = 0; i < 17; ++i) bits[i] = 0;
+  for (int i = 0; i < 256; ++i) vals[i] = 0;
+  for (;;) {                                                // step 2: merge the two smallest; "<=" lets the larger index win a tie
+    int c1 = -1, c2 = -1;
+    int32_t v = 0x7fffffff;
+    for (int i = 0; i < 257; ++i)
+      if (freq[i] && freq[i] <= v) { v = freq[i]; c1 = i; }
+    v = 0x7fffffff;
+    for (int i = 0; i < 257; ++i)
+      if (freq[i] && freq[i] <= v && i != c1) { v = freq[i]; c2 = i; }
+    if (c2 < 0) break;
+    freq[c1] += freq[c2];
+    freq[c2] = 0;
+    ++codesize[c1];                                         // step 3: every symbol of both chains moves one level down
+    while (others[c1] >= 0) { c1 = others[c1]; ++codesize[c1]; }
+    others[c1] = c2;
+    ++codesize[c2];
+    while (others[c2] >= 0) { c2 = others[c2]; ++codesize[c2]; }
+  }
+  for (int i = 0; i < 257; ++i)
+    if (codesize[i]) {
+      if (codesize[i] > 32) return 0;
+      ++nbits[codesize[i]];
+    }
+  for (int i = 32; i > 16; --i)                             // step 4, figure K.3: a pair of length i becomes one of length i - 1 and a
+    while (nbits[i] > 0) {                                  // shorter code (from i - 2, or the next length up that has one) grows by one bit
+      int j = i - 2;
+      while (j > 0 && nbits[j] == 0) --j;
+      if (j == 0) return 0;                                 // cannot happen for lengths of a prefix code
+      nbits[i] -= 2; ++nbits[i - 1]; nbits[j + 1] += 2; --nbits[j];
+    }
+  int last = 16;
+  while (last > 0 && nbits[last] == 0) --last;
+  if (last > 0) --nbits[last];                              // step 5: the pseudo-symbol holds the longest code
+  for (int i = 1; i <= 16; ++i) bits[i] = (uint8_t)nbits[i];
+  int p = 0;
+  for (int l = 1; l <= 32; ++l)                             // step 6: by the length before the cut, then by value
+    for (int j = 0; j < 256; ++j)
+      if (codesize[j] == l) vals[p++] = (uint8_t)j;
+  return 1;
 }

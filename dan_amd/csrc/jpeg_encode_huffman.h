@@ -39,8 +39,23 @@
 #define DH_JHUF_MAX_FILE ((int64_t)1 << 30)                          /* an image whose file bound reaches this stays with the host stage */
 #define DH_JHUF_INVALID ((uint64_t)1 << 63)                          /* flag on a workgroup's bit sum: a value without a baseline code */
 
+// optimize (DANHIP_JPEG_ENC_OPTIMIZE): image i owns the first bytes of the device workspace, DH_JHUF_OPT_STRIDE of them from i * stride
+#define DH_JHUF_OPT_COUNTS 0                                         /* uint32 [4][257]: the symbol statistics, table order as C::tab */
+#define DH_JHUF_OPT_TABS 4128                                        /* uint32 [4][256]: code | length << 16, what the walk reads */
+#define DH_JHUF_OPT_BITSVALS 8224                                    /* per table uint8 bits[17], vals[256] */
+#define DH_JHUF_OPT_WORDS 9328                                       /* int32 [4]: the length of the markers below, 3 spare */
+#define DH_JHUF_OPT_HEADER 9344                                      /* the image's markers with its own DHT segments */
+#define DH_JHUF_OPT_HEADER_MAX (DH_JHUF_HEADER_PRE + 4 * (21 + 256) + DH_JHUF_HEADER_SOS)
+#define DH_JHUF_OPT_STRIDE 10656
+#define DH_JHUF_HEADER_PRE 177                                       /* SOI, APP0, two DQT, SOF0: the staged markers in front of the DHTs */
+#define DH_JHUF_HEADER_SOS 14                                        /* ... and behind them */
+#define DH_JHUF_HIST_ROUNDS 4                                        /* blocks a lane of the histogram launch counts */
+#define DH_JHUF_HIST_BLOCKS (DH_JHUF_HIST_ROUNDS * DH_JHUF_GROUP)    /* ... and a workgroup: its work item */
+static_assert(DH_JHUF_OPT_HEADER + DH_JHUF_OPT_HEADER_MAX <= DH_JHUF_OPT_STRIDE && DH_JHUF_OPT_STRIDE % 16 == 0, "the regions fit the stride");
+static_assert(DH_JHUF_OPT_BITSVALS + 4 * 273 <= DH_JHUF_OPT_WORDS && DH_JHUF_OPT_TABS + 4096 <= DH_JHUF_OPT_BITSVALS, "the regions do not overlap");
+
 struct DhJencHeader {              // first bytes of the staging buffer; every off_* counts bytes from the buffer's start, 16-byte aligned
-  int32_t magic, B, nprepared, max_len_groups, max_stuff_groups, reserved[3];
+  int32_t magic, B, nprepared, max_len_groups, max_stuff_groups, optimize, reserved[2];   // optimize: 0 | 1, per-image tables in the workspace
   int64_t off_images, off_tabs, off_headers, used_bytes, workspace_bytes, coef_count, file_bytes, reserved2;
 };
 
@@ -132,6 +147,31 @@ DH_JHUF_HD bool dh_jhuf_walk(C& c, const int16_t v[64], int pred, int comp, E& e
   return true;
 }
 
+// The symbols of the same walk without a table (jchuff.c htest_one_block, the gather pass of optimize=True) over a sink
+// S { void add(int t, int sym); }: table t as C::tab numbers them, sym the DC category or the AC run / size byte, ZRL 0xF0 and EOB 0x00
+// among them.  false at the same values as dh_jhuf_walk; the sink has then taken a prefix of the block.
+template <class S>
+DH_JHUF_HD bool dh_jhuf_symbols(const int16_t v[64], int pred, int comp, S& s) {
+  const int tdc = comp == 0 ? 0 : 2, tac = tdc + 1;
+  const int diff = (int)v[0] - pred;
+  int nb = dh_jhuf_bit_length((unsigned)(diff < 0 ? -diff : diff));
+  if (nb > 11) return false;
+  s.add(tdc, nb);
+  int run = 0;
+  DH_JHUF_UNROLL
+  for (int k = 1; k < 64; ++k) {
+    const int a = v[dh_jhuf_zig(k)];
+    if (a == 0) { ++run; continue; }
+    while (run > 15) { s.add(tac, 0xf0); run -= 16; }
+    nb = dh_jhuf_bit_length((unsigned)(a < 0 ? -a : a));
+    if (nb > 10) return false;
+    s.add(tac, (run << 4) | nb);
+    run = 0;
+  }
+  if (run > 0) s.add(tac, 0);
+  return true;
+}
+
 struct DhJhufCount {               // the sink of the length phase
   uint32_t bits = 0;
   DH_JHUF_HD void put(unsigned, int len) { bits += (uint32_t)len; }
@@ -170,7 +210,22 @@ DH_JHUF_HD uint64_t dh_jhuf_lane_length(C& c, const DhJencImage& im, int64_t s) 
   const int pred = pred_el >= 0 ? c.dc(pred_el) : 0;
   DhJhufCount e;
   if (!dh_jhuf_walk(c, v, pred, comp, e)) return DH_JHUF_INVALID;
-  return e.bits < DH_JHUF_BLOCK_BITS ? e.bits : DH_JHUF_BLOCK_BITS;
+  // The standard tables never exceed the bound.  An image's own tables (optimize) can give one block 16-bit codes throughout, (16 + 11) +
+  // 63 * (16 + 10) = 1665 bits: such a block is flagged like a value without a code, and the image goes to the host stage.
+  return e.bits <= DH_JHUF_BLOCK_BITS ? e.bits : DH_JHUF_INVALID;
+}
+
+// The histogram launch of optimize, one lane per block s < im.nblocks: the block's symbols into the sink; false as dh_jhuf_lane_length
+// gives DH_JHUF_INVALID for a value (the image is flagged there; its statistics are then of no use)
+template <class C, class S>
+DH_JHUF_HD bool dh_jhuf_lane_symbols(C& c, const DhJencImage& im, int64_t s, S& sink) {
+  int64_t el, pred_el;
+  int comp;
+  dh_jhuf_locate(im, s, &el, &pred_el, &comp);
+  int16_t v[64];
+  c.load_block(el, v);
+  const int pred = pred_el >= 0 ? c.dc(pred_el) : 0;
+  return dh_jhuf_symbols(v, pred, comp, sink);
 }
 
 // Phase 3, the same walk: the block's codes from bit `bit` of the unstuffed buffer.  len: what phase 1 gave for the block; a block it

@@ -24,7 +24,7 @@ record then takes the fallback as before (reason "progressive").
     images = dec.decode_batch([record_bytes, ...])        # uint8 [H,W,3] device tensors: what preprocess_for_train takes
 
 JpegEncoder is the mirror: uint8 [H,W,3] RGB images -> baseline JFIF files, byte for byte what Pillow writes with
-save(f, "JPEG", quality=q, subsampling=s) (no optimize, no progressive).  Colour conversion, chroma downsampling, forward DCT and quantisation
+save(f, "JPEG", quality=q, subsampling=s) and, with optimize=True, save(..., optimize=True) (no progressive).  Colour conversion, chroma downsampling, forward DCT and quantisation
 are two launches per BATCH on the device (csrc/jpeg_encode_exact.hip); the quantised coefficients come back in one download - in the layout the
 decoder's entropy stage produces - and host threads write the Huffman scan and the markers (csrc/jpeg_encode.cpp).  Images in host memory
 (numpy arrays, CPU tensors) run the same integer code on the host, which is also what a process without a GPU gets.
@@ -36,14 +36,19 @@ With entropy="device" (opt-in; device images only) the Huffman stage runs on the
 launches per BATCH): block lengths, prefix sums, the codes written at their bit offsets, FF stuffing, markers and EOI.  The files are the
 same bytes.  No coefficient comes back: one download brings sizes and status words, one more the files themselves, packed back to back on
 the device first.  An image the device stage flags, or leaves to the host for its size, goes through the host stage, which stays the
-authority (stats["entropy_retry"])."""
+authority (stats["entropy_retry"]).
+
+optimize=True (off by default) gives the same pixels in a smaller file, as Pillow's flag of that name does: each image's Huffman tables are
+made from its own symbol statistics by libjpeg's rule (csrc/jpeg_encode.h) and the four DHT segments carry them.  The host stage counts
+and builds on its threads; the device stage puts three launches in front of its six - clear, a histogram of the coefficient blocks'
+symbols, the tables - so that still no coefficient comes back.  Both stages give Pillow's bytes."""
 import ctypes
 import time
 
 import numpy as np
 import torch
 
-from .._lib import JpegDesc, JpegEncDesc, JpegInfo, call, lib, ptr, stream
+from .._lib import JPEG_ENC_OPTIMIZE, JpegDesc, JpegEncDesc, JpegInfo, call, lib, ptr, stream
 from . import dataset_common
 
 MAX_THREADS = 16                                          # DANHIP_JPEG_MAX_THREADS
@@ -231,7 +236,7 @@ _SUBSAMPLING = {0: MODE_444, "4:4:4": MODE_444, 2: MODE_420, "4:2:0": MODE_420} 
 
 
 class JpegEncoder(object):
-    def __init__(self, quality=75, subsampling="4:2:0", threads=4, entropy="host"):
+    def __init__(self, quality=75, subsampling="4:2:0", threads=4, entropy="host", optimize=False):
         if entropy not in ("host", "device"):
             raise ValueError("entropy must be 'host' or 'device', got %r" % (entropy,))
         if subsampling not in _SUBSAMPLING:
@@ -242,6 +247,7 @@ class JpegEncoder(object):
         self.mode = _SUBSAMPLING[subsampling]
         self.threads = max(1, min(int(threads), MAX_THREADS))
         self.entropy = entropy
+        self.optimize = bool(optimize)
         self.stats = {"device": 0, "host": 0, "launches": 0, "entropy_seconds": 0.0, "download_bytes": 0, "entropy_device": 0,
                       "entropy_launches": 0, "entropy_retry": 0}
         self.coef = None                                  # the last device batch's coefficients on the host (tests compare them)
@@ -283,7 +289,11 @@ class JpegEncoder(object):
         nstaging = L.danhip_jpeg_encode_scan_staging_bytes(B)
         staging = torch.empty(nstaging, dtype=torch.uint8, pin_memory=True)
         prepared = (ctypes.c_int32 * B)()
-        call("danhip_jpeg_encode_scan_prepare", descs, B, ncoef, nfile, ctypes.c_void_p(staging.data_ptr()), nstaging, prepared)
+        if self.optimize:
+            call("danhip_jpeg_encode_scan_prepare_ex", descs, B, ncoef, nfile, JPEG_ENC_OPTIMIZE, ctypes.c_void_p(staging.data_ptr()), nstaging,
+                 prepared)
+        else:
+            call("danhip_jpeg_encode_scan_prepare", descs, B, ncoef, nfile, ctypes.c_void_p(staging.data_ptr()), nstaging, prepared)
         staging_dev = staging.to(dev, non_blocking=True)
         ws = self._buffer("workspace", max(L.danhip_jpeg_encode_scan_workspace_bytes(ctypes.c_void_p(staging.data_ptr())), 16), dev)
         files = self._buffer("files", nfile, dev)
@@ -364,7 +374,11 @@ class JpegEncoder(object):
         files = np.empty(totals[2], dtype=np.uint8)       # the bound of every file; pages a file does not reach are never touched
         sizes = (ctypes.c_int64 * B)()
         t0 = time.perf_counter()
-        call("danhip_jpeg_encode_entropy_batch", ctypes.c_void_p(coef.data_ptr()), ncoef, descs, B, self.threads, ctypes.c_void_p(files.ctypes.data),
-             totals[2], sizes)
+        if self.optimize:
+            call("danhip_jpeg_encode_entropy_batch_ex", ctypes.c_void_p(coef.data_ptr()), ncoef, descs, B, self.threads, JPEG_ENC_OPTIMIZE,
+                 ctypes.c_void_p(files.ctypes.data), totals[2], sizes)
+        else:
+            call("danhip_jpeg_encode_entropy_batch", ctypes.c_void_p(coef.data_ptr()), ncoef, descs, B, self.threads,
+                 ctypes.c_void_p(files.ctypes.data), totals[2], sizes)
         self.stats["entropy_seconds"] += time.perf_counter() - t0
         return [files[descs[i].file_offset:descs[i].file_offset + sizes[i]].tobytes() for i in range(B)]

@@ -7,7 +7,7 @@ the boxes with score > 0.2 on the image and write it to debug_dir/<name>.jpg.
 Flags carry the reference's names and defaults (each script's tf.app.flags block; tests/golden/eval_flags.json).  Accepted and ignored:
 data_format, num_classes, train_image_size and batch_size (the reference's graph takes one image of any size; they configure nothing
 there either).  The port's own: --device, --precision, --batch_images (JPEGs read, decoded and detected as one group), --decode_entropy, --encode_entropy,
---image_list (one `event/name` per line instead of wider_face_split/wider_face_<subset>.mat, which needs scipy), --gt_dir (the directory
+--encode_optimize (the debug images' encoder makes each image's own Huffman tables, as Pillow's optimize=True; off by default), --image_list (one `event/name` per line instead of wider_face_split/wider_face_<subset>.mat, which needs scipy), --gt_dir (the directory
 of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat / wider_hard_<subset>.mat: the average precision is
 computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default) and
 --lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
@@ -77,6 +77,8 @@ def build_parser(model):
     p.add_argument("--decode_entropy", choices=("host", "device"), default="host", help="where the JPEG Huffman stage of the decoder runs (default host)")
     p.add_argument("--encode_entropy", choices=("host", "device"), default="host",
                    help="where the JPEG Huffman stage of the debug images' encoder runs (default host; the files are the same bytes)")
+    p.add_argument("--encode_optimize", action="store_true",
+                   help="debug images with Huffman tables of their own, as Pillow's save(optimize=True): the same pixels in smaller files (default off)")
     p.add_argument("--image_list", default=None, help="text file with one event/name per line, instead of wider_face_split/wider_face_<subset>.mat")
     p.add_argument("--gt_dir", default=None, help="directory of wider_face_<subset>.mat and wider_{easy,medium,hard}_<subset>.mat: compute and print the AP")
     p.add_argument("--debug_quality", type=int, default=75, help="JPEG quality of the debug images (default 75)")
@@ -206,7 +208,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     print("restored %s: %d variables" % (path, len(names)), file=out, flush=True)
 
     decoder = JpegDecoder(device, entropy=args.decode_entropy)
-    encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy) if args.debug_dir else None
+    encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy, optimize=args.encode_optimize) if args.debug_dir else None
     if args.debug_dir:
         os.makedirs(args.debug_dir, exist_ok=True)
     min_height = MIN_HEIGHT[model]

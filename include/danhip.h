@@ -1083,8 +1083,9 @@ int danhip_crc32c_batch(const danhip_crc_segment* table_host, int32_t n, uint32_
  * parts from the textbook (edges and dummy blocks, the reciprocal quantiser, the quality scaling, APP0).
  *
  * Scope: quality 1 .. 100; mode DANHIP_JPEG_420 (Pillow's default, subsampling=2) or DANHIP_JPEG_444 (subsampling=0); sides 1 ..
- * DANHIP_JPEG_MAX_DIM; no optimize, no progressive.  The file is SOI, JFIF APP0, two DQT, SOF0, four DHT (the standard tables of T.81
- * K.3), SOS, the stuffed scan padded with 1 bits, EOI.  Grey input, 4:2:2, restart intervals and optimised tables are not made.
+ * DANHIP_JPEG_MAX_DIM; optimize=True through the calls of "JPEG encode: optimised Huffman tables" below; no progressive.  The file is SOI,
+ * JFIF APP0, two DQT, SOF0, four DHT (the standard tables of T.81 K.3, or the image's own), SOS, the stuffed scan padded with 1 bits, EOI.
+ * Grey input, 4:2:2, restart intervals and progressive files are not made.
  *
  * danhip_jpeg_encode_prepare: one descriptor per image from (width, height) and the call's (mode, quality): geometry by the rules of the
  *   decoder (whole MCUs), reciprocal quantisation tables, and offsets handed out in order into the coefficient buffer (int16 elements), the
@@ -1192,6 +1193,48 @@ int danhip_jpeg_encode_huffman_batch(const void* staging_host, const void* stagi
 int danhip_jpeg_encode_entropy_emulate_batch(const void* staging, size_t staging_bytes, const danhip_jpeg_enc_desc* descs, int32_t B,
                                              const int16_t* coef, int64_t coef_count, uint8_t* files_out, int64_t file_bytes,
                                              int64_t* sizes_out, int32_t* status_out, int64_t* range_errors);
+
+/* --------------------------------------------------------------------------------------------------
+ * JPEG encode: optimised Huffman tables (ABI version 20), opt-in: the bytes of Pillow's save(..., optimize=True) - the same coefficients,
+ * coded with tables made from the image's own symbol statistics by libjpeg's jpeg_gen_optimal_table rule (csrc/jpeg_encode.h
+ * dh_jenc_optimal_table says where that is not the textbook Huffman code).  The layout of the file is unchanged; the four DHT segments
+ * (DC 0, AC 0, DC 1, AC 1 in front of SOS) carry the image's tables.  Every call above keeps its prototype, its launches and its bytes.
+ *
+ * danhip_jpeg_optimal_table_host: the table rule alone.  counts[257]: occurrences of symbol 0 .. 255 (entry 256 is not read: the rule gives
+ *   the reserved pseudo-symbol the count 1); bits_out[l] = codes of length l, bits_out[0] = 0; vals_out: the symbols in DHT order, 0 behind
+ *   the last.  DANHIP_EINVAL when the counts sum to 2^31 - 1 or more or give a code of more than 32 bits before the cut to 16 bits.
+ * danhip_jpeg_encode_entropy_batch_ex: danhip_jpeg_encode_entropy_batch with flags; DANHIP_JPEG_ENC_OPTIMIZE makes each thread count its
+ *   image's symbols (every block the scan writes, dummy blocks included), build the four tables and write the scan with them.
+ * danhip_jpeg_encode_scan_prepare_ex: danhip_jpeg_encode_scan_prepare with flags.  With DANHIP_JPEG_ENC_OPTIMIZE the staging buffer asks
+ *   danhip_jpeg_encode_huffman_batch for DANHIP_JPEG_ENCODE_OPTIMIZE_LAUNCHES launches in front of its own, whatever B, the sizes and the
+ *   data are (*launches is then the sum), and the workspace grows by danhip_jpeg_encode_optimize_layout's stride per image:
+ *     1 clear      one workgroup per image zeroes the image's region
+ *     2 histogram  (work item, image): a workgroup counts the symbols of up to out[6] blocks in scan order - a lane per block and round, the
+ *                  DC predictor taken as the length launch takes it - into one 4 x 257 uint32 table per wave in LDS (integer LDS atomics),
+ *                  then adds the non-zero sums into the image's table (integer global atomics: the result does not depend on the order)
+ *     3 tables     one workgroup per image, one wave per table, its first lane runs dh_jenc_optimal_table over LDS; then all lanes write
+ *                  bits / vals, the code | length << 16 table the length and write launches read, and the image's markers: the staged
+ *                  ones with the four DHT segments replaced
+ *   The six launches then read tables, markers and marker length through the image's region.  A symbol that does not occur has no code.
+ *   The device's own bounds hold as before: a block of more than 1658 bits - possible only with own tables, at most 1665 - is flagged like
+ *   a value without a code (DANHIP_JPEG_ENC_DEV_RANGE) and the image goes to the host stage; the markers are at most as long as the standard
+ *   ones when every value has a baseline code (12 DC and 162 AC symbols at most), and their region holds out[7] bytes, four full segments.
+ *   danhip_jpeg_encode_entropy_emulate_batch refuses such a staging buffer.
+ * danhip_jpeg_encode_optimize_layout: out[8] = {region stride, offsets in a region of: the counts (uint32 [4][257]), the code | length table
+ *   (uint32 [4][256]), bits / vals (uint8 [4][17 + 256]), the words (int32 [4], the first the markers' length), the markers; blocks per
+ *   work item of the histogram launch; the markers' capacity}.  Image i's region starts at byte i * stride of the workspace.
+ * danhip_jpeg_optimal_tables_device: the tables launch alone over n regions in device memory (16-byte aligned, n * stride bytes) whose
+ *   counts the caller filled: writes the code | length table and bits / vals of each (the markers are left alone).  For tests of the rule.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_JPEG_ENCODE_OPTIMIZE_LAUNCHES 3
+#define DANHIP_JPEG_ENC_OPTIMIZE 1      /* flags of the _ex calls */
+int danhip_jpeg_optimal_table_host(const int32_t counts[257], uint8_t bits_out[17], uint8_t vals_out[256]);
+int danhip_jpeg_encode_entropy_batch_ex(const int16_t* coef, int64_t coef_count, const danhip_jpeg_enc_desc* descs, int32_t B, int32_t threads,
+                                        int32_t flags, uint8_t* files_out, int64_t files_capacity, int64_t* sizes_out);
+int danhip_jpeg_encode_scan_prepare_ex(const danhip_jpeg_enc_desc* descs, int32_t B, int64_t coef_count, int64_t file_bytes, int32_t flags,
+                                       void* staging, size_t staging_bytes, int32_t* status_out);
+int danhip_jpeg_encode_optimize_layout(int32_t out[8]);                              /* returns the stride; out may be NULL */
+int danhip_jpeg_optimal_tables_device(void* regions_dev, int32_t n, void* stream);
 
 /* --------------------------------------------------------------------------------------------------
  * Box drawing on uint8 [H,W,3] device images (ABI version 15; csrc/draw_exact.hip): the rectangles of utility/draw_toolbox.py
