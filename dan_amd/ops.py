@@ -2059,7 +2059,44 @@ def batch_norm_train(x, gamma, beta, moving_mean=None, moving_var=None, eps=1e-5
     return _BatchNorm.apply(x, gamma, beta, moving_mean, moving_var, eps, momentum, relu)
 
 
+class _BatchNormFrozen(torch.autograd.Function):
+    """tf.layers.batch_normalization(training=False) (+ optional ReLU) where a gradient is tracked (frozen statistics: freeze_bn, or a unit
+    differentiated in inference mode): y = (x - mean) rstd gamma + beta with the moving statistics as constants, so dx = dy gamma rstd,
+    dgamma = sum dy xhat, dbeta = sum dy.  Backward is two existing launches: danhip_batchnorm_bwd for the two sums (its dx, which
+    subtracts the batch means of the training form, goes to a scratch tensor) and the apply kernel on dy with mean = beta = 0 for dx."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, mean, rstd, relu):
+        C = x.shape[-1]
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        call("danhip_batchnorm_fwd_infer", ptr(x), ptr(gamma.detach()), ptr(beta.detach()), ptr(mean), ptr(rstd), ptr(y), x.numel() // C, C, int(relu), stream())
+        ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else None)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd, y = ctx.saved_tensors
+        C = x.shape[-1]
+        M = x.numel() // C
+        dy = dy.contiguous()
+        if ctx.relu:
+            dy = dy.clone()
+            call("danhip_relu_bwd_bias_grad", ptr(dy), ptr(y), None, M, C, stream())
+        dx, unused = torch.empty_like(x), torch.empty_like(x)
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        zero = torch.zeros(C, dtype=torch.float32, device=x.device)
+        call("danhip_batchnorm_bwd", ptr(x), ptr(dy), ptr(gamma), ptr(mean), ptr(rstd), ptr(unused), ptr(dgamma), ptr(dbeta), M, C, stream())
+        call("danhip_batchnorm_fwd_infer", ptr(dy), ptr(gamma), ptr(zero), ptr(zero), ptr(rstd), ptr(dx), M, C, 0, stream())
+        return dx, dgamma, dbeta, None, None, None
+
+
 def batch_norm_infer(x, gamma, beta, moving_mean, moving_var, eps=1e-5, relu=False):
+    if torch.is_grad_enabled() and x.dtype == ACT and not _is_limbs(x) and (x.requires_grad or gamma.requires_grad or beta.requires_grad):
+        # (without this the call below would cut the graph: nothing in front of a frozen batch norm received a gradient)
+        return _BatchNormFrozen.apply(x, gamma, beta, moving_mean, torch.rsqrt(moving_var + eps), relu)
     x = _f32_in(x)
     C = x.shape[-1]
     y = torch.empty_like(x)

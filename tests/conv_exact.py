@@ -236,6 +236,20 @@ def check_dgrad_inputs(inp):
     assert int((m == 0).sum()) >= 1 and int((m < 0).sum()) >= 1 and int((m > 0).sum()) >= 1
 
 
+def check_dgrad_unreached(inp, shp):
+    """A 1x1 / stride-2 data gradient has no term on a pixel with an odd row or column: the reference is 0 there and the buffer the call
+    finds is not - so the acc = 0 comparison is a test of the zero store, the acc = 1 one of leaving the old value.  (A 1x1 map has no such
+    pixel; the first half holds there emptily.)  -> the number of unreached pixels"""
+    if not (shp[5] == 1 and shp[6] == 1 and shp[7] == 2):
+        return None
+    H, W = shp[1], shp[2]
+    odd = ((torch.arange(H) % 2 == 1).reshape(H, 1) | (torch.arange(W) % 2 == 1).reshape(1, W)).reshape(1, H, W, 1)
+    assert int(((inp["dx"] != 0) & odd).sum()) == 0, "a 1x1 / stride-2 data gradient with a term on an odd row or column"
+    if H * W > 1:
+        assert int(((inp["old"] != 0) & odd).sum()) >= 1, "the pre-filled dx is zero on every unreached pixel: a missing zero store would not show"
+    return int(odd.sum()) * shp[0]
+
+
 def check_wgrad_inputs(inp):
     x = inp["x"]
     assert x.shape[0] * x.shape[1] * x.shape[2] + 8 < 2 ** 24 and inp["dw"].abs().max().item() < 2 ** 24 and inp["db"].abs().max().item() < 2 ** 24
@@ -462,6 +476,32 @@ VALID_CASES = [
     ("fwd_valid_3x3", "fwd", S(1, 9, 11, 64, 64), FLAT + "256, 64, 1, true>", None, "splitk"),
     ("dgrad_valid_3x3", "dgrad", S(1, 9, 11, 64, 64), FLAT + "256, 64, 1, true>", None, "splitk"),
     ("wgrad_valid_3x3", "wgrad", S(1, 9, 11, 64, 64), "conv_wgrad_kernel<64, 64, 2>", None, ""),
+]
+
+# ---- the ResNet backbone's convolutions (net/resnet_danet.py) at its channel counts: the 1x1 / stride-2 projection shortcut and `reduce`
+# (padding='valid', what the backbone passes; for a 1x1 window 'valid' and 'same' describe the same map, one shape runs under both), K or
+# Cout of 2048, and the 3x3 / stride-2 extra layers on the 2x2 and 1x1 maps a 64-pixel input leaves them.
+# A 1x1 / stride-2 data gradient reaches one pixel in four: acc = 0 must store 0 on the others (dx is pre-filled with `old`), acc = 1 must
+# leave `old` there; the weight gradient must skip the same three quarters of x; an odd map samples its last row and column, an even one
+# never reads them.
+#   (id, shape, valid, forward family, forward extra, data-gradient family, data-gradient extra, weight-gradient family); the families are the
+#   label functions' answers, extra "splitk" where plan_splitk splits K on 256 CUs.  Forward: the streaming GEMM takes 2048 output pixels and
+#   up - pw_s2_taps is the projection on a map large enough for its one-tap TAPS form, every other shape runs the flat-M kernel.  Data
+#   gradient: the streaming GEMM declines dstride != 1, so every stride-2 shape is the flat-M kernel's fractionally strided gather.
+F128 = FLAT + "128, 128, 2, true>"
+WG128 = "conv_wgrad_kernel<128, 128, 2>"
+RESNET_CASES = [
+    ("pw_s2_256_512", S(2, 15, 17, 256, 512, 1, 2), True, F128, "", F128, "splitk", WG128),              # projection shortcut, odd map
+    ("pw_s2_256_512_same", S(2, 15, 17, 256, 512, 1, 2), False, F128, "", F128, "splitk", WG128),
+    ("pw_s2_256_128", S(2, 15, 17, 256, 128, 1, 2), True, F128, "", F128, "", WG128),                    # strided reduce
+    ("pw_s2_512_1024_even", S(2, 8, 10, 512, 1024, 1, 2), True, F128, "splitk", F128, "splitk", WG128),  # even map: last row / column never read
+    ("pw_s2_1024_2048", S(1, 9, 7, 1024, 2048, 1, 2), True, F128, "splitk", F128, "splitk", WG128),      # the widest projection
+    ("pw_s2_1x1map", S(2, 1, 1, 256, 512, 1, 2), True, F128, "", F128, "splitk", WG128),                 # one pixel in, one pixel out
+    ("pw_k2048", S(1, 5, 7, 2048, 512, 1, 1), True, F128, "splitk", F128, "splitk", WG128),              # conv6_1
+    ("pw_cout2048", S(1, 6, 6, 512, 2048, 1, 1), True, F128, "splitk", F128, "splitk", WG128),           # increase of the last stage
+    ("x3s2_2x2", S(2, 2, 2, 512, 512, 3, 2), False, F128, "splitk", F128, "splitk", WG128),              # conv6_2: 2x2 -> 1x1
+    ("x3s2_1x1map", S(2, 1, 1, 128, 256, 3, 2), False, F128, "splitk", F128, "splitk", WG128),           # conv7_2: only the centre tap exists
+    ("pw_s2_taps", S(2, 63, 67, 256, 512, 1, 2), True, PW + "256, 3, false, true, true>", "", F128, "splitk", WG128),      # 32 x 34 outputs: 17 items
 ]
 
 # ---- channel-slice views (danhip_conv2d_{fwd,bwd_data,bwd_weight}_strided): every operand is channels c0 : c0 + C of a wider NHWC buffer whose
@@ -788,6 +828,9 @@ def all_cases():
     out += [("pool_" + n, "pool", s, f, dict(edge="")) for n, s, f in POOL_EDGES]
     out += [("fold_%dx%dx%d" % nhw, "fold", S(*nhw, 64, 64), "conv3x3_c64_kernel<true, true>", dict(edge="")) for nhw in FOLD_SHAPES]
     out += [(n, k, s, f, dict(edge=e, cin_real=c, valid=True)) for n, k, s, f, c, e in VALID_CASES]
+    for n, s, v, ff, fe, df, de, wf in RESNET_CASES:
+        out += [("fwd_" + n, "fwd", s, ff, dict(edge=fe, valid=v)), ("dgrad_" + n, "dgrad", s, df, dict(edge=de, valid=v)),
+                ("wgrad_" + n, "wgrad", s, wf, dict(edge="", valid=v))]
     out += [("vfwd_" + n, "vfwd", s, f, dict(edge=e, geom=g, inside=i)) for n, s, f, g, i, e in VFWD_CASES]
     out += [("vdgrad_" + n, "vdgrad", s, f, dict(edge=e, geom=g)) for n, s, f, g, e in VDGRAD_CASES]
     out += [("vwgrad_" + n, "vwgrad", s, f, dict(edge=e, geom=g)) for n, s, f, g, e in VWGRAD_CASES]
@@ -816,7 +859,8 @@ def check_case_inputs(case, cus=256):
         check_dgrad_inputs(inp)
         if edge == "splitk":
             assert plan_splitk(shp, 1, cus, valid)[0] >= 2, "the case is there for a split K"
-        return dict(max=inp["dx"].abs().max().item())
+        unreached = check_dgrad_unreached(inp, shp)
+        return dict(max=inp["dx"].abs().max().item(), **({} if unreached is None else dict(unreached=unreached)))
     if kind == "wgrad":
         inp = wgrad_inputs(shp, cin_real=extra.get("cin_real"), valid=valid)
         check_wgrad_inputs(inp)
@@ -869,6 +913,7 @@ MOVED = {
     "dgrad_taps_192_320": _SPLITS + (("plain", PW),),
     "dgrad_pw256_3x3": _SPLITS,
     "row_pointwise_dgrad": (("acc", PW),),
+    "fwd_pw_s2_taps": _NO_F32_RES,                                    # (no split: K = 256 is four K tiles; every other ResNet row is flat-M in every variant)
     "fold_1x30x62": (("unfolded", "conv3x3_c64_kernel<true>"),),      # the same kernel without the folded gradient
     "fold_3x40x96": (("unfolded", "conv3x3_c64_kernel<true>"),),
 }
@@ -985,6 +1030,7 @@ def run_dgrad(api, cid, shp, family, extra):
     valid = bool(extra.get("valid"))
     inp = dgrad_inputs(shp, valid=valid)
     check_dgrad_inputs(inp)
+    check_dgrad_unreached(inp, shp)
     d, L, ptr = api.desc(shp, valid), api.L, api.ptr
     dp = ctypes.byref(d)
     dy, mask, old = api.a16(inp["dy"]), api.a16(inp["mask"]), api.a16(inp["old"])

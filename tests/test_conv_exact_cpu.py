@@ -154,6 +154,48 @@ def test_case_meets_its_conditions_on_the_reference(case):
     print(case[0], figs)
 
 
+def test_resnet_rows_are_listed_under_the_families_the_label_functions_name():
+    """The ResNet table's families are the host label functions' answers (256 CUs without a device), with and without scratch and for the
+    plain and the masked data gradient; at least one forward row is the streaming GEMM's tap form with a 1x1 window, at least one data
+    gradient the flat-M kernel at stride 2 (its fractionally strided gather: the streaming GEMM declines dstride != 1); 'valid' and 'same'
+    of a 1x1 window are one descriptor and one reference; the unreached-pixel condition fails on a reference with a term there."""
+    from dan_amd import build as B
+    from dan_amd._lib import ConvDesc, bind
+    B.build()
+    L = bind(ctypes.CDLL(B.OUT))
+    taps_1x1 = strided_gather = 0
+    for n, shp, valid, ff, fe, df, de, wf in CE.RESNET_CASES:
+        N, H, W, Cin, Cout, kh, kw, s = shp
+        d = ConvDesc()
+        d.N, d.H, d.W, d.Cin, d.Cout, d.kh, d.kw, d.stride = N, H, W, Cin, Cout, kh, kw, s
+        d.Ho, d.Wo = CE.out_size(H, kh, s, valid), CE.out_size(W, kw, s, valid)
+        p = ctypes.byref(d)
+        assert (d.Ho, d.Wo) == (CE.out_size(H, kh, s, not valid), CE.out_size(W, kw, s, not valid)) or kh > 1
+        for scratch in (0, 16):
+            assert L.danhip_conv_kernel_label(p, 0 | scratch).decode() == ff, (n, scratch)
+            for which in (1, 5):
+                assert L.danhip_conv_kernel_label(p, which | scratch).decode() == df, (n, which, scratch)
+        assert L.danhip_conv_wgrad_kernel_label(p).decode() == wf, n
+        assert (fe == "splitk") == (CE.plan_splitk(shp, 0, 256, valid)[0] >= 2) and (de == "splitk") == (CE.plan_splitk(shp, 1, 256, valid)[0] >= 2), n
+        taps_1x1 += ff.startswith(CE.PW) and ff.endswith("true>") and kh == kw == 1
+        strided_gather += df.startswith(CE.FLAT) and s == 2
+    assert taps_1x1 >= 1 and strided_gather >= 1
+    shp = CE.S(2, 15, 17, 256, 512, 1, 2)
+    for make, keys in ((CE.forward_inputs, ("pre",)), (CE.dgrad_inputs, ("dx",)), (CE.wgrad_inputs, ("dw", "db"))):
+        a, b = make(shp, valid=True), make(shp, valid=False)
+        assert all(torch.equal(a[k], b[k]) for k in keys)
+    inp = dict(CE.dgrad_inputs(shp, valid=True))
+    assert CE.check_dgrad_unreached(inp, shp) == 2 * (15 * 17 - 8 * 9)
+    inp["dx"] = inp["dx"].clone()
+    inp["dx"][0, 1, 0, 0] = 1.0
+    with pytest.raises(AssertionError):
+        CE.check_dgrad_unreached(inp, shp)
+    inp = dict(CE.dgrad_inputs(shp, valid=True))
+    inp["old"] = torch.zeros_like(inp["old"])
+    with pytest.raises(AssertionError):
+        CE.check_dgrad_unreached(inp, shp)
+
+
 def test_average_pool_reference_is_the_oracle_pool():
     g = torch.Generator().manual_seed(4)
     x = torch.randn((2, 5, 7, 3), generator=g).double()
