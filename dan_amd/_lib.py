@@ -346,6 +346,10 @@ _TABLE = {
     "danhip_conv_transpose4x4s2_wgrad_slabs": (I32, [I32] * 7),
     "danhip_conv_transpose4x4s2_wgrad": (STATUS, [P, P, P, P] + [I32] * 7 + [P, SZ, P]),
     "danhip_conv_transpose4x4s2_add_fwd_f32": (STATUS, [P, P, P, P, P] + [I32] * 7 + [P]),
+    # ---- fused batch-norm tails (batch norm + residual add + ReLU)
+    "danhip_bn_act_fwd_train": (STATUS, [P, P, P, P, P, P, P, P, P, I64, I32, FL, FL, INT, P, P]),
+    "danhip_bn_act_fwd_infer": (STATUS, [P, P, P, P, P, P, P, I64, I32, INT, P]),
+    "danhip_bn_act_bwd": (STATUS, [P, P, P, P, P, P, P, P, P, P, I64, I32, INT, P]),
 }
 PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
 SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for

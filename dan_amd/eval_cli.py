@@ -12,6 +12,8 @@ of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat
 computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default) and
 --lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
 train_*'s flag of the same name.  transposed has no split-operand form: with --precision split the command exits with a message.
+--backbone {vgg16,resnet50,resnet101,resnet152} (eval_dan; default vgg16) is train_dan's flag of the same name: batch norm runs on the
+checkpoint's moving statistics.  It has no fp32 or split-operand kernel: a ResNet backbone runs with --precision act only (a message otherwise).
 
 Per group: the files are read, decoded on the device (dataset.jpeg.JpegDecoder; a stream it refuses takes its Pillow fallback) and
 detected (eval_dan.detect_image_list); ONE download brings (dets, num) to the host for the text files; the evaluator takes the device
@@ -54,6 +56,7 @@ DEBUG_SCORE = 0.2            # eval_dan.py:456
 PYRAMID = {"sfd": False, "pb": True, "dan": True, "dan_deform": True}       # eval_sfd.py:323-328 has no multi_scale_test_pyramid
 MIN_HEIGHT = {"sfd": 10, "pb": 9, "dan": 10, "dan_deform": 10}              # write_to_txt's row filter (eval_pb.py:252)
 LFPN_UPSAMPLE = ("bilinear", "transposed")                                  # --lfpn_upsample (net/pb_net.py LFPN_UPSAMPLE)
+BACKBONES = ("vgg16", "resnet50", "resnet101", "resnet152")                 # --backbone (train_dan.BACKBONES)
 
 
 def flag_defaults(model):
@@ -88,6 +91,10 @@ def build_parser(model):
         p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
                        help="the LFPN of the checkpoint's graph: bilinear resize (default) or the learnable 4x4 stride-2 transposed convolution "
                             "(train_*'s --lfpn_upsample transposed); transposed does not run with --precision split")
+    if model == "dan":                                                      # (the reference has no deformable ResNet backbone)
+        p.add_argument("--backbone", choices=BACKBONES, default="vgg16",
+                       help="the backbone of the checkpoint's graph: vgg16 (default) or a ResNet with batch norm (train_dan's --backbone); "
+                            "a ResNet runs with --precision act only")
     return p
 
 
@@ -140,7 +147,7 @@ def ground_truth(args):
 
 
 # ------------------------------------------------------------------------------------------------------------ the models
-def build_detector(model, device, precision, seed=20180817, lfpn_upsample="bilinear"):
+def build_detector(model, device, precision, seed=20180817, lfpn_upsample="bilinear", backbone="vgg16"):
     """eval_dan.Detector around the model's inference graph with its script's anchors.  The variables are created here, by one forward
     of a 64 x 64 image (their shapes do not depend on the image size), so that a checkpoint finds them: the store makes a variable when a
     layer first asks for it."""
@@ -155,7 +162,8 @@ def build_detector(model, device, precision, seed=20180817, lfpn_upsample="bilin
         net = eval_dan.Detector(PBModel(device=device, seed=seed, lfpn_upsample=lfpn_upsample), lambda h, w, d: AnchorConfig(h, w, d), precision)     # ratios (1.,): eval_pb.py:311
     else:
         from .train_dan import DANModel, dan_anchor_config
-        net = eval_dan.Detector(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=lfpn_upsample), dan_anchor_config, precision)
+        net = eval_dan.Detector(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=lfpn_upsample, backbone=backbone), dan_anchor_config,
+                                precision)
     with torch.no_grad():
         net.model.forward(torch.zeros((1, 64, 64, 3), dtype=torch.uint8, device=device))
     return net
@@ -185,6 +193,9 @@ def main(argv=None, model="sfd", gt=None, out=None):
     lfpn_upsample = getattr(args, "lfpn_upsample", "bilinear")
     if lfpn_upsample == "transposed" and args.precision == "split":
         raise SystemExit("--lfpn_upsample transposed has no split-operand form: use --precision act or fp32")
+    backbone = getattr(args, "backbone", "vgg16")
+    if backbone != "vgg16" and args.precision != "act":
+        raise SystemExit("--backbone %s runs with --precision act only: batch norm has no fp32 or split-operand kernel" % backbone)
     import torch
     from . import eval_dan
     from .dataset.jpeg import JpegDecoder, JpegEncoder
@@ -196,7 +207,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     if gt is None and args.gt_dir:
         gt = ground_truth(args)
 
-    net = build_detector(model, device, args.precision, lfpn_upsample=lfpn_upsample)
+    net = build_detector(model, device, args.precision, lfpn_upsample=lfpn_upsample, backbone=backbone)
     path = args.checkpoint_path
     if os.path.isdir(path):
         path = checkpoint.latest_checkpoint(path)

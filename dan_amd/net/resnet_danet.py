@@ -11,19 +11,37 @@ class ResNetBackbone(danet.VGG16Backbone):
     _block_settings = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}                       # :106-110
 
     def __init__(self, depth=50, data_format="channels_last", freeze_bn=False, bn_epsilon=1e-05, bn_momentum=0.997, use_fused_bn=True,
-                 variables=None):
+                 variables=None, fused_tail=False):
+        """fused_tail: every batch norm runs on the fused tail kernels (ops.batch_norm_act_*: one apply pass, masked two-launch backward) and a
+        bottleneck unit ends in ONE such call - increase's batch norm + shortcut + ReLU - instead of batch norm, torch add, torch ReLU.  Same
+        variables, names, creation order and buffers either way."""
         super().__init__(data_format, bn_epsilon, bn_momentum, use_fused_bn, variables=variables)
         if depth not in self._block_settings:
             raise ValueError("depth must be 50, 101 or 152")
         self._depth = depth
         self._bn_trainable = not freeze_bn
+        self._fused_tail = bool(fused_tail)
 
     # conv (no bias, 'same' or 'valid') -> batch norm -> optional ReLU; batch statistics only when training and BN is trainable (:183-184)
-    def _cbn(self, inputs, filters, kernel_size, strides, scope, training, padding, relu):
+    def _cbn(self, inputs, filters, kernel_size, strides, scope, training, padding, relu, shortcut=None):
         kh, kw = kernel_size
         w = self.vs.get(scope + "/conv2d/kernel", (kh, kw, getattr(inputs, "_real_channels", inputs.shape[-1]), filters), "glorot")
         y = ops.conv2d(inputs, w, None, stride=strides, relu=False, padding=padding)
-        return self._bn(y, scope, training and self._bn_trainable, relu=relu)
+        if not self._fused_tail:
+            assert shortcut is None
+            return self._bn(y, scope, training and self._bn_trainable, relu=relu)
+        return self._bn_act(y, scope, training and self._bn_trainable, relu, shortcut)
+
+    def _bn_act(self, inputs, scope, training, relu, shortcut):
+        """sfd_net's _bn (the same variables and buffers in the same order) on the fused tail kernels, with the unit's shortcut folded in."""
+        c = inputs.shape[-1]
+        gamma = self.vs.get(scope + "/bn/gamma", (c,), 1.0)
+        beta = self.vs.get(scope + "/bn/beta", (c,), "zeros")
+        mm = self.vs.buffer(scope + "/bn/moving_mean", (c,), 0.0)
+        mv = self.vs.buffer(scope + "/bn/moving_variance", (c,), 1.0)
+        if training:
+            return ops.batch_norm_act_train(inputs, gamma, beta, mm, mv, eps=self._bn_epsilon, momentum=self._bn_momentum, relu=relu, shortcut=shortcut)
+        return ops.batch_norm_act_infer(inputs, gamma, beta, mm, mv, eps=self._bn_epsilon, relu=relu, shortcut=shortcut)
 
     def conv_bn_relu(self, inputs, filters, kernel_size, strides, scope, training, padding="same", dilate_rate=1, reuse=None):
         """net/resnet_danet.py:176-191."""
@@ -41,6 +59,8 @@ class ResNetBackbone(danet.VGG16Backbone):
         y = self.conv_bn_relu(inputs, filters // 2, (1, 1), strides, scope + "/reduce", training, padding="valid")
         # the reference pads by one pixel and convolves 'valid': identical to the 3x3 'same' convolution at stride 1
         y = self.conv_bn_relu(y, filters // 2, (3, 3), 1, scope + "/block_3x3", training, padding="same")
+        if self._fused_tail:                                                                       # increase's batch norm + shortcut + ReLU: one call
+            return self._cbn(y, filters * 2, (1, 1), 1, scope + "/increase", training, "same", True, shortcut=shortcut)
         y = self.conv_bn(y, filters * 2, (1, 1), 1, scope + "/increase", training)
         return torch.relu(y + shortcut)
 

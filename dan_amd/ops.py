@@ -2105,6 +2105,81 @@ def batch_norm_infer(x, gamma, beta, moving_mean, moving_var, eps=1e-5, relu=Fal
     return y
 
 
+class _BatchNormAct(torch.autograd.Function):
+    """Batch norm (+ residual add) (+ ReLU) as ONE node on the fused tail kernels (csrc/bn_act.hip): y = act(xhat gamma + beta + shortcut),
+    the tail of conv_bn / conv_bn_relu and of a bottleneck unit (net/resnet_danet.py:157-218).  frozen: the moving statistics are constants
+    (training=False with a gradient tracked).  Backward is one library call - two launches - on dy as it comes: the ReLU mask [y > 0] is
+    applied inside both passes, and the shortcut's gradient is written by the pass that writes dx."""
+
+    @staticmethod
+    def forward(ctx, x, shortcut, gamma, beta, moving_mean, moving_var, eps, momentum, relu, frozen):
+        C = x.shape[-1]
+        M = x.numel() // C
+        y = torch.empty_like(x)
+        if frozen:
+            mean, rstd = moving_mean, torch.rsqrt(moving_var + eps)
+            call("danhip_bn_act_fwd_infer", ptr(x), ptr(shortcut), ptr(gamma.detach()), ptr(beta.detach()), ptr(mean), ptr(rstd), ptr(y), M, C, int(relu),
+                 stream())
+        else:
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+            ws = torch.empty(2 * C, dtype=torch.float64, device=x.device)      # sum x, sum x^2 in double
+            call("danhip_bn_act_fwd_train", ptr(x), ptr(shortcut), ptr(gamma.detach()), ptr(beta.detach()), ptr(y), ptr(mean), ptr(rstd), ptr(moving_mean),
+                 ptr(moving_var), M, C, float(eps), float(momentum), int(relu), ptr(ws), stream())
+        ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else None)
+        ctx.frozen, ctx.has_shortcut = frozen, shortcut is not None
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 10
+        x, gamma, mean, rstd, y = ctx.saved_tensors
+        C = x.shape[-1]
+        M = x.numel() // C
+        dy = dy.contiguous()                                                # (no copy when it is)
+        dx = torch.empty_like(x)
+        dsc = torch.empty_like(x) if (ctx.has_shortcut and ctx.needs_input_grad[1]) else None
+        sums = torch.empty((2, C), dtype=torch.float32, device=x.device)    # dgamma, dbeta side by side: one clear inside the call
+        call("danhip_bn_act_bwd", ptr(x), ptr(dy), ptr(y), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dsc), ptr(sums[0]), ptr(sums[1]), M, C,
+             int(ctx.frozen), stream())
+        return dx, dsc, sums[0], sums[1], None, None, None, None, None, None
+
+
+def _bn_act_fused(x, shortcut):
+    """The fused tail takes 16-bit activations of the build's type (not fp32 tensors, not limb views: precision fp32 / split)."""
+    return x.dtype == ACT and not _is_limbs(x) and (shortcut is None or (shortcut.dtype == ACT and not _is_limbs(shortcut)))
+
+
+def _bn_act_unfused(y, shortcut, relu):
+    if shortcut is not None:
+        y = add(y, shortcut)
+    return torch.relu(y) if relu and shortcut is not None else y
+
+
+def batch_norm_act_train(x, gamma, beta, moving_mean=None, moving_var=None, eps=1e-5, momentum=0.997, relu=False, shortcut=None):
+    """act(batch_norm(x, batch statistics) + shortcut) with the moving averages updated once: one autograd node, one apply pass forward,
+    two launches backward.  A non-16-bit input takes the separate ops (batch_norm_train + add + ReLU)."""
+    if not _bn_act_fused(x, shortcut):
+        return _bn_act_unfused(batch_norm_train(x, gamma, beta, moving_mean, moving_var, eps, momentum, relu and shortcut is None), shortcut, relu)
+    if shortcut is not None:
+        assert shortcut.shape == x.shape, "batch_norm_act: the shortcut has the shape of x"
+        shortcut = shortcut.contiguous()
+    return _BatchNormAct.apply(x.contiguous(), shortcut, gamma, beta, moving_mean, moving_var, eps, momentum, bool(relu), False)
+
+
+def batch_norm_act_infer(x, gamma, beta, moving_mean, moving_var, eps=1e-5, relu=False, shortcut=None):
+    """The same with the moving statistics (training=False): one launch without a gradient, one autograd node with one.  A non-16-bit or
+    limb input (precision fp32 / split) takes the separate ops (batch_norm_infer + add + ReLU)."""
+    if not _bn_act_fused(x, shortcut):
+        return _bn_act_unfused(batch_norm_infer(x, gamma, beta, moving_mean, moving_var, eps, relu and shortcut is None), shortcut, relu)
+    if shortcut is not None:
+        assert shortcut.shape == x.shape, "batch_norm_act: the shortcut has the shape of x"
+        shortcut = shortcut.contiguous()
+    return _BatchNormAct.apply(x.contiguous(), shortcut, gamma, beta, moving_mean, moving_var, eps, 0.0, bool(relu), True)
+
+
 class _DeformSample(torch.autograd.Function):
     """Deformable im2col (cpp/Deform/deform_conv.cu:229-275) and its backward (col2im :281-328, col2im_coord :335-389):
     x bf16 [N,H,W,C], offsets bf16 [N,Ho,Wo,dg*2*kh*kw] -> S bf16 [N,Ho,Wo,kh*kw*C] (k = tap*C + c)."""

@@ -11,7 +11,9 @@ feeds to summaries this port does not write).  Three flags are this port's own: 
 --no_prefetch, exists for measuring the loader thread against the plain generator (profiles/r15/train_driver.md); a fifth,
 --lfpn_upsample {bilinear,transposed} (train_pb, train_dan, train_dan_deform; default bilinear: the reference's graph), makes the LFPN merge
 through a learnable 4x4 / stride-2 transposed convolution (net/pb_net.py build_lfpn) - a checkpoint written without it resumes or warm-starts
-with the new variables at their initialiser.  Checkpoints are written
+with the new variables at their initialiser; a sixth, --backbone {vgg16,resnet50,resnet101,resnet152} (train_dan; default vgg16), trains DAN on
+the reference's ResNet + batch-norm backbone (net/resnet_danet.py): seeded initialisers or a resume from model_dir - a warm start from
+--checkpoint_path and --deterministic are refused with a message before the device is touched.  Checkpoints are written
 with a CRC-32C on every tensor (checksums="device": packed and checksummed on the GPU, profiles/r16/checkpoint_crc.md) and every tensor CRC
 is checked on resume and on a warm start before a variable is written; --no_checkpoint_checksums turns both off.
 
@@ -83,6 +85,7 @@ KEEP_CHECKPOINT_MAX = 5                                                     # Ru
 PREFETCH_DEPTH = 2
 MAX_THREADS = 16
 LFPN_UPSAMPLE = ("bilinear", "transposed")                                  # --lfpn_upsample (net/pb_net.py LFPN_UPSAMPLE)
+BACKBONES = ("vgg16", "resnet50", "resnet101", "resnet152")                 # --backbone (train_dan.BACKBONES)
 
 
 def flag_defaults(model):
@@ -121,6 +124,11 @@ def build_parser(model):
         p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
                        help="how the LFPN brings the upper level to the lateral's size: bilinear resize (the reference's graph, default) or a "
                             "learnable 4x4 stride-2 transposed convolution (new variables <lfpn>/fpn_k/upsample_deconv/{kernel,bias})")
+    if model == "dan":                                                      # (the reference has no deformable ResNet backbone)
+        p.add_argument("--backbone", choices=BACKBONES, default="vgg16",
+                       help="vgg16 (the reference's script, default) or the reference's ResNet-50/101/152 backbone with batch norm; a ResNet starts "
+                            "from seeded initialisers or resumes from model_dir (no warm start: --checkpoint_path maps VGG names only) and has no "
+                            "--deterministic form")
     return p
 
 
@@ -200,7 +208,8 @@ class _Setup(object):
             from .preprocessing import dan_preprocessing as P
             from .train_dan import DANModel, DANTrainer, encode_batch_dan
             anchors = AnchorConfig(size, size, device, args.match_threshold, args.neg_threshold, ratios=_dan_ratios())
-            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=args.lfpn_upsample), anchors, routing_seed=seed,
+            self.trainer = DANTrainer(DANModel(device=device, seed=seed, deform=(model == "dan_deform"), lfpn_upsample=args.lfpn_upsample,
+                                               backbone=getattr(args, "backbone", "vgg16")), anchors, routing_seed=seed,
                                       **deterministic_route(model, trainer_kw))
             self.preprocess = lambda images, boxes, draws: P.preprocess_batch_for_train(images, boxes, shape, ANCHOR_SCALES, draws=draws)
             self.encode = lambda boxes: encode_batch_dan(anchors, boxes)
@@ -357,8 +366,15 @@ def main(argv=None, model="sfd"):
                          % (model, os.environ["WORLD_SIZE"]))
     if args.num_classes != 2:
         raise SystemExit("--num_classes %d: the loss and metric kernels are two-way (face / background)" % args.num_classes)
-    import torch
     from .utility import checkpoint
+    backbone = getattr(args, "backbone", "vgg16")
+    if backbone != "vgg16":                                                   # refused here, before the device is touched
+        if args.deterministic:
+            raise SystemExit("--deterministic with --backbone %s: batch norm has no ordered (bit-reproducible) form" % backbone)
+        if not checkpoint.latest_checkpoint(args.model_dir) and _warm_start_path(args.checkpoint_path):
+            raise SystemExit("--backbone %s cannot warm-start from --checkpoint_path %s: the checkpoint name mapping covers the VGG-16 variables only "
+                             "(train from the seeded initialisers, or resume from --model_dir)" % (backbone, args.checkpoint_path))
+    import torch
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     os.makedirs(args.model_dir, exist_ok=True)

@@ -16,28 +16,48 @@ def dan_anchor_config(height, width, device):
     return AnchorConfig(height, width, device, match_threshold=0.35, neg_threshold=0.35, ratios=DAN_ANCHOR_RATIOS)
 
 
+BACKBONES = ("vgg16", "resnet50", "resnet101", "resnet152")      # DANModel(backbone=...), the command lines' --backbone
+
+
 class DANModel(object):
-    def __init__(self, device="cuda", seed=20180817, deform=False, lfpn_upsample="bilinear"):
-        """lfpn_upsample (the command lines' --lfpn_upsample {bilinear,transposed}): "bilinear" (the reference's graph) or "transposed" - the three LFPNs merge through a learnable 4x4 / stride-2
+    def __init__(self, device="cuda", seed=20180817, deform=False, lfpn_upsample="bilinear", backbone="vgg16"):
+        """backbone (the command lines' --backbone): "vgg16" (the reference's scripts) or "resnet50" / "resnet101" / "resnet152" - the reference's
+        net/resnet_danet.py backbone with batch norm, on the fused tail kernels (ResNetBackbone(depth, fused_tail=True)); it has no deformable
+        variant.  Batch norm follows forward's `training`.
+        lfpn_upsample (the command lines' --lfpn_upsample {bilinear,transposed}): "bilinear" (the reference's graph) or "transposed" - the three LFPNs merge through a learnable 4x4 / stride-2
         transposed convolution (net/pb_net.py build_lfpn; new variables <lfpn scope>/fpn_k/upsample_deconv/{kernel,bias})."""
         if lfpn_upsample not in pb_net.LFPN_UPSAMPLE:
             raise ValueError("lfpn_upsample must be one of %s, got %r" % (", ".join(pb_net.LFPN_UPSAMPLE), lfpn_upsample))
+        if backbone not in BACKBONES:
+            raise ValueError("backbone must be one of %s, got %r" % (", ".join(BACKBONES), backbone))
+        if deform and backbone != "vgg16":
+            raise ValueError("deform=True with backbone %r: the reference has no deformable ResNet backbone" % backbone)
         self.lfpn_upsample = lfpn_upsample
+        self.backbone_name = backbone
+        self.batch_norm = backbone != "vgg16"                # (DANTrainer refuses deterministic=True for it: batch norm has no ordered form)
         self.vs = VariableStore(device=device, seed=seed)
         self.deform = bool(deform)                            # (DetectorTrainer refuses deterministic=True for it; ops_ctx=ops.deterministic_context() is its spelling of the mode)
         if deform:
             from .net import danet_deform
             self.backbone = danet_deform.VGG16Backbone("channels_last", variables=self.vs)
+        elif self.batch_norm:
+            from .net import resnet_danet
+            self.backbone = resnet_danet.ResNetBackbone(int(backbone[len("resnet"):]), variables=self.vs, fused_tail=True)
         else:
             self.backbone = danet.VGG16Backbone("channels_last", variables=self.vs)
 
-    def forward(self, images_u8):
-        """train_dan.py:410-428 -> ((loc1 [B,A,4], cls1 [B,A,2]), (loc2, cls2), feature map sizes)."""
+    def forward(self, images_u8, training=None):
+        """train_dan.py:410-428 -> ((loc1 [B,A,4], cls1 [B,A,2]), (loc2, cls2), feature map sizes).  training (default: whether a gradient is
+        being tracked) selects batch statistics or moving statistics in a batch-norm backbone; the VGG backbone has none and ignores it."""
+        if training is None:
+            training = torch.is_grad_enabled()
         prec = getattr(self, "precision", "act")
+        if self.batch_norm and prec in ("fp32", "split"):
+            raise NotImplementedError("precision %r with backbone %s: batch norm has no fp32 / split-operand kernel (use act)" % (prec, self.backbone_name))
         with sfd_net.precision_scope(prec):
             b = self.backbone
             x = sfd_net.prepare_input(images_u8, prec)
-            feats = b.get_featmaps(x, training=True)
+            feats = b.get_featmaps(x, training=training)
             feats = b.build_lfpn(feats, skip_last=3, upsample=self.lfpn_upsample)
             s1 = b.get_features_stage1(feats, name="prediction_modules_stage1")
             s1 = b.build_lfpn(s1, skip_last=3, name="lfpn_stage1", upsample=self.lfpn_upsample)
@@ -110,6 +130,9 @@ class DANTrainer(DetectorTrainer):
     DETERMINISTIC = True          # (the VGG model: tests/test_deterministic_gpu.py; the deformable one through ops.deterministic_context(): tests/test_deterministic_deform_gpu.py)
 
     def __init__(self, model, anchors, routing_seed=20180817, **kw):
+        if getattr(model, "batch_norm", False) and (kw.get("deterministic") or getattr(kw.get("ops_ctx"), "deterministic", False)):
+            raise NotImplementedError("deterministic: batch norm (backbone %s) has no ordered form - the float atomics of its statistics and "
+                                      "parameter gradients" % model.backbone_name)
         super().__init__(model, **kw)
         self.anchors = anchors
         self.routing_seed = routing_seed

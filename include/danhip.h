@@ -92,7 +92,7 @@ int danhip_act_dtype(void);   /* DANHIP_BF16 or DANHIP_F16 */
  *   - danhip_relu_bwd_bias_grad (db != NULL), danhip_l2norm_bwd, danhip_l2norm_bwd_pool_scatter, danhip_detection_loss_fwd and
  *     danhip_sgd_momentum_flat[_dynamic] (l2_out != NULL) return DANHIP_EINVAL: call their _ws forms (declared next to them);
  *   - danhip_deform_sample_bwd and danhip_deform_conv_bwd* run their ordered form for ONE shape class (below) and need its larger workspace;
- *   - out of scope, DANHIP_EINVAL: danhip_conv2d_bwd_data_bits_first, danhip_batchnorm_fwd_train, danhip_batchnorm_bwd, the deformable backward
+ *   - out of scope, DANHIP_EINVAL: danhip_conv2d_bwd_data_bits_first, danhip_batchnorm_fwd_train, danhip_batchnorm_bwd, danhip_bn_act_*, the deformable backward
  *     of every other shape class, danhip_deform_psroi_pool_bwd (their float atomics have no ordered form).
  * With the option at 0 the _ws forms behave exactly as the plain calls (the workspace is ignored).
  *
@@ -1323,6 +1323,32 @@ int danhip_conv_transpose4x4s2_wgrad(const void* x, const void* dout, float* dw,
                                      int32_t Wo, int32_t Cin, int32_t Cout, void* workspace, size_t workspace_bytes, void* stream);
 int danhip_conv_transpose4x4s2_add_fwd_f32(const float* x, const float* w, const float* bias, const float* lateral, float* out, int32_t N,
                                            int32_t Hi, int32_t Wi, int32_t Ho, int32_t Wo, int32_t Cin, int32_t Cout, void* stream);
+
+/* --------------------------------------------------------------------------------------------------
+ * Fused batch-norm tails (ABI version 21; csrc/bn_act.hip): what closes a conv -> BN -> ReLU layer and a ResNet bottleneck unit
+ * (net/resnet_danet.py:157-218), over the channel axis of [M,C] 16-bit activations (M = N*H*W), C % 8 == 0, C <= 2048, any M:
+ *
+ *   y = act(xhat * gamma + beta + shortcut),  xhat = (x - mean) * rstd,  act = ReLU when relu != 0, else the identity
+ *
+ *   - shortcut ([M,C], 16-bit) may be NULL; the sum is kept in fp32 and rounded to 16 bits ONCE, at the store;
+ *   - every activation and per-channel array is 16-byte aligned (DANHIP_EINVAL otherwise).
+ * danhip_bn_act_fwd_train: batch statistics and the moving-average update are those of danhip_batchnorm_fwd_train (the same two kernels,
+ *   the same launches, workspace = 2*C doubles, 8-byte aligned; moving_mean / moving_var may be NULL), then ONE apply launch.
+ * danhip_bn_act_fwd_infer: the apply launch alone with the caller's mean and rstd = rsqrt(var + eps).
+ * danhip_bn_act_bwd: y != NULL says the forward had relu != 0; the mask [y > 0] is applied on the fly in both passes (no masked copy of dy):
+ *     g = dy * [y > 0];   dbeta = sum g,  dgamma = sum g * xhat   (OVERWRITTEN; fp32 atomics; one clear when dbeta == dgamma + C)
+ *     dx = gamma * rstd * (g - dbeta / M - xhat * dgamma / M)     or, frozen != 0 (mean / rstd are constants):  dx = g * gamma * rstd
+ *     dshortcut = g                                                (unless NULL; written in the same pass as dx)
+ *   Two launches: reduce, apply.
+ * With the option "deterministic" set the three calls return DANHIP_EINVAL, as danhip_batchnorm_* do (their float atomics have no ordered form).
+ * ------------------------------------------------------------------------------------------------ */
+int danhip_bn_act_fwd_train(const uint16_t* x, const uint16_t* shortcut, const float* gamma, const float* beta, uint16_t* y, float* save_mean,
+                            float* save_rstd, float* moving_mean, float* moving_var, int64_t M, int32_t C, float eps, float momentum,
+                            int relu, float* workspace, void* stream);
+int danhip_bn_act_fwd_infer(const uint16_t* x, const uint16_t* shortcut, const float* gamma, const float* beta, const float* mean,
+                            const float* rstd, uint16_t* y, int64_t M, int32_t C, int relu, void* stream);
+int danhip_bn_act_bwd(const uint16_t* x, const uint16_t* dy, const uint16_t* y, const float* gamma, const float* mean, const float* rstd,
+                      uint16_t* dx, uint16_t* dshortcut, float* dgamma, float* dbeta, int64_t M, int32_t C, int frozen, void* stream);
 
 #ifdef __cplusplus
 }
