@@ -350,6 +350,9 @@ _TABLE = {
     "danhip_bn_act_fwd_train": (STATUS, [P, P, P, P, P, P, P, P, P, I64, I32, FL, FL, INT, P, P]),
     "danhip_bn_act_fwd_infer": (STATUS, [P, P, P, P, P, P, P, I64, I32, INT, P]),
     "danhip_bn_act_bwd": (STATUS, [P, P, P, P, P, P, P, P, P, P, I64, I32, INT, P]),
+    # ---- face chips
+    "danhip_face_chips_workspace": (STATUS, [I32, I32, ctypes.POINTER(SZ)]),
+    "danhip_face_chips_u8": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, FL, P, P, P, I32, P, SZ, P]),
 }
 PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
 SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for

@@ -1,0 +1,178 @@
+// Face chips (include/danhip.h, "Face chips"), compiled with -ffp-contract=off: every detection of every image of a ragged list cropped
+// and resized to S x S in TWO launches, nothing read back.
+//   * face_chips_select : ONE workgroup of 1024 lanes loops over the n_images * rows_per_image slots, 1024 at a time, applies the
+//                         rectangle rule (face_chip_rect below: integers only, 64-bit intermediates) and numbers the valid slots in
+//                         (image, row) order by an exclusive prefix sum (wave ballots + 16 wave totals in LDS + a running base).  A single
+//                         looping workgroup instead of chained ones: slot counts are a few thousand (8 images x 750 rows = 6 rounds), the
+//                         order then needs no counter in memory, no spinning on another workgroup and no atomics, and a 0-byte workspace.
+//                         It writes chip_src rows of the first max_chips valid slots and the TRUE total to *count.
+//   * face_chips_resize : workgroups walk (chip, tile) items, a tile = 256 runs of 4 consecutive output pixels of one row (12 bytes per lane,
+//                         three dword stores where the run is whole and its address 4-byte aligned, single bytes otherwise), and leave at
+//                         chip >= min(*count, max_chips).  The pixel arithmetic is resize_u8.h's with the crop's top-left byte as the source,
+//                         the image's pitch, the crop's size and scale = crop / S in double.  The chip's geometry is uniform per workgroup
+//                         (scalar loads); per lane there are only dy, dx and the 12 result bytes.  No LDS, no atomics.
+#include <cmath>
+
+#include "common.h"
+#include "resize_u8.h"
+
+namespace {
+
+constexpr int kSelThreads = 1024, kRun = 4, kTileThreads = 256, kMaxS = 1024, kMaxMargin = 4000, kMaxGrid = 1024;     // 4 resize workgroups per compute unit
+
+// draw_exact.hip's corner: int() of the float, toward zero, clamped to +-2^30; false for NaN and the infinities
+__device__ __forceinline__ bool chip_corner(float v, long* out) {
+  if (!(fabsf(v) <= 3.0e38f)) return false;
+  v = fminf(fmaxf(v, -1073741824.0f), 1073741824.0f);
+  *out = (long)(int)v;
+  return true;
+}
+
+// The rectangle of a detection row in an H x W image, or false.  |corner| <= 2^30, margin_pm <= 4000: every product is below 2^44.
+__device__ __forceinline__ bool face_chip_rect(const float* __restrict__ row, int H, int W, int margin_pm, bool square, int* rect) {
+  long x1, y1, x2, y2;
+  if (!(chip_corner(row[0], &x1) && chip_corner(row[1], &y1) && chip_corner(row[2], &x2) && chip_corner(row[3], &y2))) return false;
+  long w = x2 - x1 + 1, h = y2 - y1 + 1;
+  if (w < 1 || h < 1) return false;
+  const long mx = w * margin_pm / 1000, my = h * margin_pm / 1000;      // non-negative operands: floor
+  x1 -= mx; x2 += mx; y1 -= my; y2 += my;
+  w += 2 * mx; h += 2 * my;
+  if (square) {
+    const long s = w > h ? w : h;
+    x1 -= (s - w) / 2; x2 = x1 + s - 1;
+    y1 -= (s - h) / 2; y2 = y1 + s - 1;
+  }
+  x1 = x1 < 0 ? 0 : x1; y1 = y1 < 0 ? 0 : y1;
+  x2 = x2 > W - 1 ? W - 1 : x2; y2 = y2 > H - 1 ? H - 1 : y2;
+  if (x1 > x2 || y1 > y2) return false;
+  rect[0] = (int)x1; rect[1] = (int)y1; rect[2] = (int)x2; rect[3] = (int)y2;
+  return true;
+}
+
+__global__ __launch_bounds__(kSelThreads) void face_chips_select_kernel(const danhip_resize_item* __restrict__ images, int n_images,
+                                                                        const float* __restrict__ dets, const int32_t* __restrict__ num,
+                                                                        int rows, int margin_pm, int square, float threshold,
+                                                                        int32_t* __restrict__ chip_src, int32_t* __restrict__ count, int max_chips) {
+  __shared__ int wave_total[kSelThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int slots = n_images * rows;                             // < 2^24 (the entry point checks)
+  int base = 0;                                                  // valid slots before this round
+  for (int first = 0; first < slots; first += kSelThreads) {
+    const int slot = first + t;
+    int rect[4] = {0, 0, 0, 0};
+    int image = 0, row = 0;
+    bool ok = false;
+    if (slot < slots) {
+      image = slot / rows;
+      row = slot - image * rows;
+      if (row < num[image]) {
+        const float* d = dets + (size_t)slot * 5;
+        ok = !(d[4] < threshold) && face_chip_rect(d, images[image].H, images[image].W, margin_pm, square != 0, rect);
+      }
+    }
+    const unsigned long long m = __ballot(ok);
+    if (lane == 0) wave_total[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < kSelThreads / 64; ++j) {
+      const int v = wave_total[j];
+      before += j < wave ? v : 0;
+      total += v;
+    }
+    const int index = base + before + __popcll(m & ((1ull << lane) - 1ull));
+    if (ok && index < max_chips) {
+      int32_t* o = chip_src + (size_t)index * 6;
+      o[0] = image; o[1] = row; o[2] = rect[0]; o[3] = rect[1]; o[4] = rect[2]; o[5] = rect[3];
+    }
+    base += total;
+    __syncthreads();                                             // wave_total is rewritten in the next round
+  }
+  if (t == 0) *count = base;
+}
+
+__global__ __launch_bounds__(kTileThreads) void face_chips_resize_kernel(const danhip_resize_item* __restrict__ images,
+                                                                         const uint8_t* __restrict__ src, const int32_t* __restrict__ chip_src,
+                                                                         const int32_t* __restrict__ count, int max_chips, int S,
+                                                                         int runs_per_row, int tiles_per_chip, uint8_t* __restrict__ chips) {
+  const int total = *count, n = total < max_chips ? total : max_chips;
+  const int runs = S * runs_per_row;                             // <= 1024 * 256
+  for (long item = blockIdx.x; item < (long)n * tiles_per_chip; item += gridDim.x) {
+    const int chip = (int)(item / tiles_per_chip), tile = (int)(item - (long)chip * tiles_per_chip);
+    const int r = tile * kTileThreads + (int)threadIdx.x;
+    if (r >= runs) continue;
+    const int32_t* g = chip_src + (size_t)chip * 6;              // uniform per workgroup
+    const danhip_resize_item* im = images + g[0];
+    const int xc1 = g[2], yc1 = g[3], cw = g[4] - xc1 + 1, ch = g[5] - yc1 + 1;
+    const long pitch = im->pitch;
+    const uint8_t* crop = src + im->src_offset + (long)yc1 * pitch + (long)xc1 * 3;
+    const double scale_x = (double)cw / (double)S, scale_y = (double)ch / (double)S;
+    const int dy = r / runs_per_row, dx0 = (r - dy * runs_per_row) * kRun;
+    uint8_t px[kRun * 3];
+#pragma unroll
+    for (int p = 0; p < kRun; ++p) {
+      const int dx = dx0 + p < S ? dx0 + p : S - 1;              // the tail repeats the last pixel; it is not stored
+      resize_u8_linear_pixel(crop, pitch, ch, cw, 3, false, scale_x, scale_y, dy, dx, px + 3 * p);
+    }
+    uint8_t* o = chips + ((size_t)chip * S * S + (size_t)dy * S + dx0) * 3;
+    if (dx0 + kRun <= S && ((uintptr_t)o & 3u) == 0) {
+      uint32_t* o4 = (uint32_t*)o;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        o4[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) | ((uint32_t)px[4 * k + 3] << 24);
+    } else {
+#pragma unroll
+      for (int p = 0; p < kRun; ++p)
+        if (dx0 + p < S) { o[3 * p] = px[3 * p]; o[3 * p + 1] = px[3 * p + 1]; o[3 * p + 2] = px[3 * p + 2]; }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int danhip_face_chips_workspace(int32_t n_images, int32_t rows_per_image, size_t* bytes) {
+  DH_REQUIRE(bytes, DANHIP_EINVAL, "face_chips_workspace: NULL bytes");
+  DH_REQUIRE(n_images >= 0 && rows_per_image >= 0 && (int64_t)n_images * rows_per_image <= (1 << 24), DANHIP_EINVAL,
+             "face_chips_workspace: n_images %d x rows_per_image %d outside 0 .. 2^24 slots", n_images, rows_per_image);
+  *bytes = 0;                                                    // the select launch is one looping workgroup: nothing is kept between workgroups
+  return DANHIP_OK;
+}
+
+extern "C" int danhip_face_chips_u8(const danhip_resize_item* images_host, const danhip_resize_item* images_dev, int32_t n_images,
+                                    const uint8_t* src, int64_t src_bytes, const float* dets, const int32_t* num, int32_t rows_per_image,
+                                    int32_t S, int32_t margin_pm, int32_t square, float score_threshold, uint8_t* chips_out,
+                                    int32_t* chip_src_out, int32_t* count_out, int32_t max_chips, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  DH_REQUIRE(S >= 1 && S <= kMaxS, DANHIP_EINVAL, "face_chips_u8: S %d outside 1 .. %d", S, kMaxS);
+  DH_REQUIRE(margin_pm >= 0 && margin_pm <= kMaxMargin, DANHIP_EINVAL, "face_chips_u8: margin_pm %d outside 0 .. %d", margin_pm, kMaxMargin);
+  DH_REQUIRE(square == 0 || square == 1, DANHIP_EINVAL, "face_chips_u8: square is 0 or 1");
+  DH_REQUIRE(!std::isnan(score_threshold), DANHIP_EINVAL, "face_chips_u8: score_threshold is NaN");
+  DH_REQUIRE(max_chips >= 0, DANHIP_EINVAL, "face_chips_u8: max_chips %d is negative", max_chips);
+  size_t need = 0;
+  if (danhip_face_chips_workspace(n_images, rows_per_image, &need) != DANHIP_OK) return DANHIP_EINVAL;
+  DH_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), DANHIP_EINVAL, "face_chips_u8: workspace of %zu bytes, %zu needed",
+             workspace_bytes, need);
+  DH_REQUIRE(count_out, DANHIP_EINVAL, "face_chips_u8: NULL count_out");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_images == 0 || rows_per_image == 0) return danhip_zero_async(count_out, 4, s);
+  DH_REQUIRE(images_host && images_dev && src && dets && num, DANHIP_EINVAL, "face_chips_u8: NULL images / src / dets / num");
+  DH_REQUIRE(max_chips == 0 || (chips_out && chip_src_out), DANHIP_EINVAL, "face_chips_u8: NULL chips_out / chip_src_out");
+  for (int32_t i = 0; i < n_images; ++i) {
+    const danhip_resize_item& it = images_host[i];
+    DH_REQUIRE(it.H >= 1 && it.W >= 1 && (int64_t)it.pitch >= 3 * (int64_t)it.W && it.src_offset >= 0, DANHIP_EINVAL,
+               "face_chips_u8: image %d: a non-positive size, pitch below 3 * W or a negative offset", i);
+    DH_REQUIRE(it.src_offset + (int64_t)(it.H - 1) * it.pitch + 3 * (int64_t)it.W <= src_bytes, DANHIP_EINVAL,
+               "face_chips_u8: image %d reads past the source buffer", i);
+  }
+  hipLaunchKernelGGL(face_chips_select_kernel, dim3(1), dim3(kSelThreads), 0, s, images_dev, (int)n_images, dets, num, (int)rows_per_image,
+                     (int)margin_pm, (int)square, score_threshold, chip_src_out, count_out, (int)max_chips);
+  DH_LAUNCH_CHECK();
+  if (max_chips == 0) return DANHIP_OK;
+  const int runs_per_row = cdiv(S, kRun), tiles_per_chip = cdiv((long)S * runs_per_row, kTileThreads);
+  const int64_t cap = (int64_t)n_images * rows_per_image < max_chips ? (int64_t)n_images * rows_per_image : max_chips;
+  const int grid = dh_grid_for(cap * tiles_per_chip, 1, kMaxGrid);
+  hipLaunchKernelGGL(face_chips_resize_kernel, dim3(grid), dim3(kTileThreads), 0, s, images_dev, src, chip_src_out, count_out, (int)max_chips,
+                     (int)S, runs_per_row, tiles_per_chip, chips_out);
+  DH_LAUNCH_CHECK();
+  return DANHIP_OK;
+}

@@ -9,7 +9,9 @@ data_format, num_classes, train_image_size and batch_size (the reference's graph
 there either).  The port's own: --device, --precision, --batch_images (JPEGs read, decoded and detected as one group), --decode_entropy, --encode_entropy,
 --encode_optimize (the debug images' encoder makes each image's own Huffman tables, as Pillow's optimize=True; off by default), --image_list (one `event/name` per line instead of wider_face_split/wider_face_<subset>.mat, which needs scipy), --gt_dir (the directory
 of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat / wider_hard_<subset>.mat: the average precision is
-computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default) and
+computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default), --chips_dir (with --chips_size, --chips_margin and
+--chips_threshold: every detection of score >= the threshold cropped and resized on the device by utility.face_chips' rule and written to
+chips_dir/<event>/<name>_<row>.jpg through the debug images' encoder, one encode call per group; off by default, and then nothing changes) and
 --lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
 train_*'s flag of the same name.  transposed has no split-operand form: with --precision split the command exits with a message.
 --backbone {vgg16,resnet50,resnet101,resnet152} (eval_dan; default vgg16) is train_dan's flag of the same name: batch norm runs on the
@@ -87,6 +89,12 @@ def build_parser(model):
     p.add_argument("--debug_quality", type=int, default=75, help="JPEG quality of the debug images (default 75)")
     p.add_argument("--debug_labels", action="store_true",
                    help="draw each box's score ('%%.1f%%%%' of score * 100) in white on a filled tab above it (default: rectangles only)")
+    p.add_argument("--chips_dir", default=None,
+                   help="write every detection as a face chip to chips_dir/<event>/<name>_<row>.jpg at --debug_quality (default: none are made)")
+    p.add_argument("--chips_size", type=int, default=112, help="side of a face chip in pixels, 1 .. 1024 (default 112)")
+    p.add_argument("--chips_margin", type=float, default=0.0,
+                   help="fraction of the box side added on each side before the crop is squared and clipped to the image, 0 .. 4 (default 0)")
+    p.add_argument("--chips_threshold", type=float, default=None, help="score a detection needs to become a chip (default: --select_threshold)")
     if model != "sfd":                                                      # (S3FD has no LFPN)
         p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
                        help="the LFPN of the checkpoint's graph: bilinear resize (default) or the learnable 4x4 stride-2 transposed convolution "
@@ -190,12 +198,21 @@ def main(argv=None, model="sfd", gt=None, out=None):
         raise SystemExit("--batch_images %d: at least 1" % args.batch_images)
     if not 1 <= args.debug_quality <= 100:
         raise SystemExit("--debug_quality %d: 1 .. 100" % args.debug_quality)
+    if args.chips_dir:
+        from .utility import face_chips                           # (importing it does not touch the device)
+        try:
+            face_chips.check_size(args.chips_size)
+            chips_pm = face_chips.margin_per_mille(args.chips_margin)
+        except ValueError as e:
+            raise SystemExit("--chips_size / --chips_margin: %s" % e)
+        chips_threshold = args.select_threshold if args.chips_threshold is None else args.chips_threshold
     lfpn_upsample = getattr(args, "lfpn_upsample", "bilinear")
     if lfpn_upsample == "transposed" and args.precision == "split":
         raise SystemExit("--lfpn_upsample transposed has no split-operand form: use --precision act or fp32")
     backbone = getattr(args, "backbone", "vgg16")
     if backbone != "vgg16" and args.precision != "act":
         raise SystemExit("--backbone %s runs with --precision act only: batch norm has no fp32 or split-operand kernel" % backbone)
+    import numpy as np
     import torch
     from . import eval_dan
     from .dataset.jpeg import JpegDecoder, JpegEncoder
@@ -222,6 +239,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy, optimize=args.encode_optimize) if args.debug_dir else None
     if args.debug_dir:
         os.makedirs(args.debug_dir, exist_ok=True)
+    chip_encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy, optimize=args.encode_optimize) if args.chips_dir else None
     min_height = MIN_HEIGHT[model]
     on_device = min_height == 10 and args.select_threshold == eval_dan.SELECT_THRESHOLD       # the filter danhip_wider_quantize restates
     evaluator = None
@@ -230,7 +248,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     image_root = os.path.join(args.data_dir, "WIDER_val" if args.subset == "val" else "WIDER_test", "images")
     save_root = os.path.join(args.det_dir, args.subset)
     every = max(args.log_every_n_steps, 1)
-    total, debug_paths = 0, []
+    total, debug_paths, chip_paths = 0, [], []
     for index, (event, files) in enumerate(events):
         os.makedirs(os.path.join(save_root, event), exist_ok=True)
         for start in range(0, len(files), args.batch_images):
@@ -265,6 +283,20 @@ def main(argv=None, model="sfd", gt=None, out=None):
                     debug_paths.append(os.path.join(args.debug_dir, group[b] + ".jpg"))
                     with open(debug_paths[-1], "wb") as f:
                         f.write(data)
+            if chip_encoder is not None:
+                # the rows that give a chip, from the rows already on the host (the rule is integers only: host and device agree), so the
+                # chip buffer is sized to them and the files are named without a second download
+                thr = np.float32(chips_threshold)
+                owners = [(b, r) for b in range(B) for r in range(counts[b]) if not rows[b, r, 4] < thr and
+                          face_chips.rule(rows[b, r], int(images[b].shape[0]), int(images[b].shape[1]), chips_pm, True) is not None]
+                if owners:
+                    chips = face_chips.extract(images, dets, num, size=args.chips_size, margin=args.chips_margin, square=True,
+                                               score_threshold=chips_threshold, max_chips=len(owners)).chips
+                    os.makedirs(os.path.join(args.chips_dir, event), exist_ok=True)
+                    for (b, r), data in zip(owners, chip_encoder.encode_batch(list(chips))):
+                        chip_paths.append(os.path.join(args.chips_dir, event, "%s_%d.jpg" % (group[b], r)))
+                        with open(chip_paths[-1], "wb") as f:
+                            f.write(data)
             total += B
             out.write("\r>> Predicting event:%d/%d num:%d/%d" % (index + 1, len(events), start + B, len(files)))
             out.flush()
@@ -276,4 +308,4 @@ def main(argv=None, model="sfd", gt=None, out=None):
         ap = collections.OrderedDict((s, res[s]) for s in gt.subsets)
         for s, v in ap.items():
             print("%s AP: %.6f" % (s, v), file=out, flush=True)
-    return {"images": total, "debug": debug_paths, "ap": ap, "decoder": decoder.stats, "encoder": None if encoder is None else encoder.stats}
+    return {"images": total, "debug": debug_paths, "chips": chip_paths, "ap": ap, "decoder": decoder.stats, "encoder": None if encoder is None else encoder.stats}

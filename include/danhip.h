@@ -1350,6 +1350,43 @@ int danhip_bn_act_fwd_infer(const uint16_t* x, const uint16_t* shortcut, const f
 int danhip_bn_act_bwd(const uint16_t* x, const uint16_t* dy, const uint16_t* y, const float* gamma, const float* mean, const float* rstd,
                       uint16_t* dx, uint16_t* dshortcut, float* dgamma, float* dbeta, int64_t M, int32_t C, int frozen, void* stream);
 
+/* --------------------------------------------------------------------------------------------------
+ * Face chips (ABI version 22; csrc/face_chips_exact.hip; dan_amd/utility/face_chips.py): every detection of every image of a list cropped
+ * and resized to uint8 [S, S, 3] in TWO launches, whatever the number of images and detections; nothing is read back.
+ * The rectangle rule is this project's own, integers only (restated by dan_amd/utility/face_chips.py rule).  For row r of image i
+ * (H x W), dets[i, r] = (x1, y1, x2, y2, score) fp32, the layout eval_dan.detect_image_list returns:
+ *   corners = the floats truncated toward zero (Python's int(); clamped to +-2^30, as danhip_draw_boxes_u8 does); w = x2 - x1 + 1,
+ *   h = y2 - y1 + 1;
+ *   no chip when r >= num[i], score < score_threshold (an fp32 compare: a score equal to the threshold is kept), a coordinate is NaN or
+ *   infinite, or w < 1 or h < 1;
+ *   margin: x1 -= mx, x2 += mx with mx = w * margin_pm / 1000, y1 -= my, y2 += my with my = h * margin_pm / 1000 (integer divisions of
+ *   non-negative numbers; margin_pm in per mille, 0 .. 4000);
+ *   square != 0, after the margin: s = max(w', h') of the grown sides; x1 -= (s - w') / 2, x2 = x1 + s - 1, likewise y: the shorter
+ *   side gets (s - side) / 2 in front and the rest behind;
+ *   then the rectangle is intersected with [0, W-1] x [0, H-1] (no zero padding): xc1, yc1, xc2, yc2; an empty intersection gives no chip.
+ *   Intermediates are 64-bit: |corner| <= 2^30 and margin_pm <= 4000 keep every product below 2^44.
+ *   The chip is cv2.resize(image[yc1 : yc2 + 1, xc1 : xc2 + 1], (S, S), INTER_LINEAR): danhip_resize_u8_linear's arithmetic (the kernels
+ *   share one device function) with the crop's top-left byte as the source, the image's pitch, the crop's size and scale = crop / S in double.
+ * Valid slots are numbered in (image, row) ascending order by a prefix sum inside ONE workgroup that loops over the slots (no atomics,
+ * nothing the order could depend on).  *count_out receives the TRUE number of valid slots; the first min(count, max_chips) of them are
+ * written, the rest of chips_out / chip_src_out is not touched: count > max_chips tells the caller of the overflow.
+ *   images_host / images_dev: one danhip_resize_item per image, in host memory (validated) and in device memory (read by the kernels);
+ *     src_offset (from `src`, any byte alignment), H, W and pitch are read, the other fields are not (danhip_resize_item_init with
+ *     fx = fy = 1 fills an item);
+ *   dets fp32 [n_images, rows_per_image, 5], num int32 [n_images]; n_images * rows_per_image <= 2^24;
+ *   chips_out uint8 [max_chips, S, S, 3]; chip_src_out int32 [max_chips, 6] = (image, row, xc1, yc1, xc2, yc2); count_out int32 [1];
+ *   1 <= S <= 1024; workspace: danhip_face_chips_workspace bytes (0 today: the query and the arguments are there so that another
+ *   numbering scheme needs no new entry point; NULL is accepted when the query answers 0).
+ * DANHIP_EINVAL with a message and no launch: S or margin_pm out of range, square outside 0 / 1, a NaN threshold, max_chips < 0, a
+ * negative or too large n_images / rows_per_image, a workspace below the query, a NULL pointer, an image whose size is not positive,
+ * whose pitch is below 3 * W or whose bytes leave [0, src_bytes).  n_images == 0 or rows_per_image == 0: *count_out = 0, success.
+ * ------------------------------------------------------------------------------------------------ */
+int danhip_face_chips_workspace(int32_t n_images, int32_t rows_per_image, size_t* bytes);
+int danhip_face_chips_u8(const danhip_resize_item* images_host, const danhip_resize_item* images_dev, int32_t n_images, const uint8_t* src,
+                         int64_t src_bytes, const float* dets, const int32_t* num, int32_t rows_per_image, int32_t S, int32_t margin_pm,
+                         int32_t square, float score_threshold, uint8_t* chips_out, int32_t* chip_src_out, int32_t* count_out,
+                         int32_t max_chips, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
