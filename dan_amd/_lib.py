@@ -353,6 +353,8 @@ _TABLE = {
     # ---- face chips
     "danhip_face_chips_workspace": (STATUS, [I32, I32, ctypes.POINTER(SZ)]),
     "danhip_face_chips_u8": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, FL, P, P, P, I32, P, SZ, P]),
+    "danhip_face_chips_ex_workspace": (STATUS, [I32, I32, I32, I32, ctypes.POINTER(SZ)]),
+    "danhip_face_chips_u8_ex": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, FL, P, P, P, I32, P, SZ, P, I32, I32, P]),   # + filter, pad, fill_rgb
 }
 PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
 SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for

@@ -11,7 +11,8 @@ there either).  The port's own: --device, --precision, --batch_images (JPEGs rea
 of wider_face_<subset>.mat / wider_easy_<subset>.mat / wider_medium_<subset>.mat / wider_hard_<subset>.mat: the average precision is
 computed on the device and printed), --debug_quality, --debug_labels (draw each box's score on a tab above it; off by default), --chips_dir (with --chips_size, --chips_margin and
 --chips_threshold: every detection of score >= the threshold cropped and resized on the device by utility.face_chips' rule and written to
-chips_dir/<event>/<name>_<row>.jpg through the debug images' encoder, one encode call per group; off by default, and then nothing changes) and
+chips_dir/<event>/<name>_<row>.jpg through the debug images' encoder, one encode call per group; off by default, and then nothing changes;
+--chips_filter {linear,area} and --chips_pad choose the antialiased downscale and the whole, black-padded square instead of the clipped one) and
 --lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
 train_*'s flag of the same name.  transposed has no split-operand form: with --precision split the command exits with a message.
 --backbone {vgg16,resnet50,resnet101,resnet152} (eval_dan; default vgg16) is train_dan's flag of the same name: batch norm runs on the
@@ -95,6 +96,10 @@ def build_parser(model):
     p.add_argument("--chips_margin", type=float, default=0.0,
                    help="fraction of the box side added on each side before the crop is squared and clipped to the image, 0 .. 4 (default 0)")
     p.add_argument("--chips_threshold", type=float, default=None, help="score a detection needs to become a chip (default: --select_threshold)")
+    p.add_argument("--chips_filter", choices=("linear", "area"), default="linear",
+                   help="how a chip is resized: linear (OpenCV's INTER_LINEAR, default) or area (antialiased: a box filter where the crop shrinks)")
+    p.add_argument("--chips_pad", action="store_true",
+                   help="keep the squared crop whole and fill what leaves the image with black, instead of clipping it to the image (default off)")
     if model != "sfd":                                                      # (S3FD has no LFPN)
         p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
                        help="the LFPN of the checkpoint's graph: bilinear resize (default) or the learnable 4x4 stride-2 transposed convolution "
@@ -206,6 +211,8 @@ def main(argv=None, model="sfd", gt=None, out=None):
         except ValueError as e:
             raise SystemExit("--chips_size / --chips_margin: %s" % e)
         chips_threshold = args.select_threshold if args.chips_threshold is None else args.chips_threshold
+        # (--chips_filter is one of argparse's choices; either new flag takes danhip_face_chips_u8_ex, whose rule has a side cap)
+        chips_cap = face_chips.MAX_SIDE if args.chips_filter != "linear" or args.chips_pad else None
     lfpn_upsample = getattr(args, "lfpn_upsample", "bilinear")
     if lfpn_upsample == "transposed" and args.precision == "split":
         raise SystemExit("--lfpn_upsample transposed has no split-operand form: use --precision act or fp32")
@@ -288,10 +295,12 @@ def main(argv=None, model="sfd", gt=None, out=None):
                 # chip buffer is sized to them and the files are named without a second download
                 thr = np.float32(chips_threshold)
                 owners = [(b, r) for b in range(B) for r in range(counts[b]) if not rows[b, r, 4] < thr and
-                          face_chips.rule(rows[b, r], int(images[b].shape[0]), int(images[b].shape[1]), chips_pm, True) is not None]
+                          face_chips.rule(rows[b, r], int(images[b].shape[0]), int(images[b].shape[1]), chips_pm, True, pad=args.chips_pad,
+                                          cap=chips_cap) is not None]
                 if owners:
                     chips = face_chips.extract(images, dets, num, size=args.chips_size, margin=args.chips_margin, square=True,
-                                               score_threshold=chips_threshold, max_chips=len(owners)).chips
+                                               score_threshold=chips_threshold, max_chips=len(owners), filter=args.chips_filter,
+                                               pad=args.chips_pad).chips
                     os.makedirs(os.path.join(args.chips_dir, event), exist_ok=True)
                     for (b, r), data in zip(owners, chip_encoder.encode_batch(list(chips))):
                         chip_paths.append(os.path.join(args.chips_dir, event, "%s_%d.jpg" % (group[b], r)))

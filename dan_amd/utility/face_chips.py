@@ -1,16 +1,21 @@
-"""Face chips: every detection of every image of a list cropped and resized to size x size on the device (danhip_face_chips_u8,
-csrc/face_chips_exact.hip): two launches whatever the number of images and detections, nothing read back.
+"""Face chips: every detection of every image of a list cropped and resized to size x size on the device (danhip_face_chips_u8 and
+danhip_face_chips_u8_ex, csrc/face_chips_exact.hip): two launches whatever the number of images and detections, nothing read back.
 
     chips, chip_src, count = extract(images, dets, num, size=112)
+    chips, chip_src, count = extract(images, dets, num, size=112, filter="area", pad=True)
 
 images: list of uint8 [H_i, W_i, 3] device tensors (separate tensors or views into one buffer, at any byte offset; rows may be further
 apart than 3 * W_i bytes); dets fp32 [B, R, 5] rows (x1, y1, x2, y2, score) and num int32 [B]: what eval_dan.detect_image_list returns.
 chips uint8 [max_chips, size, size, 3], chip_src int32 [max_chips, 6] = (image, row, xc1, yc1, xc2, yc2), count int32 [1]: the number of
 rows that give a chip, in (image, row) order; the first min(count, max_chips) rows of chips / chip_src are written.
 
-The rectangle rule is the project's own (include/danhip.h, "Face chips"); `rule` restates it in Python integers.  The chip is OpenCV's
-INTER_LINEAR resize of the clamped rectangle (oracle/evalpipe.py:cv2_resize_linear_u8), bit for bit.  Out of scope: alignment by landmarks,
-zero padding for boxes that leave the image, antialiased downscaling."""
+The rectangle rule is the project's own (include/danhip.h, "Face chips"); `rule` restates it in Python integers.  By default the rectangle
+is clipped to the image and the chip is OpenCV's INTER_LINEAR resize of it (oracle/evalpipe.py:cv2_resize_linear_u8), bit for bit.
+pad=True keeps the rectangle whole - square and centred on the box - and reads `fill` where it leaves the image (chip_src then carries the
+unclipped corners).  filter="area" is an antialiased downscale by the project's own integer rule, restated by `area_weights`: a box filter
+on an axis that shrinks, exact half-pixel linear interpolation on one that does not, one rounding.  Either of the two takes
+danhip_face_chips_u8_ex, which gives no chip for a rectangle with a side above MAX_SIDE.  Out of scope: alignment by landmarks (the
+detectors predict none), border modes other than a constant, chips during training."""
 import ctypes
 import math
 
@@ -21,6 +26,8 @@ from .._lib import ResizeItem, call, ptr, stream
 
 MAX_SIZE = 1024            # danhip_face_chips_u8: 1 <= S <= 1024
 MAX_MARGIN_PM = 4000       # 0 <= margin_pm <= 4000
+MAX_SIDE = 32768           # DANHIP_FACE_CHIPS_MAX_SIDE: danhip_face_chips_u8_ex gives no chip for a longer side
+FILTERS = {"linear": 0, "area": 1}      # DANHIP_FACE_CHIPS_LINEAR / DANHIP_FACE_CHIPS_AREA
 _CLAMP = 1 << 30
 
 
@@ -38,9 +45,24 @@ def check_size(size):
     return int(size)
 
 
-def rule(dets_row, H, W, margin_pm=0, square=True):
+def check_filter(filter):
+    if filter not in FILTERS:
+        raise ValueError("filter %r is not one of %s" % (filter, ", ".join(sorted(FILTERS))))
+    return FILTERS[filter]
+
+
+def check_fill(fill):
+    fill = tuple(fill)
+    if len(fill) != 3 or any(int(v) != v or not 0 <= int(v) <= 255 for v in fill):
+        raise ValueError("fill %r is not three values of 0 .. 255" % (fill,))
+    return tuple(int(v) for v in fill)
+
+
+def rule(dets_row, H, W, margin_pm=0, square=True, pad=False, cap=None):
     """The rectangle of one detection row (x1, y1, x2, y2, ...) in an H x W image -> (xc1, yc1, xc2, yc2), inclusive, or None.  Integers only
-    after the corners are read; the score threshold and num[i] are the caller's."""
+    after the corners are read; the score threshold and num[i] are the caller's.  pad: the rectangle is not clipped to the image (one that
+    misses the image altogether is still None).  cap: None for a side longer than it (MAX_SIDE is danhip_face_chips_u8_ex's; the default
+    None is danhip_face_chips_u8, which has no cap); the side is that of the rectangle returned."""
     c = []
     for v in dets_row[:4]:
         v = float(np.float32(v))
@@ -60,10 +82,38 @@ def rule(dets_row, H, W, margin_pm=0, square=True):
         x2 = x1 + s - 1
         y1 -= (s - h) // 2
         y2 = y1 + s - 1
-    x1, y1, x2, y2 = max(x1, 0), max(y1, 0), min(x2, W - 1), min(y2, H - 1)
-    if x1 > x2 or y1 > y2:
+    if x2 < 0 or y2 < 0 or x1 > W - 1 or y1 > H - 1:
+        return None
+    if not pad:
+        x1, y1, x2, y2 = max(x1, 0), max(y1, 0), min(x2, W - 1), min(y2, H - 1)
+    if cap is not None and (x2 - x1 + 1 > cap or y2 - y1 + 1 > cap):
         return None
     return x1, y1, x2, y2
+
+
+def area_weights(n, S, j):
+    """One axis of filter="area": n source positions resampled to S outputs -> (indices, weights, D) of output j: the source positions
+    with a nonzero weight, ascending, their integer weights, and the divisor D the weights sum to.
+    n > S: a box filter, D = n; position i covers [i * S, (i + 1) * S) and output j covers [j * n, (j + 1) * n): the weight is the overlap.
+    n <= S: half-pixel linear interpolation in exact integers, D = 2 * S; t = (2 * j + 1) * n - S, i0 = t // (2 * S), f = t - 2 * S * i0:
+    2 * S - f on clamp(i0) and f on clamp(i0 + 1), clamped to 0 .. n - 1 (two taps clamped onto one position are returned as one)."""
+    n, S, j = int(n), int(S), int(j)
+    assert n >= 1 and S >= 1 and 0 <= j < S
+    taps = {}
+    if n > S:
+        for i in range(j * n // S, ((j + 1) * n - 1) // S + 1):
+            taps[i] = min((j + 1) * n, (i + 1) * S) - max(j * n, i * S)
+        D = n
+    else:
+        t = (2 * j + 1) * n - S
+        i0 = t // (2 * S)                                                  # Python's //: toward minus infinity
+        f = t - 2 * S * i0
+        for i, w in ((i0, 2 * S - f), (i0 + 1, f)):
+            i = min(max(i, 0), n - 1)
+            taps[i] = taps.get(i, 0) + w
+        D = 2 * S
+    indices = sorted(i for i, w in taps.items() if w > 0)
+    return indices, [taps[i] for i in indices], D
 
 
 class FaceChips(tuple):
@@ -89,11 +139,15 @@ class FaceChips(tuple):
         return out
 
 
-def extract(images, dets, num, size=112, margin=0.0, square=True, score_threshold=0.0, max_chips=None, out=None):
+def extract(images, dets, num, size=112, margin=0.0, square=True, score_threshold=0.0, max_chips=None, out=None, *, filter="linear", pad=False,
+            fill=(0, 0, 0)):
     """-> FaceChips (chips, chip_src, count), device tensors; nothing is synchronised.  margin: the fraction of the box side added on each
     side, converted to per mille once, here.  max_chips=None: len(images) * rows_per_image, room for every row.  out: (chips, chip_src,
-    count) tensors of a previous call (or the caller's own, of max_chips rows) to write into instead of new ones."""
+    count) tensors of a previous call (or the caller's own, of max_chips rows) to write into instead of new ones.  filter: "linear" or
+    "area"; pad: keep the rectangle whole and read `fill` (three values of 0 .. 255) outside the image.  filter="linear", pad=False is
+    danhip_face_chips_u8; anything else danhip_face_chips_u8_ex."""
     size, pm = check_size(size), margin_per_mille(margin)
+    filter_id, fill = check_filter(filter), check_fill(fill)
     images = list(images)
     B = len(images)
     device = dets.device
@@ -129,7 +183,10 @@ def extract(images, dets, num, size=112, margin=0.0, square=True, score_threshol
             call("danhip_resize_item_init", ctypes.c_void_p(staging.data_ptr() + i * nitem), im.data_ptr() - base, H, W, int(im.stride(0)), 0, H, W,
                  1.0, 1.0, 0, 0, ctypes.byref(nt))
         table = staging.to(device, non_blocking=True)
-    call("danhip_face_chips_u8", None if staging is None else ctypes.c_void_p(staging.data_ptr()), ptr(table), B, ctypes.c_void_p(base), src_bytes,
-         ptr(dets), ptr(num), R, size, pm, int(bool(square)), float(score_threshold), ptr(chips), ptr(chip_src), ptr(count), int(max_chips),
-         None, 0, stream())
+    args = (None if staging is None else ctypes.c_void_p(staging.data_ptr()), ptr(table), B, ctypes.c_void_p(base), src_bytes, ptr(dets), ptr(num),
+            R, size, pm, int(bool(square)), float(score_threshold), ptr(chips), ptr(chip_src), ptr(count), int(max_chips), None, 0, stream())
+    if filter_id == 0 and not pad:
+        call("danhip_face_chips_u8", *args)
+    else:
+        call("danhip_face_chips_u8_ex", *(args + (filter_id, int(bool(pad)), (ctypes.c_uint8 * 3)(*fill))))
     return FaceChips(chips, chip_src, count, B)

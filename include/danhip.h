@@ -1363,7 +1363,8 @@ int danhip_bn_act_bwd(const uint16_t* x, const uint16_t* dy, const uint16_t* y, 
  *   non-negative numbers; margin_pm in per mille, 0 .. 4000);
  *   square != 0, after the margin: s = max(w', h') of the grown sides; x1 -= (s - w') / 2, x2 = x1 + s - 1, likewise y: the shorter
  *   side gets (s - side) / 2 in front and the rest behind;
- *   then the rectangle is intersected with [0, W-1] x [0, H-1] (no zero padding): xc1, yc1, xc2, yc2; an empty intersection gives no chip.
+ *   then the rectangle is intersected with [0, W-1] x [0, H-1] (danhip_face_chips_u8 and pad = 0 of danhip_face_chips_u8_ex; pad = 1 is
+ *   below): xc1, yc1, xc2, yc2; an empty intersection gives no chip.
  *   Intermediates are 64-bit: |corner| <= 2^30 and margin_pm <= 4000 keep every product below 2^44.
  *   The chip is cv2.resize(image[yc1 : yc2 + 1, xc1 : xc2 + 1], (S, S), INTER_LINEAR): danhip_resize_u8_linear's arithmetic (the kernels
  *   share one device function) with the crop's top-left byte as the source, the image's pitch, the crop's size and scale = crop / S in double.
@@ -1386,6 +1387,48 @@ int danhip_face_chips_u8(const danhip_resize_item* images_host, const danhip_res
                          int64_t src_bytes, const float* dets, const int32_t* num, int32_t rows_per_image, int32_t S, int32_t margin_pm,
                          int32_t square, float score_threshold, uint8_t* chips_out, int32_t* chip_src_out, int32_t* count_out,
                          int32_t max_chips, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------------------
+ * Face chips, extended (ABI version 23; csrc/face_chips_exact.hip): zero-padded rectangles and an antialiased (area) downscale.
+ * danhip_face_chips_u8_ex takes danhip_face_chips_u8's 19 arguments in order, then filter, pad and fill_rgb; danhip_face_chips_u8 itself
+ * keeps its kernels and its bytes.  Still TWO launches per call (a select launch of the same single looping workgroup, one resize launch),
+ * nothing read back, no atomics.  Everything up to and including squaring is the rule above, unchanged.
+ *   pad = 1: the rectangle is NOT intersected with the image: chip_src carries the unclipped (x1, y1, x2, y2), which may be negative or
+ *     beyond W-1 / H-1; a rectangle whose intersection with the image is empty still gives no chip; a position of the rectangle outside
+ *     the image reads the constant fill_rgb[c] (3 bytes in HOST memory, read before the call returns; NULL = zeros).  pad = 0: the clipping
+ *     above.
+ *   Side cap: no chip when a side of the rectangle (the unclipped one when pad = 1, the clipped one otherwise) exceeds
+ *     DANHIP_FACE_CHIPS_MAX_SIDE = 32768.  It keeps every sum below 2^38 (255 * 2^30) and bounds the work per chip.  (Only here:
+ *     danhip_face_chips_u8 has no cap.)
+ *   filter = DANHIP_FACE_CHIPS_LINEAR (0): the chip is cv2.resize(crop, (S, S), INTER_LINEAR) bit for bit, crop = the rectangle, padded
+ *     when pad = 1: the arithmetic above with a pixel fetch that answers fill outside the image (replication at the border is that of
+ *     the RECTANGLE, as cv2.resize of the padded crop does it).  filter = 0, pad = 0 gives danhip_face_chips_u8's bytes.
+ *   filter = DANHIP_FACE_CHIPS_AREA (1): this project's own rule, integers only, separable, ONE rounding.  For an axis with n source
+ *     positions (the rectangle's side) and S outputs, output j has integer weights over the source positions i and a divisor D:
+ *       n > S (the axis shrinks), box filter, D = n: source position i covers [i*S, (i+1)*S), output j covers [j*n, (j+1)*n);
+ *         weight(i) = max(0, min((j+1)*n, (i+1)*S) - max(j*n, i*S)), nonzero for i = floor(j*n / S) .. floor(((j+1)*n - 1) / S);
+ *         the weights sum to n;
+ *       n <= S, exact half-pixel linear, D = 2*S: t = (2*j + 1)*n - S, i0 = floor(t / (2*S)) (toward minus infinity), f = t - 2*S*i0;
+ *         weight 2*S - f on clamp(i0, 0, n-1) and f on clamp(i0 + 1, 0, n-1) (the clamp is to the rectangle, not the image); n == S is
+ *         the identity.
+ *     A chip byte is (sum_y sum_x wy * wx * p(y, x) + (Dx*Dy) / 2) / (Dx*Dy), both divisions integer divisions of non-negative 64-bit
+ *     numbers (round half up); p is the image byte, or fill_rgb[c] outside the image.  The two axes choose their form independently
+ *     (with pad = 0 a clipped rectangle can shrink on one axis and grow on the other).  No floating point.
+ *     The kernel is separable within a workgroup: one (chip, output row, 256 output columns) item per workgroup at a time; bands of
+ *     source rows are read with consecutive lanes on consecutive bytes, reduced to exact horizontal sums (uint32, at most 255 * 32768
+ *     < 2^23) in LDS, and finished vertically in 64 bits.
+ * danhip_face_chips_ex_workspace: 0 bytes today (the band lives in LDS); it validates n_images, rows_per_image, S and filter.
+ * DANHIP_EINVAL with a message and no launch: filter outside 0 / 1, pad outside 0 / 1, and everything danhip_face_chips_u8 refuses.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_FACE_CHIPS_MAX_SIDE 32768
+#define DANHIP_FACE_CHIPS_LINEAR 0
+#define DANHIP_FACE_CHIPS_AREA 1
+int danhip_face_chips_ex_workspace(int32_t n_images, int32_t rows_per_image, int32_t S, int32_t filter, size_t* bytes);
+int danhip_face_chips_u8_ex(const danhip_resize_item* images_host, const danhip_resize_item* images_dev, int32_t n_images, const uint8_t* src,
+                            int64_t src_bytes, const float* dets, const int32_t* num, int32_t rows_per_image, int32_t S, int32_t margin_pm,
+                            int32_t square, float score_threshold, uint8_t* chips_out, int32_t* chip_src_out, int32_t* count_out,
+                            int32_t max_chips, void* workspace, size_t workspace_bytes, void* stream, int32_t filter, int32_t pad,
+                            const uint8_t fill_rgb[3]);
 
 #ifdef __cplusplus
 }
