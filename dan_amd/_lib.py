@@ -355,6 +355,15 @@ _TABLE = {
     "danhip_face_chips_u8": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, FL, P, P, P, I32, P, SZ, P]),
     "danhip_face_chips_ex_workspace": (STATUS, [I32, I32, I32, I32, ctypes.POINTER(SZ)]),
     "danhip_face_chips_u8_ex": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, FL, P, P, P, I32, P, SZ, P, I32, I32, P]),   # + filter, pad, fill_rgb
+    # ---- face redaction (the last six make no GPU call: csrc/redact_walk.h's index arithmetic)
+    "danhip_redact_workspace": (STATUS, [I32, I32, ctypes.POINTER(SZ)]),
+    "danhip_redact_u8": (STATUS, [P, P, I32, P, I64, P, P, I32, I32, I32, I32, I32, FL, P, P, P, P, I64, P, P, SZ, P]),
+    "danhip_redact_extent": (INT, [I32, I32, I32]),                     # e (>= 1), or DANHIP_EINVAL
+    "danhip_redact_item_count": (I64, [I32, P, I32, I32, I32]),         # -1 for arguments outside the rule
+    "danhip_redact_tile": (STATUS, [I32, I32, P, I32, I32, I32, I64, P]),
+    "danhip_redact_window": (STATUS, [I32, I32, I32, I32, I32, P]),
+    "danhip_redact_cell": (STATUS, [P, I32, I64, P]),
+    "danhip_redact_in_shape": (INT, [I32, P, I32, I32]),                # 1 / 0, or DANHIP_EINVAL
 }
 PROTOTYPES = {name: (INT if res is STATUS else res, args) for name, (res, args) in _TABLE.items()}
 SIGNATURES = {name: args for name, (res, args) in _TABLE.items() if res is STATUS}      # the calls `call` / `check` are for

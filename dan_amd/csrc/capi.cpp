@@ -20,7 +20,7 @@ void danhip_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* danhip_last_error(void) { return g_err; }
-extern "C" int danhip_version(void) { return 23; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch); 10: option "deterministic", danhip_ordered_reduce_f32, danhip_reduce_workspace_bytes and the _ws forms of the L2-norm / bias-gradient / loss / optimizer entry points; 11: danhip_augment_item_init / danhip_augment_preprocess_batch (the training input pass for a whole batch in a constant number of launches); 12: danhip_resize_item_init / danhip_resize_u8_linear_batch / danhip_detect_select (the test-time pipeline for images of different sizes); 13: danhip_cls_accuracy (the training metric, counted on the device); 14: danhip_crc32c_host / _combine / _batch (CRC-32C of checkpoint tensors on the host and on the device); 15: danhip_jpeg_encode_* (baseline JPEG encode, byte for byte Pillow's) and danhip_draw_boxes_u8 (box drawing on device images); 16: danhip_jpeg_encode_scan_* / _huffman_batch / _entropy_emulate_batch (the encoder's Huffman stage on the device); 17: the deformable backward in deterministic mode (ordered far corners): danhip_deform_sample_bwd_ordered_workspace_bytes / danhip_deform_conv_bwd_ordered_workspace_bytes / danhip_deform_far_ordered / danhip_deform_far_ordered_emulate; 18: danhip_draw_boxes_labels_u8 / danhip_draw_glyph / danhip_draw_format_score (the score label of the debug images); 19: danhip_conv_transpose4x4s2_* (transposed convolution 4x4 / stride 2: the LFPN's learnable upsampling); 20: danhip_jpeg_optimal_table_host / danhip_jpeg_encode_entropy_batch_ex / danhip_jpeg_encode_scan_prepare_ex / danhip_jpeg_encode_optimize_layout / danhip_jpeg_optimal_tables_device (the JPEG encoder's optimize=True, on the host and on the device); 21: danhip_bn_act_* (fused batch-norm tails: batch norm + residual add + ReLU in one apply pass, masked backward); 22: danhip_face_chips_workspace / danhip_face_chips_u8 (face chips: every detection cropped and resized on the device in two launches); 23: danhip_face_chips_u8_ex / danhip_face_chips_ex_workspace (zero-padded chips, area downscale)
+extern "C" int danhip_version(void) { return 24; }   // 2: danhip_deform_sample_bwd takes workspace_bytes; 3: danhip_comm_* (RCCL called directly); 4: danhip_comm_async_error / danhip_comm_abort; 5: danhip_wider_* (WIDER FACE AP); 6: danhip_jpeg_* (baseline JPEG decode); 7: danhip_jpeg_scan_* / danhip_jpeg_huffman_decode_batch (Huffman stage on the device); 8: danhip_jpeg_*_ex (opt-in progressive streams on the host entropy stage); 9: danhip_heads_split_fwd / danhip_heads_grad_pad (all head levels in one launch); 10: option "deterministic", danhip_ordered_reduce_f32, danhip_reduce_workspace_bytes and the _ws forms of the L2-norm / bias-gradient / loss / optimizer entry points; 11: danhip_augment_item_init / danhip_augment_preprocess_batch (the training input pass for a whole batch in a constant number of launches); 12: danhip_resize_item_init / danhip_resize_u8_linear_batch / danhip_detect_select (the test-time pipeline for images of different sizes); 13: danhip_cls_accuracy (the training metric, counted on the device); 14: danhip_crc32c_host / _combine / _batch (CRC-32C of checkpoint tensors on the host and on the device); 15: danhip_jpeg_encode_* (baseline JPEG encode, byte for byte Pillow's) and danhip_draw_boxes_u8 (box drawing on device images); 16: danhip_jpeg_encode_scan_* / _huffman_batch / _entropy_emulate_batch (the encoder's Huffman stage on the device); 17: the deformable backward in deterministic mode (ordered far corners): danhip_deform_sample_bwd_ordered_workspace_bytes / danhip_deform_conv_bwd_ordered_workspace_bytes / danhip_deform_far_ordered / danhip_deform_far_ordered_emulate; 18: danhip_draw_boxes_labels_u8 / danhip_draw_glyph / danhip_draw_format_score (the score label of the debug images); 19: danhip_conv_transpose4x4s2_* (transposed convolution 4x4 / stride 2: the LFPN's learnable upsampling); 20: danhip_jpeg_optimal_table_host / danhip_jpeg_encode_entropy_batch_ex / danhip_jpeg_encode_scan_prepare_ex / danhip_jpeg_encode_optimize_layout / danhip_jpeg_optimal_tables_device (the JPEG encoder's optimize=True, on the host and on the device); 21: danhip_bn_act_* (fused batch-norm tails: batch norm + residual add + ReLU in one apply pass, masked backward); 22: danhip_face_chips_workspace / danhip_face_chips_u8 (face chips: every detection cropped and resized on the device in two launches); 23: danhip_face_chips_u8_ex / danhip_face_chips_ex_workspace (zero-padded chips, area downscale); 24: danhip_redact_* (face redaction: blur, mosaic, fill)
 extern "C" int danhip_act_dtype(void) {
 #ifdef DANHIP_FP16
   return DANHIP_F16;

@@ -13,6 +13,10 @@ computed on the device and printed), --debug_quality, --debug_labels (draw each 
 --chips_threshold: every detection of score >= the threshold cropped and resized on the device by utility.face_chips' rule and written to
 chips_dir/<event>/<name>_<row>.jpg through the debug images' encoder, one encode call per group; off by default, and then nothing changes;
 --chips_filter {linear,area} and --chips_pad choose the antialiased downscale and the whole, black-padded square instead of the clipped one) and
+--redact_dir (with --redact_mode {blur,mosaic,fill}, --redact_shape {rect,ellipse}, --redact_strength, --redact_margin and
+--redact_threshold: EVERY image of the run with its detections of score >= the threshold made unrecognisable on the device by
+utility.redact's rule and written to redact_dir/<event>/<name>.jpg through the debug images' encoder, one encode call per group; off by
+default, and then nothing changes) and
 --lfpn_upsample {bilinear,transposed} (eval_pb, eval_dan, eval_dan_deform; default bilinear): the graph of a checkpoint trained with
 train_*'s flag of the same name.  transposed has no split-operand form: with --precision split the command exits with a message.
 --backbone {vgg16,resnet50,resnet101,resnet152} (eval_dan; default vgg16) is train_dan's flag of the same name: batch norm runs on the
@@ -100,6 +104,15 @@ def build_parser(model):
                    help="how a chip is resized: linear (OpenCV's INTER_LINEAR, default) or area (antialiased: a box filter where the crop shrinks)")
     p.add_argument("--chips_pad", action="store_true",
                    help="keep the squared crop whole and fill what leaves the image with black, instead of clipping it to the image (default off)")
+    p.add_argument("--redact_dir", default=None,
+                   help="write every image with its detections redacted to redact_dir/<event>/<name>.jpg at --debug_quality (default: none are made)")
+    p.add_argument("--redact_mode", choices=("blur", "mosaic", "fill"), default="blur",
+                   help="what replaces a face: a box blur scaled to it (default), a mosaic of cell means, or black")
+    p.add_argument("--redact_shape", choices=("rect", "ellipse"), default="rect", help="the box itself (default) or the ellipse inscribed in it")
+    p.add_argument("--redact_strength", type=float, default=0.125,
+                   help="blur radius / mosaic cell side as a fraction of the box's longer side, 0.001 .. 1 (default 0.125)")
+    p.add_argument("--redact_margin", type=float, default=0.0, help="fraction of the box side added on each side, 0 .. 4 (default 0)")
+    p.add_argument("--redact_threshold", type=float, default=None, help="score a detection needs to be redacted (default: --select_threshold)")
     if model != "sfd":                                                      # (S3FD has no LFPN)
         p.add_argument("--lfpn_upsample", choices=LFPN_UPSAMPLE, default="bilinear",
                        help="the LFPN of the checkpoint's graph: bilinear resize (default) or the learnable 4x4 stride-2 transposed convolution "
@@ -196,7 +209,7 @@ def written_rows(det, select_threshold, min_height):
 # ------------------------------------------------------------------------------------------------------------ main
 def main(argv=None, model="sfd", gt=None, out=None):
     """gt: a wider_eval.WiderGroundTruth to score against (instead of --gt_dir); out: where the progress and AP lines go (sys.stdout).
-    -> {"images": n, "debug": [paths], "ap": {subset: AP} or None, "decoder": stats, "encoder": stats or None}."""
+    -> {"images": n, "debug": [paths], "chips": [paths], "redacted": [paths], "ap": {subset: AP} or None, "decoder": stats, "encoder": stats or None}."""
     args = build_parser(model).parse_args(argv)
     out = sys.stdout if out is None else out
     if args.batch_images < 1:
@@ -213,6 +226,14 @@ def main(argv=None, model="sfd", gt=None, out=None):
         chips_threshold = args.select_threshold if args.chips_threshold is None else args.chips_threshold
         # (--chips_filter is one of argparse's choices; either new flag takes danhip_face_chips_u8_ex, whose rule has a side cap)
         chips_cap = face_chips.MAX_SIDE if args.chips_filter != "linear" or args.chips_pad else None
+    if args.redact_dir:
+        from .utility import redact                               # (importing it does not touch the device)
+        try:
+            redact.strength_per_mille(args.redact_strength)
+            redact.margin_per_mille(args.redact_margin)
+            redact_threshold = redact.check_threshold(args.select_threshold if args.redact_threshold is None else args.redact_threshold)
+        except ValueError as e:
+            raise SystemExit("--redact_strength / --redact_margin / --redact_threshold: %s" % e)
     lfpn_upsample = getattr(args, "lfpn_upsample", "bilinear")
     if lfpn_upsample == "transposed" and args.precision == "split":
         raise SystemExit("--lfpn_upsample transposed has no split-operand form: use --precision act or fp32")
@@ -247,6 +268,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     if args.debug_dir:
         os.makedirs(args.debug_dir, exist_ok=True)
     chip_encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy, optimize=args.encode_optimize) if args.chips_dir else None
+    redact_encoder = JpegEncoder(quality=args.debug_quality, entropy=args.encode_entropy, optimize=args.encode_optimize) if args.redact_dir else None
     min_height = MIN_HEIGHT[model]
     on_device = min_height == 10 and args.select_threshold == eval_dan.SELECT_THRESHOLD       # the filter danhip_wider_quantize restates
     evaluator = None
@@ -255,7 +277,7 @@ def main(argv=None, model="sfd", gt=None, out=None):
     image_root = os.path.join(args.data_dir, "WIDER_val" if args.subset == "val" else "WIDER_test", "images")
     save_root = os.path.join(args.det_dir, args.subset)
     every = max(args.log_every_n_steps, 1)
-    total, debug_paths, chip_paths = 0, [], []
+    total, debug_paths, chip_paths, redact_paths = 0, [], [], []
     for index, (event, files) in enumerate(events):
         os.makedirs(os.path.join(save_root, event), exist_ok=True)
         for start in range(0, len(files), args.batch_images):
@@ -280,6 +302,14 @@ def main(argv=None, model="sfd", gt=None, out=None):
                 else:
                     for b, i in enumerate(index_of):
                         evaluator.add_rows(i, torch.from_numpy(written_rows(rows[b, :counts[b]], args.select_threshold, min_height)))
+            if redact_encoder is not None:                       # before the debug images: those are drawn in place
+                pictures, _ = redact.apply(images, dets, num, mode=args.redact_mode, shape=args.redact_shape, strength=args.redact_strength,
+                                           margin=args.redact_margin, score_threshold=redact_threshold)
+                os.makedirs(os.path.join(args.redact_dir, event), exist_ok=True)
+                for name, data in zip(group, redact_encoder.encode_batch(pictures)):
+                    redact_paths.append(os.path.join(args.redact_dir, event, name + ".jpg"))
+                    with open(redact_paths[-1], "wb") as f:
+                        f.write(data)
             drawn = [b for b in range(B) if (start + b) % every == 0] if encoder is not None else []
             if drawn:
                 boxes = [dets[b, :counts[b], :4] for b in drawn]
@@ -317,4 +347,4 @@ def main(argv=None, model="sfd", gt=None, out=None):
         ap = collections.OrderedDict((s, res[s]) for s in gt.subsets)
         for s, v in ap.items():
             print("%s AP: %.6f" % (s, v), file=out, flush=True)
-    return {"images": total, "debug": debug_paths, "chips": chip_paths, "ap": ap, "decoder": decoder.stats, "encoder": None if encoder is None else encoder.stats}
+    return {"images": total, "debug": debug_paths, "chips": chip_paths, "redacted": redact_paths, "ap": ap, "decoder": decoder.stats, "encoder": None if encoder is None else encoder.stats}

@@ -1430,6 +1430,74 @@ int danhip_face_chips_u8_ex(const danhip_resize_item* images_host, const danhip_
                             int32_t max_chips, void* workspace, size_t workspace_bytes, void* stream, int32_t filter, int32_t pad,
                             const uint8_t fill_rgb[3]);
 
+/* --------------------------------------------------------------------------------------------------
+ * Face redaction (ABI version 24; csrc/redact_exact.hip, csrc/redact_walk.h; dan_amd/utility/redact.py): every detection of every image
+ * of a list blurred, pixelated or filled, out of place, in DANHIP_REDACT_LAUNCHES launches whatever the number of images, detections and
+ * sizes; nothing is read back.  The rule is this project's own, integers only after the corners are truncated, ONE rounding (restated by
+ * dan_amd/utility/redact.py rule_pixel / reference).  For image i (H x W, uint8 RGB), row r is dets[i, r] = (x1, y1, x2, y2, score):
+ *   Rectangle: the face-chip rectangle above with square = 0, pad = 0 and the side cap: corners = int() of the floats clamped to +-2^30,
+ *     w, h >= 1, margin_pm per mille on each side, intersected with the image: (x1, y1, x2, y2), clipped sides wc = x2 - x1 + 1,
+ *     hc = y2 - y1 + 1.  No rectangle when r >= num[i], score < score_threshold (fp32 compare: equal is kept), a coordinate is NaN or
+ *     infinite, w < 1 or h < 1, the intersection is empty, or a clipped side exceeds DANHIP_FACE_CHIPS_MAX_SIDE.
+ *   Extent: e = clamp(max(wc, hc) * strength_pm / 1000, 1, DANHIP_REDACT_MAX_EXTENT) (integer division; strength_pm 1 .. 1000).
+ *     DANHIP_REDACT_MAX_EXTENT = 255: a window sum is at most 255 * 511 * 511 < 2^32.
+ *   Shape: DANHIP_REDACT_RECT (0): every pixel of the rectangle.  DANHIP_REDACT_ELLIPSE (1): pixel (px, py) of it when
+ *     (2*(px-x1)+1-wc)^2 * hc^2 + (2*(py-y1)+1-hc)^2 * wc^2 <= wc^2 * hc^2, in 64 bits (the side cap keeps it below 2^62).
+ *   Ownership: a pixel inside the shapes of several valid rows of its image belongs to the one with the HIGHEST row index; a pixel inside
+ *     no shape is copied unchanged.
+ *   Value: every mode reads the ORIGINAL image only, so the result depends on no execution order.
+ *     DANHIP_REDACT_FILL (2): channel c = fill_rgb[c] (3 bytes in HOST memory, read before the call returns).
+ *     DANHIP_REDACT_MOSAIC (1): cell side c = max(2, e); cells anchored at (x1, y1), each clipped to the rectangle; every channel is
+ *       (S + A / 2) / A, S = the sum of the original bytes of the clipped cell, A = its pixel count, integer divisions.  With the ellipse the
+ *       mean is still that of the whole clipped cell; only the pixels inside the ellipse are written.
+ *     DANHIP_REDACT_BLUR (0): one box filter of radius e; the window [px-e, px+e] x [py-e, py+e] is intersected with the IMAGE (not the
+ *       rectangle: the surroundings bleed in); (S + A / 2) / A with A the number of window pixels inside the image.
+ * The launches: redact_select (ONE looping workgroup: the table of valid rectangles with their extents and the running number of work items
+ * before each, in (image, row) order; no atomics), redact_copy (every pixel of every image, source to destination) and ONE work launch of the
+ * mode.  Work items of blur and fill are tiles of DANHIP_REDACT_BAND output rows x DANHIP_REDACT_STRIP columns of one rectangle; of mosaic,
+ * one cell.  A blur item keeps one uint32 vertical running sum per byte column of its strip plus the halo in LDS (adding the entering and
+ * subtracting the leaving source row per output row) and takes every pixel's horizontal window sum from a prefix scan of them: the work
+ * per pixel does not depend on e.  An item of row r writes a pixel only if no later valid row of the image holds it (a short list of the
+ * later rectangles that meet the item's tile, built per item in LDS; no atomics, no races: every destination byte has one writer per launch).
+ *   images_host / images_dev, src, src_bytes, dets, num, rows_per_image: as for danhip_face_chips_u8.
+ *   dst_items_host / dst_items_dev: one danhip_resize_item per image for the destination: src_offset is the byte offset from `dst` (any
+ *     alignment), H, W, pitch; H and W equal the source's.  The other fields are not read.
+ *   count_out int32 [1]: the number of valid rectangles.  workspace: danhip_redact_workspace bytes (the table).
+ * DANHIP_EINVAL with a message and no launch: mode or shape out of range, strength_pm outside 1 .. 1000, margin_pm outside 0 .. 4000, a NaN
+ * threshold, a NULL pointer, negative counts or n_images * rows_per_image > 2^24, an image whose size is not positive, whose pitch is below
+ * 3 * W or whose bytes leave its buffer, a destination whose size differs from its source or that overlaps a source image or another
+ * destination, a workspace below the query.  n_images == 0: success, nothing is done.  rows_per_image == 0: the images are copied,
+ * *count_out = 0 (dets and num may be NULL).
+ * The index arithmetic of the walk (csrc/redact_walk.h: plain functions the kernels call) is exported for the host, no GPU call is made:
+ *   danhip_redact_extent -> e of clipped sides; danhip_redact_item_count -> items of a rectangle (blur / fill: tiles, row-major; mosaic: cells,
+ *   row-major), band / strip are the tile's sides (the kernels pass DANHIP_REDACT_BAND / _STRIP);
+ *   danhip_redact_tile: item -> out[8] = (tx1, ty1, tx2, ty2 of the tile, inclusive; sx1, sy1, sx2, sy2 = the source columns and rows a blur
+ *   item of extent e reads: the tile grown by e, intersected with the image);
+ *   danhip_redact_window: pixel -> out[5] = (lo_x, lo_y, hi_x, hi_y, A) of the blur window; danhip_redact_cell: cell -> out[5] = (cx1, cy1,
+ *   cx2, cy2, A); danhip_redact_in_shape -> 1 / 0.  Each answers DANHIP_EINVAL (or -1 for the int64 count) for arguments outside the rule.
+ * ------------------------------------------------------------------------------------------------ */
+#define DANHIP_REDACT_LAUNCHES 3
+#define DANHIP_REDACT_MAX_EXTENT 255
+#define DANHIP_REDACT_BAND 64
+#define DANHIP_REDACT_STRIP 256
+#define DANHIP_REDACT_BLUR 0
+#define DANHIP_REDACT_MOSAIC 1
+#define DANHIP_REDACT_FILL 2
+#define DANHIP_REDACT_RECT 0
+#define DANHIP_REDACT_ELLIPSE 1
+int danhip_redact_workspace(int32_t n_images, int32_t rows_per_image, size_t* bytes);
+int danhip_redact_u8(const danhip_resize_item* images_host, const danhip_resize_item* images_dev, int32_t n_images, const uint8_t* src,
+                     int64_t src_bytes, const float* dets, const int32_t* num, int32_t rows_per_image, int32_t mode, int32_t shape,
+                     int32_t strength_pm, int32_t margin_pm, float score_threshold, const uint8_t fill_rgb[3],
+                     const danhip_resize_item* dst_items_host, const danhip_resize_item* dst_items_dev, uint8_t* dst, int64_t dst_bytes,
+                     int32_t* count_out, void* workspace, size_t workspace_bytes, void* stream);
+int danhip_redact_extent(int32_t wc, int32_t hc, int32_t strength_pm);
+int64_t danhip_redact_item_count(int32_t mode, const int32_t rect[4], int32_t e, int32_t band, int32_t strip);
+int danhip_redact_tile(int32_t H, int32_t W, const int32_t rect[4], int32_t e, int32_t band, int32_t strip, int64_t item, int32_t out[8]);
+int danhip_redact_window(int32_t H, int32_t W, int32_t e, int32_t px, int32_t py, int32_t out[5]);
+int danhip_redact_cell(const int32_t rect[4], int32_t c, int64_t cell, int32_t out[5]);
+int danhip_redact_in_shape(int32_t shape, const int32_t rect[4], int32_t px, int32_t py);
+
 #ifdef __cplusplus
 }
 #endif
